@@ -10,8 +10,12 @@ of this rank: reset-terminated -> random-legal policy -> env step (+observe), i.
 65,536 concurrent 2-player games per GPU, random-action policy, synthetic (random-policy) play.
 Games are independent, so N GPUs run N shards with no data-path collective (weak scaling).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel: env step) and, at N=1,
-`cpu_baseline` (the CPU oracle timed on this box's host cores — a reported baseline, not the target).
+Prints ONE JSON line on rank 0 with `ms_per_step` (one timed step, wall clock) and `roofline` (dominant kernel: env step,
+from the timed region alone).  A plain run does only that: set up, warm up, time the K steps, print.  `--full` adds the legs
+that take runs of their own: the timed region repeated (`repeats`), streaming ceilings and device state, the step kernel
+alone, the exchange leg at N > 1 and, at N=1, the env configs[4] / GEMM / learner / actor / training legs and `cpu_baseline`
+(the CPU oracle timed on this box's host cores — a reported baseline, not the target).
+`--dump-outputs DIR` writes what the timed rollout left in its last step (a fixed seeded sample of games) as DIR/*.npy.
 """
 import argparse
 import json
@@ -30,6 +34,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s spec, 
 GAMES_PER_GPU = 65536
 PLAYERS, HAND = 2, 5
 EPS = [0.1 ** (1 + 7 * i / 79) for i in range(80)]  # utils.generate_explore_eps(0.1, 7, 80)
+DUMP_GAMES = 4096    # --dump-outputs: games sampled (seed 0) = 4,096 x 6.6 KB = 27 MB at F = 783
 
 
 def algorithmic_bytes_per_step(P, F, A, H, sad):
@@ -725,6 +730,18 @@ def streaming_ceilings(dev, nbytes=448 * 1024 * 1024, reps=15):
     torch.cuda.empty_cache()
     return out
 
+def dump_outputs(env, out_dir):
+    """--dump-outputs: the tensors a caller of rollout_random holds after its last iteration (obs(), reward, terminal and the actions
+    the policy chose), for the same seeded sample of games every run, as float32 .npy files"""
+    import numpy as np
+    idx = np.arange(env.G) if env.G <= DUMP_GAMES else np.sort(np.random.default_rng(0).choice(env.G, DUMP_GAMES, replace=False))
+    sel = torch.from_numpy(idx).to(env.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("priv_s", env.priv_s), ("legal_move", env.legal_move), ("own_hand", env.own_hand), ("eps", env.eps),
+                    ("reward", env.reward), ("terminal", env.terminal), ("action", env.a)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.index_select(0, sel).to(torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -747,6 +764,14 @@ def main():
     ap.add_argument("--lock-us", type=int, default=30,
                     help="phase lock between the partition chains (hsad_env_set_rollout_stagger): partition k starts each "
                          "launch this long after partition k-1, so one partition's logic phase overlaps the others' HBM stream")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the repeated timed region, device state and streaming ceilings, the "
+                         "step kernel's own timing, the exchange leg (N > 1) and, at N = 1, the env configs[4], GEMM, learner, actor, "
+                         "training and CPU-baseline legs (--no-* drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed rollout left in its last step (rank 0's observation, legal moves, own hand, eps, "
+                         "reward, terminal and actions) as DIR/<name>.npy in float32, for a fixed seeded sample of at most %d games"
+                         % DUMP_GAMES)
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -826,7 +851,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    state_before = device_state(local_dev) if rank == 0 else None
+    state_before = device_state(local_dev) if rank == 0 and args.full else None
     stage[0] = "warm-up + barrier"
     if os.environ.get("HSAD_BENCH_WEDGE_RANK") == str(rank) and world > 1:      # (fault injection for the watchdog's test: this rank never arrives)
         time.sleep(10 ** 6)
@@ -845,25 +870,28 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     iter_ms = k0.elapsed_time(k1) / args.steps                      # all partitions of one iteration (they overlap)
-    # spread (not part of the contract's timed region): the same K-step region again and again until >= 0.5 s of GPU time
-    rep_ms = []
-    sampler = DeviceSampler(local_dev) if rank == 0 else None
-    if sampler is not None:
-        sampler.__enter__()
-    while sum(rep_ms) < (1500.0 if rank == 0 else 500.0) or len(rep_ms) < 5:      # (rank 0: long enough for a few rocm-smi readings under load)
-        r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        r0.record()
-        env.rollout_random(args.steps, policy_seed)
-        r1.record()
-        torch.cuda.synchronize()
-        rep_ms.append(r0.elapsed_time(r1))
-        if len(rep_ms) >= 2000:
-            break
-    if sampler is not None:
-        sampler.__exit__()
-    rep_sorted = sorted(x / args.steps for x in rep_ms)
-    state_after = device_state(local_dev) if rank == 0 else None
-    ceil = streaming_ceilings(dev) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs)
+    if args.full:
+        # spread (not part of the contract's timed region): the same K-step region again and again until >= 0.5 s of GPU time
+        rep_ms = []
+        sampler = DeviceSampler(local_dev) if rank == 0 else None
+        if sampler is not None:
+            sampler.__enter__()
+        while sum(rep_ms) < (1500.0 if rank == 0 else 500.0) or len(rep_ms) < 5:      # (rank 0: long enough for a few rocm-smi readings under load)
+            r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            r0.record()
+            env.rollout_random(args.steps, policy_seed)
+            r1.record()
+            torch.cuda.synchronize()
+            rep_ms.append(r0.elapsed_time(r1))
+            if len(rep_ms) >= 2000:
+                break
+        if sampler is not None:
+            sampler.__exit__()
+        rep_sorted = sorted(x / args.steps for x in rep_ms)
+        state_after = device_state(local_dev) if rank == 0 else None
+        ceil = streaming_ceilings(dev) if rank == 0 else None
     if persistent:
         # one launch = args.chunk iterations of all G games (the last one shorter if steps is not a multiple), back to back
         # on the caller's stream between the two events: average launch duration = region / launches
@@ -895,12 +923,13 @@ def main():
             e1.record()
         torch.cuda.synchronize()
         return sum(e0.elapsed_time(e1) for e0, e1 in ev) / len(ev)
-    pairs(True)
-    step_raw_ms, pair_overhead_ms = pairs(True), pairs(False)
-    step_ms = step_raw_ms - pair_overhead_ms
-    env.check_errors()
     bytes_per_step = algorithmic_bytes_per_step(env.P, env.F, env.A, env.H, False)
-    achieved_step = bytes_per_step * G / (step_ms * 1e-3) / 1e9
+    if args.full:
+        pairs(True)
+        step_raw_ms, pair_overhead_ms = pairs(True), pairs(False)
+        step_ms = step_raw_ms - pair_overhead_ms
+        env.check_errors()
+        achieved_step = bytes_per_step * G / (step_ms * 1e-3) / 1e9
     achieved = bytes_per_step * G / (iter_ms * 1e-3) / 1e9        # all concurrent launches together = the chip's rate
     per_launch = bytes_per_step * (G / K) * iters_per_launch / (fused_ms * 1e-3) / 1e9
 
@@ -914,10 +943,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "repeats": {"regions": len(rep_ms), "steps_per_region": args.steps, "gpu_seconds": sum(rep_ms) / 1e3,
-                        "ms_per_step_median": rep_sorted[len(rep_sorted) // 2], "ms_per_step_min": rep_sorted[0], "ms_per_step_max": rep_sorted[-1],
-                        "value_at_median_per_gpu": G / (rep_sorted[len(rep_sorted) // 2] * 1e-3),
-                        "note": "the timed region repeated (HIP events, this rank) until >= 0.5 s of GPU time; `value` is the contract's single region"},
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -949,30 +974,38 @@ def main():
                 "launches": n_launch, "iterations_per_launch": iters_per_launch,
                 "launches_per_iteration": K if not persistent else 1.0 / iters_per_launch, "iteration_ms": iter_ms,
                 "per_launch_achieved": per_launch,
-                # spread of the timed region on this device (the `repeats` block above, kept here where a parser that only keeps the
-                # contract's keys still finds it) and this device's own streaming ceilings measured in this run
-                "ms_per_step_median": rep_sorted[len(rep_sorted) // 2], "ms_per_step_min": rep_sorted[0], "ms_per_step_max": rep_sorted[-1],
-                "regions_repeated": len(rep_ms),
-                "achieved_at_median": bytes_per_step * G / (rep_sorted[len(rep_sorted) // 2] * 1e-3) / 1e9,
-                "write_ceiling_gbs": ceil["write"], "copy_ceiling_gbs": ceil["copy"],
-                "frac_of_write_ceiling": achieved / ceil["write"],
-                "frac_of_write_ceiling_at_median": bytes_per_step * G / (rep_sorted[len(rep_sorted) // 2] * 1e-3) / 1e9 / ceil["write"],
-                "ceiling_note": "write_ceiling = torch fill_ of 448 MB (one iteration's traffic at this shape, 98 % writes), copy_ceiling = "
-                                "copy_ of the same size (read + write bytes), median of 15 event pairs each, measured in this run on this "
-                                "device right behind the timed region",
                 "launch_boundary_note": "one launch = %d iterations; a %d-step region is %d launch(es): short regions pay the launch "
                                         "boundary (pipeline fill + tail) once per launch -- DESIGN 3a measures 80 us / iteration at 10 "
                                         "iterations per launch against 68 us at >= 50" % (args.chunk, args.steps, n_launch) if persistent else None,
-                "device_state_before": state_before, "device_state_after": state_after,
-                "device_state_during_repeats": sampler.samples[:6] if sampler is not None else None,
             },
-            "roofline_step_kernel": {
-                "bound": "hbm", "kernel": "env_kernel<1,2,5> (HanabiEnv::step + observe with actions from HBM, the "
-                                          "hsad_env_step entry point)",
-                "achieved": achieved_step, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_step / HBM_PEAK_GBS,
-                "traffic": measured_traffic_bytes(G, 1), "avg_launch_ms": step_ms,
-                "event_pair_ms": step_raw_ms, "empty_event_pair_ms": pair_overhead_ms,
-            },
+        }
+    if rank == 0 and args.full:
+        med = rep_sorted[len(rep_sorted) // 2]
+        out["repeats"] = {"regions": len(rep_ms), "steps_per_region": args.steps, "gpu_seconds": sum(rep_ms) / 1e3,
+                          "ms_per_step_median": med, "ms_per_step_min": rep_sorted[0], "ms_per_step_max": rep_sorted[-1],
+                          "value_at_median_per_gpu": G / (med * 1e-3),
+                          "note": "the timed region repeated (HIP events, this rank) until >= 0.5 s of GPU time; `value` is the contract's single region"}
+        out["roofline"].update({
+            # spread of the timed region on this device (the `repeats` block above, kept here where a parser that only keeps the
+            # contract's keys still finds it) and this device's own streaming ceilings measured in this run
+            "ms_per_step_median": med, "ms_per_step_min": rep_sorted[0], "ms_per_step_max": rep_sorted[-1],
+            "regions_repeated": len(rep_ms),
+            "achieved_at_median": bytes_per_step * G / (med * 1e-3) / 1e9,
+            "write_ceiling_gbs": ceil["write"], "copy_ceiling_gbs": ceil["copy"],
+            "frac_of_write_ceiling": achieved / ceil["write"],
+            "frac_of_write_ceiling_at_median": bytes_per_step * G / (med * 1e-3) / 1e9 / ceil["write"],
+            "ceiling_note": "write_ceiling = torch fill_ of 448 MB (one iteration's traffic at this shape, 98 % writes), copy_ceiling = "
+                            "copy_ of the same size (read + write bytes), median of 15 event pairs each, measured in this run on this "
+                            "device right behind the timed region",
+            "device_state_before": state_before, "device_state_after": state_after,
+            "device_state_during_repeats": sampler.samples[:6] if sampler is not None else None,
+        })
+        out["roofline_step_kernel"] = {
+            "bound": "hbm", "kernel": "env_kernel<1,2,5> (HanabiEnv::step + observe with actions from HBM, the "
+                                      "hsad_env_step entry point)",
+            "achieved": achieved_step, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_step / HBM_PEAK_GBS,
+            "traffic": measured_traffic_bytes(G, 1), "avg_launch_ms": step_ms,
+            "event_pair_ms": step_raw_ms, "empty_event_pair_ms": pair_overhead_ms,
         }
     if world > 1:
         # who is in the job: every rank's device and what the collective backend itself reports
@@ -985,7 +1018,7 @@ def main():
             out["backend"] = args.dist_backend + (" (= RCCL)" if args.dist_backend == "nccl" else "")
             out["rccl_ranks"] = _d.get_world_size() if args.dist_backend == "nccl" else None
     stage[0] = "exchange leg"
-    if world > 1 and not os.environ.get("HSAD_BENCH_NO_EXCHANGE"):
+    if world > 1 and args.full and not os.environ.get("HSAD_BENCH_NO_EXCHANGE"):
         # the exchange leg is collective: a rank that never arrives would leave the others inside a collective for good and the
         # headline number, already measured, unprinted.  A watchdog prints the line without the leg and ends the process instead.
         import threading
@@ -1016,16 +1049,16 @@ def main():
             torch.cuda.empty_cache()
         watchdog.cancel()
     if rank == 0:
-        if world == 1 and not args.no_actor:
+        if world == 1 and args.full and not args.no_actor:
             out["env_configs4"] = env_config4_bench(dev, sad=False)
             out["env_configs4_sad"] = env_config4_bench(dev, sad=True)
-        if world == 1 and not args.no_learner:
+        if world == 1 and args.full and not args.no_learner:
             out["gemm_core"] = gemm_core_bench(dev)
             out["learner"] = learner_bench(dev)
-        if world == 1 and not args.no_actor:
+        if world == 1 and args.full and not args.no_actor:
             out["actor"] = actor_bench(dev)
             out["one_gpu_training"] = training_bench(dev, extra_args=tuple(os.environ.get("HSAD_BENCH_TRAINING_ARGS", "").split()))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         # what in this line is NOT measured by this run: the HBM-traffic and MFMA-busy counter figures are read from the committed rocprofv3
         # PMC passes (a PMC pass cannot run inside the driver's command); every time, rate and fraction is measured here

@@ -4,7 +4,9 @@ the replay / sequence writer -- hanabi_sad_amd/csrc/hsad_stream_fence.h, the hea
 thread and three training threads.  TSAN fails the run on any data race in the fence's tables; the model fails it when two operations of
 which one is a flush are not ordered on the (modelled) device; a plain build of the same harness must show that the pre-round-4 entry
 points (guard not held across the enqueue) DO produce such holes, i.e. that the harness can see what it is there for."""
+import functools
 import os
+import platform
 import shutil
 import subprocess
 
@@ -13,6 +15,18 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "tsan", "stream_fence_tsan.cc")
 INC = os.path.join(ROOT, "hanabi_sad_amd", "csrc")
+
+
+@functools.lru_cache(maxsize=None)
+def _no_aslr():
+    """prefix for a sanitised run.  TSan's x86-64 shadow layout needs the program and its libraries inside the ranges it keeps for the
+    application; a host that randomises mmap with more bits than those ranges allow (vm.mmap_rnd_bits = 32) stops the runtime at start-up
+    with `unexpected memory mapping`.  Address randomisation off for the sanitised process alone (setarch -R: the personality newer TSan
+    runtimes re-execute themselves with) keeps it inside; where that personality cannot be set the process runs as it is."""
+    cmd = ["setarch", platform.machine(), "-R"]
+    if shutil.which("setarch") and subprocess.run(cmd + ["true"], capture_output=True).returncode == 0:
+        return tuple(cmd)
+    return ()
 
 
 def _build(tmp_path, name, flags):
@@ -27,7 +41,7 @@ def _build(tmp_path, name, flags):
 def test_stream_fence_is_race_free_and_orders_flushes_under_tsan(tmp_path):
     exe = _build(tmp_path, "fence_tsan", ["-fsanitize=thread", "-DHSAD_TSAN_BUILD"])
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66 report_signal_unsafe=0")
-    out = subprocess.run([exe, "2500"], capture_output=True, text=True, timeout=300, env=env)
+    out = subprocess.run([*_no_aslr(), exe, "2500"], capture_output=True, text=True, timeout=300, env=env)
     assert "ThreadSanitizer" not in out.stderr and out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert " 0 ordering violations" in out.stdout and out.stdout.strip().endswith("OK")
 
@@ -61,7 +75,7 @@ def test_staging_slot_ring_never_refills_a_slot_of_a_queued_draw_under_tsan(tmp_
     lost operation."""
     exe = _build_ring(tmp_path, "ring_tsan", ["-fsanitize=thread"])
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66 report_signal_unsafe=0")
-    out = subprocess.run([exe, "3000"], capture_output=True, text=True, timeout=300, env=env)
+    out = subprocess.run([*_no_aslr(), exe, "3000"], capture_output=True, text=True, timeout=300, env=env)
     assert "ThreadSanitizer" not in out.stderr and out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert "12000 operations, 0 slot violations" in out.stdout and out.stdout.strip().endswith("OK")
 
@@ -75,7 +89,7 @@ def test_the_ring_harness_sees_the_null_stream_bug_of_round_5(tmp_path):
     assert out.returncode == 0 and out.stdout.strip().endswith("BUG SEEN"), out.stdout[-2000:]
     exe = _build_ring(tmp_path, "ring_bug_tsan", ["-DHSAD_SLOT_RING_BUG_NULL_STREAM", "-fsanitize=thread"])
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66 report_signal_unsafe=0")
-    out = subprocess.run([exe, "1000"], capture_output=True, text=True, timeout=300, env=env)
+    out = subprocess.run([*_no_aslr(), exe, "1000"], capture_output=True, text=True, timeout=300, env=env)
     assert "ThreadSanitizer: data race" in out.stderr, out.stderr[-2000:]
 
 
@@ -93,7 +107,7 @@ def test_actor_run_ahead_ring_bounds_the_host_under_tsan(tmp_path):
     out = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=thread", "-I", INC, AHEAD_SRC, "-o", exe, "-pthread"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66 report_signal_unsafe=0")
-    out = subprocess.run([exe, "2000"], capture_output=True, text=True, timeout=300, env=env)
+    out = subprocess.run([*_no_aslr(), exe, "2000"], capture_output=True, text=True, timeout=300, env=env)
     assert "ThreadSanitizer" not in out.stderr and out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert out.stdout.strip().endswith("OK") and ", 0 violations" in out.stdout
     exe = str(tmp_path / "ahead_bug")

@@ -17,16 +17,16 @@ for leg in ${LEGS:-env env5 env5_literal gemm learner actor}; do
 done
 python $R/tools/pmc_summarize.py $O/${RN}_pmc_hbm_traffic.json $SPEC > $O/pmc_summary.txt 2>&1
 cp $O/${RN}_pmc_hbm_traffic.json $R/profiles/${RN}_pmc_hbm_traffic.json
-cd $R && timeout 900 python bench.py > $O/${RN}_bench.json 2> $O/bench.err
+cd $R && timeout 900 python bench.py --full > $O/${RN}_bench.json 2> $O/bench.err
 # kernel stats of the timed env region alone (the learner / actor legs launch the same env kernels at other sizes) ...
 rm -rf /tmp/ps /tmp/ps2
-cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps -o r1 -- python $R/bench.py --no-cpu-baseline --no-learner --no-actor > $O/${RN}_bench_under_rocprof.json 2> $O/rocprof_stats.err
+cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps -o r1 -- python $R/bench.py --full --no-cpu-baseline --no-learner --no-actor > $O/${RN}_bench_under_rocprof.json 2> $O/rocprof_stats.err
 cp $(find /tmp/ps -name "*kernel_stats.csv" | head -1) $O/${RN}_bench_kernel_stats.csv
 # same lease, same command: the line's avg_launch_ms against rocprof's AverageNs (exit code 1 = more than 5 % apart)
 python $R/tools/bench_vs_rocprof.py $O/${RN}_bench.json $O/${RN}_bench_under_rocprof.json $O/${RN}_bench_kernel_stats.csv $O/${RN}_bench_vs_rocprof.json > $O/bench_vs_rocprof.txt 2>&1; echo "bench vs rocprof: rc $?"
 cp $O/${RN}_bench_vs_rocprof.json $R/profiles/ 2>/dev/null
 # ... and of the whole default command (env + learner + actor legs)
-cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps2 -o r2 -- python $R/bench.py --no-cpu-baseline > $O/${RN}_bench_full_under_rocprof.json 2> $O/rocprof_stats_full.err
+cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps2 -o r2 -- python $R/bench.py --full --no-cpu-baseline > $O/${RN}_bench_full_under_rocprof.json 2> $O/rocprof_stats_full.err
 cp $(find /tmp/ps2 -name "*kernel_stats.csv" | head -1) $O/${RN}_bench_full_kernel_stats.csv
 # one learner update, kernel by kernel (what the in-update figures of bench.py can be recomputed from without bench.py)
 rm -rf /tmp/pl

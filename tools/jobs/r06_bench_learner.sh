@@ -1,6 +1,6 @@
 set -u
 O=gpurun_out; mkdir -p $O
-timeout 900 python bench.py --no-cpu-baseline > $O/r06f_bench.json 2> $O/r06f_bench.err
+timeout 900 python bench.py --full --no-cpu-baseline > $O/r06f_bench.json 2> $O/r06f_bench.err
 python - <<'PY'
 import json
 b=json.loads(open("gpurun_out/r06f_bench.json").read().strip().splitlines()[-1])

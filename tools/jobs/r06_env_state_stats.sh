@@ -1,7 +1,7 @@
 # how often does a bench process run the env kernel in its fast state (3.3 ms per 50-iteration launch) / slow state (4.0 ms), and does a
 # burst of host load in front of the process matter?  alternating: plain, after 8 s of 64 busy host cores
 cd /tmp; R=$GRAFT_REPO_ROOT
-one() { python $R/bench.py --no-cpu-baseline --no-learner --no-actor 2>/dev/null | python -c "
+one() { python $R/bench.py --full --no-cpu-baseline --no-learner --no-actor 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -97,7 +97,9 @@ struct EnvParams {
   int pw64, ld16, obs_f32;
   float* reward;
   uint8_t* terminal;
-  unsigned long long* dbg;  // optional per-wave phase timestamps [grid][8] (hsad_env_debug_timing)
+  unsigned long long* dbg;  // optional wall_clock64 stamps of thread 0 at phase boundaries: [grid][8] (hsad_env_debug_timing), or per
+                            // iteration of a persistent launch [grid][dbg_iters][16] (hsad_env_debug_trace; slot map: env_stamp)
+  int dbg_iters;
   // phase lock of stream partitions (hsad_env_rollout_random with K > 1): partition p > 0 starts its launch `lock_ticks`
   // (10 ns units) after partition p-1 started the launch with the same tag, so that one partition's latency-bound logic
   // phase keeps overlapping the other's HBM stream.  Timing only: a bounded wait, results never depend on it.
@@ -369,9 +371,40 @@ __device__ __forceinline__ uint32_t hand_match_mask(uint32_t hw, bool by_color, 
 }
 
 #define ST(pl) s_st[(pl) * kWave + lane]
-#define STAMP(k)                                                                                        \
+// Stamp slots.  Legacy layout [grid][8] (dbg_iters = 0): slots 0-7 of the one record of the launch.  Trace layout
+// [grid][dbg_iters][16] (dbg_iters > 0): one record per iteration `it` of a persistent launch (iterations past dbg_iters share the last).
+//   env_body (single-phase):   0 iteration start, 1 planes staged in LDS (wave 0's first waited load + barrier), 2 logic done (barrier),
+//                              3 rows built, 4 planes written back (barrier), 5 rows streamed (thread 0), 6 / 7 reset: window loaded / dealt
+//   env_rollout_pipe_kernel:   0 iteration start, 1 wave 0's outstanding stores drained (s_waitcnt vmcnt(0), trace layout only),
+//                              11 wave 0's logic done, 2 end of phase A (barrier), 3 rows built, 4 end of phase B (barrier),
+//                              8 stream wave (thread 64): rows of `it - 1` streamed and cleared, 5 last record only: epilogue stream done,
+//                              6 / 7 as above
+//   both, trace layout:        9 HW_REG_HW_ID, 10 HW_REG_XCC_ID of the workgroup (written with slot 0)
+__device__ __forceinline__ void env_stamp(const EnvParams& ep, int it, int k, unsigned long long v) {
+  const size_t blk = (size_t)(ep.g_begin / ep.gpw) + blockIdx.x;
+  if (ep.dbg_iters > 0)
+    ep.dbg[(blk * ep.dbg_iters + (size_t)min(it, ep.dbg_iters - 1)) * 16 + k] = v;
+  else if (k < 8)
+    ep.dbg[((size_t)(ep.g_begin / kWave) + blockIdx.x) * 8 + k] = v;
+}
+#define STAMP_T(k, t)                                                                                   \
   do {                                                                                                  \
-    if (ep.dbg && threadIdx.x == 0) ep.dbg[((size_t)(ep.g_begin / kWave) + blockIdx.x) * 8 + (k)] = wall_clock64(); \
+    if (ep.dbg && threadIdx.x == (t)) env_stamp(ep, dbg_it, (k), wall_clock64());                      \
+  } while (0)
+#define STAMP(k) STAMP_T(k, 0)
+// slot 0 of an iteration, plus (trace layout) where the workgroup runs
+#define STAMP_START()                                                                                   \
+  do {                                                                                                  \
+    if (ep.dbg && threadIdx.x == 0) {                                                                   \
+      env_stamp(ep, dbg_it, 0, wall_clock64());                                                         \
+      if (ep.dbg_iters > 0) {                                                                           \
+        unsigned hw_id, xcc_id;                                                                         \
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));                            \
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));                          \
+        env_stamp(ep, dbg_it, 9, hw_id);                                                                \
+        env_stamp(ep, dbg_it, 10, xcc_id);                                                              \
+      }                                                                                                 \
+    }                                                                                                   \
   } while (0)
 #define PLH(p) (PL_FIXED + (p))
 #define PLKCP(p) (PL_FIXED + P + (p))
@@ -855,102 +888,39 @@ __device__ __forceinline__ int policy_pick(uint64_t seed, uint64_t game, uint64_
 constexpr int kEnvThreads = 4 * kWave;  // at most; EnvParams::nthreads (128 | 256) is what a launch uses.  wave 0: game logic; the
                                       // other waves: LDS zeroing; all: row building + streaming
 
+// The workgroup's ng games' rows, LDS -> HBM, by threads [t, t + n) of the workgroup: one contiguous, 16-byte aligned range
+// per output tensor (float32 observation, the packed forms when bound, legal moves, own hand)
+__device__ __forceinline__ void stream_rows(const EnvParams& ep, const uint32_t* s_obs, const uint32_t* s_legal, const uint32_t* s_own,
+                                            int g0, int ng, int P, int H, int t, int n) {
+  const size_t PF = (size_t)P * ep.F, PA = (size_t)P * ep.A, PO = (size_t)P * 3 * H;
+  if (!ep.obs_f32) {
+    // device consumers only: no float32 observation leaves the chip
+  } else if (ep.nt_stores) {
+    stream_bits_f32_aligned<true>(s_obs, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t, n);
+  } else {
+    stream_bits_f32_aligned<false>(s_obs, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t, n);
+  }
+  stream_rows_packed(ep, s_obs, 0, ng * P, (size_t)g0 * P, t, n);
+  stream_bits_f32_aligned<false>(s_legal, ep.legal + (size_t)g0 * PA, (uint32_t)(ng * PA), t, n);
+  stream_bits_f32_aligned<false>(s_own, ep.own + (size_t)g0 * PO, (uint32_t)(ng * PO), t, n);
+}
+
+// zero the obs / legal / own bit rows (contiguous in LDS from s_obs) by threads [t, t + n)
+__device__ __forceinline__ void clear_rows(const EnvParams& ep, uint32_t* s_obs, int t, int n) {
+  const int nz = ep.obs_words + ep.legal_words + ep.own_words;
+  uint4* z4 = reinterpret_cast<uint4*>(s_obs);
+  for (int k = t; k < (nz >> 2); k += n) z4[k] = make_uint4(0u, 0u, 0u, 0u);
+  for (int k = (nz & ~3) + t; k < nz; k += n) s_obs[k] = 0u;
+}
+
+// The game logic of one iteration for the 64 games of the logic wave (wave 0): reset-if-terminated (MODE 0 / 3), then the
+// policy (MODE 2 / 3) or the given actions (MODE 1) and the env step, all on the state planes staged in s_st.
 template <int MODE, int TP, int TH>
-__device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
-                                         const int g_bias = 0) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  uint32_t* s_st = smem;
-  uint32_t* s_obs = s_st + ep.npl * kWave;
-  uint32_t* s_legal = s_obs + ep.obs_words;
-  uint32_t* s_own = s_legal + ep.legal_words;
-  uint32_t* s_win = s_own + ep.own_words;  // reset kernel only: [win_words][kWave]
-  uint32_t* s_grec = s_win + (MODE == 0 || MODE == 3 ? ep.win_words * kWave : 0);  // [kWave] SAD greedy records
-  float* s_eps = reinterpret_cast<float*>(s_grec + kWave);  // [min(n_eps, 128)] copy of the eps list (reset only)
-
-  const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1);
-  const int wave = tid >> 6;
-  const int nthreads = ep.nthreads, nwaves = nthreads >> 6;
-  const int g0 = ep.g_begin + blockIdx.x * ep.gpw + g_bias;   // g_bias: always 0 (see env_rollout_kernel)
-  const int g = g0 + lane;
-  const bool valid = lane < ep.gpw && g < ep.G;
-  const int ng = min(ep.gpw, ep.G - g0);
-  if (ng <= 0) return;   // 32-game workgroups: the padded game count (a multiple of 64) may add a whole empty workgroup
+__device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
+                                          uint32_t* s_st, uint32_t* s_win, const float* s_eps, const int lane, const int g,
+                                          const bool active, const bool do_reset, Rng& rng, uint32_t& greedy_rec, float& reward,
+                                          bool& term, const int dbg_it = 0) {
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
-
-  if (MODE == 3 && ep.phase) {
-    if (blockIdx.x == 0 && tid == 0) {   // announce this launch (time first, then the tag that validates it)
-      __hip_atomic_store(ep.phase + 2 * ep.part + 1, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ep.phase + 2 * ep.part, ep.launch_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (ep.n_part > 1 && ep.lock_ticks > 0 && lane == 0) {
-      // ring order A(i), B(i), ..., A(i+1): wait for the predecessor's launch (same iteration, or the previous one for
-      // partition 0) to have STARTED lock_ticks ago.  If the predecessor is already further along, or silent for 200 us,
-      // just go: the lock is an optimisation, never a dependency.
-      const int pred = (ep.part + ep.n_part - 1) % ep.n_part;
-      const unsigned long long want = ep.part > 0 ? ep.launch_tag : ep.launch_tag - 1ull;
-      const unsigned long long t_in = wall_clock64();
-      while (want >= ep.first_tag && wall_clock64() - t_in < 20000ull) {
-        const unsigned long long tg = __hip_atomic_load(ep.phase + 2 * pred, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        if (tg > want) break;                        // predecessor already ahead: nothing to align with
-        if (tg == want) {
-          const unsigned long long ref = __hip_atomic_load(ep.phase + 2 * pred + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          while ((long long)(wall_clock64() - ref) < (long long)ep.lock_ticks && wall_clock64() - t_in < 20000ull)
-            __builtin_amdgcn_s_sleep(8);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(8);
-      }
-    }
-  }
-  STAMP(0);
-  const uint32_t misc0 = ep.planes[(size_t)PL_MISC * ep.Gpad + g];
-  bool active;
-  const bool needs_reset = valid && (!((misc0 >> 15) & 1u) || ((misc0 >> 14) & 1u));
-  if (MODE == 0) {
-    active = needs_reset;
-    if (__ballot(active) == 0ull) return;
-  } else {
-    active = valid;
-  }
-  const bool do_reset = (MODE == 0 || MODE == 3) && needs_reset;
-  // wave 0 stages all state planes in LDS (loads issued in batches of 8 so they overlap);
-  // wave 1 meanwhile clears the bit-row buffers
-  if (wave == 0) {
-    for (int pl0 = 0; pl0 < ep.npl; pl0 += 8) {
-      uint32_t v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = ep.planes[(size_t)min(pl0 + j, ep.npl - 1) * ep.Gpad + g];
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (pl0 + j < ep.npl) ST(pl0 + j) = v[j];
-    }
-  } else {
-    const int nz = ep.obs_words + ep.legal_words + ep.own_words;
-    const int zt = tid - kWave, zn = nthreads - kWave;            // the clearing waves' thread index / count
-    uint4* z4 = reinterpret_cast<uint4*>(s_obs);
-    for (int k = zt; k < (nz >> 2); k += zn) z4[k] = make_uint4(0u, 0u, 0u, 0u);
-    for (int k = (nz & ~3) + zt; k < nz; k += zn) s_obs[k] = 0u;
-    if (MODE == 0 || MODE == 3)
-      for (int k = zt; k < min(ep.n_eps, 128); k += zn) s_eps[k] = ep.eps_list[k];
-  }
-  __syncthreads();
-  STAMP(1);
-
-  Rng rng;
-  rng.mt = ep.mt + (size_t)g * kMtN;
-  rng.draws = ST(PL_DRAWS);
-  rng.la0 = ST(PL_LA0);
-  rng.la1 = ST(PL_LA1);
-  rng.la_n = (int)((ST(PL_MISC) >> 22) & 3u);
-  rng.spos = (rng.draws + (uint32_t)rng.la_n) % (uint32_t)kMtN;
-  rng.win = nullptr;
-  rng.w_c = rng.w_n = 0;
-  uint32_t greedy_rec = 0;
-  float reward = 0.f;
-  bool term = false;
-
-  if (wave == 0) {
   if (MODE == 0 || MODE == 3) {
     // ---- prefetch window: every mt19937 word this reset will regenerate, in one round trip ----
     const int W = ep.win_w;
@@ -1204,6 +1174,102 @@ __device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __r
       }
     }
   }
+}
+
+template <int MODE, int TP, int TH>
+__device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
+                                         const int g_bias = 0, const int dbg_it = 0) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  uint32_t* s_st = smem;
+  uint32_t* s_obs = s_st + ep.npl * kWave;
+  uint32_t* s_legal = s_obs + ep.obs_words;
+  uint32_t* s_own = s_legal + ep.legal_words;
+  uint32_t* s_win = s_own + ep.own_words;  // reset kernel only: [win_words][kWave]
+  uint32_t* s_grec = s_win + (MODE == 0 || MODE == 3 ? ep.win_words * kWave : 0);  // [kWave] SAD greedy records
+  float* s_eps = reinterpret_cast<float*>(s_grec + kWave);  // [min(n_eps, 128)] copy of the eps list (reset only)
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wave = tid >> 6;
+  const int nthreads = ep.nthreads, nwaves = nthreads >> 6;
+  const int g0 = ep.g_begin + blockIdx.x * ep.gpw + g_bias;   // g_bias: always 0 (see env_rollout_kernel)
+  const int g = g0 + lane;
+  const bool valid = lane < ep.gpw && g < ep.G;
+  const int ng = min(ep.gpw, ep.G - g0);
+  if (ng <= 0) return;   // 32-game workgroups: the padded game count (a multiple of 64) may add a whole empty workgroup
+  const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
+
+  if (MODE == 3 && ep.phase) {
+    if (blockIdx.x == 0 && tid == 0) {   // announce this launch (time first, then the tag that validates it)
+      __hip_atomic_store(ep.phase + 2 * ep.part + 1, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ep.phase + 2 * ep.part, ep.launch_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (ep.n_part > 1 && ep.lock_ticks > 0 && lane == 0) {
+      // ring order A(i), B(i), ..., A(i+1): wait for the predecessor's launch (same iteration, or the previous one for
+      // partition 0) to have STARTED lock_ticks ago.  If the predecessor is already further along, or silent for 200 us,
+      // just go: the lock is an optimisation, never a dependency.
+      const int pred = (ep.part + ep.n_part - 1) % ep.n_part;
+      const unsigned long long want = ep.part > 0 ? ep.launch_tag : ep.launch_tag - 1ull;
+      const unsigned long long t_in = wall_clock64();
+      while (want >= ep.first_tag && wall_clock64() - t_in < 20000ull) {
+        const unsigned long long tg = __hip_atomic_load(ep.phase + 2 * pred, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        if (tg > want) break;                        // predecessor already ahead: nothing to align with
+        if (tg == want) {
+          const unsigned long long ref = __hip_atomic_load(ep.phase + 2 * pred + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          while ((long long)(wall_clock64() - ref) < (long long)ep.lock_ticks && wall_clock64() - t_in < 20000ull)
+            __builtin_amdgcn_s_sleep(8);
+          break;
+        }
+        __builtin_amdgcn_s_sleep(8);
+      }
+    }
+  }
+  STAMP_START();
+  const uint32_t misc0 = ep.planes[(size_t)PL_MISC * ep.Gpad + g];
+  bool active;
+  const bool needs_reset = valid && (!((misc0 >> 15) & 1u) || ((misc0 >> 14) & 1u));
+  if (MODE == 0) {
+    active = needs_reset;
+    if (__ballot(active) == 0ull) return;
+  } else {
+    active = valid;
+  }
+  const bool do_reset = (MODE == 0 || MODE == 3) && needs_reset;
+  // wave 0 stages all state planes in LDS (loads issued in batches of 8 so they overlap);
+  // wave 1 meanwhile clears the bit-row buffers
+  if (wave == 0) {
+    for (int pl0 = 0; pl0 < ep.npl; pl0 += 8) {
+      uint32_t v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = ep.planes[(size_t)min(pl0 + j, ep.npl - 1) * ep.Gpad + g];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (pl0 + j < ep.npl) ST(pl0 + j) = v[j];
+    }
+  } else {
+    const int zt = tid - kWave, zn = nthreads - kWave;            // the clearing waves' thread index / count
+    clear_rows(ep, s_obs, zt, zn);
+    if (MODE == 0 || MODE == 3)
+      for (int k = zt; k < min(ep.n_eps, 128); k += zn) s_eps[k] = ep.eps_list[k];
+  }
+  __syncthreads();
+  STAMP(1);
+
+  Rng rng;
+  rng.mt = ep.mt + (size_t)g * kMtN;
+  rng.draws = ST(PL_DRAWS);
+  rng.la0 = ST(PL_LA0);
+  rng.la1 = ST(PL_LA1);
+  rng.la_n = (int)((ST(PL_MISC) >> 22) & 3u);
+  rng.spos = (rng.draws + (uint32_t)rng.la_n) % (uint32_t)kMtN;
+  rng.win = nullptr;
+  rng.w_c = rng.w_n = 0;
+  uint32_t greedy_rec = 0;
+  float reward = 0.f;
+  bool term = false;
+
+  if (wave == 0) {
+    env_logic<MODE, TP, TH>(ep, a_in, g_in, s_st, s_win, s_eps, lane, g, active, do_reset, rng, greedy_rec, reward, term, dbg_it);
     s_grec[lane] = greedy_rec;
   }
   __syncthreads();
@@ -1229,17 +1295,7 @@ __device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __r
 
   const size_t PF = (size_t)P * ep.F, PA = (size_t)P * ep.A, PO = (size_t)P * 3 * H;
   if (MODE >= 1) {
-    // all ng games of the wave: one contiguous, 16-byte aligned range per output tensor
-    if (!ep.obs_f32) {
-      // device consumers only: no float32 observation leaves the chip
-    } else if (ep.nt_stores) {
-      stream_bits_f32_aligned<true>(s_obs, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), tid, nthreads);
-    } else {
-      stream_bits_f32_aligned<false>(s_obs, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), tid, nthreads);
-    }
-    stream_rows_packed(ep, s_obs, 0, ng * P, (size_t)g0 * P, tid, nthreads);
-    stream_bits_f32_aligned<false>(s_legal, ep.legal + (size_t)g0 * PA, (uint32_t)(ng * PA), tid, nthreads);
-    stream_bits_f32_aligned<false>(s_own, ep.own + (size_t)g0 * PO, (uint32_t)(ng * PO), tid, nthreads);
+    stream_rows(ep, s_obs, s_legal, s_own, g0, ng, P, H, tid, nthreads);
     if (valid && wave == 0) {
       for (int p = 0; p < P; ++p) ep.eps[(size_t)g * P + p] = __uint_as_float(ST(PLEPS(p)));
       ep.reward[g] = reward;
@@ -1283,8 +1339,7 @@ __global__ __launch_bounds__(kEnvThreads) void env_kernel(EnvParams ep, const in
 // sees a steady write stream -- what the phase-locked partitions approximate with three launches per iteration.
 // g_bias is an opaque zero: with a loop-invariant game index the compiler hoists every per-lane address of the body out of
 // the loop and ends up at 258 VGPRs (95 without the loop), i.e. one wave per SIMD instead of five.
-template <int TP, int TH>
-__global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void env_rollout_kernel(EnvParams ep) {
+__device__ __forceinline__ void rollout_stagger(const EnvParams& ep) {
   if (ep.stagger_ticks > 0) {
     // which workgroups start late: (mode 0, rounds 1-5) by XCD = block id mod 8; (1) by block-id group of 32 inside the XCD -- the workgroups
     // that share a CU when the dispatcher walks the XCD's CUs breadth first; (2) by block id inside the XCD mod 4 -- the same when it fills a
@@ -1300,13 +1355,125 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     const unsigned long long t_in = wall_clock64(), wait = (unsigned long long)k * (unsigned long long)ep.stagger_ticks;
     while (wall_clock64() - t_in < wait) __builtin_amdgcn_s_sleep(16);
   }
+}
+
+template <int TP, int TH>
+__global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void env_rollout_kernel(EnvParams ep) {
+  rollout_stagger(ep);
 #pragma clang loop unroll(disable)
   for (int iter = 0; iter < ep.n_iter; ++iter) {
     if (iter) __syncthreads();   // the previous iteration's rows have left LDS before they are cleared again
     int zero = 0;
     asm volatile("" : "+s"(zero));
-    env_body<3, TP, TH>(ep, nullptr, nullptr, zero);
+    env_body<3, TP, TH>(ep, nullptr, nullptr, zero, iter);
   }
+}
+
+// Wave-specialised, software-pipelined persistent rollout (128-thread workgroups, knowledge_mode 0).  Wave 0, the logic
+// wave, runs the game logic of iteration k while wave 1, the stream wave, streams the rows of iteration k - 1 out of LDS and clears
+// them (phase A); then both waves build the rows of k (phase B).  The logic wave issues no observation stores, so its waited loads
+// (act counters, legal masks, mt19937 words) never queue behind a stream of kilobyte stores (vmcnt counts stores too); the stream
+// wave issues no global loads.  HBM is written during the logic phase of every workgroup instead of only when the workgroups of a
+// CU happen to be out of phase.  The state planes stay in LDS for the whole launch (loaded once, written back after the last
+// iteration: nothing else reads them while the launch runs).  Same arithmetic, draw order and values as env_rollout_kernel: only
+// which wave writes the rows, and when, differs.
+template <int TP, int TH>
+__global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void env_rollout_pipe_kernel(EnvParams ep) {
+  rollout_stagger(ep);
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  uint32_t* s_st = smem;
+  uint32_t* s_obs = s_st + ep.npl * kWave;
+  uint32_t* s_legal = s_obs + ep.obs_words;
+  uint32_t* s_own = s_legal + ep.legal_words;
+  uint32_t* s_win = s_own + ep.own_words;
+  uint32_t* s_grec = s_win + ep.win_words * kWave;
+  float* s_eps = reinterpret_cast<float*>(s_grec + kWave);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wave = tid >> 6;
+  const int g0 = ep.g_begin + blockIdx.x * ep.gpw;
+  const int ng = min(ep.gpw, ep.G - g0);
+  if (ng <= 0) return;
+  const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
+
+  // prologue: the logic wave stages the state planes, the stream wave clears the rows and copies the eps list
+  if (wave == 0) {
+    const int g = g0 + lane;
+    for (int pl0 = 0; pl0 < ep.npl; pl0 += 8) {
+      uint32_t v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = ep.planes[(size_t)min(pl0 + j, ep.npl - 1) * ep.Gpad + g];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (pl0 + j < ep.npl) ST(pl0 + j) = v[j];
+    }
+  } else {
+    clear_rows(ep, s_obs, lane, kWave);
+    for (int k = lane; k < min(ep.n_eps, 128); k += kWave) s_eps[k] = ep.eps_list[k];
+  }
+  __syncthreads();
+
+#pragma clang loop unroll(disable)
+  for (int iter = 0; iter < ep.n_iter; ++iter) {
+    int zero = 0;
+    asm volatile("" : "+s"(zero));   // opaque zero: keeps the per-lane addresses inside the loop (see env_rollout_kernel)
+    const int g = g0 + zero + lane;
+    const bool valid = lane < ep.gpw && g < ep.G;
+    const int dbg_it = iter;
+    STAMP_START();
+    // ---- phase A: logic of iteration `iter` (wave 0) | rows of iteration `iter - 1` to HBM, then cleared (wave 1) ----
+    Rng rng = {};
+    float reward = 0.f;
+    bool term = false;
+    if (wave == 0) {
+      if (ep.dbg && ep.dbg_iters > 0) {   // trace only: how long the previous iteration's stores keep wave 0's first load waiting
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        STAMP(1);
+      }
+      const uint32_t misc0 = ST(PL_MISC);
+      const bool do_reset = valid && (!((misc0 >> 15) & 1u) || ((misc0 >> 14) & 1u));
+      rng.mt = ep.mt + (size_t)g * kMtN;
+      rng.draws = ST(PL_DRAWS);
+      rng.la0 = ST(PL_LA0);
+      rng.la1 = ST(PL_LA1);
+      rng.la_n = (int)((misc0 >> 22) & 3u);
+      rng.spos = (rng.draws + (uint32_t)rng.la_n) % (uint32_t)kMtN;
+      uint32_t greedy_rec = 0;
+      env_logic<3, TP, TH>(ep, nullptr, nullptr, s_st, s_win, s_eps, lane, g, valid, do_reset, rng, greedy_rec, reward, term, dbg_it);
+      s_grec[lane] = greedy_rec;
+      STAMP(11);
+    } else if (iter > 0) {
+      stream_rows(ep, s_obs, s_legal, s_own, g0, ng, P, H, lane, kWave);
+      clear_rows(ep, s_obs, lane, kWave);
+      STAMP_T(8, kWave);
+    }
+    __syncthreads();
+    STAMP(2);
+    // ---- phase B: both waves build the rows of `iter`; wave 0 finishes the look-ahead refill and writes the scalars ----
+    Refill rf;
+    refill_issue(rf, rng, valid && wave == 0);
+    if (valid) build_rows<TP, TH>(ep, s_st, lane, g, s_obs, s_legal, s_own, s_grec[lane], wave, 2);
+    STAMP(3);
+    if (valid && wave == 0) {
+      refill_finish(rf, rng);
+      ST(PL_DRAWS) = rng.draws;
+      ST(PL_LA0) = rng.la0;
+      ST(PL_LA1) = rng.la1;
+      ST(PL_MISC) = (ST(PL_MISC) & ~(3u << 22)) | ((uint32_t)rng.la_n << 22);
+      for (int p = 0; p < P; ++p) ep.eps[(size_t)g * P + p] = __uint_as_float(ST(PLEPS(p)));
+      ep.reward[g] = reward;
+      ep.terminal[g] = term ? 1 : 0;
+      if (iter == ep.n_iter - 1)
+        for (int pl = 0; pl < ep.npl; ++pl) ep.planes[(size_t)pl * ep.Gpad + g] = ST(pl);
+    }
+    __syncthreads();   // rows complete before wave 1 streams them; wave 1 done reading s_st before wave 0 changes it
+    STAMP(4);
+  }
+  // epilogue: both waves stream the last iteration's rows
+  stream_rows(ep, s_obs, s_legal, s_own, g0, ng, P, H, tid, ep.nthreads);
+  const int dbg_it = ep.n_iter - 1;
+  STAMP(5);
 }
 
 // ---- init: zero planes, seed mt19937 (std::mt19937::seed: x0 = s; x_i = 1812433253*(x ^ x>>30) + i) ---
@@ -1499,6 +1666,8 @@ struct hsad_env {
   int n_part;         // streams created so far
   int n_part_active;  // partitions used by hsad_env_rollout_random (1 = caller's stream only)
   int rollout_chunk;  // > 0: hsad_env_rollout_random runs persistent launches of this many iterations (hsad_env_set_rollout_chunk)
+  int rollout_pipe;   // persistent launches use the pipelined schedule where it applies (developer switch HSAD_ENV_PIPE=0: the
+                      // single-phase schedule of env_rollout_kernel everywhere, for A/B)
   hipStream_t part_stream[16];
   hipEvent_t part_done[16];
   hipEvent_t part_begin[16];   // timing-enabled pair with part_done: per-partition chain time of the last rollout
@@ -1535,17 +1704,25 @@ EnvKernelFn pick_env_kernel(int mode, int P, int H) {
 }
 
 typedef void (*EnvRolloutFn)(EnvParams);
-EnvRolloutFn pick_rollout_kernel(int P, int H) {
-  if (P == 2 && H == 5) return env_rollout_kernel<2, 5>;
-  if (P == 5 && H == 4) return env_rollout_kernel<5, 4>;
-  if (P == 3 && H == 5) return env_rollout_kernel<3, 5>;
-  if (P == 4 && H == 4) return env_rollout_kernel<4, 4>;
-  return env_rollout_kernel<0, 0>;
+// the pipelined schedule (env_rollout_pipe_kernel) needs exactly one stream wave and no V0-belief fix-up of the streamed rows;
+// 256-thread workgroups (few games per GPU) and knowledge_mode 1 run env_rollout_kernel
+bool rollout_pipelined(const hsad_env* e) { return e->rollout_pipe && e->ep.nthreads == 2 * kWave && e->ep.kmode == 0; }
+
+EnvRolloutFn pick_rollout_kernel(int P, int H, bool pipe) {
+#define HSAD_ROLLOUT_SPECIALISE(PP, HH) \
+  if (P == PP && H == HH) return pipe ? env_rollout_pipe_kernel<PP, HH> : env_rollout_kernel<PP, HH>;
+  HSAD_ROLLOUT_SPECIALISE(2, 5)
+  HSAD_ROLLOUT_SPECIALISE(5, 4)
+  HSAD_ROLLOUT_SPECIALISE(3, 5)
+  HSAD_ROLLOUT_SPECIALISE(4, 4)
+#undef HSAD_ROLLOUT_SPECIALISE
+  return pipe ? env_rollout_pipe_kernel<0, 0> : env_rollout_kernel<0, 0>;
 }
 
 int configure_env_kernels(hsad_env* e) {
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_rollout_kernel(e->ep.P, e->ep.H)),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes_reset));
+  for (const bool pipe : {false, true})
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_rollout_kernel(e->ep.P, e->ep.H, pipe)),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes_reset));
   for (int mode = 0; mode < 4; ++mode) {
     const size_t lds = (mode == 1 || mode == 2) ? e->lds_bytes : e->lds_bytes_reset;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_env_kernel(mode, e->ep.P, e->ep.H)),
@@ -1576,7 +1753,7 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
   ep.a_out = a_out;
   ep.g_out = g_out;
   if (mode == 3 && n_iter > 1)
-    hipLaunchKernelGGL(pick_rollout_kernel(ep.P, ep.H), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds, stream, ep);
+    hipLaunchKernelGGL(pick_rollout_kernel(ep.P, ep.H, rollout_pipelined(e)), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds, stream, ep);
   else
     hipLaunchKernelGGL(pick_env_kernel(mode, ep.P, ep.H), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds,
                        stream, ep, a, g);
@@ -1676,6 +1853,7 @@ int hsad_env_create(const hsad_env_config* cfg, hsad_env** out) {
   e->last_rollout_parts = 0;
   e->n_part_active = 1;
   e->rollout_chunk = 0;
+  e->rollout_pipe = getenv("HSAD_ENV_PIPE") ? atoi(getenv("HSAD_ENV_PIPE")) != 0 : 1;
   e->fork = nullptr;
   if (e->lds_bytes_reset > 160 * 1024) {
     const size_t need = e->lds_bytes_reset;
@@ -1953,8 +2131,18 @@ int hsad_env_export_state(hsad_env* e, int32_t* out, void* stream) {
 int hsad_env_debug_timing(hsad_env* e, uint64_t* buf) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");
   e->ep.dbg = reinterpret_cast<unsigned long long*>(buf);
+  e->ep.dbg_iters = 0;
   return HSAD_OK;
 }
+
+int hsad_env_debug_trace(hsad_env* e, uint64_t* buf, int n_iters) {
+  if (!e || (buf && n_iters < 1)) return set_error(HSAD_ERR_INVALID, "bad argument");
+  e->ep.dbg = reinterpret_cast<unsigned long long*>(buf);
+  e->ep.dbg_iters = buf ? n_iters : 0;
+  return HSAD_OK;
+}
+
+int64_t hsad_env_rollout_lds_bytes(const hsad_env* e) { return e ? (int64_t)e->lds_bytes_reset : 0; }
 
 int hsad_env_error_count(hsad_env* e, int32_t* count, int32_t* first_game, int32_t* first_code) {
   if (!e || !count) return set_error(HSAD_ERR_INVALID, "null argument");

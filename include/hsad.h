@@ -169,6 +169,12 @@ int hsad_env_export_state(hsad_env* env, int32_t* out, void* stream);
 /* Developer aid: when buf != NULL (device uint64 [ceil(G/64), 8]) the reset/step kernels store
  * s_memtime stamps at their phase boundaries (load, logic, build rows, write-back, stream). */
 int hsad_env_debug_timing(hsad_env* env, uint64_t* buf);
+/* Developer aid: per-iteration trace of a persistent rollout.  buf (device uint64 [Gpad / games_per_workgroup, n_iters, 16]) receives
+ * wall_clock64 stamps (100 MHz) of every iteration plus each workgroup's HW_ID / XCC_ID; slot map in csrc/hsad_env.hip (env_stamp).
+ * buf == NULL switches the trace (and hsad_env_debug_timing) off. */
+int hsad_env_debug_trace(hsad_env* env, uint64_t* buf, int n_iters);
+/* Dynamic LDS bytes per workgroup of the reset / rollout kernels (what a persistent rollout launch requests). */
+int64_t hsad_env_rollout_lds_bytes(const hsad_env* env);
 
 /* Number of games that hit an API-contract error (illegal move, step on a finished game) since
  * the last call; synchronises the device.  first_game/first_code (may be NULL) describe the first. */

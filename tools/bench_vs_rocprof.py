@@ -14,7 +14,7 @@ bench, under, stats_csv, out_path = sys.argv[1:5]
 b, u = last_json(bench), last_json(under)
 avg_ns = calls = None
 for row in csv.DictReader(open(stats_csv)):
-    if "env_rollout_kernel" in row.get("Name", ""):
+    if "env_rollout_kernel" in row.get("Name", "") or "env_rollout_pipe_kernel" in row.get("Name", ""):   # single-phase / pipelined schedule
         avg_ns, calls = float(row["AverageNs"]), int(row["Calls"])
         break
 r = b["roofline"]

@@ -1,0 +1,109 @@
+"""Per-iteration trace of one persistent rollout launch at configs[1] (65,536 two-player games): where each workgroup's time goes,
+and how many workgroups stream observations on each CU and on the chip over time.
+
+  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--json OUT]
+
+The driver's shape is --warmup 5 --iters 20 (one 5-iteration launch, then the traced 20-iteration launch).  --schedule single runs
+env_rollout_kernel (HSAD_ENV_PIPE=0), pipe the default env_rollout_pipe_kernel.  Stamps are wall_clock64 (100 MHz, 10 ns) of
+hsad_env_debug_trace; slot map in csrc/hsad_env.hip (env_stamp).  Streaming intervals: single-phase = [write-back done, rows streamed]
+of each iteration; pipelined = [iteration start, stream wave done] of iterations 1.. (the rows of the previous one) plus the epilogue."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TICK_US = 0.01
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--schedule", choices=("pipe", "single"), default="pipe")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    os.environ["HSAD_ENV_PIPE"] = "1" if args.schedule == "pipe" else "0"
+    import torch
+    from hanabi_sad_amd import BatchedHanabiEnv, _lib
+    G = 65536
+    eps = [0.1 ** (1 + 7 * i / 79) for i in range(80)]
+    env = BatchedHanabiEnv(G, seed=1, eps_list=eps, device="cuda:0", track_deck_history=False)
+    env.set_rollout_chunk(max(50, args.iters))
+    assert env.threads_per_workgroup == 128
+    nwg = (G + env.games_per_workgroup - 1) // env.games_per_workgroup
+    env.rollout_random(args.warmup, 12345)
+    buf = torch.zeros(nwg * args.iters * 16, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    _lib.check(env.lib.hsad_env_debug_trace(env.h, buf.data_ptr(), args.iters))
+    env.rollout_random(args.iters, 12345)
+    torch.cuda.synchronize()
+    _lib.check(env.lib.hsad_env_debug_trace(env.h, None, 0))
+    env.check_errors()
+    s = buf.view(nwg, args.iters, 16).cpu().numpy().astype(np.int64)
+    rec = analyse(s, args.schedule == "pipe", args)
+    print(json.dumps(rec, indent=1))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
+def analyse(s, pipe, args):
+    nwg, n, _ = s.shape
+    t0 = s[:, 0, 0].min()
+    t = (s[:, :, :9] - t0).astype(np.float64) * TICK_US            # µs since the first workgroup started
+    t = np.concatenate([t, (s[:, :, 11:12] - t0) * TICK_US], axis=2)  # slot 11 -> column 9
+    hw, xcc = s[:, 0, 9], s[:, 0, 10]
+    cu = ((xcc & 0xF) << 8) | (((hw >> 13) & 7) << 5) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xF)   # XCC, SE, SH, CU
+    rec = {"schedule": "env_rollout_pipe_kernel<2,5>" if pipe else "env_rollout_kernel<2,5>", "iters": n, "warmup": args.warmup,
+           "workgroups": nwg, "cus_seen": int(len(np.unique(cu)))}
+    it_len = np.diff(t[:, :, 0], axis=1)                            # start(k+1) - start(k)
+    med = lambda a: float(np.median(a))
+    if pipe:
+        # phase A: [0,1] drain, [1,11] logic, [11,2] wait for the stream wave; phase B: [2,3] build, [3,4] refill + scalars + barrier
+        ph = {"drain_us": t[:, :, 1] - t[:, :, 0], "logic_us": t[:, :, 9] - t[:, :, 1], "wait_for_stream_wave_us": t[:, :, 2] - t[:, :, 9],
+              "build_us": t[:, :, 3] - t[:, :, 2], "phase_b_rest_us": t[:, :, 4] - t[:, :, 3]}
+        ph["stream_wave_stream_clear_us"] = (t[:, 1:, 8] - t[:, 1:, 0])
+        streams = [(t[:, k, 0], t[:, k, 8]) for k in range(1, n)] + [(t[:, n - 1, 4], t[:, n - 1, 5])]
+        end = t[:, n - 1, 5]
+    else:
+        ph = {"load_planes_incl_drain_us": t[:, :, 1] - t[:, :, 0], "logic_us": t[:, :, 2] - t[:, :, 1], "build_us": t[:, :, 3] - t[:, :, 2],
+              "write_back_us": t[:, :, 4] - t[:, :, 3], "stream_us": t[:, :, 5] - t[:, :, 4]}
+        streams = [(t[:, k, 4], t[:, k, 5]) for k in range(n)]
+        end = t[:, n - 1, 5]
+    rec["median_per_workgroup_iteration"] = {k: round(med(np.median(v[:, 1:] if v.shape[1] > 1 else v, axis=1)), 2) for k, v in ph.items()}
+    rec["iteration_us_median"] = round(med(it_len), 2) if n > 1 else None
+    rec["launch_us"] = round(float(end.max()), 1)
+    rec["start_spread_us"] = round(float(t[:, 0, 0].max() - t[:, 0, 0].min()), 2)
+    rec["end_spread_us"] = round(float(end.max() - end.min()), 2)
+    # streaming workgroups over time, 0.5 µs bins, chip-wide and per CU
+    T = float(end.max())
+    nb = int(T / 0.5) + 1
+    chip = np.zeros(nb)
+    per_cu = {}
+    for a, b in streams:
+        for w in range(nwg):
+            i0, i1 = int(a[w] / 0.5), int(b[w] / 0.5)
+            chip[i0:i1 + 1] += 1
+            per_cu.setdefault(int(cu[w]), np.zeros(nb))[i0:i1 + 1] += 1
+    steady = slice(int(t[:, 0, 0].max() / 0.5) + 1, int(end.min() / 0.5))   # every workgroup started, none finished
+    share = np.zeros(4)
+    for c, v in per_cu.items():
+        vv = np.minimum(v[steady], 3).astype(int)
+        share += np.bincount(vv, minlength=4)[:4]
+    share /= max(share.sum(), 1)
+    rec["per_cu_share_of_steady_time_with_0_1_2_3plus_streaming"] = [round(float(x), 3) for x in share]
+    cs = chip[steady]
+    rec["chip_streaming_workgroups_steady"] = {"mean": round(float(cs.mean()), 1), "p5": float(np.percentile(cs, 5)),
+                                               "p50": float(np.percentile(cs, 50)), "p95": float(np.percentile(cs, 95))}
+    step = max(1, nb // 40)
+    rec["chip_streaming_workgroups_series"] = {"bin_us": 0.5 * step, "values": [int(chip[i:i + step].mean()) for i in range(0, nb, step)]}
+    return rec
+
+
+if __name__ == "__main__":
+    main()

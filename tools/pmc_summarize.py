@@ -71,13 +71,15 @@ def mean(v):
 KERNELS = {   # leg -> [(label, name regex, algorithmic bytes per launch or None, note)]
     "env": [("env_rollout_kernel<2,5> persistent fused reset+policy+step+observe, G=65536, 50 iterations per launch",
              r"env_rollout_kernel<2, 5>", ALGO_ENV * 50, "iterations_per_launch=50"),
+            ("env_rollout_pipe_kernel<2,5> persistent fused reset+policy+step+observe, logic and stream waves pipelined (the default since "
+             "round 7), G=65536, 50 iterations per launch", r"env_rollout_pipe_kernel<2, 5>", ALGO_ENV * 50, "iterations_per_launch=50"),
             ("env_kernel<3,2,5> fused reset+policy+step+observe (rollout), G=65536 in 3 partition launches", r"env_kernel<3, 2, 5>", ALGO_ENV / 3, ""),
             ("env_kernel<1,2,5> step+observe, G=65536", r"env_kernel<1, 2, 5>", ALGO_ENV, ""),
             ("env_kernel<0,2,5> reset-terminated, G=65536", r"env_kernel<0, 2, 5>", None, "")],
     "env5": [("env_rollout_kernel<5,4> persistent fused rollout, configs[4] per GPU: G=16384 5-player hand-4 SAD + colour shuffle, 50 iterations per launch",
-              r"env_rollout_kernel<5, 4>", ALGO_ENV5 * 50, "iterations_per_launch=50")],
+              r"env_rollout(_pipe)?_kernel<5, 4>", ALGO_ENV5 * 50, "iterations_per_launch=50")],
     "env5_literal": [("env_rollout_kernel<5,4> persistent fused rollout, configs[4] literally: G=16384 5-player hand-4 colour shuffle, no SAD, "
-                      "50 iterations per launch", r"env_rollout_kernel<5, 4>", ALGO_ENV5_LITERAL * 50, "iterations_per_launch=50")],
+                      "50 iterations per launch", r"env_rollout(_pipe)?_kernel<5, 4>", ALGO_ENV5_LITERAL * 50, "iterations_per_launch=50")],
     "gemm": [("gemm8_kernel<G8_F32> (the 256 x 256 core) LSTM input projection 10240x2048x512, fp32 output", r"gemm8_kernel<1", GEMM_ALGO, ""),
              ("gemm_nt_bf16_kernel<128,128> LSTM input projection 10240x2048x512, fp32 output", r"gemm_nt_bf16_kernel<128, 128>", GEMM_ALGO, "")],
     "learner": [("learner update: lstm_fused_fwd_kernel<16> (2 nets x 2 layers x 80 steps per launch)", r"lstm_fused_fwd_kernel<16>", FUSED_FWD_ALGO, ""),

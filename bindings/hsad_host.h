@@ -84,10 +84,12 @@ struct DevBuf {      // device memory this host owns (zero-filled)
 struct EnvCfg {
   int players = 2, hand = 5, seed = 1, bomb = 0, max_len = 80;
   bool sad = false, shuffle_obs = false, shuffle_color = false;
+  hsad_env_rules rules{5, 5, 8, 3};   // HLE colors / ranks / max_information_tokens / max_life_tokens
   std::vector<float> eps;
   bool same_but_seed(const EnvCfg& o) const {
     return players == o.players && hand == o.hand && bomb == o.bomb && max_len == o.max_len && sad == o.sad && shuffle_obs == o.shuffle_obs &&
-           shuffle_color == o.shuffle_color && eps == o.eps;
+           shuffle_color == o.shuffle_color && eps == o.eps && rules.colors == o.rules.colors && rules.ranks == o.rules.ranks &&
+           rules.max_information_tokens == o.rules.max_information_tokens && rules.max_life_tokens == o.rules.max_life_tokens;
   }
 };
 
@@ -114,7 +116,7 @@ struct BatchedEnv {
     k.eps_list = c.eps.data();
     k.device = dev;
     k.track_deck_history = deck_history;
-    ck(hsad_env_create(&k, &h));
+    ck(hsad_env_create_rules(&k, &c.rules, &h));
     P = hsad_env_num_players(h);
     F = hsad_env_feature_size(h);
     A = hsad_env_num_action(h);
@@ -171,6 +173,26 @@ class HanabiEnv {
     cfg.hand = get("hand_size", 5);
     cfg.seed = get("seed", 1);
     cfg.bomb = get("bomb", 0);
+    // HLE's game keys: the rules are honoured within their bounds, the rest refused unless at HLE's default (hanalearn.game_rules)
+    auto rule = [&](const char* k, int dflt, int lo, int hi) {
+      const int v = get(k, dflt);
+      if (v < lo || v > hi)
+        throw std::invalid_argument(std::string("HanabiEnv: ") + k + " must be " + std::to_string(lo) + ".." + std::to_string(hi) +
+                                    " (got " + std::to_string(v) + ")");
+      return v;
+    };
+    cfg.rules.colors = rule("colors", 5, 1, 5);
+    cfg.rules.ranks = rule("ranks", 5, 1, 5);
+    cfg.rules.max_information_tokens = rule("max_information_tokens", 8, 1, 8);
+    cfg.rules.max_life_tokens = rule("max_life_tokens", 3, 1, 3);
+    if (get("observation_type", 1) != 1)
+      throw std::invalid_argument("HanabiEnv: observation_type " + params.at("observation_type") + " is not supported (only 1, card knowledge)");
+    {
+      auto it = params.find("random_start_player");
+      // the values accepted as "off", exactly: the same as hanalearn.RANDOM_START_OFF of the Python face
+      if (it != params.end() && it->second != "0" && it->second != "false" && it->second != "False")
+        throw std::invalid_argument("HanabiEnv: random_start_player is not supported (got " + it->second + ")");
+    }
     cfg.max_len = max_len;
     cfg.sad = sad;
     cfg.shuffle_obs = shuffle_obs;

@@ -26,6 +26,12 @@ class EnvConfig(C.Structure):
     ]
 
 
+class EnvRules(C.Structure):
+    """hsad_env_rules: the game's colours, ranks and token limits (the full game is 5, 5, 8, 3)"""
+    _fields_ = [("colors", C.c_int32), ("ranks", C.c_int32), ("max_information_tokens", C.c_int32),
+                ("max_life_tokens", C.c_int32)]
+
+
 class Field(C.Structure):
     _fields_ = [("width", C.c_int32), ("dtype", C.c_int32)]
 
@@ -75,6 +81,9 @@ SIGNATURES = {
     "hsad_last_error": (C.c_char_p, []),
     "hsad_version": (C.c_char_p, []),
     "hsad_env_create": (C.c_int, [C.POINTER(EnvConfig), C.POINTER(_P)]),
+    "hsad_env_create_rules": (C.c_int, [C.POINTER(EnvConfig), C.POINTER(EnvRules), C.POINTER(_P)]),
+    "hsad_env_get_rules": (C.c_int, [_P, C.POINTER(EnvRules)]),
+    "hsad_env_max_deck_size": (C.c_int, [_P]),
     "hsad_env_destroy": (None, [_P]),
     "hsad_env_feature_size": (C.c_int, [_P]),
     "hsad_env_num_action": (C.c_int, [_P]),

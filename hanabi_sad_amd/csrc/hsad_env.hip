@@ -106,6 +106,10 @@ struct EnvParams {
   unsigned long long* phase;  // [16][2]: {tag, wall_clock64 at launch start} per partition, or NULL
   int part, n_part, lock_ticks;
   unsigned long long launch_tag, first_tag;   // first_tag: tag of the first iteration of this rollout call
+  // the game's rules (hsad_env_create_rules).  Read only by the variant instantiations (V = true); the full game's kernels
+  // (V = false) compile them in as constants.  variant = 0 for 5 colours, 5 ranks, 8 information and 3 life tokens.
+  int nC, nR, max_info, max_life, deck_max, variant;
+  unsigned long long deck_full;    // the full deck's 2-bit card counts, type colour*5+rank (unused types 0)
 };
 
 constexpr uint32_t kIdentityPerm = (0u) | (1u << 3) | (2u << 6) | (3u << 9) | (4u << 12);
@@ -119,6 +123,44 @@ __host__ __device__ constexpr uint64_t full_deck_bits() {
   }
   return d;
 }
+
+// deck of a variant: card instances 3 (rank 0), 1 (rank R-1), 2 otherwise; rank 0 is tested first (R = 1: 3 cards per colour)
+__host__ __device__ constexpr uint64_t deck_bits(int C, int R) {
+  uint64_t d = 0;
+  for (int c = 0; c < C; ++c)
+    for (int r = 0; r < R; ++r) d |= (uint64_t)(r == 0 ? 3 : (r == R - 1 ? 1 : 2)) << (2 * (c * 5 + r));
+  return d;
+}
+
+// The game's rules as the kernels see them.  Card types keep the full game's colour*5+rank layout in every plane whatever C
+// and R are (a variant's unused types simply count 0), so only the rules and the encoder's section geometry vary.  The full
+// game's rules are static constants (FullRules: its kernels see literals, as before variants existed); a variant's are read
+// from EnvParams (Rules).  Both are used as `ru.C` etc.
+struct Rules {
+  int C, R, MI, ML;    // colours, ranks, max information tokens, max life tokens
+  int deck;            // MaxDeckSize
+  uint64_t full;       // deck_bits(C, R)
+  uint32_t cmask, rmask;  // plausible colours / ranks of a fresh card
+  int CR, KS, DW;      // bits per card, knowledge stride per card (CR + C + R), discard thermometer width per colour
+};
+struct FullRules {
+  static constexpr int C = 5, R = 5, MI = 8, ML = 3, deck = 50;
+  static constexpr uint64_t full = full_deck_bits();
+  static constexpr uint32_t cmask = 31u, rmask = 31u;
+  static constexpr int CR = 25, KS = 35, DW = 10;
+};
+template <bool V>
+struct RulesOf {
+  static __device__ __forceinline__ FullRules make(const EnvParams&) { return FullRules{}; }
+};
+template <>
+struct RulesOf<true> {
+  static __device__ __forceinline__ Rules make(const EnvParams& ep) {
+    const int C = ep.nC, R = ep.nR;
+    return Rules{C, R, ep.max_info, ep.max_life, ep.deck_max, ep.deck_full, (1u << C) - 1u, (1u << R) - 1u, C * R,
+                 C * R + C + R, R == 1 ? 3 : 2 * R};
+  }
+};
 
 // ---- mt19937, incremental form -----------------------------------------------------------------
 // The generator state is advanced one word per draw:  x[i] <- x[i+397] ^ twist(x[i], x[i+1]),
@@ -356,6 +398,40 @@ __device__ __forceinline__ MoveDec decode_uid(int uid, int P, int H) {
   return m;
 }
 
+// the same for a variant's C colours and R ranks
+__device__ __forceinline__ MoveDec decode_uid(int uid, int P, int H, const Rules& ru) {
+  MoveDec m{0, 0, 0, 0};
+  if (uid < 0) return m;
+  if (uid < H) {
+    m.type = 2;
+    m.idx = uid;
+    return m;
+  }
+  uid -= H;
+  if (uid < H) {
+    m.type = 1;
+    m.idx = uid;
+    return m;
+  }
+  uid -= H;
+  if (uid < (P - 1) * ru.C) {
+    m.type = 3;
+    m.off = 1 + uid / ru.C;
+    m.val = uid % ru.C;
+    return m;
+  }
+  uid -= (P - 1) * ru.C;
+  if (uid < (P - 1) * ru.R) {
+    m.type = 4;
+    m.off = 1 + uid / ru.R;
+    m.val = uid % ru.R;
+    return m;
+  }
+  return m;
+}
+
+__device__ __forceinline__ MoveDec decode_uid(int uid, int P, int H, const FullRules&) { return decode_uid(uid, P, H); }
+
 // per-slot match mask of a packed hand word; cards are 5-bit colour*5+rank
 __device__ __forceinline__ uint32_t hand_match_mask(uint32_t hw, bool by_color, int val) {
   const int len = (hw >> 25) & 7;
@@ -413,12 +489,13 @@ __device__ __forceinline__ void env_stamp(const EnvParams& ep, int it, int k, un
 #define PLEPS(p) (PL_FIXED + 4 * P + (p))
 #define PLPERM(p) (PL_FIXED + 5 * P + (p))
 
-__device__ __forceinline__ bool move_is_legal(int P, const uint32_t* s_st, int lane, const MoveDec& m) {
+template <class Ru>
+__device__ __forceinline__ bool move_is_legal(int P, const uint32_t* s_st, int lane, const MoveDec& m, const Ru& ru) {
   const uint32_t board = ST(PL_BOARD);
   const int cur = board_cur(board);
   if (m.type == 0 || cur < 0) return false;
   if (m.type == 1 || m.type == 2) {
-    if (m.type == 2 && board_info(board) >= 8) return false;
+    if (m.type == 2 && board_info(board) >= ru.MI) return false;
     const int len = (ST(PLH(cur)) >> 25) & 7;
     return m.idx < len;
   }
@@ -432,7 +509,8 @@ __device__ __forceinline__ bool move_is_legal(int P, const uint32_t* s_st, int l
 // history-item record of `move` applied by the player on turn in the current state (no mutation);
 // also used for the SAD greedy move (the reference applies it to a clone only to read this back:
 // cpp/hanabi_env.cc:82-91).
-__device__ __forceinline__ uint32_t make_history(int P, const uint32_t* s_st, int lane, const MoveDec& m) {
+template <class Ru>
+__device__ __forceinline__ uint32_t make_history(int P, const uint32_t* s_st, int lane, const MoveDec& m, const Ru& ru) {
   const uint32_t board = ST(PL_BOARD);
   const int cur = board_cur(board);
   uint32_t rec = (uint32_t)m.type | ((uint32_t)cur << 3);
@@ -444,11 +522,11 @@ __device__ __forceinline__ uint32_t make_history(int P, const uint32_t* s_st, in
     rec |= (uint32_t)c << 23;
     rec |= (uint32_t)r << 26;
     if (m.type == 2) {
-      if (board_info(board) < 8) rec |= 1u << 30;
+      if (board_info(board) < ru.MI) rec |= 1u << 30;
     } else {
       if (r == board_fw(board, c)) {
         rec |= 1u << 29;
-        if (r + 1 == 5 && board_info(board) < 8) rec |= 1u << 30;
+        if (r + 1 == ru.R && board_info(board) < ru.MI) rec |= 1u << 30;
       }
     }
   } else {
@@ -479,8 +557,9 @@ __device__ __forceinline__ uint32_t advance_player(int P, int H, const uint32_t*
 }
 
 // deal one card to the first short hand (kDeal branch of HanabiState::ApplyMove + ApplyRandomChance)
+template <class Ru>
 __device__ __forceinline__ void deal_one(const EnvParams& ep, int P, int H, uint32_t* s_st, int lane, Rng& rng,
-                                         int g) {
+                                         int g, const Ru& ru) {
   uint64_t deck = (uint64_t)ST(PL_DECK_LO) | ((uint64_t)ST(PL_DECK_HI) << 32);
   uint32_t misc = ST(PL_MISC);
   int deck_size = (misc >> 8) & 63;
@@ -488,7 +567,7 @@ __device__ __forceinline__ void deal_one(const EnvParams& ep, int P, int H, uint
   deck -= (uint64_t)1 << (2 * t);
   ST(PL_DECK_LO) = (uint32_t)deck;
   ST(PL_DECK_HI) = (uint32_t)(deck >> 32);
-  if (ep.track_dh) ep.deck_hist[(size_t)g * 52 + (50 - deck_size)] = (uint8_t)t;
+  if (ep.track_dh) ep.deck_hist[(size_t)g * 52 + (ru.deck - deck_size)] = (uint8_t)t;
   deck_size -= 1;
   misc = (misc & ~(63u << 8)) | ((uint32_t)deck_size << 8);
   ST(PL_MISC) = misc;
@@ -499,8 +578,8 @@ __device__ __forceinline__ void deal_one(const EnvParams& ep, int P, int H, uint
   const int len = (hw >> 25) & 7;
   hw = (hw & ~(7u << 25)) | ((uint32_t)t << (5 * len)) | ((uint32_t)(len + 1) << 25);
   ST(PLH(to)) = hw;
-  ST(PLKCP(to)) |= 31u << (5 * len);
-  ST(PLKRP(to)) |= 31u << (5 * len);
+  ST(PLKCP(to)) |= ru.cmask << (5 * len);
+  ST(PLKRP(to)) |= ru.rmask << (5 * len);
   ST(PLKH(to)) &= ~(63u << (6 * len));
   ST(PL_BOARD) = advance_player(P, H, s_st, lane, ST(PL_BOARD), deck_size);
 }
@@ -627,7 +706,8 @@ __device__ __forceinline__ void stream_bits_f32_aligned(const uint32_t* bits, fl
 
 __device__ __forceinline__ uint32_t perm_c(uint32_t pm, int c) { return (pm >> (3 * c)) & 7u; }
 
-__device__ __forceinline__ uint64_t encode_last_action(int P, int H, uint32_t rec, int observer, uint32_t pm) {
+template <class Ru>
+__device__ __forceinline__ uint64_t encode_last_action(int P, int H, uint32_t rec, int observer, uint32_t pm, const Ru& ru) {
   const int type = rec & 7;
   if (!type) return 0;
   int rel = (int)((rec >> 3) & 7) - observer;
@@ -643,23 +723,24 @@ __device__ __forceinline__ uint64_t encode_last_action(int P, int H, uint32_t re
   }
   off += P;
   if (type == 3) m |= 1ull << (off + perm_c(pm, (rec >> 9) & 7));
-  off += 5;
+  off += ru.C;
   if (type == 4) m |= 1ull << (off + ((rec >> 12) & 7));
-  off += 5;
+  off += ru.R;
   if (type >= 3) m |= (uint64_t)((rec >> 18) & 31u) << off;
   off += H;
   if (type <= 2) m |= 1ull << (off + ((rec >> 15) & 7));
   off += H;
-  if (type <= 2) m |= 1ull << (off + perm_c(pm, (rec >> 23) & 7) * 5 + ((rec >> 26) & 7));
-  off += 25;
+  if (type <= 2) m |= 1ull << (off + perm_c(pm, (rec >> 23) & 7) * ru.R + ((rec >> 26) & 7));
+  off += ru.CR;
   if (type == 1) m |= (uint64_t)((rec >> 29) & 3u) << off;
   return m;
 }
 
 // legal-move mask of player p in the current state (uids colour-permuted for that observer); noop iff nothing
 // else is legal (HanabiState::LegalMoves + cpp/hanabi_env.cc:171-191)
-template <int TH>
-__device__ __forceinline__ uint64_t legal_mask_of(int P, int H, int A, const uint32_t* s_st, int lane, int p, uint32_t pm) {
+template <int TH, class Ru>
+__device__ __forceinline__ uint64_t legal_mask_of(int P, int H, int A, const uint32_t* s_st, int lane, int p, uint32_t pm,
+                                                  const Ru& ru) {
   const uint32_t board = ST(PL_BOARD);
   const int cur = board_cur(board), info = board_info(board);
   uint64_t lm = 0;
@@ -667,7 +748,7 @@ __device__ __forceinline__ uint64_t legal_mask_of(int P, int H, int A, const uin
     const uint32_t hw = ST(PLH(p));
     const int len = (hw >> 25) & 7;
     const uint64_t lenmask = (1ull << len) - 1ull;
-    if (info < 8) lm |= lenmask;
+    if (info < ru.MI) lm |= lenmask;
     lm |= lenmask << H;
     if (info > 0) {
       for (int o = 1; o < P; ++o) {
@@ -685,8 +766,8 @@ __device__ __forceinline__ uint64_t legal_mask_of(int P, int H, int A, const uin
             rm |= 1u << r;
           }
         }
-        lm |= (uint64_t)cm << (2 * H + (o - 1) * 5);
-        lm |= (uint64_t)rm << (2 * H + (P - 1) * 5 + (o - 1) * 5);
+        lm |= (uint64_t)cm << (2 * H + (o - 1) * ru.C);
+        lm |= (uint64_t)rm << (2 * H + (P - 1) * ru.C + (o - 1) * ru.R);
       }
     }
   }
@@ -696,11 +777,13 @@ __device__ __forceinline__ uint64_t legal_mask_of(int P, int H, int A, const uin
 
 // Build the observation / legal-move / own-hand bit rows of this lane's game for every observer
 // (HanabiEnv::computeFeatureAndLegalMove, cpp/hanabi_env.cc:115-205, on top of the canonical encoder).
-template <int TP, int TH>
+template <int TP, int TH, bool V = false>
 __device__ __forceinline__ void build_rows(const EnvParams& ep, const uint32_t* s_st, int lane, int g, uint32_t* s_obs,
                                            uint32_t* s_legal, uint32_t* s_own, uint32_t greedy_rec, int p_begin,
                                            int p_step) {
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
+  const auto ru = RulesOf<V>::make(ep);
+  const uint32_t CR = (uint32_t)ru.CR, RR = (uint32_t)ru.R;
   const uint32_t board = ST(PL_BOARD);
   const uint32_t misc = ST(PL_MISC);
   const int deck_size = (misc >> 8) & 63;
@@ -728,32 +811,32 @@ __device__ __forceinline__ void build_rows(const EnvParams& ep, const uint32_t* 
           if (o > 0) {
             const int card = (hw >> (5 * i)) & 31;
             const int c = (card * 13) >> 6, r = card - 5 * c;
-            or_bit(s_obs, base + (uint32_t)((o * H + i) * 25) + perm_c(pm, c) * 5u + (uint32_t)r);
+            or_bit(s_obs, base + (uint32_t)((o * H + i) * ru.CR) + perm_c(pm, c) * RR + (uint32_t)r);
           }
           const uint32_t cp = (kcp >> (5 * i)) & 31u, rp = (krp >> (5 * i)) & 31u;
           const uint32_t h6 = (kh >> (6 * i)) & 63u;
           uint64_t m = 0;
 #pragma unroll
-          for (int c = 0; c < 5; ++c) m |= ((cp >> c) & 1u) ? ((uint64_t)rp << (perm_c(pm, c) * 5u)) : 0ull;
-          if (h6 & 7u) m |= 1ull << (25u + perm_c(pm, (int)(h6 & 7u) - 1));
-          if (h6 >> 3) m |= 1ull << (30u + (h6 >> 3) - 1u);
-          or_bits64(s_obs, base + (uint32_t)ep.OK + (uint32_t)((o * H + i) * 35), m);
+          for (int c = 0; c < 5; ++c) m |= ((cp >> c) & 1u) ? ((uint64_t)rp << (perm_c(pm, c) * RR)) : 0ull;
+          if (h6 & 7u) m |= 1ull << (CR + perm_c(pm, (int)(h6 & 7u) - 1));
+          if (h6 >> 3) m |= 1ull << (CR + (uint32_t)ru.C + (h6 >> 3) - 1u);
+          or_bits64(s_obs, base + (uint32_t)ep.OK + (uint32_t)((o * H + i) * ru.KS), m);
         }
       }
     }
-    or_bits32(s_obs, base + (uint32_t)(P * H * 25), miss);
+    or_bits32(s_obs, base + (uint32_t)(P * H * ru.CR), miss);
     // board: deck thermometer | fireworks one-hot | info thermometer | life thermometer
     or_bits64(s_obs, base + (uint32_t)ep.OB, (1ull << deck_size) - 1ull);
     uint64_t bm = 0;
 #pragma unroll
     for (int c = 0; c < 5; ++c) {
       const int f = board_fw(board, c);
-      bm |= (f > 0) ? (1ull << (perm_c(pm, c) * 5u + (uint32_t)f - 1u)) : 0ull;
+      bm |= (f > 0) ? (1ull << (perm_c(pm, c) * RR + (uint32_t)f - 1u)) : 0ull;
     }
-    bm |= (uint64_t)((1u << info) - 1u) << 25;
-    bm |= (uint64_t)((1u << life) - 1u) << 33;
+    bm |= (uint64_t)((1u << info) - 1u) << CR;
+    bm |= (uint64_t)((1u << life) - 1u) << (CR + (uint32_t)ru.MI);
     or_bits64(s_obs, base + (uint32_t)(ep.OB + ep.DECKW), bm);
-    // discards: thermometers of width 3,2,2,2,1 per colour
+    // discards: thermometers of width 3,2,2,2,1 per colour (a variant's R ranks: 3, 2 ... 2, 1; R = 1: 3)
     uint64_t dm = 0;
 #pragma unroll
     for (int c = 0; c < 5; ++c) {
@@ -762,14 +845,14 @@ __device__ __forceinline__ void build_rows(const EnvParams& ep, const uint32_t* 
       for (int r = 0; r < 5; ++r) {
         const uint32_t n = cnt2(disc, c * 5 + r);
         const uint32_t roff = (r == 0) ? 0u : (1u + 2u * (uint32_t)r);
-        dm |= (uint64_t)((1u << n) - 1u) << (pc * 10u + roff);
+        dm |= (uint64_t)((1u << n) - 1u) << (pc * (uint32_t)ru.DW + roff);
       }
     }
     or_bits64(s_obs, base + (uint32_t)ep.OD, dm);
-    or_bits64(s_obs, base + (uint32_t)ep.OL, encode_last_action(P, H, lastmv, p, pm));
-    if (ep.sad) or_bits64(s_obs, base + (uint32_t)ep.F0, encode_last_action(P, H, greedy_rec, p, pm));
+    or_bits64(s_obs, base + (uint32_t)ep.OL, encode_last_action(P, H, lastmv, p, pm, ru));
+    if (ep.sad) or_bits64(s_obs, base + (uint32_t)ep.F0, encode_last_action(P, H, greedy_rec, p, pm, ru));
 
-    const uint64_t lm = legal_mask_of<TH>(P, H, ep.A, s_st, lane, p, pm);
+    const uint64_t lm = legal_mask_of<TH>(P, H, ep.A, s_st, lane, p, pm, ru);
     or_bits64(s_legal, (uint32_t)(lane * P + p) * (uint32_t)ep.A, lm);
     ep.legal_bits[(size_t)g * P + p] = lm;
     if (ep.legal_out) ep.legal_out[(size_t)g * P + p] = lm;
@@ -793,8 +876,8 @@ __device__ __forceinline__ void build_rows(const EnvParams& ep, const uint32_t* 
 }
 
 // publicly remaining count of each card type (total - discards - fireworks), 2 bits each
-__device__ __forceinline__ uint64_t public_counts(uint64_t disc, uint32_t board) {
-  uint64_t pc = full_deck_bits() - disc;  // per-field subtraction never borrows (disc <= total)
+__device__ __forceinline__ uint64_t public_counts(uint64_t disc, uint32_t board, uint64_t full) {
+  uint64_t pc = full - disc;  // per-field subtraction never borrows (disc <= total)
 #pragma unroll
   for (int c = 0; c < 5; ++c) {
     const int f = board_fw(board, c);
@@ -806,27 +889,29 @@ __device__ __forceinline__ uint64_t public_counts(uint64_t disc, uint32_t board)
 // V0-belief fix-up of the knowledge section (knowledge_mode=1): every plausible entry becomes
 // count/total as fp32 (EncodeV0Belief in the oracle).  Executed by the whole wave for the games whose
 // bit in `active` is set; scattered 4-byte stores over the already streamed 0/1 values.
+template <bool V>
 __device__ void v0_fixup(const EnvParams& ep, const uint32_t* s_st, const uint32_t* s_obs, uint64_t active, int g0,
                          int lane_id) {
   const int P = ep.P, H = ep.H;
-  const int per_row = P * H * 25;
+  const auto ru = RulesOf<V>::make(ep);
+  const int per_row = P * H * ru.CR;
   while (active) {
     const int lg = __builtin_ctzll(active);
     active &= active - 1;
     const uint32_t board = s_st[PL_BOARD * kWave + lg];
     const uint64_t disc = (uint64_t)s_st[PL_DISC_LO * kWave + lg] | ((uint64_t)s_st[PL_DISC_HI * kWave + lg] << 32);
-    const uint64_t pub = public_counts(disc, board);
+    const uint64_t pub = public_counts(disc, board, ru.full);
     for (int e = lane_id; e < P * per_row; e += kWave) {
       const int p = e / per_row;
       const int rem = e - p * per_row;
-      const int slot = rem / 25;  // o*H + i
-      const int j = rem - slot * 25;
+      const int slot = rem / ru.CR;  // o*H + i
+      const int j = rem - slot * ru.CR;
       const int o = slot / H, i = slot - o * H;
       int q = p + o;
       if (q >= P) q -= P;
       const uint32_t hw = s_st[PLH(q) * kWave + lg];
       if (i >= (int)((hw >> 25) & 7)) continue;
-      const uint32_t bitpos = (uint32_t)(lg * P + p) * (uint32_t)ep.F + (uint32_t)ep.OK + (uint32_t)(slot * 35 + j);
+      const uint32_t bitpos = (uint32_t)(lg * P + p) * (uint32_t)ep.F + (uint32_t)ep.OK + (uint32_t)(slot * ru.KS + j);
       if (!get1(s_obs, bitpos)) continue;
       const uint32_t permw = ep.shuffle_color ? s_st[PLPERM(p) * kWave + lg] : kIdentityPermBoth;
       const uint32_t inv = permw >> 15;
@@ -837,11 +922,11 @@ __device__ void v0_fixup(const EnvParams& ep, const uint32_t* s_st, const uint32
         if ((cp >> c) & 1u)
           for (int r = 0; r < 5; ++r)
             if ((rp >> r) & 1u) total += (float)cnt2(pub, c * 5 + r);
-      const int pcol = j / 5, r = j - 5 * pcol;
+      const int pcol = j / ru.R, r = j - ru.R * pcol;
       const int real_c = (int)perm_c(inv, pcol);
       const float cnt = (float)cnt2(pub, real_c * 5 + r);
       const float v = (total > 0.f) ? cnt / total : 0.f;
-      ep.priv_s[(size_t)(g0 + lg) * P * ep.F + (size_t)p * ep.F + ep.OK + slot * 35 + j] = v;
+      ep.priv_s[(size_t)(g0 + lg) * P * ep.F + (size_t)p * ep.F + ep.OK + slot * ru.KS + j] = v;
     }
   }
 }
@@ -915,12 +1000,13 @@ __device__ __forceinline__ void clear_rows(const EnvParams& ep, uint32_t* s_obs,
 
 // The game logic of one iteration for the 64 games of the logic wave (wave 0): reset-if-terminated (MODE 0 / 3), then the
 // policy (MODE 2 / 3) or the given actions (MODE 1) and the env step, all on the state planes staged in s_st.
-template <int MODE, int TP, int TH>
+template <int MODE, int TP, int TH, bool V = false>
 __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
                                           uint32_t* s_st, uint32_t* s_win, const float* s_eps, const int lane, const int g,
                                           const bool active, const bool do_reset, Rng& rng, uint32_t& greedy_rec, float& reward,
                                           bool& term, const int dbg_it = 0) {
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
+  const auto ru = RulesOf<V>::make(ep);
   if (MODE == 0 || MODE == 3) {
     // ---- prefetch window: every mt19937 word this reset will regenerate, in one round trip ----
     const int W = ep.win_w;
@@ -962,33 +1048,41 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
       rng.spos = (wbase + (uint32_t)W) % (uint32_t)kMtN;
 
       // HanabiEnv::reset (cpp/hanabi_env.cc:9-47): fresh HanabiState, deal until no chance node
-      const uint64_t deck = full_deck_bits();
+      const uint64_t deck = ru.full;
       ST(PL_DECK_LO) = (uint32_t)deck;
       ST(PL_DECK_HI) = (uint32_t)(deck >> 32);
       ST(PL_DISC_LO) = 0;
       ST(PL_DISC_HI) = 0;
-      ST(PL_BOARD) = (8u << 15) | (3u << 19) | ((uint32_t)P << 21) | (0u << 24) | (0u << 27);
-      ST(PL_MISC) = (ST(PL_MISC) & (63u << 16)) | (50u << 8) | (1u << 15);  // keep last_score; started
+      ST(PL_BOARD) = ((uint32_t)ru.MI << 15) | ((uint32_t)ru.ML << 19) | ((uint32_t)P << 21) | (0u << 24) | (0u << 27);
+      ST(PL_MISC) = (ST(PL_MISC) & (63u << 16)) | ((uint32_t)ru.deck << 8) | (1u << 15);  // keep last_score; started
       ST(PL_LASTMV) = 0;
       {
         // initial deal (ApplyRandomChance until every hand is full: players in seat order, H cards each) with the
         // deck and the hand being filled held in registers — one LDS store per plane at the end instead of ~35
         // dependent LDS round trips per card
         uint64_t dk = deck;
-        int dsize = 50;
+        int dsize = ru.deck;
         const uint32_t full_k = (H >= 5) ? 0x1ffffffu : ((1u << (5 * H)) - 1u);
+        uint32_t full_kc = full_k, full_kr = full_k;   // every colour / rank plausible in each of the H slots
+        if (V) {
+          full_kc = full_kr = 0u;
+          for (int i = 0; i < H; ++i) {
+            full_kc |= ru.cmask << (5 * i);
+            full_kr |= ru.rmask << (5 * i);
+          }
+        }
         for (int p = 0; p < P; ++p) {
           uint32_t hw = 0;
           for (int i = 0; i < H; ++i) {
             const int t = deal_pick(ep.deal_mode, dk, dsize, rng);
             dk -= (uint64_t)1 << (2 * t);
-            if (ep.track_dh) ep.deck_hist[(size_t)g * 52 + (50 - dsize)] = (uint8_t)t;
+            if (ep.track_dh) ep.deck_hist[(size_t)g * 52 + (ru.deck - dsize)] = (uint8_t)t;
             dsize -= 1;
             hw |= (uint32_t)t << (5 * i);
           }
           ST(PLH(p)) = hw | ((uint32_t)H << 25);
-          ST(PLKCP(p)) = full_k;
-          ST(PLKRP(p)) = full_k;
+          ST(PLKCP(p)) = full_kc;
+          ST(PLKRP(p)) = full_kr;
           ST(PLKH(p)) = 0;
         }
         ST(PL_DECK_LO) = (uint32_t)dk;
@@ -1006,13 +1100,27 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
         const int fix = (int)(rng_next(rng) % (uint32_t)P);
         for (int p = 0; p < P; ++p) {
           uint32_t arr = kIdentityPerm;
-          if (p != fix) {
+          auto swp = [&](int i, int j) {
+            const uint32_t vi = (arr >> (3 * i)) & 7u, vj = (arr >> (3 * j)) & 7u;
+            arr = (arr & ~(7u << (3 * i))) | (vj << (3 * i));
+            arr = (arr & ~(7u << (3 * j))) | (vi << (3 * j));
+          };
+          if (V && p != fix) {
+            // libstdc++ std::shuffle of C colours: an even C swaps slot 1 first on a {0, 1} draw, then two swaps per
+            // uniform_int draw over [0, (i+1)(i+2)) (C = 1 draws nothing); positions C..4 stay the identity
+            int i = 1;
+            if ((ru.C & 1) == 0) {
+              swp(1, (int)uniform_below(2u, rng));
+              i = 2;
+            }
+            for (; i + 1 < ru.C; i += 2) {
+              const uint32_t b1 = (uint32_t)i + 2u;
+              const uint32_t x = uniform_below((uint32_t)(i + 1) * b1, rng);
+              swp(i, (int)(x / b1));
+              swp(i + 1, (int)(x % b1));
+            }
+          } else if (p != fix) {
             // libstdc++ std::shuffle, 5 elements: two swaps per uniform_int draw
-            auto swp = [&](int i, int j) {
-              const uint32_t vi = (arr >> (3 * i)) & 7u, vj = (arr >> (3 * j)) & 7u;
-              arr = (arr & ~(7u << (3 * i))) | (vj << (3 * i));
-              arr = (arr & ~(7u << (3 * j))) | (vi << (3 * j));
-            };
             uint32_t x = uniform_below(6u, rng);
             swp(1, (int)(x / 3u));
             swp(2, (int)(x % 3u));
@@ -1056,7 +1164,7 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
             // legal bits of the state the policy acts on: the stored side output, or (MODE 3, game restarted a
             // moment ago in this very launch) recomputed from the fresh state
             const uint64_t mask = do_reset ? legal_mask_of<TH>(P, H, ep.A, s_st, lane, p,
-                                                               ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm)
+                                                               ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru)
                                            : ep.legal_bits[(size_t)g * P + p];
             const int pa = policy_pick(ep.policy_seed, (uint64_t)g, (uint64_t)counter, p, 0, mask);
             const int pg = policy_pick(ep.policy_seed, (uint64_t)g, (uint64_t)counter, p, 1, mask);
@@ -1071,19 +1179,19 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
           uid = (int)a_in[(size_t)g * P + cur];
           if (ep.sad) guid = (int)g_in[(size_t)g * P + cur];
         }
-        MoveDec mv = decode_uid(uid, P, H);
+        MoveDec mv = decode_uid(uid, P, H, ru);
         const uint32_t pinv = ep.shuffle_color ? (ST(PLPERM(cur)) >> 15) : kIdentityPerm;
         if (mv.type == 3) mv.val = (int)perm_c(pinv, mv.val);  // maybeInversePermuteColor_
-        bool ok = move_is_legal(P, s_st, lane, mv);
+        bool ok = move_is_legal(P, s_st, lane, mv, ru);
         if (!ok) log_error(ep, g, 1);
         if (ok && ep.sad) {
-          MoveDec gm = decode_uid(guid, P, H);
+          MoveDec gm = decode_uid(guid, P, H, ru);
           if (gm.type == 3) gm.val = (int)perm_c(pinv, gm.val);
-          if (!move_is_legal(P, s_st, lane, gm)) {
+          if (!move_is_legal(P, s_st, lane, gm, ru)) {
             ok = false;
             log_error(ep, g, 2);
           } else {
-            greedy_rec = make_history(P, s_st, lane, gm);
+            greedy_rec = make_history(P, s_st, lane, gm, ru);
           }
         }
         if (ok) {
@@ -1091,7 +1199,7 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
           const int deck_size = (misc >> 8) & 63;
           const int life0 = board_life(board);
           const int prev_score = (life0 <= 0 && ep.bomb) ? 0 : board_fw_sum(board);
-          const uint32_t rec = make_history(P, s_st, lane, mv);
+          const uint32_t rec = make_history(P, s_st, lane, mv, ru);
           // ---- HanabiState::ApplyMove ----
           if (deck_size == 0) board = board_set(board, 21, 7u, (uint32_t)(board_turns(board) - 1));
           if (mv.type <= 2) {
@@ -1154,7 +1262,7 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
           // ---- HanabiEnv::step tail (cpp/hanabi_env.cc:94-108) ----
           const int life1 = board_life(board);
           const int fsum = board_fw_sum(board);
-          term = (life1 < 1) || (fsum >= 25) || (board_turns(board) <= 0);
+          term = (life1 < 1) || (fsum >= ru.CR) || (board_turns(board) <= 0);
           const int score = (life1 <= 0 && ep.bomb) ? 0 : fsum;
           reward = (float)(score - prev_score);
           if (ep.max_len > 0 && num_step == ep.max_len) {
@@ -1164,7 +1272,7 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
           misc = (misc & ~255u) | (uint32_t)num_step;
           ST(PL_MISC) = misc;
           if (!term) {
-            while (board_cur(ST(PL_BOARD)) < 0) deal_one(ep, P, H, s_st, lane, rng, g);
+            while (board_cur(ST(PL_BOARD)) < 0) deal_one(ep, P, H, s_st, lane, rng, g, ru);
           }
           misc = ST(PL_MISC);
           misc = (misc & ~(1u << 14)) | ((term ? 1u : 0u) << 14);
@@ -1176,7 +1284,7 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
   }
 }
 
-template <int MODE, int TP, int TH>
+template <int MODE, int TP, int TH, bool V = false>
 __device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
                                          const int g_bias = 0, const int dbg_it = 0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -1269,7 +1377,7 @@ __device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __r
   bool term = false;
 
   if (wave == 0) {
-    env_logic<MODE, TP, TH>(ep, a_in, g_in, s_st, s_win, s_eps, lane, g, active, do_reset, rng, greedy_rec, reward, term, dbg_it);
+    env_logic<MODE, TP, TH, V>(ep, a_in, g_in, s_st, s_win, s_eps, lane, g, active, do_reset, rng, greedy_rec, reward, term, dbg_it);
     s_grec[lane] = greedy_rec;
   }
   __syncthreads();
@@ -1279,7 +1387,7 @@ __device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __r
   Refill rf;
   refill_issue(rf, rng, active && wave == 0);
   // both waves build rows: wave w takes observers w, w+2, ...
-  if (active) build_rows<TP, TH>(ep, s_st, lane, g, s_obs, s_legal, s_own, s_grec[lane], wave, nwaves);
+  if (active) build_rows<TP, TH, V>(ep, s_st, lane, g, s_obs, s_legal, s_own, s_grec[lane], wave, nwaves);
   STAMP(3);
   if (active && wave == 0) {
     refill_finish(rf, rng);
@@ -1303,7 +1411,7 @@ __device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __r
     }
     if (ep.kmode == 1) {
       __syncthreads();
-      if (wave == 0) v0_fixup(ep, s_st, s_obs, __ballot(valid), g0, lane);
+      if (wave == 0) v0_fixup<V>(ep, s_st, s_obs, __ballot(valid), g0, lane);
     }
   } else {
     if (wave != 0) return;  // the reset kernel streams a handful of games per block: one wave is plenty
@@ -1321,16 +1429,17 @@ __device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __r
       for (int p = 0; p < P; ++p) ep.eps[(size_t)g * P + p] = __uint_as_float(ST(PLEPS(p)));
     if (ep.kmode == 1) {
       __syncthreads();
-      v0_fixup(ep, s_st, s_obs, todo_all, g0, lane);
+      v0_fixup<V>(ep, s_st, s_obs, todo_all, g0, lane);
     }
   }
   STAMP(5);
 }
 
-template <int MODE, int TP, int TH>
+// V: a variant's rules from EnvParams (generic players / hand size only); the full game's instances have V = false
+template <int MODE, int TP, int TH, bool V = false>
 __global__ __launch_bounds__(kEnvThreads) void env_kernel(EnvParams ep, const int64_t* __restrict__ a_in,
                                                           const int64_t* __restrict__ g_in) {
-  env_body<MODE, TP, TH>(ep, a_in, g_in);
+  env_body<MODE, TP, TH, V>(ep, a_in, g_in);
 }
 
 // Persistent rollout: games are independent, so a workgroup simply runs n_iter iterations (reset finished games + policy +
@@ -1357,7 +1466,7 @@ __device__ __forceinline__ void rollout_stagger(const EnvParams& ep) {
   }
 }
 
-template <int TP, int TH>
+template <int TP, int TH, bool V = false>
 __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void env_rollout_kernel(EnvParams ep) {
   rollout_stagger(ep);
 #pragma clang loop unroll(disable)
@@ -1365,7 +1474,7 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     if (iter) __syncthreads();   // the previous iteration's rows have left LDS before they are cleared again
     int zero = 0;
     asm volatile("" : "+s"(zero));
-    env_body<3, TP, TH>(ep, nullptr, nullptr, zero, iter);
+    env_body<3, TP, TH, V>(ep, nullptr, nullptr, zero, iter);
   }
 }
 
@@ -1535,12 +1644,12 @@ __global__ void legal_query_kernel(EnvParams ep, const int32_t* __restrict__ uid
   if (g >= ep.G) return;
   const uint32_t board = GP(PL_BOARD);
   const int cur = board_cur(board);
-  const MoveDec m = decode_uid(uid[g], ep.P, ep.H);
+  const MoveDec m = decode_uid(uid[g], ep.P, ep.H, RulesOf<true>::make(ep));
   bool ok = false;
   if (m.type != 0 && cur >= 0) {
     if (m.type <= 2) {
       const int len = (GP(PLH(cur)) >> 25) & 7;
-      ok = (m.idx < len) && !(m.type == 2 && board_info(board) >= 8);
+      ok = (m.idx < len) && !(m.type == 2 && board_info(board) >= ep.max_info);
     } else if (board_info(board) > 0 && m.off >= 1 && m.off < ep.P) {
       int q = cur + m.off;
       if (q >= ep.P) q -= ep.P;
@@ -1554,7 +1663,7 @@ __global__ void deck_history_kernel(EnvParams ep, uint8_t* __restrict__ out, int
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ep.G) return;
   const uint32_t misc = GP(PL_MISC);
-  const int n = ((misc >> 15) & 1u) ? 50 - (int)((misc >> 8) & 63u) : 0;
+  const int n = ((misc >> 15) & 1u) ? ep.deck_max - (int)((misc >> 8) & 63u) : 0;
   count[g] = ep.track_dh ? n : 0;
   for (int i = 0; i < 50; ++i) out[(size_t)g * 50 + i] = (ep.track_dh && i < n) ? ep.deck_hist[(size_t)g * 52 + i] : 0;
 }
@@ -1679,8 +1788,17 @@ namespace {
 
 typedef void (*EnvKernelFn)(EnvParams, const int64_t*, const int64_t*);
 
-// compile-time (players, hand) specialisations; anything else runs the generic <0,0> instance
-EnvKernelFn pick_env_kernel(int mode, int P, int H) {
+// compile-time (players, hand) specialisations; anything else runs the generic <0,0> instance.  Variants (any rules but the
+// full game's) run the generic instance with the rules read from EnvParams.
+EnvKernelFn pick_env_kernel(int mode, int P, int H, bool variant) {
+  if (variant) {
+    switch (mode) {
+      case 0: return env_kernel<0, 0, 0, true>;
+      case 1: return env_kernel<1, 0, 0, true>;
+      case 2: return env_kernel<2, 0, 0, true>;
+      default: return env_kernel<3, 0, 0, true>;
+    }
+  }
 #define HSAD_ENV_SPECIALISE(PP, HH)                 \
   if (P == PP && H == HH) {                         \
     switch (mode) {                                 \
@@ -1705,10 +1823,13 @@ EnvKernelFn pick_env_kernel(int mode, int P, int H) {
 
 typedef void (*EnvRolloutFn)(EnvParams);
 // the pipelined schedule (env_rollout_pipe_kernel) needs exactly one stream wave and no V0-belief fix-up of the streamed rows;
-// 256-thread workgroups (few games per GPU) and knowledge_mode 1 run env_rollout_kernel
-bool rollout_pipelined(const hsad_env* e) { return e->rollout_pipe && e->ep.nthreads == 2 * kWave && e->ep.kmode == 0; }
+// 256-thread workgroups (few games per GPU), knowledge_mode 1 and variants run env_rollout_kernel
+bool rollout_pipelined(const hsad_env* e) {
+  return e->rollout_pipe && e->ep.nthreads == 2 * kWave && e->ep.kmode == 0 && !e->ep.variant;
+}
 
-EnvRolloutFn pick_rollout_kernel(int P, int H, bool pipe) {
+EnvRolloutFn pick_rollout_kernel(int P, int H, bool pipe, bool variant) {
+  if (variant) return env_rollout_kernel<0, 0, true>;
 #define HSAD_ROLLOUT_SPECIALISE(PP, HH) \
   if (P == PP && H == HH) return pipe ? env_rollout_pipe_kernel<PP, HH> : env_rollout_kernel<PP, HH>;
   HSAD_ROLLOUT_SPECIALISE(2, 5)
@@ -1721,11 +1842,11 @@ EnvRolloutFn pick_rollout_kernel(int P, int H, bool pipe) {
 
 int configure_env_kernels(hsad_env* e) {
   for (const bool pipe : {false, true})
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_rollout_kernel(e->ep.P, e->ep.H, pipe)),
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_rollout_kernel(e->ep.P, e->ep.H, pipe, e->ep.variant != 0)),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes_reset));
   for (int mode = 0; mode < 4; ++mode) {
     const size_t lds = (mode == 1 || mode == 2) ? e->lds_bytes : e->lds_bytes_reset;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_env_kernel(mode, e->ep.P, e->ep.H)),
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_env_kernel(mode, e->ep.P, e->ep.H, e->ep.variant != 0)),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   return HSAD_OK;
@@ -1753,9 +1874,9 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
   ep.a_out = a_out;
   ep.g_out = g_out;
   if (mode == 3 && n_iter > 1)
-    hipLaunchKernelGGL(pick_rollout_kernel(ep.P, ep.H, rollout_pipelined(e)), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds, stream, ep);
+    hipLaunchKernelGGL(pick_rollout_kernel(ep.P, ep.H, rollout_pipelined(e), ep.variant != 0), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds, stream, ep);
   else
-    hipLaunchKernelGGL(pick_env_kernel(mode, ep.P, ep.H), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds,
+    hipLaunchKernelGGL(pick_env_kernel(mode, ep.P, ep.H, ep.variant != 0), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds,
                        stream, ep, a, g);
 }
 
@@ -1771,12 +1892,25 @@ int hsad_internal_set_error(int code, const char* msg) {
 }
 const char* hsad_version(void) { return "hsad 0.1 gfx950"; }
 
-int hsad_env_create(const hsad_env_config* cfg, hsad_env** out) {
+int hsad_env_create(const hsad_env_config* cfg, hsad_env** out) { return hsad_env_create_rules(cfg, nullptr, out); }
+
+int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rules, hsad_env** out) {
   if (!cfg || !out) return set_error(HSAD_ERR_INVALID, "null argument");
   *out = nullptr;
+  const hsad_env_rules full = {5, 5, 8, 3};
+  const hsad_env_rules ru = rules ? *rules : full;
+  if (ru.colors < 1 || ru.colors > 5) return set_error(HSAD_ERR_INVALID, "colors must be 1..5");
+  if (ru.ranks < 1 || ru.ranks > 5) return set_error(HSAD_ERR_INVALID, "ranks must be 1..5");
+  if (ru.max_information_tokens < 1 || ru.max_information_tokens > 8)
+    return set_error(HSAD_ERR_INVALID, "max_information_tokens must be 1..8");
+  if (ru.max_life_tokens < 1 || ru.max_life_tokens > 3) return set_error(HSAD_ERR_INVALID, "max_life_tokens must be 1..3");
+  const int Cn = ru.colors, Rn = ru.ranks;
+  const int deck_max = Cn * (Rn == 1 ? 3 : 2 * Rn);   // C * (3 + 2 (R - 2) + 1)
   if (cfg->num_games < 1) return set_error(HSAD_ERR_INVALID, "num_games must be >= 1");
   if (cfg->players < 2 || cfg->players > 5) return set_error(HSAD_ERR_INVALID, "players must be 2..5");
   if (cfg->hand_size < 1 || cfg->hand_size > 5) return set_error(HSAD_ERR_INVALID, "hand_size must be 1..5");
+  if (cfg->players * cfg->hand_size > deck_max)
+    return set_error(HSAD_ERR_INVALID, "players * hand_size (%d) exceeds the deck (%d cards)", cfg->players * cfg->hand_size, deck_max);
   if (cfg->shuffle_obs) return set_error(HSAD_ERR_INVALID, "shuffle_obs is not supported (reference asserts it off)");
   if (cfg->n_eps < 1 || !cfg->eps_list) return set_error(HSAD_ERR_INVALID, "eps_list must hold >= 1 value");
   if (cfg->knowledge_mode != 0 && cfg->knowledge_mode != 1) return set_error(HSAD_ERR_INVALID, "knowledge_mode 0|1");
@@ -1795,14 +1929,22 @@ int hsad_env_create(const hsad_env_config* cfg, hsad_env** out) {
   ep.Gpad = (ep.G + kWave - 1) / kWave * kWave;
   ep.P = P;
   ep.H = H;
-  ep.A = 2 * H + 2 * (P - 1) * 5 + 1;
-  ep.DECKW = 50 - P * H;
-  ep.LAL = P + 4 + P + 5 + 5 + H + H + 25 + 2;
-  ep.OB = P * H * 25 + P;
-  ep.OD = ep.OB + ep.DECKW + 25 + 8 + 3;
-  ep.OL = ep.OD + 50;
+  ep.nC = Cn;
+  ep.nR = Rn;
+  ep.max_info = ru.max_information_tokens;
+  ep.max_life = ru.max_life_tokens;
+  ep.deck_max = deck_max;
+  ep.deck_full = deck_bits(Cn, Rn);
+  ep.variant = (Cn != 5 || Rn != 5 || ep.max_info != 8 || ep.max_life != 3) ? 1 : 0;
+  // canonical encoder sections: hands | board | discards | last action | card knowledge (| SAD's last action)
+  ep.A = 2 * H + (P - 1) * (Cn + Rn) + 1;
+  ep.DECKW = deck_max - P * H;
+  ep.LAL = P + 4 + P + Cn + Rn + H + H + Cn * Rn + 2;
+  ep.OB = P * H * Cn * Rn + P;
+  ep.OD = ep.OB + ep.DECKW + Cn * Rn + ep.max_info + ep.max_life;
+  ep.OL = ep.OD + deck_max;
   ep.OK = ep.OL + ep.LAL;
-  ep.F0 = ep.OK + P * H * 35;
+  ep.F0 = ep.OK + P * H * (Cn * Rn + Cn + Rn);
   ep.F = ep.F0 + (cfg->sad ? ep.LAL : 0);
   ep.max_len = cfg->max_len;
   ep.sad = cfg->sad ? 1 : 0;
@@ -1816,7 +1958,8 @@ int hsad_env_create(const hsad_env_config* cfg, hsad_env** out) {
   ep.deal_mode = cfg->deal_mode ? 1 : 0;
   ep.nt_stores = getenv("HSAD_NT_STORES") ? atoi(getenv("HSAD_NT_STORES")) : 1;  // write-once obs stream: bypass L2 residency  // 1 = always take the literal fp64 discrete_distribution path
   {
-    const int n_static = 2 * P * H + P + (ep.shuffle_color ? 1 + 2 * (P - 1) : 0);
+    const int shuffle_draws = Cn == 1 ? 0 : (Cn % 2 == 0 ? 1 : 0) + (Cn - 1) / 2;   // std::shuffle of C colours
+    const int n_static = 2 * P * H + P + (ep.shuffle_color ? 1 + shuffle_draws * (P - 1) : 0);
     ep.win_w = n_static + 2 < 64 ? n_static + 2 : 64;
     ep.win_words = ep.win_w <= 32 ? ep.win_w : 2 * ep.win_w + 1;
   }
@@ -1920,7 +2063,16 @@ void hsad_env_destroy(hsad_env* e) {
 
 int hsad_env_feature_size(const hsad_env* e) { return e ? e->ep.F : 0; }
 int hsad_env_num_action(const hsad_env* e) { return e ? e->ep.A : 0; }
-int hsad_env_hand_feature_size(const hsad_env* e) { return e ? e->ep.H * 25 : 0; }
+int hsad_env_hand_feature_size(const hsad_env* e) { return e ? e->ep.H * e->ep.nC * e->ep.nR : 0; }
+int hsad_env_get_rules(const hsad_env* e, hsad_env_rules* out) {
+  if (!e || !out) return set_error(HSAD_ERR_INVALID, "null argument");
+  out->colors = e->ep.nC;
+  out->ranks = e->ep.nR;
+  out->max_information_tokens = e->ep.max_info;
+  out->max_life_tokens = e->ep.max_life;
+  return HSAD_OK;
+}
+int hsad_env_max_deck_size(const hsad_env* e) { return e ? e->ep.deck_max : 0; }
 int hsad_env_num_games(const hsad_env* e) { return e ? e->ep.G : 0; }
 int hsad_env_num_players(const hsad_env* e) { return e ? e->ep.P : 0; }
 int hsad_env_games_per_workgroup(const hsad_env* e) { return e ? e->ep.gpw : 0; }

@@ -11,7 +11,10 @@ from . import _lib
 class BatchedHanabiEnv:
     def __init__(self, num_games, players=2, hand_size=5, seed=1, bomb=0, eps_list=(0.0,), max_len=80, sad=False,
                  shuffle_obs=False, shuffle_color=False, knowledge_mode=0, device="cuda:0", track_deck_history=True,
-                 deal_mode=0, games_per_workgroup=0, threads_per_workgroup=0):
+                 deal_mode=0, games_per_workgroup=0, threads_per_workgroup=0, colors=5, ranks=5, max_information_tokens=8,
+                 max_life_tokens=3):
+        """colors / ranks / max_information_tokens / max_life_tokens: the game's rules (HLE's keys; the full game is
+        5 / 5 / 8 / 3, each may be lowered to 1).  Every size (F, A, hand_feature_size) follows the rules."""
         self.lib = _lib.load_library()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -21,10 +24,13 @@ class BatchedHanabiEnv:
         cfg = _lib.EnvConfig(num_games, players, hand_size, int(bomb), int(seed), int(max_len), int(bool(sad)),
                              int(bool(shuffle_obs)), int(bool(shuffle_color)), int(knowledge_mode), len(eps_list),
                              dev_index, int(bool(track_deck_history)), int(deal_mode), int(games_per_workgroup), eps)
+        rules = _lib.EnvRules(int(colors), int(ranks), int(max_information_tokens), int(max_life_tokens))
         self.h = C.c_void_p()
-        _lib.check(self.lib.hsad_env_create(C.byref(cfg), C.byref(self.h)))
+        _lib.check(self.lib.hsad_env_create_rules(C.byref(cfg), C.byref(rules), C.byref(self.h)))
         L = self.lib
         self.G, self.P, self.H = num_games, players, hand_size
+        self.colors, self.ranks = int(colors), int(ranks)
+        self.max_information_tokens, self.max_life_tokens = int(max_information_tokens), int(max_life_tokens)
         self.F = L.hsad_env_feature_size(self.h)
         self.A = L.hsad_env_num_action(self.h)
         self.sad = bool(sad)
@@ -81,6 +87,15 @@ class BatchedHanabiEnv:
 
     def hand_feature_size(self):
         return self.lib.hsad_env_hand_feature_size(self.h)
+
+    def rules(self):
+        """the game's rules as the library holds them: {colors, ranks, max_information_tokens, max_life_tokens}"""
+        r = _lib.EnvRules()
+        _lib.check(self.lib.hsad_env_get_rules(self.h, C.byref(r)))
+        return {k: int(getattr(r, k)) for k, _ in _lib.EnvRules._fields_}
+
+    def max_deck_size(self):
+        return self.lib.hsad_env_max_deck_size(self.h)
 
     def state_bytes(self):
         return int(self.lib.hsad_env_state_bytes(self.h))

@@ -13,11 +13,12 @@ from .r2d2 import R2D2Agent, R2D2NetKernels
 
 
 def evaluate(weights, num_game, seed, bomb, sad, *, num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16",
-             shuffle_color=False):
+             shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3):
     """-> (mean score, fraction of perfect games, scores list, num perfect) like eval.evaluate.  `weights`: a weight dict, or
     an R2D2Agent / net already on the device (its online net acts for every player)"""
     env = BatchedHanabiEnv(num_game, players=num_player, hand_size=hand_size, seed=seed, bomb=bomb, eps_list=[0.0],
-                           max_len=-1, sad=bool(sad), shuffle_color=bool(shuffle_color), device=device, track_deck_history=False)
+                           max_len=-1, sad=bool(sad), shuffle_color=bool(shuffle_color), device=device, track_deck_history=False,
+                           colors=colors, ranks=ranks, max_information_tokens=max_information_tokens, max_life_tokens=max_life_tokens)
     if isinstance(weights, R2D2Agent):
         agent = R2D2Agent(weights.online, weights.online, 1, 0.99)
     elif hasattr(weights, "act") and hasattr(weights, "get_h0"):
@@ -56,7 +57,7 @@ def evaluate(weights, num_game, seed, bomb, sad, *, num_player=2, hand_size=5, d
             env.step(aa, aa)
             n, g, c = _drain_errors(env)
     scores = env.query()[:, 5].cpu().numpy().astype(np.int64)
-    perfect = int((scores == 25).sum())
+    perfect = int((scores == colors * ranks).sum())   # every firework complete: 25 in the full game
     return float(scores.mean()), perfect / num_game, scores.tolist(), perfect
 
 

@@ -9,11 +9,37 @@ from .env import BatchedHanabiEnv
 from .rela import ThreadLoop, _dev_key
 
 
+# HLE's HanabiGame keys this env honours with their bounds (the full game's value is the default), and those it refuses
+# unless they hold HLE's default.  Keys HLE does not know are ignored, as by the reference's parameter map.
+RULE_KEYS = (("colors", 5, 1, 5), ("ranks", 5, 1, 5), ("max_information_tokens", 8, 1, 8), ("max_life_tokens", 3, 1, 3))
+# the values of random_start_player accepted as "off", exactly (the compiled face, bindings/hsad_host.h, accepts the same)
+RANDOM_START_OFF = ("0", "false", "False")
+
+
+def game_rules(params):
+    """{colors, ranks, max_information_tokens, max_life_tokens} of a HanabiGame params dict; ValueError naming the key for
+    a value outside the bounds, observation_type != 1 (card knowledge) or random_start_player set"""
+    rules = {}
+    for key, dflt, lo, hi in RULE_KEYS:
+        v = int(params.get(key, dflt))
+        if not lo <= v <= hi:
+            raise ValueError("HanabiEnv: %s must be %d..%d (got %d)" % (key, lo, hi, v))
+        rules[key] = v
+    if int(params.get("observation_type", 1)) != 1:
+        raise ValueError("HanabiEnv: observation_type %s is not supported (only 1, card knowledge)" % params["observation_type"])
+    if str(params.get("random_start_player", "0")) not in RANDOM_START_OFF:
+        raise ValueError("HanabiEnv: random_start_player is not supported (got %s)" % params["random_start_player"])
+    return rules
+
+
 class HanabiEnv:
     def __init__(self, params, eps_list, max_len, sad, shuffle_obs, shuffle_color, verbose, device=None):
         self.cfg = dict(players=int(params["players"]), hand_size=int(params.get("hand_size", 5)),
                         seed=int(params.get("seed", 1)), bomb=int(params.get("bomb", 0)), eps_list=tuple(eps_list),
                         max_len=int(max_len), sad=bool(sad), shuffle_obs=bool(shuffle_obs), shuffle_color=bool(shuffle_color))
+        rules = game_rules(params)
+        if any(rules[k] != d for k, d, _, _ in RULE_KEYS):   # the full game keeps exactly the config it always had
+            self.cfg.update(rules)
         self.device = device   # None: the current device when driven standalone; the model runner's device inside a thread loop
         self._impl = None      # a 1-game device env, created on first standalone use
         self._vec = None       # (HanabiVecEnv, index) once appended to a vector env: the game then lives in ITS batch

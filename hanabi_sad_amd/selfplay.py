@@ -52,6 +52,11 @@ def init_weights(in_dim, hid_dim, out_dim, hand_size, seed, num_lstm_layer=2, nu
     return W
 
 
+def game_rules(args):
+    """the rule keywords of BatchedHanabiEnv / evaluate from the command line (absent in older argument namespaces: the full game)"""
+    return {k: int(getattr(args, k, d)) for k, d in (("colors", 5), ("ranks", 5), ("max_information_tokens", 8), ("max_life_tokens", 3))}
+
+
 class Trainer:
     def __init__(self, args, device="cuda:0", rank=0, world=1):
         self.args, self.device, self.rank, self.world = args, torch.device(device), rank, world
@@ -62,7 +67,7 @@ class Trainer:
         self.env = BatchedHanabiEnv(args.num_game if self.acting else 1, players=args.num_player, hand_size=args.hand_size,
                                     seed=args.seed + rank * args.num_game, bomb=args.train_bomb, eps_list=eps,
                                     max_len=args.max_len, sad=bool(args.sad), shuffle_color=bool(args.shuffle_color),
-                                    device=device, track_deck_history=False)
+                                    device=device, track_deck_history=False, **game_rules(args))
         W = init_weights(self.env.F, args.rnn_hid_dim, self.env.A, args.hand_size, args.seed, num_lstm_layer=args.num_lstm_layer)
         self.param_names = list(param_order(1, args.num_lstm_layer))
         # only the learner rank holds optimizer state; actor ranks receive parameters by broadcast
@@ -257,6 +262,12 @@ def parse_args(argv=None):
     p.add_argument("--sad", type=int, default=1)
     p.add_argument("--num_player", type=int, default=2)
     p.add_argument("--hand_size", type=int, default=5)
+    # the game's rules (HLE's keys; the full game by default): e.g. Hanabi-Small is --colors 2 --hand_size 2
+    # --max_information_tokens 3 --max_life_tokens 1
+    p.add_argument("--colors", type=int, default=5)
+    p.add_argument("--ranks", type=int, default=5)
+    p.add_argument("--max_information_tokens", type=int, default=8)
+    p.add_argument("--max_life_tokens", type=int, default=3)
     p.add_argument("--lr", type=float, default=6.25e-5)
     p.add_argument("--eps", type=float, default=1.5e-5)
     p.add_argument("--grad_clip", type=float, default=5.0)
@@ -489,7 +500,8 @@ def run_epochs(tr, args, rank=0, link=None):
         # context.pause() has no counterpart: actors and learner alternate on this GPU, nothing runs while we evaluate
         eval_seed = (9917 + epoch * 999999) % 7777777
         score, perfect, _, _ = evaluate(tr.learner.online.w, args.num_eval_game, eval_seed, args.eval_bomb, args.sad,
-                                        num_player=args.num_player, hand_size=args.hand_size, device=str(tr.device))
+                                        num_player=args.num_player, hand_size=args.hand_size, device=str(tr.device),
+                                        **game_rules(args))
         saved = False
         if saver is not None:
             force = "model_epoch%d" % epoch if (epoch > 0 and epoch % 50 == 0) else None

@@ -65,6 +65,25 @@ typedef struct hsad_env_config {
 int hsad_env_create(const hsad_env_config* cfg, hsad_env** out);
 void hsad_env_destroy(hsad_env* env);
 
+/* The game's rules: HLE's `colors`, `ranks`, `max_information_tokens`, `max_life_tokens` (HanabiGame params, passed
+ * whole by the reference: cpp/hanabi_env.h:27).  The full game is 5 / 5 / 8 / 3; each may be lowered to 1.  Card
+ * instances per colour: 3 of rank 0, 1 of rank R-1, 2 of every other rank (R = 1: 3); deck = C * sum.  Every size
+ * follows: A = 2H + (P-1)(C+R) + 1, F = P*H*C*R + P + (deck - P*H) + C*R + max_info + max_life + deck
+ * + LAL + P*H*(C*R + C + R) with LAL = 2P + 4 + C + R + 2H + C*R + 2 (SAD: + LAL). */
+typedef struct hsad_env_rules {
+  int32_t colors;                  /* 1..5 */
+  int32_t ranks;                   /* 1..5 */
+  int32_t max_information_tokens;  /* 1..8 */
+  int32_t max_life_tokens;         /* 1..3 */
+} hsad_env_rules;
+
+/* hsad_env_create with the game's rules; rules == NULL is the full game (exactly hsad_env_create).  Refuses values outside
+ * the bounds above and a deal larger than the deck (players * hand_size > deck). */
+int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rules, hsad_env** out);
+int hsad_env_get_rules(const hsad_env* env, hsad_env_rules* out);
+/* HanabiGame::MaxDeckSize: 50 for the full game */
+int hsad_env_max_deck_size(const hsad_env* env);
+
 /* HanabiEnv::featureSize / numAction / handFeatureSize (cpp/hanabi_env.h:53-72) and batch dims. */
 int hsad_env_feature_size(const hsad_env* env);
 int hsad_env_num_action(const hsad_env* env);

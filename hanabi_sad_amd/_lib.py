@@ -168,6 +168,8 @@ SIGNATURES = {
     "hsad_gemm_nt_bf16_group_splitk": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P]),
     "hsad_lstm_cell_fused_pair": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [_P] * 17),
     "hsad_lstm_set_exchange_mode": (C.c_int, [C.c_int]),
+    "hsad_lstm_debug_stall": (C.c_int, [C.c_int] * 6),
+    "hsad_lstm_debug_stall_fired": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
     "hsad_lstm_debug_timing": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
     "hsad_lstm_debug_timing32": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
     "hsad_lstm_debug_enable": (C.c_int, [C.c_int]),

@@ -935,45 +935,48 @@ int hsad_r2d2_learner_create(hsad_r2d2_net* online, hsad_r2d2_net* target, int T
   L->m = L->gflat + np;
   L->v = L->m + np;
   L->osc = L->v + np;
-  // counter blocks (zero-initialised: a ping-pong launch clears its partner for the next one)
+  // counter blocks (zero-initialised: a ping-pong launch clears its partner for the next one).  Every block starts 16-byte aligned: a
+  // launch's group words at its start are 64-bit atomics, and a block of an odd word count (odd row blocks x odd T) misaligned the next
+  // one -- the fused forward faulted at B = 96, T = 3.
+  auto blk = [](size_t words) { return (words + 3) & ~(size_t)3; };
   size_t sw = 0;
   for (int k = 0; k < 2; ++k)
     for (int r = 0; r < 4; ++r) {
       L->sync_words[k][r] = (size_t)(r + 1) * nrb * (Tc + 2) + 4;
-      sw += 2 * L->sync_words[k][r];
+      sw += 2 * blk(L->sync_words[k][r]);
     }
   const size_t s1 = nrb * ((size_t)T + 2) + 4;
   size_t fw = 0;
   for (int k = 0; k < 3; ++k) {
     L->fsync_words[k] = ((size_t)1 << k) * nrb * ((size_t)T + 2) + 4;
-    fw += 2 * L->fsync_words[k];
+    fw += 2 * blk(L->fsync_words[k]);
   }
   L->fbsync_words = (size_t)8 * nrb * ((size_t)T + 2) + 4;      // (split placement: two counter sets for the two recurrences + a projection stage)
-  fw += 2 * L->fbsync_words;
-  if (L->sync_buf.need((sw + s1 + fw) * 4)) {
+  fw += 2 * blk(L->fbsync_words);
+  if (L->sync_buf.need((sw + blk(s1) + fw) * 4)) {
     delete L;
     return HSAD_ERR_NOMEM;
   }
-  (void)hipMemset(L->sync_buf.p, 0, (sw + s1 + fw) * 4);
+  (void)hipMemset(L->sync_buf.p, 0, (sw + blk(s1) + fw) * 4);
   unsigned* sp = L->sync_buf.as<unsigned>();
   for (int k = 0; k < 2; ++k)
     for (int r = 0; r < 4; ++r) {
       for (int f = 0; f < 2; ++f) {
         L->sync[k][r][f] = sp;
-        sp += L->sync_words[k][r];
+        sp += blk(L->sync_words[k][r]);
       }
       L->flip[k][r] = 0;
     }
   L->sync1 = sp;
-  sp += s1;
+  sp += blk(s1);
   for (int k = 0; k < 3; ++k)
     for (int f = 0; f < 2; ++f) {
       L->fsync[k][f] = sp;
-      sp += L->fsync_words[k];
+      sp += blk(L->fsync_words[k]);
     }
   for (int f = 0; f < 2; ++f) {
     L->fbsync[f] = sp;
-    sp += L->fbsync_words;
+    sp += blk(L->fbsync_words);
   }
   for (int i = 0; i < 8; ++i) {
     L->ev_ck[i] = nullptr;
@@ -1517,7 +1520,7 @@ static int loss_bwd_impl(hsad_r2d2_learner* L, void* stream) {
         L->fb_split = use_split;
         L->fb_proj = use_proj;
         L->fb_sink = use_sink;
-        HIP_TRY(hipMemsetAsync(L->fbsync[0], 0, 2 * L->fbsync_words * 4, s));
+        HIP_TRY(hipMemsetAsync(L->fbsync[0], 0, (size_t)(L->fbsync[1] - L->fbsync[0] + L->fbsync_words) * 4, s));
         L->fbflip = 0;
         L->fb_tc = TL;
       }

@@ -55,6 +55,9 @@ namespace {
 static inline size_t seq_sync_words(int nrec, int T, int nrb) { return (size_t)nrec * nrb * (T + 2); }
 static int g_force_cross_xcd = 0;   // hsad_lstm_set_exchange_mode
 static int g_lstm_dbg_enable = 0;   // hsad_lstm_debug_enable (fused kernels: the phase stamps cost ~0.1 us each)
+static int g_stall_kernel = -1;      // hsad_lstm_debug_stall: which launch gets g_stall (-1: none)
+static LstmStall g_stall = {-1, -1, -1, -1, 0u};
+static LstmStall stall_for(int kernel) { return g_stall_kernel == kernel ? g_stall : LstmStall{-1, -1, -1, -1, 0u}; }
 
 // CUs of the current device: the persistent recurrences spin on sibling workgroups, so a launch must fit the chip with one
 // workgroup per CU (their LDS footprint allows no second one)
@@ -814,6 +817,29 @@ int hsad_lstm_set_exchange_mode(int force_cross_xcd) {
   return HSAD_OK;
 }
 
+int hsad_lstm_debug_stall(int kernel, int record, int row_block, int unit_block, int step, int microseconds) {
+  if (kernel < 0) {
+    g_stall_kernel = -1;
+    g_stall = LstmStall{-1, -1, -1, -1, 0u};
+    return HSAD_OK;
+  }
+  if (kernel > HSAD_STALL_BPTT_32 || record < 0 || row_block < 0 || unit_block < 0 || step < 0 || microseconds < 0)
+    return nfail(HSAD_ERR_INVALID, "lstm_debug_stall: bad arguments");
+  g_stall_kernel = kernel;
+  g_stall = LstmStall{record, row_block, unit_block, step, (unsigned)std::min(microseconds, 200) * 100u};      // 100 MHz clock
+  return HSAD_OK;
+}
+
+int hsad_lstm_debug_stall_fired(uint64_t* count, int reset) {
+  HIP_TRY(hipDeviceSynchronize());
+  if (count) HIP_TRY(hipMemcpyFromSymbol(count, HIP_SYMBOL(g_lstm_stall_fired), sizeof(uint64_t)));
+  if (reset) {
+    const uint64_t z = 0;
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_lstm_stall_fired), &z, sizeof(z)));
+  }
+  return HSAD_OK;
+}
+
 namespace {
 // residency stand-in of a pending communication kernel (an RCCL receive whose peer has not sent yet): every workgroup sleeps on its CU
 // until the host sets *flag (pinned host memory) or max_ticks of the 100 MHz clock have passed
@@ -1423,6 +1449,7 @@ int hsad_lstm_forward_fused(int nnet, int nlayer, int T, int Bn, int H, const hs
   m.force_cross_xcd = g_force_cross_xcd;
   m.zero_ptr = (unsigned*)next_sync_scratch;
   m.zero_words = next_sync_scratch ? (int)words : 0;
+  m.stall = stall_for(HSAD_STALL_FWD);
   const size_t lds = (size_t)(4 * 32 * H + 32 * 40) * sizeof(bf16_t) + 16 + 32;   // h tile + ring of three X tiles + publish staging + verdict / poll words
   hipEvent_t te0 = nullptr, te1 = nullptr;
   if (g_fused_timing.on) {
@@ -1603,6 +1630,7 @@ int hsad_lstm_backward_fused(int nnet, int nlayer, int Tc, int Bn, int H, const 
   m.force_cross_xcd = g_force_cross_xcd;
   m.zero_ptr = (unsigned*)next_sync_scratch;
   m.zero_words = next_sync_scratch ? (int)words : 0;
+  m.stall = stall_for(HSAD_STALL_BPTT_32);
   const size_t lds = (size_t)(32 * (4 * H + 8) + 32 * 136) * sizeof(bf16_t) + 16 + 16 * 64 * 16;
   hipEvent_t te0 = nullptr, te1 = nullptr;
   if (g_fused_timing.on) {
@@ -1711,6 +1739,7 @@ static int lstm_bptt_wide_launch(int Tc, int Bn, const hsad_lstm_fused_bwd_rec* 
   m.ctr_stride = ctr_stride;
   m.zero_ptr = (unsigned*)next_sync_scratch;
   m.zero_words = next_sync_scratch ? (int)words : 0;
+  m.stall = stall_for(HSAD_STALL_BPTT_WIDE);
   // K-split reduction 16 KB + staging of the published block + verdict words
   const size_t lds = (size_t)16 * 64 * 16 + (size_t)16 * (256 + 8) * sizeof(bf16_t) + 64;
   static bool attr_set = false;

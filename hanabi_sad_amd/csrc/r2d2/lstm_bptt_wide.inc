@@ -34,7 +34,10 @@ struct BpttWideStage {
   const bf16_t* tin;        // the tiles this stage contracts: own tiles of step t + 1 (0), the feeding layer's tiles of step t (1, 2)
   unsigned* tin_counters;   // the feeding stage's counters
   unsigned* counters;       // [nrb][ctr_stride] this stage's own, ONE running word per row block: += 1 per member and step, so "step t is
-                            // complete" (tile published (0) / dO rows published (1); unused (2)) reads word >= 8 (T - t) -- steps complete in order
+                            // complete" (tile published (0) / dO rows published (1); unused (2)) reads word >= 8 (T - t).  VALID ONLY WHILE NO
+                            // MEMBER RUNS MORE THAN ONE STEP AHEAD OF ANOTHER: 7 members two steps ahead of a stalled eighth add up to the same
+                            // word.  A recurrence (0) waits for all 8 members' step t + 1 before its step t anyway; the projection stage (1) waits
+                            // for it on this word before every step (its consumer reads member nb's rows only); the sink (2) signals nobody.
   int trace_slot;
   // recurrence
   const float* gates;       // fragment-major saved activations (lstm_fused_fwd_kernel)
@@ -67,6 +70,7 @@ struct BpttWideArgs {
   int force_cross_xcd;
   int ctr_stride;           // words between the row blocks' counters (32 = a 128-byte line each; less when the sequence is short: the
                             // region was sized for one word per step)
+  LstmStall stall;          // test hook (hsad_lstm_debug_stall): rec = stage
   unsigned* zero_ptr;
   int zero_words;
 };
@@ -87,6 +91,7 @@ __global__ __launch_bounds__(256) void lstm_bptt_wide_kernel(BpttWideArgs m) {
   const int stage = slot >> 3, nb = slot & 7;
   if (rb >= m.nrb || stage >= m.nstage) return;
   const BpttWideStage& a = m.st[stage];
+  const int stall_t = stall_step(m.stall, stage, rb, nb);
   const int nrb = m.nrb, T = m.T, Bn = m.Bn;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int kofs = (lane >> 4) * 8;
@@ -276,7 +281,10 @@ __global__ __launch_bounds__(256) void lstm_bptt_wide_kernel(BpttWideArgs m) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) mk[r] = bf2f(a.mask16[((size_t)t * Bn + rbase + r) * H + u]);
       }
-      if (!wait2(a.tin_counters, 8u * (unsigned)(T - t), nullptr, 0u, t)) return;
+      // the feeding layer's tile of step t; a projection stage also waits until all 8 members have published step t + 1 (their running
+      // counter: see BpttWideStage::counters -- without it a member could fall two steps behind its peers unnoticed by the consumer)
+      if (!wait2(a.tin_counters, 8u * (unsigned)(T - t), (a.kind == 1 && t < T - 1) ? a.counters : nullptr, 8u * (unsigned)(T - 1 - t), t)) return;
+      if (t == stall_t) lstm_stall_here(m.stall.ticks);
       LSTM_TRACE(2)
       float unused_[4];
       tile_product(a.tin + ((size_t)t * nrb + rb) * tile_elems, t, std::false_type{}, nullptr, unused_);
@@ -368,6 +376,7 @@ __global__ __launch_bounds__(256) void lstm_bptt_wide_kernel(BpttWideArgs m) {
                  8u * (unsigned)(T - t), t))
         return false;
     }
+    if (t == stall_t) lstm_stall_here(m.stall.ticks);
     LSTM_TRACE(2)
     f32x4 accf = f32x4{0.f, 0.f, 0.f, 0.f};
     if (rec) {

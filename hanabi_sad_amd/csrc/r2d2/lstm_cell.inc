@@ -498,6 +498,27 @@ __device__ u64_t* g_lstm_trace = nullptr;
 #define LSTM_TRACE(k) \
   if (trc) trc[t * kTraceK + (k)] = wall_clock64();
 
+// test-only stall of one workgroup at one step of a persistent recurrence launch (hsad_lstm_debug_stall): the launch's own record / stage
+// index, row block, unit block and step; rec < 0 = off.  The kernels compare the step once per step against stall_step(), which is -1 for
+// every workgroup but the matching one.
+struct LstmStall {
+  int rec, rb, nb, step;
+  unsigned ticks;           // 100 MHz clock ticks (<= 200 us: far below the ~8 M polls after which a wait gives up)
+};
+__device__ u64_t g_lstm_stall_fired;      // += 1 per stall served (hsad_lstm_debug_stall_fired)
+__device__ __forceinline__ int stall_step(const LstmStall& s, const int rec, const int rb, const int nb) {
+  return (s.rec == rec && s.rb == rb && s.nb == nb) ? s.step : -1;
+}
+// thread 0 sleeps on the clock, then every thread waits for it; called with no inline-asm load in flight
+__device__ __forceinline__ void lstm_stall_here(const unsigned ticks) {
+  if (threadIdx.x == 0) {
+    const u64_t until = wall_clock64() + ticks;
+    while (wall_clock64() < until) __builtin_amdgcn_s_sleep(32);
+    atomicAdd(&g_lstm_stall_fired, 1ull);
+  }
+  __syncthreads();
+}
+
 template <bool STATE, bool DBG = false>   // STATE: the new fp32 state (c, h) leaves the kernel next to the bf16 layer output; false: only h_out16 (target pass)
 __global__ __launch_bounds__(512) void lstm_cell_gemm256_kernel(LstmCellArgs a) {
   constexpr int BM = 256, BN = 256;

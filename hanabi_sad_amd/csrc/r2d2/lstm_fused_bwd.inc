@@ -62,7 +62,8 @@ struct LstmFusedBwdArgs {
 
 template <int KB>  // KB = 4H / 32
 __device__ __forceinline__ void lstm_fused_bwd_body(const LstmFusedBwdArgs& a, const int rb, const int nb, const int nrb, const int nunit_blocks,
-                                                    u64_t* group_word, const int nmember, const int force_cross_xcd) {
+                                                    u64_t* group_word, const int nmember, const int force_cross_xcd, const int stall_t,
+                                                    const unsigned stall_ticks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int K = KB * 32, H = K / 4, KQ = KB / 4;
   constexpr int WS = K + 8;
@@ -159,6 +160,7 @@ __device__ __forceinline__ void lstm_fused_bwd_body(const LstmFusedBwdArgs& a, c
     for (int t = a.T - 1; t >= 0; --t) {
       LSTM_TRACE(0)
       if (!wait_ctr(a.xin_counters, (unsigned)(t * nrb + rb), 0, nullptr, 0u, fast_x, fast_x)) return;
+      if (t == stall_t) lstm_stall_here(stall_ticks);
       LSTM_TRACE(2)
       const bf16_t* b0 = a.xin + ((size_t)t * nrb + rb) * tile_elems + (size_t)wave * KQ * 1024 + lane_off;
 #pragma unroll
@@ -334,6 +336,7 @@ __device__ __forceinline__ void lstm_fused_bwd_body(const LstmFusedBwdArgs& a, c
       } else {
         __syncthreads();
       }
+      if (t == stall_t) lstm_stall_here(stall_ticks);      // (test hook: behind the own group's wait, in front of the tile's loads)
       LSTM_STAMP(dbg_base + 2)   // wait for dG_{t+1}
       LSTM_TRACE(2)
       if (t < a.T - 1) {
@@ -378,6 +381,8 @@ __device__ __forceinline__ void lstm_fused_bwd_body(const LstmFusedBwdArgs& a, c
       any = true;
       LSTM_STAMP(dbg_base + 3)   // dG tile loads + MFMAs
       LSTM_TRACE(3)
+    } else if (t == stall_t) {      // (the sequence's last step: no own wait -- behind the X stream's product)
+      lstm_stall_here(stall_ticks);
     }
     if (has_dOc) {     // this step's dO rows from the projection stage (it runs ahead with the layer above: normally already seen)
       if (!dO_seen && !wait_ctr(a.dO_counters, (unsigned)(t * nrb + rb), 0, nullptr, 0u, 0, 0)) return;
@@ -509,6 +514,7 @@ struct LstmFusedBwdArgsN {
   unsigned* zero_ptr;
   int zero_words;
   int split;
+  LstmStall stall;      // test hook (hsad_lstm_debug_stall): rec = the internal record net * nl + layer
 };
 
 template <int KB>
@@ -522,7 +528,8 @@ __global__ __launch_bounds__(256) void lstm_fused_bwd_kernel(LstmFusedBwdArgsN m
     if (g >= m.nnet * m.nrb * m.nl) return;
     const int SG = g / m.nl, layer = g - SG * m.nl;
     const int net = SG / m.nrb, rb = SG - net * m.nrb;
-    lstm_fused_bwd_body<KB>(m.r[net * m.nl + layer], rb, nb, m.nrb, m.nunit, m.group_words + g, m.nunit, m.force_cross_xcd);
+    lstm_fused_bwd_body<KB>(m.r[net * m.nl + layer], rb, nb, m.nrb, m.nunit, m.group_words + g, m.nunit, m.force_cross_xcd,
+                            stall_step(m.stall, net * m.nl + layer, rb, nb), m.stall.ticks);
     return;
   }
   const int per = m.nl * m.nunit;
@@ -531,6 +538,7 @@ __global__ __launch_bounds__(256) void lstm_fused_bwd_kernel(LstmFusedBwdArgsN m
   if (SG >= m.nnet * m.nrb) return;
   const int layer = within / m.nunit, nb = within - layer * m.nunit;
   const int net = SG / m.nrb, rb = SG - net * m.nrb;
-  lstm_fused_bwd_body<KB>(m.r[net * m.nl + layer], rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd);
+  lstm_fused_bwd_body<KB>(m.r[net * m.nl + layer], rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd,
+                          stall_step(m.stall, net * m.nl + layer, rb, nb), m.stall.ticks);
 }
 

@@ -51,7 +51,8 @@ struct LstmFusedArgs {
 
 template <int KB, bool STACKED, bool KEEP>  // KB = H / 32; STACKED: input published by the layer below during this launch; KEEP: gates / cseq stored
 __device__ __forceinline__ void lstm_fused_fwd_body(const LstmFusedArgs& a, const int rb, const int nb, const int nrb, const int nunit,
-                                                    u64_t* group_word, const int nmember, const int force_cross_xcd) {
+                                                    u64_t* group_word, const int nmember, const int force_cross_xcd, const int stall_t,
+                                                    const unsigned stall_ticks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int H = KB * 32;
   constexpr int TILE = 32 * H;                 // elements of one activation tile (32 rows x H)
@@ -380,6 +381,7 @@ __device__ __forceinline__ void lstm_fused_fwd_body(const LstmFusedArgs& a, cons
       LSTM_STAMP(dbg_base + 4)   // whole X tile (late): wait + DMA + MFMAs
     }
     if (pf && x_have != xp) pf = false;
+    if (t == stall_t) lstm_stall_here(stall_ticks);      // (test hook: every wait and product of the step done, its publish late)
     // lanes n and n + 8 hold {i|f, g|o} of one unit for both row halves: swap so that lane n < 8 finishes row half 0 and lane
     // n >= 8 row half 1 (i, f, g, o of ONE (unit, row half) each)
     float hlast[4];
@@ -494,6 +496,7 @@ struct LstmFusedArgsN {
   int force_cross_xcd;
   unsigned* zero_ptr;   // optional: the NEXT launch's sync scratch, zeroed by this launch
   int zero_words;
+  LstmStall stall;      // test hook (hsad_lstm_debug_stall): rec = net * nl + layer
 };
 
 template <int KB>
@@ -510,12 +513,13 @@ __global__ __launch_bounds__(256) void lstm_fused_fwd_kernel(LstmFusedArgsN m) {
   const int layer = within / m.nunit, nb = within - layer * m.nunit;
   const int net = SG / m.nrb, rb = SG - net * m.nrb;
   const LstmFusedArgs& a = m.r[net * m.nl + layer];
+  const int st = stall_step(m.stall, net * m.nl + layer, rb, nb);
   if (!a.xin_counters) {
-    if (a.gates) lstm_fused_fwd_body<KB, false, true>(a, rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd);
-    else lstm_fused_fwd_body<KB, false, false>(a, rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd);
+    if (a.gates) lstm_fused_fwd_body<KB, false, true>(a, rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd, st, m.stall.ticks);
+    else lstm_fused_fwd_body<KB, false, false>(a, rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd, st, m.stall.ticks);
   } else {
-    if (a.gates) lstm_fused_fwd_body<KB, true, true>(a, rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd);
-    else lstm_fused_fwd_body<KB, true, false>(a, rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd);
+    if (a.gates) lstm_fused_fwd_body<KB, true, true>(a, rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd, st, m.stall.ticks);
+    else lstm_fused_fwd_body<KB, true, false>(a, rb, nb, m.nrb, m.nunit, m.group_words + SG, per, m.force_cross_xcd, st, m.stall.ticks);
   }
 }
 

@@ -402,6 +402,17 @@ int hsad_lstm_cell_set_variant(int tile, int pp);
 /* testing: force_cross_xcd != 0 makes every persistent recurrence use the cross-XCD hand-off protocol even when its
  * workgroups are co-located (the default, 0, picks per group at start-up); results must not depend on it */
 int hsad_lstm_set_exchange_mode(int force_cross_xcd);
+/* testing: make one workgroup of a persistent recurrence launch late on purpose.  While set, every launch of `kernel` (HSAD_STALL_*)
+ * copies the hook into its arguments; the one workgroup (record, row_block, unit_block) sleeps `microseconds` (at most 200; a bounded
+ * delay, far below any wait's give-up) in step `step`, behind that step's counter wait and in front of its hand-off stores, and adds 1
+ * to a device word.  record: the launch's own index -- fused forward net * nlayer + layer, wide BPTT the stage (0 top layer,
+ * 1 projection, 2 lower layer, 3 sink), 32 x 32 BPTT the internal record.  kernel < 0 clears the hook.  Results must not change. */
+#define HSAD_STALL_FWD 0
+#define HSAD_STALL_BPTT_WIDE 1
+#define HSAD_STALL_BPTT_32 2
+int hsad_lstm_debug_stall(int kernel, int record, int row_block, int unit_block, int step, int microseconds);
+/* the device word of hsad_lstm_debug_stall: stalls served since the last reset (synchronises the device) */
+int hsad_lstm_debug_stall_fired(uint64_t* count, int reset);
 /* developer phase timers of the persistent recurrences (100 MHz ticks summed over the steps of one workgroup; slots
  * 0-5 forward: wait, h loads, MFMA, cell update, publish, state stores; 8-11 backward: wait, loads+MFMA, cell backward,
  * publish); out16 may be NULL; reset != 0 clears them */

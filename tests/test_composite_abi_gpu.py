@@ -372,33 +372,83 @@ def test_short_sequences_run_the_persistent_launches_with_narrower_counter_strid
     is short the region (sized for one word per step) only holds a narrower stride (2 words at T = 2).  The 16-row x 64-unit BPTT launch
     against the 32 x 32 one (own counter layout, a word per step) on the same forward: same loss, priorities and LSTM weight gradients bit
     for bit, twice each (the second visit reuses the ping-pong counter blocks), and no timeout word set."""
+    _wide_against_32x32(128, T, with_chunked=True)
+
+
+@pytest.mark.parametrize("B,T", [(32, 2), (32, 80), (64, 17), (96, 2), (96, 80)])
+def test_wide_bptt_at_small_batches_gives_the_bits_of_the_32x32_launch(B, T):
+    """the wide launch takes every B that is a multiple of 32 up to 128 (selfplay --batchsize 32 / 64 / 96, VDN at batchsize 16 - 48): B / 16
+    row blocks on as many XCDs -- the other XCDs' workgroups return at once --, bias_finish adds nrb partial rows and the counter stride
+    shrinks with T * B / 32.  Same comparison as above; a 1 us stall hook on each launch proves which kernel ran.  (The four-stage launch
+    needs T * B to be a multiple of 64: at B = 96 only even T reach it.)"""
+    _wide_against_32x32(B, T, with_chunked=False)
+
+
+@pytest.mark.parametrize("B,T", [(96, 3), (32, 5)])
+def test_odd_row_blocks_and_odd_sequence_lengths_keep_the_counter_blocks_aligned(B, T):
+    """the learner's counter blocks are nrb (T + 2) + 4 words: with an odd number of 32-row blocks and an odd T that is odd, and the next
+    block -- whose first words a launch adds to with 64-bit atomics (the group handshake) -- lost its 8-byte alignment; the fused forward
+    faulted at B = 96, T = 3.  Every block starts 16-byte aligned now: two updates, finite values, the same loss and priorities, no timeout.
+    (T * B is no multiple of 64 here: the BPTT runs outside the four-stage launch and adds some gradients with float atomics.)"""
     from hanabi_sad_amd.composite import CompositeLearner
     from tests.test_r2d2_kernels_gpu import _rand_batch, _rand_net
-    F, A, H, B = 838, 21, 512, 128
-    W, Wt = _rand_net(F, H, A, seed=41), _rand_net(F, H, A, seed=42)
-    batch, weight = _rand_batch(T, B, F, A, seed=T)
+    F, A, H = 838, 21, 512
+    W, Wt = _rand_net(F, H, A, seed=45), _rand_net(F, H, A, seed=46)
+    batch, weight = _rand_batch(T, B, F, A, seed=1000 * B + T)
     L = CompositeLearner(W, Wt, 3, 0.999, device=DEV)
+    res = []
+    for rep in range(2):
+        loss, prio = L.loss(batch, weight, 0.25)
+        res.append([loss.clone(), prio.clone()] + [v.clone() for v in L.grad.values()])
+    L.check_sync()
+    for i, (a, b) in enumerate(zip(*res)):
+        assert torch.isfinite(a).all(), i
+        assert torch.equal(a, b) if i < 2 else relerr(a, b) < 1e-5, (i, relerr(a, b))
+
+
+def _wide_against_32x32(B, T, with_chunked):
+    import ctypes as C
+    from hanabi_sad_amd import _lib
+    from hanabi_sad_amd.composite import CompositeLearner
+    from tests.test_r2d2_kernels_gpu import _rand_batch, _rand_net
+    lib = _lib.load_library()
+    F, A, H = 838, 21, 512
+    W, Wt = _rand_net(F, H, A, seed=41), _rand_net(F, H, A, seed=42)
+    batch, weight = _rand_batch(T, B, F, A, seed=T if B == 128 else 1000 * B + T)
+    L = CompositeLearner(W, Wt, 3, 0.999, device=DEV)
+    schedules = [("wide", 57 | (1 << 8), 1), ("32 x 32", 57 | (1 << 8) | (1 << 25), 2)] + ([("chunked", 0, -1)] if with_chunked else [])
     res = {}
     for rep in range(2):
-        for name, flags in (("wide", 57 | (1 << 8)), ("32 x 32", 57 | (1 << 8) | (1 << 25)), ("chunked", 0)):
+        for name, flags, kernel in schedules:      # kernel: HSAD_STALL_BPTT_WIDE / HSAD_STALL_BPTT_32
             L.set_fused(flags)
-            loss, prio = L.loss(batch, weight, 0.25)
+            if kernel >= 0 and rep == 0:
+                _lib.check(lib.hsad_lstm_debug_stall_fired(None, 1))
+                _lib.check(lib.hsad_lstm_debug_stall(kernel, 0, 0, 0, 0, 1))
+            try:
+                loss, prio = L.loss(batch, weight, 0.25)
+            finally:
+                lib.hsad_lstm_debug_stall(-1, 0, 0, 0, 0, 0)
             torch.cuda.synchronize()
+            if kernel >= 0 and rep == 0:
+                n = C.c_uint64(0)
+                _lib.check(lib.hsad_lstm_debug_stall_fired(C.byref(n), 1))
+                assert n.value == 1, (B, T, name, "the launch did not run", n.value)
             got = (loss.clone(), prio.clone(), {k: v.clone() for k, v in L.grad.items()})
             if name in res:
-                assert torch.equal(got[0], res[name][0]) and torch.equal(got[1], res[name][1]), (T, name)
+                assert torch.equal(got[0], res[name][0]) and torch.equal(got[1], res[name][1]), (B, T, name)
                 for k in got[2]:
                     if k.startswith("lstm.weight"):
-                        assert torch.equal(got[2][k], res[name][2][k]), (T, name, k)
+                        assert torch.equal(got[2][k], res[name][2][k]), (B, T, name, k)
             res[name] = got
     L.check_sync()
-    (lw, pw_, gw), (l3, p3, g3), (lc, pc, gc) = res["wide"], res["32 x 32"], res["chunked"]
-    assert torch.equal(lw, l3) and torch.equal(pw_, p3)
+    (lw, pw_, gw), (l3, p3, g3) = res["wide"], res["32 x 32"]
+    assert torch.equal(lw, l3) and torch.equal(pw_, p3), (B, T)
     for k in gw:
         if k.startswith("lstm.weight"):
-            assert torch.equal(gw[k], g3[k]), (T, k, relerr(gw[k], g3[k]))
-        assert relerr(gw[k], g3[k]) < 3e-4, (T, k, relerr(gw[k], g3[k]))
-        assert relerr(gw[k], gc[k]) < 6e-3, (T, k, relerr(gw[k], gc[k]))     # another schedule: fp32 summation orders differ
+            assert torch.equal(gw[k], g3[k]), (B, T, k, relerr(gw[k], g3[k]))
+        assert relerr(gw[k], g3[k]) < 3e-4, (B, T, k, relerr(gw[k], g3[k]))
+        if with_chunked:
+            assert relerr(gw[k], res["chunked"][2][k]) < 6e-3, (B, T, k, relerr(gw[k], res["chunked"][2][k]))     # another schedule: fp32 summation orders differ
 
 
 def test_fused_recurrences_soak_every_evaluation_gives_the_same_bits():

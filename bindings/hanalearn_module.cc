@@ -18,7 +18,11 @@ PYBIND11_MODULE(hanalearn, m) {
       .def("get_score", &HanabiEnv::get_score)
       .def("get_life", &HanabiEnv::get_life)
       .def("get_info", &HanabiEnv::get_info)
-      .def("get_fireworks", &HanabiEnv::get_fireworks);
+      .def("get_fireworks", &HanabiEnv::get_fireworks)
+      .def("reset", &HanabiEnv::reset, "-> {priv_s [P, F], legal_move [P, A], eps [P], own_hand [P, 3 * hand]} (cpp/hanabi_env.cc:9-47)")
+      .def("step", &HanabiEnv::step, py::arg("action"), "{a, greedy_a (optional)} int64 [P] -> (obs, reward, terminal); raises on an illegal move")
+      .def("move_is_legal", &HanabiEnv::move_is_legal, py::arg("uid"))
+      .def("deck_history", &HanabiEnv::deck_history);
 
   py::class_<HanabiVecEnv, std::shared_ptr<HanabiVecEnv>>(m, "HanabiVecEnv")
       .def(py::init<>())

@@ -22,6 +22,26 @@ PYBIND11_MODULE(rela, m) {
     HSAD_FIELD(seq_len);
 #undef HSAD_FIELD
   }
+  {
+    py::class_<FFTransition, std::shared_ptr<FFTransition>> t(m, "FFTransition");
+    t.def(py::init([](py::object obs, py::object action, py::object reward, py::object terminal, py::object bootstrap, py::object next_obs) {
+            auto dict_or_empty = [](py::object d) { return d.is_none() ? py::object(py::dict()) : d; };
+            return std::make_shared<FFTransition>(
+                FFTransition{dict_or_empty(obs), dict_or_empty(action), reward, terminal, bootstrap, dict_or_empty(next_obs)});
+          }),
+          py::arg("obs") = py::none(), py::arg("action") = py::none(), py::arg("reward") = py::none(), py::arg("terminal") = py::none(),
+          py::arg("bootstrap") = py::none(), py::arg("next_obs") = py::none());
+#define HSAD_FIELD(name) t.def_readwrite(#name, &FFTransition::name)
+    HSAD_FIELD(obs);
+    HSAD_FIELD(action);
+    HSAD_FIELD(reward);
+    HSAD_FIELD(terminal);
+    HSAD_FIELD(bootstrap);
+    HSAD_FIELD(next_obs);
+#undef HSAD_FIELD
+    t.def("index", &FFTransition::index, py::arg("i"), "element i of every batched field (transition.cc:9-27)");
+    t.def("to_dict", &FFTransition::to_dict, "obs + action + next_-prefixed next_obs + reward / terminal / bootstrap (transition.cc:29-47)");
+  }
 
   // capacity, seed, alpha (priority exponent), beta (importance exponent), prefetch (accepted, unused: sampling is a stream-ordered kernel)
   {
@@ -31,6 +51,7 @@ PYBIND11_MODULE(rela, m) {
     r.def("num_add", &RNNPrioritizedReplay::num_add, "sequences added so far");
     r.def("sample", &RNNPrioritizedReplay::sample, py::arg("batchsize"), py::arg("device"), "-> (RNNTransition of [T, B, ...] tensors, weight [B])");
     r.def("update_priority", &RNNPrioritizedReplay::update_priority, py::arg("priority"));
+    r.def("get", &RNNPrioritizedReplay::get, py::arg("idx"), "the idx-th stored sequence from the ring head, as an RNNTransition");
   }
 
   py::class_<ThreadLoop, std::shared_ptr<ThreadLoop>>(m, "ThreadLoop");

@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libhsad.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("hsad_env.hip", "hsad_replay.hip", "hsad_r2d2.hip", "hsad_r2d2_f32.hip", "hsad_agent.hip", "hsad_comm.hip",
-                                                      "hsad_actor.hip")]
+                                                      "hsad_actor.hip", "hsad_eval.hip")]
 _lib = None
 
 
@@ -97,6 +97,7 @@ SIGNATURES = {
     "hsad_env_bind_outputs": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "hsad_env_bind_packed": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int]),
     "hsad_env_reset": (C.c_int, [_P, _P]),
+    "hsad_env_reseed": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "hsad_env_step": (C.c_int, [_P, _P, _P, _P]),
     "hsad_env_policy_random": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
     "hsad_env_rollout_random": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
@@ -260,6 +261,9 @@ SIGNATURES = {
     "hsad_comm_star_collect": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "hsad_comm_star_serve": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int64, _P]),
     "hsad_comm_all_stats": (_P, [_P]),
+    "hsad_seat_gather": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "hsad_seat_scatter": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "hsad_seating_stats": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "hsad_ipc_handle_bytes": (C.c_int, []),
     "hsad_ipc_alloc": (C.c_int, [C.c_int64, C.POINTER(_P), _P, C.c_int]),
     "hsad_ipc_free": (C.c_int, [_P]),

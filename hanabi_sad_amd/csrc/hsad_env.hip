@@ -1586,20 +1586,26 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
 }
 
 // ---- init: zero planes, seed mt19937 (std::mt19937::seed: x0 = s; x_i = 1812433253*(x ^ x>>30) + i) ---
-__global__ void init_kernel(EnvParams ep) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+// game g's generator is seeded seed0 + (g % period); period <= 0: seed0 + g (hsad_env_create; hsad_env_reseed with no wrap)
+__device__ __forceinline__ void init_game(const EnvParams& ep, int g, int seed0, int period) {
   if (g >= ep.Gpad) return;
   for (int pl = 0; pl < ep.npl; ++pl) ep.planes[(size_t)pl * ep.Gpad + g] = 0u;
   if (g >= ep.G) return;
   ep.planes[(size_t)PL_MISC * ep.Gpad + g] = 0u;  // not started, last_score = -1
   uint32_t* mt = ep.mt + (size_t)g * kMtN;
-  uint32_t x = (uint32_t)(ep.seed0 + g);
+  uint32_t x = (uint32_t)(seed0 + (period > 0 ? g % period : g));
   mt[0] = x;
   for (int i = 1; i < kMtN; ++i) {
     x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
     mt[i] = x;
   }
   ep.act_count[g] = 0u;
+}
+
+__global__ void init_kernel(EnvParams ep) { init_game(ep, blockIdx.x * blockDim.x + threadIdx.x, ep.seed0, 0); }
+
+__global__ void reseed_kernel(EnvParams ep, int seed0, int period) {
+  init_game(ep, blockIdx.x * blockDim.x + threadIdx.x, seed0, period);
 }
 
 // ---- counter-based random-legal policy (kernel form; helpers are defined above env_kernel) ----
@@ -2126,6 +2132,26 @@ int hsad_env_reset(hsad_env* e, void* stream) {
   if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
   launch_env(e, 0, nullptr, nullptr, (hipStream_t)stream, 0, e->ep.Gpad);
   HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_env_reseed(hsad_env* e, int32_t seed0, int32_t period, void* stream) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  e->ep.seed0 = seed0;
+  hipLaunchKernelGGL(reseed_kernel, dim3((e->ep.Gpad + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->ep, (int)seed0, (int)period);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+// shared with csrc/hsad_eval.hip (not part of the public header): the plane of per-game status words the seat kernels read --
+// started [15] | term [14] | last_score + 1 [16..21] -- and the sizes that go with it
+int hsad_internal_env_status(const hsad_env* e, const uint32_t** misc, int* G, int* P, int* A, int* perfect_score) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  *misc = e->ep.planes + (size_t)PL_MISC * e->ep.Gpad;
+  *G = e->ep.G;
+  *P = e->ep.P;
+  *A = e->ep.A;
+  *perfect_score = e->ep.nC * e->ep.nR;
   return HSAD_OK;
 }
 

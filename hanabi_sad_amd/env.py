@@ -114,6 +114,11 @@ class BatchedHanabiEnv:
         _lib.check(self.lib.hsad_env_reset(self.h, self._stream()))
         return self.obs()
 
+    def reseed(self, seed, period=0):
+        """every game back to "not started", game g seeded seed + (g % period) (period <= 0: seed + g, as at construction);
+        the next reset() starts all games.  Groups of `period` games then play the same deals."""
+        _lib.check(self.lib.hsad_env_reseed(self.h, int(seed), int(period), self._stream()))
+
     def step(self, a, greedy_a=None):
         assert a.dtype == torch.int64 and a.is_contiguous() and a.device == self.legal_move.device
         g = greedy_a if greedy_a is not None else (a if self.sad else None)

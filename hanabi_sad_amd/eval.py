@@ -8,6 +8,7 @@ with the key names net.0.*, lstm.*_l{0,1}, fc_v.*, fc_a.*, pred.* (common_utils/
 import numpy as np
 import torch
 
+from . import _lib
 from .env import BatchedHanabiEnv
 from .r2d2 import R2D2Agent, R2D2NetKernels
 
@@ -59,6 +60,267 @@ def evaluate(weights, num_game, seed, bomb, sad, *, num_player=2, hand_size=5, d
     scores = env.query()[:, 5].cpu().numpy().astype(np.int64)
     perfect = int((scores == colors * ranks).sum())   # every firework complete: 25 in the full game
     return float(scores.mean()), perfect / num_game, scores.tolist(), perfect
+
+
+# ---------------------------------------------------------------------------------------------------------
+# cross-play: every seating of a model pool over the same deals, as one batched run
+# (pyhanabi/tools/eval_model.py produces one cell of models/op_raw_data.txt per invocation)
+# ---------------------------------------------------------------------------------------------------------
+def env_dims(num_player=2, hand_size=5, sad=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3):
+    """(feature_size, num_action) of BatchedHanabiEnv for these rules, computed on the host (the canonical encoder's sections:
+    hands | board | discards | last action | card knowledge (| SAD's last action))"""
+    P, H, Cn, Rn = int(num_player), int(hand_size), int(colors), int(ranks)
+    deck = Cn * (3 if Rn == 1 else 2 * Rn)
+    last_action = P + 4 + P + Cn + Rn + H + H + Cn * Rn + 2
+    board = deck - P * H + Cn * Rn + int(max_information_tokens) + int(max_life_tokens)
+    F = P * H * Cn * Rn + P + board + deck + last_action + P * H * (Cn * Rn + Cn + Rn)
+    return F + (last_action if sad else 0), 2 * H + (P - 1) * (Cn + Rn) + 1
+
+
+def seating_rows(seatings, num_game, num_model=None):
+    """the rows each model owns in a tournament batch: game g = s * num_game + d is deal d of seating s, its seat p is the flat row
+    g * P + p and belongs to model seatings[s][p].  -> one ascending int32 array per model (empty for a model no seating names)"""
+    seatings = np.asarray(seatings, dtype=np.int64)
+    owner = np.repeat(seatings, int(num_game), axis=0).reshape(-1)
+    K = int(num_model) if num_model is not None else (int(seatings.max()) + 1 if seatings.size else 0)
+    return [np.nonzero(owner == k)[0].astype(np.int32) for k in range(K)]
+
+
+def _model_dims(x):
+    """(in_dim, out_dim, exact) of a pool member without touching a device; exact=False: the model reads the first in_dim features
+    of a longer observation (obl.OBLAgent on the SAD observation); None when the object does not tell"""
+    if isinstance(x, dict):
+        return int(x["net.0.weight"].shape[1]), int(x["fc_a.weight"].shape[0]), True
+    net = getattr(x, "online", None)
+    if net is not None and hasattr(net, "in_dim") and hasattr(net, "A"):          # obl.OBLNetKernels
+        return int(net.in_dim), int(net.A), False
+    if net is not None and hasattr(net, "F") and hasattr(net, "A"):
+        return int(net.F), int(net.A), True
+    if hasattr(x, "F") and hasattr(x, "A"):                                         # a bare net
+        return int(x.F), int(x.A), True
+    return None
+
+
+def _check_pool(agents, seatings, num_player, F, A):
+    """the refusals of play_seatings, all before any device work; -> (models as given, paths read into weight dicts; seatings [S, P])"""
+    seatings = np.asarray(seatings)
+    if seatings.ndim != 2 or seatings.shape[1] != num_player:
+        raise ValueError("seatings must be [S, %d] (one model index per seat of a %d-player game); got shape %s"
+                         % (num_player, num_player, tuple(seatings.shape)))
+    if seatings.shape[0] < 1:
+        raise ValueError("seatings is empty")
+    if not np.issubdtype(seatings.dtype, np.integer):
+        raise ValueError("seatings must hold integer model indices; got dtype %s" % seatings.dtype)
+    K = len(agents)
+    bad = np.argwhere((seatings < 0) | (seatings >= K))
+    if len(bad):
+        s, p = bad[0]
+        raise ValueError("seating %d seat %d names model %d; the pool has models 0..%d" % (s, p, seatings[s, p], K - 1))
+    models = []
+    for k, x in enumerate(agents):
+        if isinstance(x, (str, bytes)) or hasattr(x, "__fspath__"):
+            x = load_weights(x)
+        dims = _model_dims(x)
+        if dims is not None:
+            in_dim, out_dim, exact = dims
+            if (in_dim != F if exact else in_dim > F) or out_dim != A:
+                raise ValueError("model %d has %d inputs and %d actions; the env of this game has %d features and %d actions "
+                                 "(sad and the game's rules decide both)" % (k, in_dim, out_dim, F, A))
+        models.append(x)
+    return models, seatings.astype(np.int64)
+
+
+def _acting_agent(x, precision, device):
+    """what evaluate() turns its `weights` argument into"""
+    if isinstance(x, R2D2Agent):
+        return R2D2Agent(x.online, x.online, 1, 0.99)
+    if hasattr(x, "act") and hasattr(x, "get_h0"):
+        return x
+    if hasattr(x, "trunk"):
+        return R2D2Agent(x, x, 1, 0.99)
+    if precision == "bf16":
+        from .composite import CNet, CompositeAgent
+        net = CNet(x, device)
+        return CompositeAgent(net, net, 1, 0.99)
+    net = R2D2NetKernels.make(x, device, precision)
+    return R2D2Agent(net, net, 1, 0.99)
+
+
+class SeatingScores:
+    """what play_seatings returns: scores int64 [S, num_game]; totals int64 [S, 4] = (sum score, sum score^2, perfect, finished) as
+    hsad_seating_stats reduced them on the device; mean / sem / perfect float64 [S] from those integers (sem = population std /
+    sqrt(n), tools/eval_model.py:41-42)"""
+
+    def __init__(self, scores, totals, seatings):
+        import math
+        self.scores, self.totals, self.seatings = scores, totals, seatings
+        n = scores.shape[1]
+        self.num_game = n
+        t = [[int(v) for v in row] for row in totals]
+        self.mean = np.array([r[0] / n for r in t], dtype=np.float64)
+        self.sem = np.array([math.sqrt(n * r[1] - r[0] * r[0]) / n / math.sqrt(n) for r in t], dtype=np.float64)
+        self.perfect = np.array([r[2] / n for r in t], dtype=np.float64)
+
+
+class _SeatedModel:
+    """one pool member inside a tournament batch: its rows, its act operands and its carried state"""
+
+    def __init__(self, agent, rows, env, device):
+        self.agent, self.n = agent, int(len(rows))
+        self.rows = torch.from_numpy(rows).to(device)
+        self.bf16 = bool(getattr(agent, "accepts_bf16_obs", False))
+        self.Kp = agent.online.Fp if self.bf16 else env.F
+        self.obs = torch.empty(self.n, self.Kp, dtype=torch.bfloat16 if self.bf16 else torch.float32, device=device)
+        self.legal = torch.empty(self.n, env.A, dtype=torch.float32, device=device)
+        self.eps = torch.zeros(self.n, dtype=torch.float32, device=device)
+        self.hid = None
+
+
+class _TournamentBatch:
+    """one env object of S x n games (seating-major) and the pool seated on it; play(seed) runs one chunk of n deals"""
+
+    def __init__(self, agents, seatings, n, env_kw, device):
+        S, P = seatings.shape
+        self.n, self.S = n, S
+        self.env = env = BatchedHanabiEnv(S * n, players=P, seed=0, eps_list=[0.0], max_len=-1, device=device, track_deck_history=False,
+                                          **env_kw)
+        self.lib, self.device = env.lib, env.device
+        self.models = [_SeatedModel(ag, rows, env, self.device)
+                       for ag, rows in zip(agents, seating_rows(seatings, n, len(agents))) if len(rows)]
+        widths = {m.Kp for m in self.models if m.bf16}
+        if len(widths) > 1:
+            raise _lib.HsadError("the pool's bf16 nets pad the observation to different row lengths: %s" % sorted(widths))
+        if widths:     # the env writes the first GEMM's operand itself; the 3.3 KB float32 row only if a pool member reads it
+            env.enable_packed(bf16_row_len=widths.pop(), keep_float32=any(not m.bf16 for m in self.models))
+        self.stats = torch.zeros(S, 4, dtype=torch.int64, device=self.device)
+        self.unfinished = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.host = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)]
+        self.copied = [torch.cuda.Event() for _ in range(2)]
+
+    def _act(self, m):
+        env, lib, st = self.env, self.lib, self.env._stream()
+        src = env.priv_s_bf16 if m.bf16 else env.priv_s
+        _lib.check(lib.hsad_seat_gather(m.rows.data_ptr(), m.n, env.G * env.P, 0 if m.bf16 else 2, src.data_ptr(), env.F, m.Kp,
+                                   env.legal_move.data_ptr(), env.A, m.obs.data_ptr(), m.legal.data_ptr(), st))
+        obs = {"priv_s_bf16" if m.bf16 else "priv_s": m.obs, "legal_move": m.legal, "eps": m.eps}
+        reply, m.hid = m.agent.act(obs, m.hid)
+        a, g = reply["a"].contiguous(), reply["greedy_a"].contiguous()
+        _lib.check(lib.hsad_seat_scatter(env.h, m.rows.data_ptr(), m.n, a.data_ptr(), g.data_ptr(), env.a.data_ptr(),
+                                    env.greedy_a.data_ptr(), st))
+
+    def play(self, seed, max_steps):
+        """deals seed .. seed + n - 1 for every seating -> (scores int64 [S, n], totals int64 [S, 4])"""
+        env = self.env
+        env.reseed(seed, self.n)
+        env.reset()
+        for m in self.models:
+            m.hid = m.agent.get_h0(m.n)
+        done = False
+        for t in range(max_steps):
+            for m in self.models:
+                self._act(m)
+            env.step(env.a, env.greedy_a)
+            _lib.check(self.lib.hsad_seating_stats(env.h, self.n, self.stats.data_ptr(), self.unfinished.data_ptr(), env._stream()))
+            # the host looks at ONE word, and one step late: it never waits for the step it has just enqueued (the extra step
+            # at the end only hands finished games their noop)
+            self.host[t & 1].copy_(self.unfinished, non_blocking=True)
+            self.copied[t & 1].record(torch.cuda.current_stream(self.device))
+            if t > 0:
+                self.copied[(t - 1) & 1].synchronize()
+                if int(self.host[(t - 1) & 1][0]) == 0:
+                    done = True
+                    break
+        _drain_errors(env)        # finished games were handed the noop: the "step on a finished game" notes
+        totals = self.stats.cpu().numpy()
+        if not done and int(self.unfinished.cpu()[0]) != 0:
+            raise RuntimeError("%d game(s) still running after %d steps" % (int(self.unfinished.cpu()[0]), max_steps))
+        scores = env.query()[:, 5].cpu().numpy().astype(np.int64).reshape(self.S, self.n)
+        return scores, totals
+
+
+def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_launch=1 << 18, precision="bf16", device="cuda:0",
+                  hand_size=5, shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3, max_steps=200):
+    """Every seating of a model pool over the SAME deals, in one batched run -> SeatingScores.
+
+    agents: the pool -- whatever `evaluate` accepts (weight dicts, kernel agents / nets, any object with act / get_h0 such as
+    obl.OBLAgent or rela.ContractAgent) or `.pthw` paths.  seatings: int [S, P], the model index on each seat.  Seating s plays the
+    deals seed .. seed + num_game - 1, the ones evaluate(..., seed) plays; every player acts greedily (max_len -1, eps 0).
+
+    One env object holds S x n games, seating-major, reseeded with period n (BatchedHanabiEnv.reseed); per step each model acts ONCE
+    on the rows it owns (seating_rows; fixed ascending order, so its hidden state never moves): hsad_seat_gather -> act ->
+    hsad_seat_scatter, and hsad_seating_stats reduces the per-seating statistics on the device.  bf16 kernel nets read the env's
+    packed bf16 rows; every other agent gets the float32 rows by the same index list.  games_per_launch caps S x n per env object;
+    larger jobs run in chunks of deals on the same object."""
+    try:
+        shape = tuple(np.asarray(seatings).shape)
+    except ValueError:                    # seatings of different widths
+        shape = None
+    if shape is None or len(shape) != 2 or not 2 <= shape[1] <= 5:
+        raise ValueError("seatings must be [S, players] with 2..5 players, every seating as wide as the game has seats; got %s"
+                         % ("shape %s" % (shape,) if shape is not None else "rows of different widths"))
+    P = shape[1]
+    rules = dict(colors=colors, ranks=ranks, max_information_tokens=max_information_tokens, max_life_tokens=max_life_tokens)
+    F, A = env_dims(P, hand_size, sad, **rules)
+    if num_game < 1:
+        raise ValueError("num_game must be >= 1")
+    models, seatings = _check_pool(agents, seatings, P, F, A)
+    S = seatings.shape[0]
+    acting = [_acting_agent(x, precision, device) for x in models]
+    env_kw = dict(hand_size=hand_size, bomb=bomb, sad=bool(sad), shuffle_color=bool(shuffle_color), **rules)
+    per = max(1, min(int(num_game), int(games_per_launch) // S))
+    scores = np.zeros((S, num_game), dtype=np.int64)
+    totals = np.zeros((S, 4), dtype=np.int64)
+    batches = {}
+    for start in range(0, num_game, per):
+        n = min(per, num_game - start)
+        if n not in batches:
+            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device)
+            if (batches[n].env.F, batches[n].env.A) != (F, A):
+                raise _lib.HsadError("env_dims gives (%d, %d), the library (%d, %d)" % (F, A, batches[n].env.F, batches[n].env.A))
+        sc, tt = batches[n].play(seed + start, max_steps)
+        scores[:, start:start + n] = sc
+        totals += tt
+    for b in batches.values():
+        b.env.close()
+    return SeatingScores(scores, totals, seatings)
+
+
+class CrossPlayScores:
+    """cross_play's K x K view of SeatingScores: entry [i][j] = model i on seat 0 with model j on seat 1; row_mean[i] = the mean
+    of row i with the diagonal included (the last column of models/op_raw_data.txt)"""
+
+    def __init__(self, res, K):
+        self.seatings, self.num_game = res, res.num_game
+        self.scores = res.scores.reshape(K, K, -1)
+        self.mean, self.sem, self.perfect = res.mean.reshape(K, K), res.sem.reshape(K, K), res.perfect.reshape(K, K)
+        self.row_mean = self.mean.mean(axis=1)
+
+
+def cross_play(agents, num_game, seed, bomb, sad, **kw):
+    """the two-player tournament: all K^2 ordered seatings of the pool over the same deals -> CrossPlayScores"""
+    K = len(agents)
+    seatings = [(i, j) for i in range(K) for j in range(K)]
+    return CrossPlayScores(play_seatings(agents, seatings, num_game, seed, bomb, sad, **kw), K)
+
+
+def format_cross_play_table(title, names, mean, row_mean=None):
+    """the layout of models/op_raw_data.txt: title, rule, header `name M0 ... mean`, dashes, one row per model, two decimals"""
+    mean = np.asarray(mean, dtype=np.float64)
+    row_mean = mean.mean(axis=1) if row_mean is None else row_mean
+    head = "%-6s" % "name" + "".join("  %5s" % n for n in names) + "  %6s" % "mean"
+    lines = [title, "-" * len(head), head, "------" + "  -----" * len(names) + "  ------"]
+    for n, row, m in zip(names, mean, row_mean):
+        lines.append("%-6s" % n + "".join("  %5.2f" % v for v in row) + "  %6.2f" % m)
+    return "\n".join(lines)
+
+
+def parse_cross_play_table(text):
+    """-> (title, names, mean [K, K], row_mean [K]) of a table format_cross_play_table wrote"""
+    lines = [l for l in text.splitlines() if l.strip()]
+    names = lines[2].split()[1:-1]
+    body = [l.split() for l in lines[4:4 + len(names)]]
+    vals = np.array([[float(v) for v in r[1:]] for r in body], dtype=np.float64)
+    return lines[0], names, vals[:, :-1], vals[:, -1]
 
 
 def _drain_errors(env):

@@ -1,0 +1,82 @@
+"""`python -m hanabi_sad_amd.eval_model`: the reference's pyhanabi/tools/eval_model.py -- score a published model (or a pair of
+them) over fresh deals -- plus the measurement its result file models/op_raw_data.txt tabulates: `--cross_play` plays every
+ordered pairing of a model pool over the same deals in ONE batched run (eval.cross_play) and prints the matrix in that file's
+layout.
+
+  --paper sad --weight a.pthw --num_player 2            self-play of one file (every seat the same weights)
+  --paper op  --method sad --idx1 0 --idx2 3            one cell: M0 on seat 0 with M3 on seat 1
+  --paper obl --obl_path obl.pthw                       self-play of an OBL model
+  --paper op  --method sad --idx 0 3 6 9 --cross_play   the 4 x 4 matrix
+  --paper sad --weight a.pthw b.pthw c.pthw --cross_play
+
+As in the reference the deals are seeds 1 .. num_game * num_run, bombing out keeps the score (bomb 0) and everyone acts greedily.
+Whether the env appends SAD's greedy-action section is read off the models' input width (838 vs 783 features in the 2-player
+game)."""
+import argparse
+import os
+
+from .eval import cross_play, env_dims, format_cross_play_table, play_seatings
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog="python -m hanabi_sad_amd.eval_model")
+    p.add_argument("--paper", default="sad", type=str, choices=["sad", "op", "obl"])
+    p.add_argument("--num_game", default=5000, type=int)
+    p.add_argument("--num_run", default=1, type=int, help="total num game = num_game * num_run")
+    p.add_argument("--weight", default=None, type=str, nargs="+", help="--paper sad: the weight file (several with --cross_play)")
+    p.add_argument("--num_player", default=None, type=int)
+    p.add_argument("--method", default="sad-aux-op", type=str, help="sad-aux-op/sad-aux/sad-op/sad")
+    p.add_argument("--idx1", default=1, type=int, help="which model to use?")
+    p.add_argument("--idx2", default=1, type=int)
+    p.add_argument("--device", default="cuda:0", type=str)
+    p.add_argument("--obl_path", default=None, type=str)
+    p.add_argument("--cross_play", action="store_true", help="print the score matrix of the pool (--idx / several --weight)")
+    p.add_argument("--idx", default=None, type=int, nargs="+", help="--paper op --cross_play: the zoo models of the pool")
+    p.add_argument("--root", default=None, type=str, help="folder that holds models/op/<method>/M{idx}.pthw (default: the repository)")
+    p.add_argument("--precision", default="bf16", type=str, choices=["bf16", "fp32"])
+    return p.parse_args(argv)
+
+
+def load_pool(args):
+    """-> (agents, names, title, players)"""
+    from .checkpoint import agent_from_file, load_op_model
+    if args.paper == "sad":
+        files = args.weight or []
+        if not files or not all(os.path.exists(f) for f in files):
+            raise SystemExit("--paper sad needs --weight FILE (existing file%s)" % ("s" if args.cross_play else ""))
+        if not args.cross_play and len(files) != 1:
+            raise SystemExit("several --weight files need --cross_play")
+        agents = [agent_from_file(f, args.device, 3, 0.999, args.precision) for f in files]
+        return agents, ["W%d" % i for i in range(len(files))], "SAD", args.num_player or 2
+    if args.paper == "op":
+        idx = args.idx if args.cross_play else [args.idx1, args.idx2]
+        if not idx:
+            raise SystemExit("--paper op --cross_play needs --idx I J K ...")
+        agents = [load_op_model(args.method, i, None, args.device, root=args.root, precision=args.precision)[0] for i in idx]
+        return agents, ["M%d" % i for i in idx], args.method.upper(), 2
+    from .obl import load_obl_model
+    if not args.obl_path or not os.path.exists(args.obl_path):
+        raise SystemExit("--paper obl needs --obl_path FILE")
+    return [load_obl_model(args.obl_path, args.device, args.precision)], ["OBL"], "OBL", 2
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    agents, names, title, P = load_pool(args)
+    net = agents[0].online
+    n, kw = args.num_game * args.num_run, dict(precision=args.precision, device=args.device, hand_size=5 if P <= 3 else 4)
+    sad = args.paper == "obl" or getattr(net, "F", None) == env_dims(P, kw["hand_size"], sad=True)[0]
+    if args.cross_play:
+        if P != 2:
+            raise SystemExit("--cross_play is the two-player matrix")
+        res = cross_play(agents, n, 1, 0, sad, **kw)
+        print(format_cross_play_table("self-play & cross-play of %s" % title, names, res.mean, res.row_mean))
+        return res
+    seating = [0] * P if len(agents) == 1 else list(range(P))
+    res = play_seatings(agents, [seating], n, 1, 0, sad, **kw)
+    print("score: %f +/- %f" % (res.mean[0], res.sem[0]), "; perfect: ", res.perfect[0])
+    return res
+
+
+if __name__ == "__main__":
+    main()

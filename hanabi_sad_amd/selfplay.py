@@ -296,6 +296,8 @@ def parse_args(argv=None):
     p.add_argument("--actor_sync_freq", type=int, default=10)
     p.add_argument("--act_steps_per_update", type=int, default=1)
     p.add_argument("--num_eval_game", type=int, default=1000)
+    p.add_argument("--eval_partner", type=str, nargs="+", default=[], help="weight files of fixed partners: after each epoch's self-play "
+                   "evaluation the online net plays --num_eval_game deals with each of them, in both seat orders (one batched run)")
     p.add_argument("--early_draw", type=int, default=1, help="with --draw_ahead and the composite learner: priority write-back and the next draw are "
                    "issued between the forward half and the BPTT of an update on a stream of their own (0: behind the optimizer step on the caller's stream)")
     p.add_argument("--draw_ahead", type=int, default=1, help="1: the batch of update u + 1 is drawn at the end of update u (behind its priority "
@@ -456,10 +458,14 @@ def run_epochs(tr, args, rank=0, link=None):
     """the epoch loop of selfplay.py:201-281: Tachometer / Stopwatch / MultiCounter output per epoch, then evaluation of the
     online net on fresh games (eval.py:19-66) and the top-k / every-50-epochs saves"""
     from .common import MultiCounter, Stopwatch, Tachometer, TopkSaver
-    from .eval import evaluate
+    from .eval import evaluate, play_seatings
     saver = TopkSaver(args.save_dir, 5) if (args.save_dir and rank == 0) else None
     stat, tach, sw = MultiCounter(args.save_dir or None), Tachometer(), Stopwatch()
     history = []
+    partners = []
+    if getattr(args, "eval_partner", None):
+        from .checkpoint import agent_from_file
+        partners = [agent_from_file(f, str(tr.device)) for f in args.eval_partner]
     rows = torch.zeros(args.epoch_len, 2, dtype=torch.float32, device=tr.device)   # (loss, grad_norm) per update, read once per epoch
     factor = args.num_player if args.method == "vdn" else 1
 
@@ -508,6 +514,12 @@ def run_epochs(tr, args, rank=0, link=None):
             sd = {k: tr.learner.online.w[k].detach().cpu().clone() for k in tr.param_names}
             saved = saver.save(None, sd, score, force_save_name=force)
         print("epoch %d, eval score: %.4f, perfect: %.2f, model saved: %s" % (epoch, score, perfect * 100, saved))
+        if partners:
+            # cross-play against the fixed partners: seating (online, partner, ..) and (partner, online, partner, ..) per partner
+            seatings = [[0 if p == seat else k for p in range(args.num_player)] for k in range(1, len(partners) + 1) for seat in (0, 1)]
+            xp = play_seatings([tr.learner.online.w] + partners, seatings, args.num_eval_game, eval_seed, args.eval_bomb, args.sad,
+                               hand_size=args.hand_size, device=str(tr.device), **game_rules(args))
+            print("xplay: mean %.4f (as seat 0: %.4f, as seat 1: %.4f)" % (xp.mean.mean(), xp.mean[0::2].mean(), xp.mean[1::2].mean()))
         print("==========")
         history.append((score, perfect, saved))
     return history

@@ -124,6 +124,12 @@ int hsad_env_bind_packed(hsad_env* env, uint64_t* priv_bits, uint64_t* legal_bit
  * (HanabiEnv::reset, cpp/hanabi_env.cc:9-47). */
 int hsad_env_reset(hsad_env* env, void* stream);
 
+/* Puts every game back to "not started" (what hsad_env_create leaves) with game g's generator seeded seed0 + (g % period);
+ * period <= 0 = no wrap (seed0 + g, the seeding of hsad_env_create).  A following hsad_env_reset starts all games.  Games with
+ * equal seeds that receive equal actions stay bit-identical (eps draw, colour permutation, deck): groups of `period` games
+ * replay the same deals, and one env object serves chunk after chunk of deals.  Launch-only. */
+int hsad_env_reseed(hsad_env* env, int32_t seed0, int32_t period, void* stream);
+
 /* VectorEnv::step (rela/env.h:66-87) / HanabiEnv::step (cpp/hanabi_env.cc:49-113).
  * a, greedy_a: device int64 [G, P] = reply["a"], reply["greedy_a"]; greedy_a may be NULL when sad=0. */
 int hsad_env_step(hsad_env* env, const int64_t* a, const int64_t* greedy_a, void* stream);
@@ -972,6 +978,26 @@ const int64_t* hsad_actor_last_actions(const hsad_actor* actor, const int64_t** 
 /* n-step priorities the last step pushed, float32 [*n] (per (game, player) row, VDN: per game); NULL when that step was still
  * filling the n-step window */
 const float* hsad_actor_last_priority(const hsad_actor* actor, int32_t* n);
+
+/* ---- seat kernels of a tournament batch (eval.play_seatings): one env object holds every seating of a model pool over the same
+ * deals (hsad_env_reseed with period = deals); a model acts once per step on the rows it owns, listed as flat row ids g * P + p.
+ * All three are HBM-bound, one pass, launch-only. ---- */
+/* One model's act operands in one launch: for i < n, row r = rows[i] of the env outputs ->
+ *   obs_out row i:   obs_kind 0: bf16 [n, Kp] copied from priv_s_bf16 [*, Kp] (hsad_env_bind_packed rows, 16-byte vectors)
+ *                    obs_kind 1: bf16 [n, Kp] cast and zero-padded from priv_s fp32 [*, F] (= hsad_cast_pad_bf16 of the rows)
+ *                    obs_kind 2: fp32 [n, F] copied from priv_s (agents that take the float32 observation)
+ *   legal_out row i: fp32 [n, A] copied from legal_move [*, A].
+ * rows device int32 [n], each in [0, num_rows) (checked on the device; an id outside leaves its output row untouched). */
+int hsad_seat_gather(const int32_t* rows, int n, int num_rows, int obs_kind, const void* obs_src, int F, int Kp, const float* legal_move,
+                     int A, void* obs_out, float* legal_out, void* stream);
+/* A model's chosen actions back into a / greedy_a int64 [G, P] at its rows; rows of finished (or not started) games receive the
+ * noop uid A - 1, which hsad_env_step ignores.  a_src / greedy_src int64 [n]. */
+int hsad_seat_scatter(const hsad_env* env, const int32_t* rows, int n, const int64_t* a_src, const int64_t* greedy_src, int64_t* a,
+                      int64_t* greedy_a, void* stream);
+/* Per seating s (games [s * games_per_seating, (s + 1) * games_per_seating); G must be a multiple) from the latched last scores of
+ * the finished games: stats int64 [S, 4] = sum score, sum score^2, perfect games (score == colors * ranks), finished games; and
+ * *unfinished int32 = games of the whole env not finished yet -- the one word a host loop reads.  Integer sums: exact, order-free. */
+int hsad_seating_stats(const hsad_env* env, int games_per_seating, int64_t* stats, int32_t* unfinished, void* stream);
 
 /* ---- one-sided intra-node transport (dist.py ReplayLink(transport = "ipc")): landing buffers exported by IPC handle and written by the
  * SENDER with a device-to-device copy -- SDMA over xGMI, no kernel resident on either GPU while a peer has not answered (a posted RCCL

@@ -7,7 +7,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libhsad.so")
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("hsad_env.hip", "hsad_replay.hip", "hsad_r2d2.hip", "hsad_r2d2_f32.hip", "hsad_agent.hip", "hsad_comm.hip",
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("hsad_env.hip", "hsad_replay.hip", "hsad_r2d2.hip", "hsad_r2d2_f32.hip", "hsad_agent.hip", "hsad_learner.hip", "hsad_comm.hip",
                                                       "hsad_actor.hip", "hsad_eval.hip")]
 _lib = None
 
@@ -69,6 +69,12 @@ class LstmFusedBwdRec(C.Structure):
                 ("xchg", C.c_void_p), ("saved_frag_major", C.c_int), ("tail_is_zero", C.c_int), ("xout", C.c_void_p), ("dO_stage", C.c_void_p), ("sink_WT", C.c_void_p), ("sink_out16", C.c_void_p), ("sink_mask16", C.c_void_p),
                 ("sink_xout", C.c_void_p), ("sink_outT16", C.c_void_p), ("sink_ldT", C.c_int), ("sink_bias_grad", C.c_void_p), ("dGT16", C.c_void_p), ("ldT", C.c_int), ("bias_grad0", C.c_void_p), ("bias_grad1", C.c_void_p),
                 ("bias_col_map", C.c_void_p), ("layout_steps", C.c_int), ("wide_blocks", C.c_int)]
+
+
+class LearnerPlan(C.Structure):
+    """hsad_learner_plan (include/hsad.h)"""
+    _fields_ = [(k, C.c_int32) for k in ("fwd_kind", "fwd_nets", "fwd_layers", "fwd_chunks", "bwd_kind", "bptt_chunks", "split", "proj", "sink",
+                                          "dgt_in_kernel", "group", "wide_requested", "chunk_input", "one_launch_heads", "dO_in_loss_tail")]
 
 
 class LstmFusedRec(C.Structure):
@@ -278,6 +284,7 @@ SIGNATURES = {
     "hsad_r2d2_learner_destroy": (None, [_P]),
     "hsad_r2d2_learner_set_schedule": (C.c_int, [_P, C.c_int, C.c_int]),
     "hsad_r2d2_learner_set_fused": (C.c_int, [_P, C.c_int]),
+    "hsad_r2d2_learner_plan": (C.c_int, [_P, C.POINTER(LearnerPlan)]),
     "hsad_r2d2_learner_grad": (_P, [_P]),
     "hsad_r2d2_learner_timed_out": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "hsad_r2d2_learner_inject_timeout": (C.c_int, [_P, C.c_int]),

@@ -1,4 +1,4 @@
-"""Python face of the COMPOSITE C-ABI entry points (include/hsad.h `hsad_r2d2_*`, csrc/hsad_agent.hip): the agent and the learner as
+"""Python face of the COMPOSITE C-ABI entry points (include/hsad.h `hsad_r2d2_*`, csrc/hsad_agent.hip, csrc/hsad_learner.hip): the agent and the learner as
 the reference's native side sees them -- `act`, `compute_priority` (rela/batch_runner.h:74-113, rela/r2d2_actor.h:61-172) and
 the learner step (pyhanabi/selfplay.py:208-244) -- each ONE library call.  The kernel schedule lives in the library; these
 classes only hand over pointers, so a C++ / pybind host replaces them with the stub in INTEGRATION.md.
@@ -305,6 +305,12 @@ class CompositeLearner:
             self.target.refresh()
             return
         _lib.check(self.lib.hsad_r2d2_sync_target_with_online(self.h, _s(self.device)))
+
+    def plan(self):
+        """the schedule the last loss() resolved to, as a dict of ints (hsad_r2d2_learner_plan; kinds: 0 plain, 1 chunk-pipelined, 2 fused)"""
+        p = _lib.LearnerPlan()
+        _lib.check(self.lib.hsad_r2d2_learner_plan(self.h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
 
     def check_sync(self):
         t = C.c_int32(0)

@@ -1589,7 +1589,7 @@ int hsad_lstm_backward_fused(int nnet, int nlayer, int Tc, int Bn, int H, const 
     q.dc_io = r.dc_io;
     q.dbg = g_lstm_dbg_enable == 1;
     q.trace_slot = g_lstm_dbg_enable == 2 ? (kTraceRec + j) * kTraceNb : -1;
-    static const int bwd_rot = getenv("HSAD_BWD_ROT") ? atoi(getenv("HSAD_BWD_ROT")) : 26;     // developer switches (bits): 1 rotated tile loads, 2 written-through copy behind the own signal, 4 no transposed copy (timing only!), 8 nt transposed stores, 16 nt loads of the saved activations
+    static const int bwd_rot = getenv("HSAD_BWD_ROT") ? atoi(getenv("HSAD_BWD_ROT")) : 26;     // developer switches: any non-zero value = rotated tile loads (the kernel tests the value as a whole, so the default 26 runs them too); bits: 2 written-through copy behind the own signal, 4 no transposed copy (timing only!), 8 nt transposed stores, 16 nt loads of the saved activations
     q.rot = bwd_rot;
     q.T = Tc;
     q.Bn = Bn;

@@ -30,7 +30,7 @@ struct LstmFusedBwdArgs {
   float* dc_io;
   int dbg;
   int trace_slot;           // >= 0: per-step trace rows [trace_slot + nb] of g_lstm_trace (row block 0 only)
-  int rot;                  // developer switch (HSAD_BWD_ROT): tile loads issued in an order rotated by the unit block
+  int rot;                  // developer switches (HSAD_BWD_ROT, default 26): ANY non-zero value issues the tile loads in an order rotated by the unit block (tested as a whole); bits 2 / 4 / 8 / 16 select further variants below
   int T, Bn, has_next, frag, feeds;   // feeds: a layer below consumes this layer's tiles (publish + signal step 0, too)
   // split placement (the layers of a row block on DIFFERENT XCDs, 16 workgroups each, so that half of every XCD stays free for the weight-
   // gradient GEMMs of the previous time chunk): a feeding layer publishes its tile a second time, written through (sc1) with an agent-scope

@@ -715,7 +715,7 @@ int hsad_lstm_backward_chunk(int Tc, int Bn, int H, const float* gates, const fl
                              void* sync_scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * COMPOSITE entry points (csrc/hsad_agent.hip): the agent methods the reference's native side calls through
+ * COMPOSITE entry points (csrc/hsad_agent.hip, the learner in csrc/hsad_learner.hip): the agent methods the reference's native side calls through
  * rela::BatchRunner -- `act`, `compute_priority` (rela/batch_runner.h:74-113, rela/r2d2_actor.h:61-172 ->
  * pyhanabi/r2d2.py:247-361) -- and the learner step of pyhanabi/selfplay.py:208-244 (R2D2Agent.loss r2d2.py:383-499, backward,
  * clip_grad_norm_, Adam, sync_target_with_online), each as ONE call on plain pointers.  The library owns the weights (one flat
@@ -779,30 +779,47 @@ int hsad_r2d2_learner_create(hsad_r2d2_net* online, hsad_r2d2_net* target, int T
                              float lr, float eps, float grad_clip, hsad_r2d2_learner** out);
 void hsad_r2d2_learner_destroy(hsad_r2d2_learner* learner);
 int hsad_r2d2_learner_set_schedule(hsad_r2d2_learner* learner, int chunks, int wgrad_split);
-/* Recurrence schedule of a learner (flags; the default is 0x39 = bits 0, 3, 4, 5 with one BPTT chunk: bits 3 / 4 / 5 fall back to off when
- * their 16-workgroup groups -- 2 / 3 / 4 per 32-row block -- do not fit the chip).  Synchronises.
+/* Recurrence schedule of a learner: THE table of the flag word (the default is 0x39 | 1 << 8 = bits 0, 3, 4, 5 with one BPTT chunk).  The
+ * flags say what is asked for; what a shape cannot hold falls back to off (bits 3 / 4 / 5: their 16-workgroup groups -- 2 / 3 / 4 per 32-row
+ * block -- must fit the chip) and hsad_r2d2_learner_plan reports what ran.  Synchronises.
  *   bit 0      the forward recurrences of hsad_r2d2_loss_fwd run as whole-sequence fused launches (hsad_lstm_forward_fused: projection inside
  *              the recurrence, layers one step apart, online + target net together) and BPTT as hsad_lstm_backward_fused launches (both layers,
  *              dO of the lower layer inside its recurrence) when the shape allows (H in {256, 512}, rows % 32 == 0, a (net, row block)'s
  *              workgroups fit an XCD); 0: the chunk-pipelined schedule of rounds 1-2 (stand-alone projection / dO GEMMs between chunk launches)
  *   bit 1      with bit 0: keep the chunk-pipelined BPTT (A/B of the backward schedule)
- *   bits 16-23 fused BPTT in TWO unequal chunks: steps [n, T) first, the head [0, n) last (0 = equal chunks per bits 8-15) -- the long
- *              chunk's weight gradients run next to the head's recurrence, only the head's are left for the end of the update
- *   bit 6      the single-chunk fused BPTT leaves dG row-major and two transpose passes (+ bias column sums) follow it, as in every
- *              chunked schedule; 0 (default): the launch writes dG transposed and adds the bias gradients itself
- *   bit 5      with bits 3, 4: the input layer's d x = dG0 W_ih0 (ReLU-masked) as a sink stage of the BPTT launch (one fc layer)
- *   bit 4      with bit 3: the lower layer's dO = dG1 W_ih1 in a projection stage of its own (hsad_lstm_fused_bwd_rec.dO_stage)
- *   bit 3      split placement of the fused BPTT (hsad_lstm_fused_bwd_rec.xout): the two layers of a row block on different XCDs, half of
- *              every XCD free for the chunk-wise weight gradients on the side stream; meant for bits 8-15 >= 2
  *   bit 2      hsad_r2d2_optimizer_step re-derives the LSTM matrices (95 % of the operand bytes) on the learner's side stream, next to the
  *              following update's input layer; every entry point that reads a net's LSTM operands waits for that half first (an event, no
  *              host synchronisation).  Off by default: measured 1.521 against 1.504 ms per update with everything in line
+ *   bit 3      split placement of the fused BPTT (hsad_lstm_fused_bwd_rec.xout): the two layers of a row block on different XCDs, half of
+ *              every XCD free for the chunk-wise weight gradients on the side stream; meant for bits 8-15 >= 2
+ *   bit 4      with bit 3: the lower layer's dO = dG1 W_ih1 in a projection stage of its own (hsad_lstm_fused_bwd_rec.dO_stage)
+ *   bit 5      with bits 3, 4: the input layer's d x = dG0 W_ih0 (ReLU-masked) as a sink stage of the BPTT launch
+ *   bit 6      the single-chunk fused BPTT leaves dG row-major and two transpose passes (+ bias column sums) follow it, as in every
+ *              chunked schedule; 0 (default, needs the sink stage): the launch writes dG transposed and adds the bias gradients itself
  *   bit 7      off: the four LSTM weight gradients and the input layer's of a single-chunk fused BPTT as six split-K GEMMs on two streams
- *              (round 4) instead of one grouped launch of the 256 x 256 core + one slab pass (hsad_gemm_nt_bf16_group_splitk)
+ *              (round 4) instead of one grouped launch of the 256 x 256 core + one slab pass (hsad_gemm_nt_bf16_group_splitk; one fc layer)
  *   bits 8-15  time chunks of the fused BPTT, 1..8 (the weight gradients are added up per chunk); 0 keeps the current setting
+ *   bits 16-23 fused BPTT in TWO unequal chunks: steps [n, T) first, the head [0, n) last (0 = equal chunks per bits 8-15) -- the long
+ *              chunk's weight gradients run next to the head's recurrence, only the head's are left for the end of the update
  *   bit 24     off: the chain between the two recurrences as four launches (head GEMM pair, hsad_q_head, loss tail, dO GEMM) instead of two (both
- *              nets' heads + the online dueling head in one launch; the loss tail forming d loss / d o itself) -- identical bits, A/B */
+ *              nets' heads + the online dueling head in one launch; the loss tail forming d loss / d o itself) -- identical bits, A/B
+ *   bit 25     off: the 32 x 32 blocking of the four-stage single-chunk BPTT launch instead of the 16-row x 64-unit one
+ *              (lstm_bptt_wide_kernel, taken where the shape allows) -- A/B */
 int hsad_r2d2_learner_set_fused(hsad_r2d2_learner* learner, int fused_fwd);
+/* What the last hsad_r2d2_loss_fwd ran and -- as the hsad_r2d2_loss_bwd behind it resolved it, else as it would be under the current flags --
+ * its backward half: the schedule the flags and the shape resolve to (HSAD_ERR_STATE before the first loss_fwd).  Kinds: 0 plain (per layer a
+ * projection GEMM + an unchunked recurrence), 1 chunk-pipelined, 2 fused.  Reports, changes nothing. */
+typedef struct hsad_learner_plan {
+  int32_t fwd_kind, fwd_nets, fwd_layers;   /* fused forward: nets and stacked layers per launch (else 0) */
+  int32_t fwd_chunks;                       /* time chunks of the chunk-pipelined schedule */
+  int32_t bwd_kind, bptt_chunks;
+  int32_t split, proj, sink;                /* fused BPTT: stages that were asked for and fit the chip */
+  int32_t dgt_in_kernel, group;             /* ... dG transposed + bias gradients inside the launch; one grouped weight-gradient launch */
+  int32_t wide_requested;                   /* ... the 16-row x 64-unit blocking was asked of the launcher (it takes it at H = 512, rows <= 128) */
+  int32_t chunk_input;                      /* chunked fused BPTT: the input layer's backward pass per chunk on the side stream */
+  int32_t one_launch_heads, dO_in_loss_tail;
+} hsad_learner_plan;
+int hsad_r2d2_learner_plan(const hsad_r2d2_learner* learner, hsad_learner_plan* out);
 float* hsad_r2d2_learner_grad(hsad_r2d2_learner* learner);            /* flat gradient, same layout as the net's parameters */
 int hsad_r2d2_learner_timed_out(hsad_r2d2_learner* learner, int32_t* timed_out);
 /* hsad_r2d2_loss_bwd with importance weights that arrive after the forward pass (the torch.autograd face of R2D2Agent.loss: the reference's

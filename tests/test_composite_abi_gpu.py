@@ -1,4 +1,4 @@
-"""The COMPOSITE C-ABI entry points (include/hsad.h hsad_r2d2_*; csrc/hsad_agent.hip) -- the agent and the learner as single
+"""The COMPOSITE C-ABI entry points (include/hsad.h hsad_r2d2_*; csrc/hsad_agent.hip, csrc/hsad_learner.hip) -- the agent and the learner as single
 library calls on plain pointers, what a C++ / pybind host binds.  Checked three ways:
   * against the REFERENCE's golden vectors (tests/golden/*.npz: act, compute_priority, loss, priorities, every gradient; IQL and
     VDN), with the tolerances measured for the bf16 kernels;
@@ -294,16 +294,61 @@ def test_act_in_two_halves_equals_the_single_call():
             assert torch.equal(h1["h0"], h2["h0"]) and torch.equal(h1["c0"], h2["c0"])
 
 
+def _expected_plan(flags, bchunks, n_cu, F, H, T, B, A=21, hand=5, layers=2, nfc=1, chunks=4, wgrad_split=8, num_player=1, grad=True):
+    """What hsad_r2d2_learner_plan must report for a flag word of hsad_r2d2_learner_set_fused (bchunks: the last non-zero bits 8-15) at a
+    shape on a device of n_cu CUs, from the documented conditions (include/hsad.h, DESIGN.md "Composite entry points") alone -- the library is
+    not asked.  A stage of the fused BPTT launch needs its 16-workgroup groups on the chip: 2 (split) / 3 (projection) / 4 (sink) x H / 32
+    workgroups per 32-row block; a fused forward launch needs a (net, row block)'s layers x H / 32 workgroups inside one of the 8 XCDs."""
+    bit = lambda b: bool(flags >> b & 1)
+    M, nrb, wpr = T * B, (B + 31) // 32, H // 32
+    Mp, Fp, NH = -(-M // 64) * 64, -(-F // 64) * 64, A + 1 + 3 * hand
+    pipe = layers == 2 and H in (256, 512) and B <= 512 and B % 8 == 0 and M % 64 == 0
+    fwd_chunks = chunks if pipe else 1
+    while fwd_chunks > 1 and (T % fwd_chunks or (T // fwd_chunks * B) % 64):
+        fwd_chunks -= 1
+    fits = []
+    if bit(0) and T >= 2 and H in (256, 512) and B % 32 == 0 and T * B * H * 16 < 2 ** 32:
+        fits = [(nn, g) for g in range(min(layers, 2), 0, -1) for nn in (2, 1) if g * wpr * ((nn * nrb + 7) // 8) <= n_cu // 8]
+    nets, lay = fits[0] if fits else (0, 0)
+    fwd_kind = 2 if nets else 1 if pipe else 0
+    nbc = bchunks
+    while nbc > 1 and (T % nbc or (T // nbc * B) % 64):
+        nbc -= 1
+    fused_bwd = pipe and bit(0) and not bit(1) and fwd_kind == 2 and B % 32 == 0 and 2 * wpr * ((nrb + 7) // 8) <= n_cu // 8
+    split = proj = sink = dgt = group = chunk_input = False
+    if fused_bwd:
+        if 0 < (flags >> 16 & 0xff) < T:
+            nbc = 2
+        split = bit(3) and nrb * 2 * wpr <= n_cu
+        proj = split and bit(4) and nrb * 3 * wpr <= n_cu
+        sink = proj and bit(5) and nrb * 4 * wpr <= n_cu
+        dgt = nbc == 1 and sink and not bit(6)
+        group = dgt and nfc == 1 and not bit(7) and (4 * H) % 256 == 0 and H % 256 == 0 and Mp % 128 == 0 and Fp % 4 == 0
+        chunk_input = nfc == 1 and nbc > 1 and M % 4 == 0 and H % 4 == 0 and wgrad_split > 1
+    one = num_player == 1 and not bit(24) and M >= 128 and M % 128 == 0 and H % 16 == 0 and NH <= 64 and T <= 352
+    e = dict(fwd_kind=fwd_kind, fwd_nets=nets, fwd_layers=lay, fwd_chunks=fwd_chunks, bwd_kind=2 if fused_bwd else 1 if pipe else 0,
+             bptt_chunks=nbc if fused_bwd else fwd_chunks if pipe else 1, split=split, proj=proj, sink=sink, dgt_in_kernel=dgt, group=group,
+             wide_requested=dgt and not bit(25), chunk_input=chunk_input, one_launch_heads=one,
+             dO_in_loss_tail=one and grad and -(-NH // 64) * 64 == 64 and H % 32 == 0 and H <= (512 if T <= 128 else 256))
+    return {k: int(v) for k, v in e.items()}
+
+
 @pytest.mark.parametrize("F,H,T,B,pw", [(838, 512, 80, 128, 0.25), (838, 256, 24, 64, 0.0), (783, 512, 16, 256, 0.0)])
 def test_fused_recurrences_equal_the_chunk_pipelined_schedule(F, H, T, B, pw):
     """default learner schedule -- hsad_lstm_forward_fused (projection inside the recurrence, both layers and both nets in one launch; B =
     256: one net per launch) and hsad_lstm_backward_fused (both layers in one launch, dO of the lower layer inside its recurrence; also
     in 2 time chunks with the weight gradients added up per chunk) -- vs the projection-GEMM + chunked-recurrence schedule of rounds 1-2:
     same operands, different fp32 summation orders -> agreement at the level of bf16 feedback noise; switching back and forth on a live
-    learner reproduces each schedule's own bits"""
+    learner reproduces each schedule's own bits.  What each mode RAN is read back (hsad_r2d2_learner_plan) and held to the plan the flag
+    word and the shape resolve to on this device: a mode whose name promises a stage that the shape cannot hold (B = 256: 8 row blocks x
+    3 groups x 16 workgroups = 384 > 256 CUs -- no projection, no sink stage, dG transposed behind the launch) still runs, as the degraded
+    plan asserted here"""
     from hanabi_sad_amd.composite import CompositeLearner
     from tests.test_r2d2_kernels_gpu import _rand_batch, _rand_net
     A = 21
+    n_cu = torch.cuda.get_device_properties(DEV).multi_processor_count
+    groups_fit = {k: (B + 31) // 32 * g * (H // 32) <= n_cu for k, g in (("split", 2), ("proj", 3), ("sink", 4))}
+    bchunks = 1
     W, Wt = _rand_net(F, H, A, seed=13), _rand_net(F, H, A, seed=14)
     batch, weight = _rand_batch(T, B, F, A)
     L = CompositeLearner(W, Wt, 3, 0.999, device=DEV)
@@ -319,6 +364,14 @@ def test_fused_recurrences_equal_the_chunk_pipelined_schedule(F, H, T, B, pw):
             L.set_fused(flags)
             loss, prio = L.loss(batch, weight, pw)
             torch.cuda.synchronize()
+            bchunks = (flags >> 8 & 0xff) or bchunks
+            plan = L.plan()
+            assert plan == _expected_plan(flags, bchunks, n_cu, F, H, T, B), (name, plan)
+            # the stages the mode's name promises: on when every group up to theirs fits the chip, else explicitly off
+            assert plan["split"] == int("split" in name and groups_fit["split"]), (name, plan)
+            assert plan["proj"] == int("projection" in name and groups_fit["split"] and groups_fit["proj"]), (name, plan)
+            assert plan["sink"] == int("sink" in name and all(groups_fit.values())), (name, plan)
+            assert plan["dgt_in_kernel"] == int(plan["sink"] and "2 chunks" not in name), (name, plan)
             got = (loss.clone(), prio.clone(), {k: v.clone() for k, v in L.grad.items()})
             if name in res:      # second visit: bit-identical to the first (counter blocks, ping-pong state survive the switch)
                 assert torch.equal(got[0], res[name][0]) and torch.equal(got[1], res[name][1]), name
@@ -364,6 +417,48 @@ def test_fused_recurrences_equal_the_chunk_pipelined_schedule(F, H, T, B, pw):
                 assert torch.equal(res[a][2][k], res[b][2][k]), (b, k)
             else:   # (atomics: the LSTM bias gradients are four per-row-block partial sums added in arrival order -- they cancel heavily)
                 assert relerr(res[a][2][k], res[b][2][k]) < (3e-4 if k.startswith("lstm.bias") else 1e-5), (b, k, relerr(res[a][2][k], res[b][2][k]))
+
+
+PLAN_SHAPES = [   # (H, B, T, lstm layers, fc layers, flag words in turn; None = the default word)
+    (512, 128, 4, 2, 1, (None,)),                      # 256 CUs: every stage on, wide blocks asked for, grouped weight gradients, forward {2, 2}
+    (512, 256, 4, 2, 1, (None,)),                      # 8 row blocks: split at exactly 256 workgroups, no projection -> no dgt_in_kernel, forward {1, 2}
+    (256, 32, 4, 2, 1, (None,)),                       # all stages; the wide launch is for H = 512 (asked for, the launcher keeps 32 x 32)
+    (256, 32, 4, 2, 1, (1 | (2 << 8), 0)),             # two BPTT chunks with chunk_input; then the pipelined forward and backward
+    (128, 16, 3, 2, 1, (None,)),                       # plain forward and backward
+    (256, 32, 1, 2, 1, (None,)),                       # one step: no fused forward
+    (256, 32, 4, 3, 1, (None,)),                       # three LSTM layers: no pipeline, no grouped launch
+    (256, 32, 4, 2, 2, (None,)),                       # two fc layers: fused BPTT without the grouped launch
+]
+
+
+@pytest.mark.parametrize("H,B,T,nl,nfc,words", PLAN_SHAPES)
+def test_learner_plan_at_the_smallest_shapes_of_every_branch(H, B, T, nl, nfc, words):
+    """plan_update at the smallest shape of each of its branches (A = 21, F = 128): one update per flag word, the plan read back and held to
+    _expected_plan for this device's CU count; loss and priorities finite, a second evaluation the same bits, no timeout word set"""
+    from hanabi_sad_amd.composite import CompositeLearner
+    from hanabi_sad_amd.selfplay import init_weights
+    from tests.test_r2d2_kernels_gpu import _rand_batch
+    F, A = 128, 21
+    n_cu = torch.cuda.get_device_properties(DEV).multi_processor_count
+    W, Wt = init_weights(F, H, A, 5, 51, nl, nfc), init_weights(F, H, A, 5, 52, nl, nfc)
+    batch, weight = _rand_batch(T, B, F, A, seed=1000 * B + T)
+    L = CompositeLearner(W, Wt, 3, 0.999, device=DEV)
+    bchunks = 1
+    for flags in words:
+        if flags is None:
+            flags = CompositeLearner.FUSED_DEFAULT
+        else:
+            L.set_fused(flags)
+        bchunks = (flags >> 8 & 0xff) or bchunks
+        want = _expected_plan(flags, bchunks, n_cu, F, H, T, B, layers=nl, nfc=nfc)
+        runs = []
+        for rep in range(2):
+            loss, prio = L.loss(batch, weight, 0.25)
+            assert L.plan() == want, (flags, L.plan(), want)
+            runs.append((loss.clone(), prio.clone()))
+        L.check_sync()
+        assert torch.isfinite(runs[0][0]).all() and torch.isfinite(runs[0][1]).all(), flags
+        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1]), flags
 
 
 @pytest.mark.parametrize("T", [2, 3, 5, 9, 33])

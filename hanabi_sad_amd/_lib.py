@@ -110,6 +110,10 @@ SIGNATURES = {
     "hsad_env_set_partitions": (C.c_int, [_P, C.c_int]),
     "hsad_env_set_rollout_stagger": (C.c_int, [_P, C.c_int]),
     "hsad_env_set_rollout_chunk": (C.c_int, [_P, C.c_int]),
+    "hsad_env_set_rollout_pace": (C.c_int, [_P, C.c_int]),
+    "hsad_env_rollout_pace_cap_us": (C.c_int, [_P]),
+    "hsad_env_debug_pace_bias": (C.c_int, [_P, C.c_int64]),
+    "hsad_env_debug_pace_word": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hsad_env_last_rollout_ms": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "hsad_env_query": (C.c_int, [_P, _P, _P]),
     "hsad_env_move_is_legal": (C.c_int, [_P, _P, _P, _P]),

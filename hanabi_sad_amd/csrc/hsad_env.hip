@@ -106,6 +106,13 @@ struct EnvParams {
   unsigned long long* phase;  // [16][2]: {tag, wall_clock64 at launch start} per partition, or NULL
   int part, n_part, lock_ticks;
   unsigned long long launch_tag, first_tag;   // first_tag: tag of the first iteration of this rollout call
+  // pacing of a persistent launch (rollout_pace): every workgroup adds 1 to *pace at the top of each iteration, so the word says how
+  // far the launch as a whole has come; a workgroup ahead of that mean delays its observation stream.  Timing only.
+  unsigned long long* pace;        // the env's progress word, or NULL: no pacing (and no atomics) in this launch
+  unsigned long long pace_base;    // value of *pace when this launch starts (host-tracked: no memset per launch)
+  unsigned long long pace_inv_q32; // 2^32 / pace_blocks
+  int pace_blocks;                 // workgroups of this launch that have games (and therefore count)
+  int pace_l0_q8, pace_cap_ticks;  // dead band (iterations, 8 fractional bits) and cap of one delay (100 MHz ticks)
   // the game's rules (hsad_env_create_rules).  Read only by the variant instantiations (V = true); the full game's kernels
   // (V = false) compile them in as constants.  variant = 0 for 5 colours, 5 ranks, 8 information and 3 life tokens.
   int nC, nR, max_info, max_life, deck_max, variant;
@@ -455,6 +462,7 @@ __device__ __forceinline__ uint32_t hand_match_mask(uint32_t hw, bool by_color, 
 //                              11 wave 0's logic done, 2 end of phase A (barrier), 3 rows built, 4 end of phase B (barrier),
 //                              8 stream wave (thread 64): rows of `it - 1` streamed and cleared, 5 last record only: epilogue stream done,
 //                              6 / 7 as above
+//                              12 pacing: ticks by which the stream of this iteration's rows is delayed (pace_delay)
 //   both, trace layout:        9 HW_REG_HW_ID, 10 HW_REG_XCC_ID of the workgroup (written with slot 0)
 __device__ __forceinline__ void env_stamp(const EnvParams& ep, int it, int k, unsigned long long v) {
   const size_t blk = (size_t)(ep.g_begin / ep.gpw) + blockIdx.x;
@@ -1466,12 +1474,66 @@ __device__ __forceinline__ void rollout_stagger(const EnvParams& ep) {
   }
 }
 
+// Pacing of a persistent launch.  The observation streams are limited by contention for HBM, not by the CU: a stream takes about
+// as long as there are workgroups streaming at once.  Workgroups run at persistently different rates, so the launch ends on the
+// slowest while the fastest have long left.  A workgroup that is ahead of the mean therefore holds its stream back and leaves the
+// bandwidth to the others.  Nothing is handed over and nobody waits for anybody: each workgroup reads one shared counter and
+// sleeps a bounded time that depends on nothing else, so results cannot change and a launch can only end on the workgroup it
+// would have ended on anyway.
+//   s        what the workgroup's fetch_add of iteration `iter` returned: iteration starts of the whole launch so far + pace_base
+//   lead     iter - (s - pace_base) / pace_blocks: iterations this workgroup is ahead of the mean (fixed point, 8 fractional bits)
+//   delay    (lead - L0) * t_own, at most min(t_own / 2, pace_cap_ticks); t_own = the workgroup's own last iteration time.
+//            The dead band L0 and the proportional form mean that a workgroup never sleeps itself behind the mean.
+// A lead outside [-n_iter, n_iter] cannot come from this launch (a stale base, hsad_env_debug_pace_bias): no delay.
+__device__ __forceinline__ unsigned pace_delay(const EnvParams& ep, unsigned long long s, int iter, unsigned t_own) {
+  const long long num = (long long)iter * ep.pace_blocks - (long long)(s - ep.pace_base);   // lead * pace_blocks
+  const long long span = (long long)ep.n_iter * ep.pace_blocks;                              // < 2^29 (launch_env)
+  if (num < -span || num > span) return 0u;
+  const int over_q8 = (int)((num * (long long)ep.pace_inv_q32) >> 24) - ep.pace_l0_q8;
+  if (over_q8 <= 0) return 0u;
+  t_own = min(t_own, 1u << 20);   // 10 ms: far beyond any iteration, keeps the product in range
+  const unsigned long long d = ((unsigned long long)(unsigned)over_q8 * t_own) >> 8;
+  return (unsigned)min(d, (unsigned long long)min(t_own >> 1, (unsigned)ep.pace_cap_ticks));
+}
+
+// One lane's count of an iteration start.  The per-lane opaque zero in the address keeps the compiler from rewriting the add as a
+// wave reduction (its atomic optimizer does that to any add on a uniform address), whose result it would wait for on the spot:
+// the returned value is meant to stay in flight behind the iteration's own loads.
+__device__ __forceinline__ unsigned long long pace_count(const EnvParams& ep) {
+  int z = 0;
+  unsigned long long one = 1ull;
+  asm volatile("" : "+v"(z), "+v"(one));   // (the increment too: as a loop invariant it would occupy two VGPRs for the whole launch)
+  return __hip_atomic_fetch_add(ep.pace + z, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void pace_sleep(unsigned ticks) {
+  const unsigned long long t_in = wall_clock64();
+  while (wall_clock64() - t_in < (unsigned long long)ticks) __builtin_amdgcn_s_sleep(16);
+}
+
 template <int TP, int TH, bool V = false>
 __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void env_rollout_kernel(EnvParams ep) {
   rollout_stagger(ep);
+  unsigned long long pace_s = 0ull;
+  unsigned pace_t0 = (unsigned)wall_clock64();
+  const bool paced = ep.pace && ep.g_begin + (int)blockIdx.x * ep.gpw < ep.G;   // a workgroup without games does not count
 #pragma clang loop unroll(disable)
   for (int iter = 0; iter < ep.n_iter; ++iter) {
     if (iter) __syncthreads();   // the previous iteration's rows have left LDS before they are cleared again
+    if (paced) {
+      // pacing (pace_delay): every point of this serial iteration is on the workgroup's critical path, so wave 0 sleeps right
+      // here, on the lead its previous iteration start measured (that value has long arrived: the wait for it costs nothing
+      // the first plane load below would not wait for anyway), and the other waves meet it at the body's first barrier
+      const unsigned now = (unsigned)wall_clock64(), t_own = now - pace_t0;
+      pace_t0 = now;
+      if (threadIdx.x == 0) {
+        if (iter > 0) {
+          const unsigned d = pace_delay(ep, pace_s, iter - 1, t_own);
+          if (d) pace_sleep(d);
+        }
+        pace_s = pace_count(ep);
+      }
+    }
     int zero = 0;
     asm volatile("" : "+s"(zero));
     env_body<3, TP, TH, V>(ep, nullptr, nullptr, zero, iter);
@@ -1497,6 +1559,7 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
   uint32_t* s_win = s_own + ep.own_words;
   uint32_t* s_grec = s_win + ep.win_words * kWave;
   float* s_eps = reinterpret_cast<float*>(s_grec + kWave);
+  uint32_t* s_pace = s_grec + kWave + 128;   // one word: the delay (ticks) of the next stream, logic wave -> stream wave
 
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
@@ -1520,9 +1583,11 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
   } else {
     clear_rows(ep, s_obs, lane, kWave);
     for (int k = lane; k < min(ep.n_eps, 128); k += kWave) s_eps[k] = ep.eps_list[k];
+    if (lane == 0) s_pace[0] = 0u;
   }
   __syncthreads();
 
+  unsigned pace_t0 = (unsigned)wall_clock64();
 #pragma clang loop unroll(disable)
   for (int iter = 0; iter < ep.n_iter; ++iter) {
     int zero = 0;
@@ -1531,6 +1596,11 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     const bool valid = lane < ep.gpw && g < ep.G;
     const int dbg_it = iter;
     STAMP_START();
+    // pacing: count this iteration start; the returned value is consumed in phase B, behind the logic's own waited loads
+    unsigned long long pace_s = 0ull;
+    if (ep.pace && tid == 0) pace_s = pace_count(ep);
+    const unsigned pace_now = (unsigned)wall_clock64(), pace_t_own = pace_now - pace_t0;
+    pace_t0 = pace_now;
     // ---- phase A: logic of iteration `iter` (wave 0) | rows of iteration `iter - 1` to HBM, then cleared (wave 1) ----
     Rng rng = {};
     float reward = 0.f;
@@ -1553,6 +1623,10 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       s_grec[lane] = greedy_rec;
       STAMP(11);
     } else if (iter > 0) {
+      if (ep.pace) {   // ahead of the mean: leave HBM to the others for a while (the logic wave waits at the barrier either way)
+        const unsigned d = (unsigned)__builtin_amdgcn_readfirstlane((int)s_pace[0]);
+        if (d) pace_sleep(d);
+      }
       stream_rows(ep, s_obs, s_legal, s_own, g0, ng, P, H, lane, kWave);
       clear_rows(ep, s_obs, lane, kWave);
       STAMP_T(8, kWave);
@@ -1575,6 +1649,11 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       ep.terminal[g] = term ? 1 : 0;
       if (iter == ep.n_iter - 1)
         for (int pl = 0; pl < ep.npl; ++pl) ep.planes[(size_t)pl * ep.Gpad + g] = ST(pl);
+      if (ep.pace && lane == 0) {   // the delay of the stream of these rows (phase A of iter + 1), read after the barrier below
+        const unsigned d = iter > 0 ? pace_delay(ep, pace_s, iter, pace_t_own) : 0u;
+        s_pace[0] = d;
+        if (ep.dbg && ep.dbg_iters > 0) env_stamp(ep, dbg_it, 12, d);
+      }
     }
     __syncthreads();   // rows complete before wave 1 streams them; wave 1 done reading s_st before wave 0 changes it
     STAMP(4);
@@ -1783,6 +1862,13 @@ struct hsad_env {
   int rollout_chunk;  // > 0: hsad_env_rollout_random runs persistent launches of this many iterations (hsad_env_set_rollout_chunk)
   int rollout_pipe;   // persistent launches use the pipelined schedule where it applies (developer switch HSAD_ENV_PIPE=0: the
                       // single-phase schedule of env_rollout_kernel everywhere, for A/B)
+  // pacing of persistent launches (pace_delay).  Only paced launches touch the word, and each adds exactly pace_blocks x n_iter
+  // to it, so the host knows its value at the start of the next one without a memset: *d_pace == pace_base between launches
+  int rollout_pace;               // hsad_env_set_rollout_pace; HSAD_ENV_PACE=0 at creation
+  unsigned long long* d_pace;     // the progress word (allocated with the env, zero)
+  unsigned long long pace_base;   // its value once everything launched so far has run
+  long long pace_bias;            // hsad_env_debug_pace_bias: added to the base the kernels are told, never to pace_base
+  int pace_l0_q8, pace_cap_ticks; // dead band and delay cap (developer switches HSAD_ENV_PACE_L0_Q8 / HSAD_ENV_PACE_CAP_US)
   hipStream_t part_stream[16];
   hipEvent_t part_done[16];
   hipEvent_t part_begin[16];   // timing-enabled pair with part_done: per-partition chain time of the last rollout
@@ -1828,6 +1914,11 @@ EnvKernelFn pick_env_kernel(int mode, int P, int H, bool variant) {
 }
 
 typedef void (*EnvRolloutFn)(EnvParams);
+// pacing defaults (pace_delay): no dead band beyond the one the lead's definition brings (a workgroup in step with the others reads
+// a lead of (-1, 0], so 0 already is half an iteration), one delay at most 35 us and never more than half the workgroup's own last
+// iteration.  Measured against dead bands of 0.25 / 0.5 and caps of 20 / 60 us: profiles/r08_env_pace_ab.json
+constexpr int kPaceL0Q8 = 0;
+constexpr int kPaceCapTicks = 3500;
 // the pipelined schedule (env_rollout_pipe_kernel) needs exactly one stream wave and no V0-belief fix-up of the streamed rows;
 // 256-thread workgroups (few games per GPU), knowledge_mode 1 and variants run env_rollout_kernel
 bool rollout_pipelined(const hsad_env* e) {
@@ -1879,6 +1970,21 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
   ep.stagger_mode = stagger_mode;
   ep.a_out = a_out;
   ep.g_out = g_out;
+  ep.pace = nullptr;
+  if (mode == 3 && n_iter > 1 && e->rollout_pace) {
+    // workgroups with games: the padded game count may add an empty one (32-game workgroups), which returns at once
+    const int g_end = std::min(ep.G, g_begin + g_count);
+    const long long blocks = g_end > g_begin ? (g_end - g_begin + ep.gpw - 1) / ep.gpw : 0;
+    if (blocks > 0 && blocks * n_iter < (1ll << 29)) {   // pace_delay's fixed point
+      ep.pace = e->d_pace;
+      ep.pace_base = e->pace_base + (unsigned long long)e->pace_bias;
+      ep.pace_blocks = (int)blocks;
+      ep.pace_inv_q32 = (1ull << 32) / (unsigned long long)blocks;
+      ep.pace_l0_q8 = e->pace_l0_q8;
+      ep.pace_cap_ticks = e->pace_cap_ticks;
+      e->pace_base += (unsigned long long)(blocks * n_iter);
+    }
+  }
   if (mode == 3 && n_iter > 1)
     hipLaunchKernelGGL(pick_rollout_kernel(ep.P, ep.H, rollout_pipelined(e), ep.variant != 0), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds, stream, ep);
   else
@@ -1990,7 +2096,8 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   ep.obs_words = (ep.obs_words + 3) & ~3;
   ep.legal_words = (ep.legal_words + 3) & ~3;
   ep.own_words = (ep.own_words + 3) & ~3;
-  e->lds_bytes = sizeof(uint32_t) * ((size_t)ep.npl * kWave + ep.obs_words + ep.legal_words + ep.own_words + kWave + 128);
+  // + 4: the pacing word of the pipelined rollout behind the eps copy (kept a multiple of 16 bytes)
+  e->lds_bytes = sizeof(uint32_t) * ((size_t)ep.npl * kWave + ep.obs_words + ep.legal_words + ep.own_words + kWave + 128 + 4);
   e->lds_bytes_reset = e->lds_bytes + sizeof(uint32_t) * (size_t)ep.win_words * kWave;
   e->device = cfg->device;
   e->bound = false;
@@ -2003,6 +2110,12 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->n_part_active = 1;
   e->rollout_chunk = 0;
   e->rollout_pipe = getenv("HSAD_ENV_PIPE") ? atoi(getenv("HSAD_ENV_PIPE")) != 0 : 1;
+  e->rollout_pace = getenv("HSAD_ENV_PACE") ? atoi(getenv("HSAD_ENV_PACE")) != 0 : 1;
+  e->d_pace = nullptr;
+  e->pace_base = 0;
+  e->pace_bias = 0;
+  e->pace_l0_q8 = getenv("HSAD_ENV_PACE_L0_Q8") ? std::max(0, atoi(getenv("HSAD_ENV_PACE_L0_Q8"))) : kPaceL0Q8;
+  e->pace_cap_ticks = getenv("HSAD_ENV_PACE_CAP_US") ? std::min(1000, std::max(0, atoi(getenv("HSAD_ENV_PACE_CAP_US")))) * 100 : kPaceCapTicks;
   e->fork = nullptr;
   if (e->lds_bytes_reset > 160 * 1024) {
     const size_t need = e->lds_bytes_reset;
@@ -2028,6 +2141,8 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   if ((he = hipMalloc(&ep.legal_bits, sizeof(uint64_t) * (size_t)(ep.Gpad + 64) * P)) != hipSuccess) return fail("legal bits");
   HIP_TRY(hipMemset(ep.legal_bits, 0, sizeof(uint64_t) * (size_t)(ep.Gpad + 64) * P));
   if ((he = hipMalloc(&e->d_eps_list, sizeof(float) * cfg->n_eps)) != hipSuccess) return fail("eps list");
+  if ((he = hipMalloc((void**)&e->d_pace, sizeof(unsigned long long))) != hipSuccess) return fail("pace word");
+  HIP_TRY(hipMemset(e->d_pace, 0, sizeof(unsigned long long)));
   ep.eps_list = e->d_eps_list;
   e->state_bytes = planes_b + mt_b + dh_b;
   HIP_TRY(hipMemcpy(e->d_eps_list, cfg->eps_list, sizeof(float) * cfg->n_eps, hipMemcpyHostToDevice));
@@ -2051,6 +2166,7 @@ void hsad_env_destroy(hsad_env* e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
   if (e->d_phase) (void)hipFree(e->d_phase);
+  if (e->d_pace) (void)hipFree(e->d_pace);
   if (e->ep.planes) (void)hipFree(e->ep.planes);
   if (e->ep.mt) (void)hipFree(e->ep.mt);
   if (e->ep.deck_hist) (void)hipFree(e->ep.deck_hist);
@@ -2266,6 +2382,30 @@ int hsad_env_last_rollout_ms(hsad_env* e, float* ms_per_launch, int* n_part) {
 int hsad_env_set_rollout_chunk(hsad_env* e, int iterations_per_launch) {
   if (!e || iterations_per_launch < 0) return set_error(HSAD_ERR_INVALID, "bad argument");
   e->rollout_chunk = iterations_per_launch;
+  return HSAD_OK;
+}
+
+int hsad_env_set_rollout_pace(hsad_env* e, int on) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  e->rollout_pace = on != 0;
+  return HSAD_OK;
+}
+
+int hsad_env_rollout_pace_cap_us(const hsad_env* e) { return e ? e->pace_cap_ticks / 100 : 0; }
+
+int hsad_env_debug_pace_bias(hsad_env* e, int64_t bias) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  e->pace_bias = (long long)bias;
+  return HSAD_OK;
+}
+
+int hsad_env_debug_pace_word(hsad_env* e, int64_t* device_word, int64_t* host_base) {
+  if (!e || !device_word || !host_base) return set_error(HSAD_ERR_INVALID, "null argument");
+  unsigned long long w = 0;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(&w, e->d_pace, sizeof(w), hipMemcpyDeviceToHost));
+  *device_word = (int64_t)w;
+  *host_base = (int64_t)e->pace_base;
   return HSAD_OK;
 }
 

@@ -147,6 +147,24 @@ class BatchedHanabiEnv:
         """persistent rollout: one launch runs this many iterations of every game (0 = one launch per iteration)"""
         _lib.check(self.lib.hsad_env_set_rollout_chunk(self.h, int(iterations_per_launch)))
 
+    def set_rollout_pace(self, on):
+        """persistent rollout: workgroups ahead of the launch's mean progress delay their observation stream (default on;
+        timing only, see include/hsad.h)"""
+        _lib.check(self.lib.hsad_env_set_rollout_pace(self.h, int(bool(on))))
+
+    def rollout_pace_cap_us(self):
+        return int(self.lib.hsad_env_rollout_pace_cap_us(self.h))
+
+    def debug_pace_bias(self, bias):
+        """test seam: offset of the counter base the paced kernels are told"""
+        _lib.check(self.lib.hsad_env_debug_pace_bias(self.h, int(bias)))
+
+    def debug_pace_word(self):
+        """(progress word on the device, value the host expects); synchronises"""
+        w, b = C.c_int64(0), C.c_int64(0)
+        _lib.check(self.lib.hsad_env_debug_pace_word(self.h, C.byref(w), C.byref(b)))
+        return int(w.value), int(b.value)
+
     def last_rollout_ms(self):
         """average launch duration (ms) on each partition stream of the last partitioned rollout_random"""
         import ctypes as C

@@ -159,6 +159,20 @@ int hsad_env_set_partitions(hsad_env* env, int n_part);
  * that the workgroups of a CU stream their observations at different times.  Takes precedence over partitions; 0 (the
  * default) = one launch per iteration and partition.  Results are bit-identical either way. */
 int hsad_env_set_rollout_chunk(hsad_env* env, int iterations_per_launch);
+/* Pacing of persistent launches (on by default; HSAD_ENV_PACE=0 when the env is created, or on = 0 here, turns it off).  The
+ * workgroups of a launch run at persistently different rates and the launch ends on the slowest.  Every workgroup counts its
+ * iteration starts on one device word of the env; one that is ahead of the mean by more than a dead band delays its next
+ * observation stream by (lead - dead band) x its own iteration time, at most hsad_env_rollout_pace_cap_us(), and so leaves HBM
+ * bandwidth to the others.  No workgroup waits for another and no work moves: timing only, results are bit-identical. */
+int hsad_env_set_rollout_pace(hsad_env* env, int on);
+/* longest delay of one iteration, microseconds */
+int hsad_env_rollout_pace_cap_us(const hsad_env* env);
+/* Test seams of the pacing.  bias is added to the counter base every later persistent launch is told (not to the host's own
+ * record), so that every workgroup's lead reads bias / workgroups iterations too high: all far ahead (bias > 0) or far behind (bias < 0); 0
+ * restores the truth.  A lead no launch could produce (beyond its iteration count) switches the delay off.
+ * hsad_env_debug_pace_word synchronises the device and returns the progress word and the value the host expects it to hold. */
+int hsad_env_debug_pace_bias(hsad_env* env, int64_t bias);
+int hsad_env_debug_pace_word(hsad_env* env, int64_t* device_word, int64_t* host_base);
 /* Phase lock of the partition chains of hsad_env_rollout_random: partition k starts each launch `microseconds` after
  * partition k-1 started the launch of the same iteration (bounded in-kernel wait on a device timestamp), so that one
  * partition's latency-bound logic phase keeps overlapping another's HBM stream.  Timing only -- results are identical

@@ -1,12 +1,19 @@
 """Per-iteration trace of one persistent rollout launch at configs[1] (65,536 two-player games): where each workgroup's time goes,
 and how many workgroups stream observations on each CU and on the chip over time.
 
-  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--json OUT]
+  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--json OUT]
 
 The driver's shape is --warmup 5 --iters 20 (one 5-iteration launch, then the traced 20-iteration launch).  --schedule single runs
 env_rollout_kernel (HSAD_ENV_PIPE=0), pipe the default env_rollout_pipe_kernel.  Stamps are wall_clock64 (100 MHz, 10 ns) of
 hsad_env_debug_trace; slot map in csrc/hsad_env.hip (env_stamp).  Streaming intervals: single-phase = [write-back done, rows streamed]
-of each iteration; pipelined = [iteration start, stream wave done] of iterations 1.. (the rows of the previous one) plus the epilogue."""
+of each iteration; pipelined = [iteration start, stream wave done] of iterations 1.. (the rows of the previous one) plus the epilogue.
+
+Who lags: every workgroup's rate (us per iteration over the steady part of the launch, iteration 1 to the last start) is grouped by
+where the workgroup runs (XCC; SE; SH; CU = the four co-resident workgroups) and by where it writes (octile of the block index =
+position of its rows in the output buffers); per grouping the spread between the group means is set against the spread inside the
+groups (`share_of_variance_between_groups` is the usual eta squared).  --pace off traces the unpaced launch (HSAD_ENV_PACE=0); with
+pacing on, `pace` says how many iterations delayed their stream and by how much (--l0-q8 / --cap-us: the developer switches
+HSAD_ENV_PACE_L0_Q8 / HSAD_ENV_PACE_CAP_US)."""
 import argparse
 import json
 import os
@@ -25,9 +32,17 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--schedule", choices=("pipe", "single"), default="pipe")
+    ap.add_argument("--pace", choices=("on", "off"), default="on")
+    ap.add_argument("--l0-q8", type=int, default=None)
+    ap.add_argument("--cap-us", type=int, default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     os.environ["HSAD_ENV_PIPE"] = "1" if args.schedule == "pipe" else "0"
+    os.environ["HSAD_ENV_PACE"] = "1" if args.pace == "on" else "0"
+    if args.l0_q8 is not None:
+        os.environ["HSAD_ENV_PACE_L0_Q8"] = str(args.l0_q8)
+    if args.cap_us is not None:
+        os.environ["HSAD_ENV_PACE_CAP_US"] = str(args.cap_us)
     import torch
     from hanabi_sad_amd import BatchedHanabiEnv, _lib
     G = 65536
@@ -46,6 +61,8 @@ def main():
     env.check_errors()
     s = buf.view(nwg, args.iters, 16).cpu().numpy().astype(np.int64)
     rec = analyse(s, args.schedule == "pipe", args)
+    rec["pace"] = dict(rec.get("pace", {}), on=args.pace == "on", cap_us=env.rollout_pace_cap_us(),
+                       l0_q8=args.l0_q8 if args.l0_q8 is not None else "default")
     print(json.dumps(rec, indent=1))
     if args.json:
         with open(args.json, "w") as f:
@@ -80,6 +97,15 @@ def analyse(s, pipe, args):
     rec["launch_us"] = round(float(end.max()), 1)
     rec["start_spread_us"] = round(float(t[:, 0, 0].max() - t[:, 0, 0].min()), 2)
     rec["end_spread_us"] = round(float(end.max() - end.min()), 2)
+    if n > 2:
+        rec["who_lags"] = who_lags(t, hw, xcc, cu)
+    if pipe:
+        d = s[:, :n - 1, 12].astype(np.float64) * TICK_US          # delay decided in iteration k = of the stream in k + 1
+        rec["pace"] = {"share_of_iterations_that_slept": round(float((d > 0).mean()), 4),
+                       "share_of_workgroups_that_ever_slept": round(float((d > 0).any(axis=1).mean()), 4),
+                       "sleep_us_mean_when_slept": round(float(d[d > 0].mean()), 2) if (d > 0).any() else 0.0,
+                       "sleep_us_total_per_workgroup_mean": round(float(d.sum(axis=1).mean()), 2),
+                       "sleep_us_total_per_workgroup_max": round(float(d.sum(axis=1).max()), 2)}
     # streaming workgroups over time, 0.5 µs bins, chip-wide and per CU
     T = float(end.max())
     nb = int(T / 0.5) + 1
@@ -103,6 +129,34 @@ def analyse(s, pipe, args):
     step = max(1, nb // 40)
     rec["chip_streaming_workgroups_series"] = {"bin_us": 0.5 * step, "values": [int(chip[i:i + step].mean()) for i in range(0, nb, step)]}
     return rec
+
+
+def who_lags(t, hw, xcc, cu):
+    """per-workgroup rate, grouped by place of execution and by place in the output buffers"""
+    nwg, n = t.shape[0], t.shape[1]
+    rate = (t[:, n - 1, 0] - t[:, 1, 0]) / (n - 2)                    # us per iteration, iteration 1 .. start of the last
+    se, sh = (hw >> 13) & 7, (hw >> 12) & 1
+    keys = {"xcc": xcc & 0xF, "se": se, "xcc_se": ((xcc & 0xF) << 3) | se, "xcc_se_sh": ((xcc & 0xF) << 4) | (se << 1) | sh,
+            "cu_co_resident_workgroups": cu, "block_index_octile": np.arange(nwg) * 8 // nwg}
+    out = {"rate_us_per_iteration": {"mean": round(float(rate.mean()), 2), "std": round(float(rate.std()), 2),
+                                     "min": round(float(rate.min()), 2), "p5": round(float(np.percentile(rate, 5)), 2),
+                                     "p50": round(float(np.median(rate)), 2), "p95": round(float(np.percentile(rate, 95)), 2),
+                                     "max": round(float(rate.max()), 2)}, "groupings": {}}
+    total = float(((rate - rate.mean()) ** 2).sum())
+    for name, key in keys.items():
+        ids = np.unique(key)
+        means = np.array([rate[key == i].mean() for i in ids])
+        sizes = np.array([(key == i).sum() for i in ids])
+        within = float(sum(((rate[key == i] - rate[key == i].mean()) ** 2).sum() for i in ids))
+        g = {"groups": int(len(ids)), "group_size_min_max": [int(sizes.min()), int(sizes.max())],
+             "between_group_means_std_us": round(float(np.sqrt((sizes * (means - rate.mean()) ** 2).sum() / nwg)), 3),
+             "within_groups_std_us": round(float(np.sqrt(within / nwg)), 3),
+             "share_of_variance_between_groups": round(1.0 - within / total, 4) if total > 0 else None,
+             "group_means_min_max_us": [round(float(means.min()), 2), round(float(means.max()), 2)]}
+        if len(ids) <= 16:
+            g["group_means_us"] = {str(int(i)): round(float(m), 2) for i, m in zip(ids, means)}
+        out["groupings"][name] = g
+    return out
 
 
 if __name__ == "__main__":

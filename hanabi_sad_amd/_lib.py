@@ -124,6 +124,10 @@ SIGNATURES = {
     "hsad_env_debug_trace": (C.c_int, [_P, _P, C.c_int]),
     "hsad_env_rollout_lds_bytes": (C.c_int64, [_P]),
     "hsad_env_error_count": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "hsad_env_fork": (C.c_int, [_P, _P, _P, _P, _P]),
+    "hsad_env_determinize": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
+    "hsad_env_playout_random": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
+    "hsad_env_playout_random_keyed": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P, _P]),
     "hsad_aggregate_priority": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
     "hsad_replay_create": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(Field), C.c_int, C.POINTER(_P)]),

@@ -1874,6 +1874,7 @@ struct hsad_env {
   hipEvent_t part_begin[16];   // timing-enabled pair with part_done: per-partition chain time of the last rollout
   int last_rollout_iters, last_rollout_parts;
   hipEvent_t fork;
+  int32_t* d_sel;     // [Gpad] which games hsad_env_determinize resampled (hsad_env_search.inc); allocated on first use
 };
 
 namespace {
@@ -2117,6 +2118,7 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->pace_l0_q8 = getenv("HSAD_ENV_PACE_L0_Q8") ? std::max(0, atoi(getenv("HSAD_ENV_PACE_L0_Q8"))) : kPaceL0Q8;
   e->pace_cap_ticks = getenv("HSAD_ENV_PACE_CAP_US") ? std::min(1000, std::max(0, atoi(getenv("HSAD_ENV_PACE_CAP_US")))) * 100 : kPaceCapTicks;
   e->fork = nullptr;
+  e->d_sel = nullptr;
   if (e->lds_bytes_reset > 160 * 1024) {
     const size_t need = e->lds_bytes_reset;
     delete e;
@@ -2167,6 +2169,7 @@ void hsad_env_destroy(hsad_env* e) {
   (void)hipSetDevice(e->device);
   if (e->d_phase) (void)hipFree(e->d_phase);
   if (e->d_pace) (void)hipFree(e->d_pace);
+  if (e->d_sel) (void)hipFree(e->d_sel);
   if (e->ep.planes) (void)hipFree(e->ep.planes);
   if (e->ep.mt) (void)hipFree(e->ep.mt);
   if (e->ep.deck_hist) (void)hipFree(e->ep.deck_hist);
@@ -2475,3 +2478,6 @@ int hsad_env_error_count(hsad_env* e, int32_t* count, int32_t* first_game, int32
 }
 
 }  // extern "C"
+
+// fork / determinise / observe / playout: the env as a simulator for test-time search
+#include "hsad_env_search.inc"

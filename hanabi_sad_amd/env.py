@@ -28,6 +28,10 @@ class BatchedHanabiEnv:
         self.h = C.c_void_p()
         _lib.check(self.lib.hsad_env_create_rules(C.byref(cfg), C.byref(rules), C.byref(self.h)))
         L = self.lib
+        # what a second env needs to be a fork target of this one (fork_from; search.py builds its search env from it)
+        self.config = dict(players=players, hand_size=hand_size, bomb=int(bomb), max_len=int(max_len), sad=bool(sad),
+                           shuffle_color=bool(shuffle_color), knowledge_mode=int(knowledge_mode), colors=int(colors), ranks=int(ranks),
+                           max_information_tokens=int(max_information_tokens), max_life_tokens=int(max_life_tokens))
         self.G, self.P, self.H = num_games, players, hand_size
         self.colors, self.ranks = int(colors), int(ranks)
         self.max_information_tokens, self.max_life_tokens = int(max_information_tokens), int(max_life_tokens)
@@ -172,6 +176,43 @@ class BatchedHanabiEnv:
         _lib.check(self.lib.hsad_env_last_rollout_ms(self.h, ms, C.byref(n)))
         return [float(ms[k]) for k in range(n.value)]
 
+    # -- the env as a simulator for search (include/hsad.h: hsad_env_fork / _determinize / _playout_random) --
+    def _i32(self, t, n):
+        t = torch.as_tensor(t, device=self.device).to(torch.int32).contiguous()
+        assert t.shape == (n,), "expected %d values, got %s" % (n, tuple(t.shape))
+        return t
+
+    def fork_from(self, src, src_index, seeds=None):
+        """game j of this env becomes a copy of src's game src_index[j] (int32 [G]; -1 = leave game j alone) and its rows are
+        rewritten from the copied state.  seeds=None copies the generator too; seeds (int32 [G]) reseeds game j with seeds[j]."""
+        idx = self._i32(src_index, self.G)
+        sd = self._i32(seeds, self.G) if seeds is not None else None
+        _lib.check(self.lib.hsad_env_fork(self.h, src.h, idx.data_ptr(), sd.data_ptr() if sd is not None else None, self._stream()))
+
+    def determinize(self, viewer, key, seed):
+        """resamples the hand of player viewer[g] (int32 [G]; -1 = skip) from the hands its card knowledge allows; key (int64 [G])
+        and seed select the world.  Returns tries (int32 [G]: tries used, 0 skipped, -1 gave up and kept the hand)."""
+        v = self._i32(viewer, self.G)
+        k = torch.as_tensor(key, device=self.device).to(torch.int64).contiguous()
+        assert k.shape == (self.G,)
+        tries = torch.zeros(self.G, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.hsad_env_determinize(self.h, v.data_ptr(), k.data_ptr(), int(seed) & (2 ** 64 - 1), tries.data_ptr(),
+                                                 self._stream()))
+        return tries
+
+    def playout_random(self, max_iter, policy_seed, key=None):
+        """random-legal policy -> step until every live game has ended (at most max_iter iterations), finished games left alone.
+        The observation rows are NOT rewritten (stale until the next fork_from / reset / step); terminal and query() are current.
+        key (int64 [G]) replaces the game index in the policy's hash."""
+        k = None
+        if key is not None:
+            k = torch.as_tensor(key, device=self.device).to(torch.int64).contiguous()
+            assert k.shape == (self.G,)
+        _lib.check(self.lib.hsad_env_playout_random_keyed(self.h, int(max_iter), int(policy_seed) & (2 ** 64 - 1),
+                                                          k.data_ptr() if k is not None else None, self.a.data_ptr(),
+                                                          self.greedy_a.data_ptr(), self._stream()))
+        return self.a, self.greedy_a
+
     def query(self):
         out = torch.zeros(self.G, 16, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.hsad_env_query(self.h, out.data_ptr(), self._stream()))
@@ -200,5 +241,6 @@ class BatchedHanabiEnv:
         n, g, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         _lib.check(self.lib.hsad_env_error_count(self.h, C.byref(n), C.byref(g), C.byref(c)))
         if n.value:
-            what = {1: "illegal move", 2: "illegal greedy move", 3: "step on a finished game"}.get(c.value, "?")
+            what = {1: "illegal move", 2: "illegal greedy move", 3: "step on a finished game",
+                    4: "fork source index out of range"}.get(c.value, "?")
             raise _lib.HsadError("%d game(s) violated the env contract; first: game %d, %s" % (n.value, g.value, what))

@@ -216,8 +216,53 @@ int hsad_env_debug_trace(hsad_env* env, uint64_t* buf, int n_iters);
 int64_t hsad_env_rollout_lds_bytes(const hsad_env* env);
 
 /* Number of games that hit an API-contract error (illegal move, step on a finished game) since
- * the last call; synchronises the device.  first_game/first_code (may be NULL) describe the first. */
+ * the last call; synchronises the device.  first_game/first_code (may be NULL) describe the first.
+ * Codes: 1 illegal move, 2 illegal greedy move, 3 step on a finished game, 4 hsad_env_fork source index out of range. */
 int hsad_env_error_count(hsad_env* env, int32_t* count, int32_t* first_game, int32_t* first_code);
+
+/* ---- The env as a simulator for test-time search (determinised Monte Carlo, SPARTA-style single-agent search): branch a game,
+ * resample the hidden hand, play out.  The reference has no such call; nothing below changes what reset / step / rollout compute.
+ *
+ * hsad_env_fork: dst game j becomes a copy of src game src_index[j] (device int32 [G_dst]); -1 leaves game j untouched, any other
+ * value outside [0, G_src) leaves it untouched too and is counted in dst's error log (code 4; nothing is read out of bounds).
+ * Copied: every state plane (eps and colour permutation included), the policy counter, and the deck-history row when both envs
+ * track it.  seeds == NULL copies the generator as well (its 624 words, the draw counter, the look-ahead): the fork then deals
+ * exactly what the source will deal.  seeds = device int32 [G_dst] gives game j the generator std::mt19937(seeds[j]) with no draw
+ * consumed.  A source game that is not started or is finished is copied as it is (a later hsad_env_reset restarts it).
+ * Afterwards all bound outputs of the forked games are rewritten from the copied state ("observe": the rows of the last reset or
+ * step of the source, bit for bit), reward = 0, terminal = the state's terminated bit; a game that was never started gets all-zero
+ * rows.  Untouched games keep theirs.  The SAD greedy-action section is no function of the state: it is copied from src's
+ * currently bound observation rows (bit words if bound, else float32), so a sad = 1 fork is refused when src has neither.
+ * HSAD_ERR_INVALID when players, hand size, rules, sad, shuffle_color, knowledge_mode, bomb, max_len or the device differ, when
+ * dst == src, or when dst tracks the deck history and src does not.  Launch-only; src is read on `stream`. */
+int hsad_env_fork(hsad_env* dst, hsad_env* src, const int32_t* src_index, const int32_t* seeds, void* stream);
+
+/* hsad_env_determinize: in place, resamples the hand of player viewer[g] (device int32 [G]; -1, or a game that is not started or
+ * is finished: skipped) uniformly from the hands its card knowledge allows.  key (device int64 [G]) is the "game" field of the
+ * counter-based hash, seed its seed: equal (seed, key) on equal states give equal worlds.  tries_out (device int32 [G] or NULL):
+ * tries used, 0 if skipped, -1 if the sampler gave up after 32 tries and kept the hand.  Per game, card type t = colour * 5 + rank:
+ *   pool[t] = deck count + copies in the viewer's hand;  compat_i[t] = colour(t) and rank(t) both plausible for slot i;
+ *   Zmax_i = sum_t pool[t] compat_i[t];  for try = 0..31: q = pool; for slot i = 0..L-1: Z = sum_t q[t] compat_i[t] (0 fails the
+ *   try), h = hash(seed, key, try * 8 + i, 64), k = (h * Z) >> 32, card = lowest t whose running sum of q compat_i exceeds k,
+ *   q[card] -= 1;  u = hash(seed, key, try * 8 + 7, 64);  accept iff u * prod Zmax_i < (prod Z) << 32.
+ * hash = the policy's (mix64-based) hash with stream 64.  On acceptance the hand holds the sampled cards in slot order and the deck
+ * counts become q; deck size, knowledge, discards, board, last move and generator are unchanged.  The proposal has probability
+ * prod q_i / Z_i and is kept with probability prod Z_i / Zmax_i, so accepted hands are proportional to the product of the falling
+ * counts: uniform over the physical unseen cards consistent with the knowledge (multiply-shift bias < 2^-26).  The rows of the
+ * resampled games are then rewritten by the observe pass (SAD section kept from the env's own rows).  Launch-only. */
+int hsad_env_determinize(hsad_env* env, const int32_t* viewer, const int64_t* key, uint64_t seed, int32_t* tries_out, void* stream);
+
+/* hsad_env_playout_random: up to max_iter iterations of random-legal policy -> step for every game that is started and not
+ * finished, in one launch.  A finished game is left alone (no restart, no error, no counter advance); a live game's trajectory --
+ * actions in a / greedy_a, state, draws -- is that of hsad_env_policy_random + hsad_env_step.  NO observation rows are written
+ * (nothing consumes them; the launch is bound by game logic, not by HBM): priv_s / legal_move / own_hand / eps / reward and the
+ * packed rows are STALE until the next hsad_env_fork, hsad_env_reset or hsad_env_step rewrites them.  `terminal`, hsad_env_query and
+ * the masks hsad_env_policy_random reads are current.  Every workgroup bounds its own work (max_iter) and waits for no other.
+ * _keyed: key (device int64 [G], NULL = the game index) replaces the game index in the policy's hash, so that a game's playout
+ * does not depend on the slot it sits in. */
+int hsad_env_playout_random(hsad_env* env, int max_iter, uint64_t policy_seed, int64_t* a, int64_t* greedy_a, void* stream);
+int hsad_env_playout_random_keyed(hsad_env* env, int max_iter, uint64_t policy_seed, const int64_t* key, int64_t* a, int64_t* greedy_a,
+                                  void* stream);
 
 
 /* ------------------------------------------------------------------------------------------

@@ -1,0 +1,88 @@
+"""Records for DESIGN §3g: fork + observe time, the playout's env-steps/s without the observation stream, the sampler's mean tries,
+next to hsad_env_step on the same games.  One JSON line.
+
+    python tools/search_probe.py [--games 65536] [--repeats 5]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from hanabi_sad_amd import BatchedHanabiEnv  # noqa: E402
+
+
+def timed(fn, repeats):
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=65536)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--sad", type=int, default=1)
+    args = ap.parse_args()
+    G, dev = args.games, "cuda:0"
+    kw = dict(players=2, hand_size=5, sad=bool(args.sad), eps_list=(0.0,), device=dev)
+    src = BatchedHanabiEnv(G, seed=1, **kw)
+    dst = BatchedHanabiEnv(G, seed=2, track_deck_history=False, **kw)
+    src.rollout_random(12, 3)
+    idx = torch.randperm(G, device=dev, generator=torch.Generator(device=dev).manual_seed(0)).to(torch.int32)
+    seeds = torch.arange(G, device=dev, dtype=torch.int32)
+    res = {"games": G, "sad": args.sad, "repeats": args.repeats}
+    dst.fork_from(src, idx)   # warm-up (first launch of each kernel)
+    res["fork_observe_ms"] = timed(lambda: dst.fork_from(src, idx), args.repeats)
+    res["fork_observe_reseed_ms"] = timed(lambda: dst.fork_from(src, idx, seeds), args.repeats)
+    # yardstick: one hsad_env_step of the same games (policy outside the timed region)
+    step_ms = []
+    for _ in range(args.repeats):
+        src.reset()
+        a, ga = src.policy_random(5)
+        step_ms += timed(lambda: src.step(a, ga), 1)
+    res["env_step_ms"] = step_ms
+    q = src.query()
+    viewer = torch.where(q[:, 0] == 0, q[:, 1], torch.full_like(q[:, 1], -1)).to(torch.int32)
+    key = torch.arange(G, device=dev, dtype=torch.int64)
+    det_ms, tries_mean, gave_up = [], [], 0
+    for r in range(args.repeats):
+        dst.fork_from(src, torch.arange(G, device=dev, dtype=torch.int32))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tries = dst.determinize(viewer, key, 100 + r)
+        torch.cuda.synchronize()
+        det_ms.append((time.perf_counter() - t0) * 1e3)
+        done = tries[tries > 0].float()
+        tries_mean.append(float(done.mean()))
+        gave_up += int((tries < 0).sum())
+    res["determinize_observe_ms"], res["mean_tries"], res["gave_up"] = det_ms, tries_mean, gave_up
+    # playout: every game from where the fork left it to its end
+    rates, play_ms = [], []
+    for r in range(args.repeats):
+        dst.fork_from(src, torch.arange(G, device=dev, dtype=torch.int32), seeds)
+        n0 = dst.query()[:, 6].sum().item()
+        ms = timed(lambda: dst.playout_random(100, 9 + r), 1)[0]
+        qq = dst.query()
+        assert bool((qq[:, 0] == 1).all())
+        steps = qq[:, 6].sum().item() - n0
+        play_ms.append(ms)
+        rates.append(steps / ms * 1e3)
+    dst.check_errors()
+    res["playout_ms"], res["playout_env_steps_per_s"] = play_ms, rates
+    for k in ("fork_observe_ms", "fork_observe_reseed_ms", "env_step_ms", "determinize_observe_ms", "playout_ms", "playout_env_steps_per_s"):
+        res[k + "_median"] = statistics.median(res[k])
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

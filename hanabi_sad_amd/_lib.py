@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libhsad.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("hsad_env.hip", "hsad_replay.hip", "hsad_r2d2.hip", "hsad_r2d2_f32.hip", "hsad_agent.hip", "hsad_learner.hip", "hsad_comm.hip",
-                                                      "hsad_actor.hip", "hsad_eval.hip")]
+                                                      "hsad_actor.hip", "hsad_eval.hip", "hsad_search.hip")]
 _lib = None
 
 
@@ -278,6 +278,9 @@ SIGNATURES = {
     "hsad_seat_gather": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "hsad_seat_scatter": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "hsad_seating_stats": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "hsad_search_fork_state": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "hsad_search_actions": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "hsad_search_job_stats": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "hsad_ipc_handle_bytes": (C.c_int, []),
     "hsad_ipc_alloc": (C.c_int, [C.c_int64, C.POINTER(_P), _P, C.c_int]),
     "hsad_ipc_free": (C.c_int, [_P]),

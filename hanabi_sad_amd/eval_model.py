@@ -8,6 +8,7 @@ layout.
   --paper obl --obl_path obl.pthw                       self-play of an OBL model
   --paper op  --method sad --idx 0 3 6 9 --cross_play   the 4 x 4 matrix
   --paper sad --weight a.pthw b.pthw c.pthw --cross_play
+  --paper op  --method sad --idx 0 --search_worlds 8    M0 in self-play, blueprint only and blueprint + search over the same deals
 
 As in the reference the deals are seeds 1 .. num_game * num_run, bombing out keeps the score (bomb 0) and everyone acts greedily.
 Whether the env appends SAD's greedy-action section is read off the models' input width (838 vs 783 features in the 2-player
@@ -34,6 +35,10 @@ def parse_args(argv=None):
     p.add_argument("--idx", default=None, type=int, nargs="+", help="--paper op --cross_play: the zoo models of the pool")
     p.add_argument("--root", default=None, type=str, help="folder that holds models/op/<method>/M{idx}.pthw (default: the repository)")
     p.add_argument("--precision", default="bf16", type=str, choices=["bf16", "fp32"])
+    p.add_argument("--search_worlds", default=0, type=int, help="> 0 with a single --idx: also play with blueprint-policy search "
+                   "(search.play_with_search), this many sampled worlds per legal action")
+    p.add_argument("--search_threshold", default=0.05, type=float, help="deviate from the blueprint only for a larger value gain")
+    p.add_argument("--search_seat", default=None, type=int, help="the one seat that searches (default: every seat)")
     return p.parse_args(argv)
 
 
@@ -60,8 +65,30 @@ def load_pool(args):
     return [load_obl_model(args.obl_path, args.device, args.precision)], ["OBL"], "OBL", 2
 
 
+def search_report(args):
+    """--search_worlds N with a single --idx: the model in self-play over the deals 1 .. num_game * num_run, blueprint only and
+    blueprint + search -> (SearchPlay without search, SearchPlay with it)"""
+    from .checkpoint import load_op_model
+    from .search import play_with_search
+    if args.paper != "op" or args.cross_play or not args.idx or len(args.idx) != 1:
+        raise SystemExit("--search_worlds needs --paper op and a single --idx I (no --cross_play)")
+    agent = load_op_model(args.method, args.idx[0], None, args.device, root=args.root, precision=args.precision)[0]
+    sad = getattr(agent.online, "F", None) == env_dims(2, 5, sad=True)[0]
+    n = args.num_game * args.num_run
+    kw = dict(precision=args.precision, device=args.device, threshold=args.search_threshold,
+              searcher="all" if args.search_seat is None else args.search_seat)
+    base = play_with_search(agent, n, 1, 0, sad, worlds=0, **kw)
+    res = play_with_search(agent, n, 1, 0, sad, worlds=args.search_worlds, **kw)
+    print("blueprint: %f +/- %f" % (base.mean, base.sem), "; perfect: ", base.perfect)
+    print("blueprint + search (%d worlds): %f +/- %f" % (args.search_worlds, res.mean, res.sem), "; perfect: ", res.perfect,
+          "; deviations per game: %f" % float(res.deviations.double().mean()))
+    return base, res
+
+
 def main(argv=None):
     args = parse_args(argv)
+    if args.search_worlds > 0:
+        return search_report(args)
     agents, names, title, P = load_pool(args)
     net = agents[0].online
     n, kw = args.num_game * args.num_run, dict(precision=args.precision, device=args.device, hand_size=5 if P <= 3 else 4)

@@ -1,11 +1,16 @@
-"""Determinised Monte-Carlo action values on the device env (SPARTA-style single-agent search with a random-legal rollout policy):
+"""Determinised Monte-Carlo action values on the device env (SPARTA-style single-agent search):
 for the player on turn, every legal action is tried in `worlds` sampled worlds -- the player's own hidden hand resampled from the
 hands its card knowledge allows, the deck reshuffled -- and each world is played out to the end.  Built from the env's search
 primitives (BatchedHanabiEnv.fork_from / determinize / step / playout_random); the rollouts of all (game, action, world) jobs run
-batched in one search env, `capacity` games at a time."""
+batched in one search env, `capacity` games at a time.
+
+Two rollout policies: mc_action_values plays the worlds out with random legal moves (one launch, hsad_env_playout_random);
+policy_action_values / PolicySearch play them out with the blueprint itself -- the R2D2 agent acting greedily for every seat --
+which is what can improve on that agent (choose_action, play_with_search).  The glue kernels of the second are csrc/hsad_search.hip."""
 import numpy as np
 import torch
 
+from . import _lib
 from .env import BatchedHanabiEnv
 
 Q_TERMINATED, Q_CUR_PLAYER, Q_SCORE, Q_STARTED = 0, 1, 2, 14   # include/hsad.h HSAD_Q_*
@@ -91,3 +96,290 @@ def mc_greedy_action(values):
     filled = torch.where(torch.isnan(v), torch.full_like(v, -float("inf")), v)
     best = filled.argmax(dim=1)
     return torch.where(torch.isnan(v).all(dim=1), torch.full_like(best, -1), best)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# blueprint-policy search: the sampled worlds are played out by the agent itself
+# ---------------------------------------------------------------------------------------------------------
+class SearchValues:
+    """what PolicySearch.search returns, all on the device of `totals`:
+    totals int64 [G, A, 3] = (sum score, sum score^2, worlds counted) per (root game, action) as hsad_search_job_stats reduced them;
+    values float32 [G, A] = sum / worlds in float32 from those integers, NaN where nothing was counted (illegal actions, games that
+    are not live, turns of a player who does not search); sem float32 [G, A] = population std / sqrt(worlds) from the integers;
+    blueprint_a int64 [G] = the agent's own greedy action at the root, -1 for games that were not searched."""
+
+    def __init__(self, totals, blueprint_a):
+        self.totals = totals = torch.as_tensor(totals).to(torch.int64)
+        self.blueprint_a = torch.as_tensor(blueprint_a).to(torch.int64)
+        s, sq, n = totals[..., 0], totals[..., 1], totals[..., 2]
+        nan = torch.full(s.shape, float("nan"), dtype=torch.float32, device=totals.device)
+        counted = n > 0
+        nf = torch.where(counted, n, torch.ones_like(n))
+        self.values = torch.where(counted, s.to(torch.float32) / nf.to(torch.float32), nan)
+        var_n2 = (nf * sq - s * s).clamp(min=0).to(torch.float64)        # n^2 * population variance, exact in int64
+        nd = nf.to(torch.float64)
+        self.sem = torch.where(counted, (torch.sqrt(var_n2) / nd / torch.sqrt(nd)).to(torch.float32), nan)
+
+
+def _searched_games(searcher, cur, G):
+    """bool [G] (numpy): the games whose player on turn searches.  searcher: None (everyone), a seat number, or an int [G] mask"""
+    if searcher is None:
+        return np.ones(G, dtype=bool)
+    if isinstance(searcher, (int, np.integer)):
+        return cur == int(searcher)
+    m = searcher.cpu().numpy() if isinstance(searcher, torch.Tensor) else np.asarray(searcher)
+    if m.shape != (G,):
+        raise ValueError("searcher must be None, a seat number or an int [%d] mask; got shape %s" % (G, tuple(m.shape)))
+    return m != 0
+
+
+class PolicySearch:
+    """The search env of `capacity` slots, the agent's state buffers for its capacity * P rows and the host loop that plays one
+    chunk of jobs; search() may be called move after move (play_with_search does).  `like` is any env with the root's rules."""
+
+    def __init__(self, like, agent, capacity=4096, max_steps=200):
+        self.agent, self.capacity, self.max_steps = agent, int(capacity), int(max_steps)
+        self.device = dev = like.device
+        self.bf16 = bool(getattr(agent, "accepts_bf16_obs", False))
+        self.env = env = BatchedHanabiEnv(self.capacity, seed=0, eps_list=(0.0,), device=str(dev), track_deck_history=False, **like.config)
+        self.lib = env.lib
+        if self.bf16:     # a bf16 kernel agent reads the env's packed rows: the first GEMM's operand, written by the env itself
+            env.enable_packed(bf16_row_len=agent.online.Fp, keep_float32=False)
+        env.reset()       # spare slots of a short chunk hold started games: they play on with the rest and are never counted
+        N = self.capacity * env.P
+        z = agent.get_h0(N)
+        self.h, self.c = torch.zeros_like(z["h0"]).contiguous(), torch.zeros_like(z["c0"]).contiguous()
+        self.h16 = torch.zeros(self.h.shape, dtype=torch.bfloat16, device=dev) if N >= 1024 else None
+        self.eps = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.stats4 = torch.zeros(1, 4, dtype=torch.int64, device=dev)
+        self.unfinished = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.host = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)]
+        self.copied = [torch.cuda.Event() for _ in range(2)]
+        self.iterations = 0        # env steps of the last search, over all its chunks
+        self.open_games = []       # the "games still running" words the host read during the last search (one per step, one step late)
+
+    def close(self):
+        self.env.close()
+
+    def _obs(self):
+        env = self.env
+        N = env.G * env.P
+        if self.bf16:
+            return {"priv_s_bf16": env.priv_s_bf16.view(N, -1), "legal_move": env.legal_move.view(N, env.A), "eps": self.eps}
+        return {"priv_s": env.priv_s.view(N, env.F), "legal_move": env.legal_move.view(N, env.A), "eps": self.eps}
+
+    def _play_chunk(self, player, override, bp_rows):
+        """greedy acting for every seat of every slot until all games of the search env have ended; the candidate action is forced
+        on iteration 0 only.  -> the greedy actions of the rows `bp_rows` at iteration 0 (the blueprint's move at the root)"""
+        env, lib, agent = self.env, self.lib, self.agent
+        hid = {"h0": self.h, "c0": self.c}
+        if self.h16 is not None:
+            hid["h0_16"] = self.h16
+        bp, done = None, False
+        for t in range(self.max_steps):
+            reply, hid = agent.act(self._obs(), hid)
+            a, g = reply["a"].contiguous(), reply["greedy_a"].contiguous()
+            if t == 0 and bp_rows is not None:
+                bp = g[bp_rows]
+            _lib.check(lib.hsad_search_actions(env.h, a.data_ptr(), g.data_ptr(), player.data_ptr(), override.data_ptr() if t == 0 else None,
+                                               env.a.data_ptr(), env.greedy_a.data_ptr(), env._stream()))
+            env.step(env.a, env.greedy_a)
+            _lib.check(lib.hsad_seating_stats(env.h, env.G, self.stats4.data_ptr(), self.unfinished.data_ptr(), env._stream()))
+            # the host looks at ONE word, and one step late (eval._TournamentBatch.play): it never waits for the step it has just
+            # enqueued; the extra step at the end only hands finished games their noop
+            self.host[t & 1].copy_(self.unfinished, non_blocking=True)
+            self.copied[t & 1].record(torch.cuda.current_stream(self.device))
+            self.iterations += 1
+            if t > 0:
+                self.copied[(t - 1) & 1].synchronize()
+                left = int(self.host[(t - 1) & 1][0])
+                self.open_games.append(left)
+                if left == 0:
+                    done = True
+                    break
+        if not done and int(self.unfinished.cpu()[0]) != 0:
+            raise RuntimeError("%d game(s) of the search env still running after %d steps" % (int(self.unfinished.cpu()[0]), self.max_steps))
+        return bp
+
+    def search(self, root, hid, worlds, seed, searcher=None):
+        """-> SearchValues for the root env's games; root and hid ({"h0", "c0"}: [L, root.G * root.P, H], the agent's state entering
+        the root step) are only read.  See policy_action_values."""
+        from .eval import _drain_errors
+        G, P, A, cap = root.G, root.P, root.A, self.capacity
+        dev, env, lib = self.device, self.env, self.lib
+        if (P, A) != (env.P, env.A):
+            raise ValueError("the root env has %d players / %d actions, the search env %d / %d" % (P, A, env.P, env.A))
+        h_src, c_src = hid["h0"], hid["c0"]
+        if tuple(h_src.shape) != (self.h.shape[0], G * P, self.h.shape[2]) or h_src.shape != c_src.shape:
+            raise ValueError("hid must hold h0 / c0 of shape [%d, %d, %d]; got %s" % (self.h.shape[0], G * P, self.h.shape[2], tuple(h_src.shape)))
+        h_src, c_src = h_src.contiguous(), c_src.contiguous()
+        self.iterations, self.open_games = 0, []
+        totals = torch.zeros(G, A, 3, dtype=torch.int64, device=dev)
+        blueprint = torch.full((G,), -1, dtype=torch.int64, device=dev)
+        pairs, cur = search_jobs(root)
+        if len(pairs):
+            pairs = pairs[_searched_games(searcher, cur, G)[pairs[:, 0]]]
+        if len(pairs) == 0 or worlds < 1:
+            return SearchValues(totals, blueprint)
+        n_job = len(pairs)
+        n = n_job * worlds                                   # jobs in (game, action, world) order; job k works for pair k // worlds
+        games, first_pair = np.unique(pairs[:, 0], return_index=True)
+        seed_of = np.zeros((G, worlds), dtype=np.int32)      # common random numbers: a world's seed and key know (game, world) only
+        for g in games:
+            seed_of[g] = [world_seed(seed, int(g), w) for w in range(worlds)]
+        first_job = first_pair * worlds                      # world 0 of each game's first job: where the blueprint's own move is read
+        stats = torch.zeros(n_job, 3, dtype=torch.int64, device=dev)
+        L, H = self.h.shape[0], self.h.shape[2]
+        for c0 in range(0, n, cap):
+            k = np.arange(c0, c0 + cap)
+            valid = k < n
+            kk = np.minimum(k, n - 1)
+            pj, w_c = kk // worlds, kk % worlds
+            g_c, a_c = pairs[pj, 0], pairs[pj, 1]
+            src = torch.from_numpy(np.where(valid, g_c, -1).astype(np.int32)).to(dev)      # spare slots: no fork, no job
+            seeds = torch.from_numpy(seed_of[g_c, w_c]).to(dev)
+            key = torch.from_numpy((g_c << 32) | w_c).to(dev)
+            player = torch.from_numpy(np.where(valid, cur[g_c], -1).astype(np.int32)).to(dev)
+            override = torch.from_numpy(np.where(valid, a_c, -1).astype(np.int64)).to(dev)
+            job = torch.from_numpy(np.where(valid, pj, -1).astype(np.int32)).to(dev)
+            env.fork_from(root, src, seeds)
+            env.determinize(player, key, seed)
+            _lib.check(lib.hsad_search_fork_state(src.data_ptr(), cap, G, P, L, H, h_src.data_ptr(), c_src.data_ptr(), self.h.data_ptr(),
+                                                  self.c.data_ptr(), self.h16.data_ptr() if self.h16 is not None else None, env._stream()))
+            here = (first_job >= c0) & (first_job < c0 + cap)
+            bp_rows = None
+            if here.any():
+                bp_rows = torch.from_numpy((first_job[here] - c0) * P + cur[games[here]]).to(dev)
+            bp = self._play_chunk(player, override, bp_rows)
+            if bp is not None:
+                blueprint[torch.from_numpy(games[here]).to(dev)] = bp
+            _lib.check(lib.hsad_search_job_stats(env.h, job.data_ptr(), n_job, stats.data_ptr(), env._stream()))
+        _drain_errors(env)        # finished games were handed the noop: the "step on a finished game" notes
+        pd = torch.from_numpy(pairs).to(dev)
+        totals[pd[:, 0], pd[:, 1]] = stats
+        return SearchValues(totals, blueprint)
+
+
+def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_steps=200, searcher=None):
+    """SearchValues: values[g, a] = mean final score (HSAD_Q_SCORE) over `worlds` sampled worlds when the player on turn of root game
+    g plays a and EVERY player, the searcher included, then follows the blueprint `agent` greedily to the end of the game.
+
+    agent: what eval._acting_agent produces.  An agent with accepts_bf16_obs reads the search env's packed bf16 rows, any other the
+    float32 rows.  hid: the agent's state entering the root step, {"h0", "c0"} as [L, root.G * root.P, H]; read, never written, and
+    neither is the root env.  searcher: None, a seat number or an int [G] mask -- games whose player on turn does not search get no
+    jobs, all-NaN rows and blueprint_a = -1.
+
+    Jobs are (root game, legal action of the player on turn, world), keyed and seeded as in mc_action_values (world_seed / world_key:
+    every action of a game meets the same worlds).  Per chunk of `capacity` jobs: fork_from with the seeds, determinize for the player
+    on turn, hsad_search_fork_state (the root game's LSTM state into every seat of its forks), then the loop -- agent.act on all
+    capacity * P rows, hsad_search_actions (the candidate action forced on iteration 0, the noop for finished games), env.step,
+    hsad_seating_stats for the one word the host reads a step late -- and hsad_search_job_stats.  The first act of a chunk is also
+    the blueprint's own move at the root (the searcher does not observe its own hand, so its row is the root's): blueprint_a.
+    RuntimeError if games are still running after max_steps.
+
+    The result does not depend on `capacity` (a job knows (game, action, world), never its slot; a row's result depends on no other
+    row) AS LONG AS every act call stays in one acting regime: at 1,024 rows the act kernels switch to the fused GEMM + cell path
+    (net_step in csrc/hsad_agent.hip, CompositeAgent.act, R2D2Agent._fused), whose bf16 rounding differs.  capacity * P below 1,024
+    and capacity * P from 1,024 up are two regimes.
+
+    Stated approximation: the partners' LSTM states are those of the TRUE world.  In a sampled world their observations differ in
+    the searcher's hand, so a full SPARTA would replay the history per world to rebuild them; here every seat of a fork starts from
+    the state its root game carries."""
+    ps = PolicySearch(root, agent, capacity, max_steps)
+    try:
+        return ps.search(root, hid, worlds, seed, searcher)
+    finally:
+        ps.close()
+
+
+def choose_action(values, blueprint_a, threshold=0.05):
+    """int64 [G]: the best action (lowest uid on ties) where values[best] - values[blueprint_a] > threshold, else blueprint_a;
+    -1 where blueprint_a is -1.  NaN entries never win.  Pure tensor code (CPU tensors work)."""
+    v = torch.as_tensor(values)
+    bp = torch.as_tensor(blueprint_a).to(torch.int64)
+    filled = torch.where(torch.isnan(v), torch.full_like(v, -float("inf")), v)
+    best = filled.argmax(dim=1)
+    v_best = filled.gather(1, best.unsqueeze(1)).squeeze(1)
+    v_bp = filled.gather(1, bp.clamp(min=0).unsqueeze(1)).squeeze(1)
+    deviate = (v_best - v_bp) > threshold            # NaN (nothing to compare) is False
+    return torch.where(bp < 0, torch.full_like(bp, -1), torch.where(deviate, best, bp))
+
+
+def move_seed(search_seed, move):
+    """the search seed of move number `move` of a play_with_search run: a function of (search_seed, move) alone"""
+    return _mix64((int(search_seed) & _M64) ^ _mix64(int(move) + 1)) & 0x7FFFFFFFFFFFFFFF
+
+
+class SearchPlay:
+    """what play_with_search returns: scores (list, one per deal), mean, perfect (fraction of perfect games), num_perfect,
+    deviations int64 [num_game] (moves where search overrode the blueprint) and trace: per move a pair of int64 [num_game] CPU
+    tensors (chosen, blueprint), -1 where the game's player on turn did not search"""
+
+    def __init__(self, scores, perfect_score, deviations, trace):
+        self.scores = [int(s) for s in scores]
+        self.mean = float(np.mean(scores))
+        self.num_perfect = int((np.asarray(scores) == perfect_score).sum())
+        self.perfect = self.num_perfect / len(self.scores)
+        self.sem = float(np.std(scores) / np.sqrt(len(self.scores)))
+        self.deviations, self.trace = deviations, trace
+
+
+def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05, search_seed=0, searcher="all", capacity=4096,
+                     num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16", shuffle_color=False, colors=5, ranks=5,
+                     max_information_tokens=8, max_life_tokens=3):
+    """eval.evaluate's lock-step loop over the deals seed .. seed + num_game - 1 with search on top of the blueprint -> SearchPlay.
+    Before each step: PolicySearch values for the games whose player on turn searches (searcher: "all" or a seat number),
+    choose_action, then the root steps with a = the chosen action and greedy_a = the blueprint's greedy action; the carried state
+    is advanced by the blueprint's act as usual.  The search seed of a move is move_seed(search_seed, move), so a run repeats
+    exactly.  worlds = 0 takes no search path at all and returns evaluate's scores.  The search env has min(capacity, num_game x
+    (A - 1) x worlds) slots -- the most jobs a move can have -- and capacity x P decides the acting regime (policy_action_values)."""
+    from .eval import _acting_agent, _drain_errors
+    agent = _acting_agent(agent, precision, device)
+    env = BatchedHanabiEnv(num_game, players=num_player, hand_size=hand_size, seed=seed, bomb=bomb, eps_list=[0.0], max_len=-1, sad=bool(sad),
+                           shuffle_color=bool(shuffle_color), device=device, track_deck_history=False, colors=colors, ranks=ranks,
+                           max_information_tokens=max_information_tokens, max_life_tokens=max_life_tokens)
+    seat = None if searcher == "all" else int(searcher)
+    if seat is not None and not 0 <= seat < num_player:
+        raise ValueError("searcher must be \"all\" or a seat in 0..%d" % (num_player - 1))
+    # no move has more jobs than games x playable actions x worlds: a smaller batch needs no more slots than that
+    ps = PolicySearch(env, agent, min(int(capacity), num_game * (env.A - 1) * worlds), max_steps) if worlds > 0 else None
+    N = num_game * num_player
+    deviations = torch.zeros(num_game, dtype=torch.int64, device=env.device)
+    trace = []
+    try:
+        hid = agent.get_h0(N)
+        env.reset()
+        noop = env.A - 1
+        for t in range(max_steps):
+            q = env.query()
+            done = q[:, Q_TERMINATED] == 1
+            if bool(done.all()):
+                break
+            obs = {"priv_s": env.priv_s.view(N, env.F), "legal_move": env.legal_move.view(N, env.A), "eps": env.eps.view(N)}
+            reply, new_hid = agent.act(obs, hid)
+            a, g = reply["a"].contiguous(), reply["greedy_a"].contiguous()
+            if ps is None:
+                live = (~done).unsqueeze(1)
+                a = torch.where(live, a.view(num_game, num_player), torch.full_like(a.view(num_game, num_player), noop)).contiguous()
+                env.step(a, a)
+            else:
+                sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat)
+                player = q[:, Q_CUR_PLAYER].contiguous()
+                # the blueprint's move is the root act's own greedy action (the search's first act gives the same one while both
+                # run in one acting regime; this one holds in any)
+                own = g.view(num_game, num_player).gather(1, player.to(torch.int64).clamp(0, num_player - 1).unsqueeze(1)).squeeze(1)
+                blueprint = torch.where(sv.blueprint_a >= 0, own, sv.blueprint_a)
+                chosen = choose_action(sv.values, blueprint, threshold).contiguous()
+                _lib.check(env.lib.hsad_search_actions(env.h, a.data_ptr(), g.data_ptr(), player.data_ptr(), chosen.data_ptr(),
+                                                       env.a.data_ptr(), env.greedy_a.data_ptr(), env._stream()))
+                env.step(env.a, env.greedy_a)
+                deviations += ((chosen >= 0) & (chosen != blueprint)).to(torch.int64)
+                trace.append((chosen.cpu(), blueprint.cpu()))
+            hid = new_hid
+        _drain_errors(env)
+        scores = env.query()[:, 5].cpu().numpy().astype(np.int64)
+    finally:
+        if ps is not None:
+            ps.close()
+        env.close()
+    return SearchPlay(scores, colors * ranks, deviations.cpu(), trace)

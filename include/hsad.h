@@ -1075,6 +1075,32 @@ int hsad_seat_scatter(const hsad_env* env, const int32_t* rows, int n, const int
  * *unfinished int32 = games of the whole env not finished yet -- the one word a host loop reads.  Integer sums: exact, order-free. */
 int hsad_seating_stats(const hsad_env* env, int games_per_seating, int64_t* stats, int32_t* unfinished, void* stream);
 
+/* ---- glue kernels of blueprint-policy search (search.PolicySearch): a search env of G slots plays (root game, candidate action,
+ * sampled world) jobs with the R2D2 agent acting for every seat; hsad_env_fork + hsad_env_determinize place the worlds, these three
+ * keep the rest of a chunk on the device.  All three are HBM-bound, one pass, launch-only. ---- */
+/* The agent's carried state into the forks.  State tensors are fp32 [L, G * P, H], row (l, g * P + p).  For every layer l,
+ * destination game j < G_dst and seat p < P: row (l, j * P + p) of h_dst / c_dst = row (l, src_index[j] * P + p) of h_src / c_src.
+ * h16_dst (NULL = not wanted) bf16 [L, G_dst * P, H] receives the bf16 rounding (nearest even, as hsad_cast_pad_bf16) of the copied
+ * h rows: the operand the fused cell reads for 1,024 rows or more (hid["h0_16"]).  src_index device int32 [G_dst]: -1 leaves the
+ * rows of game j untouched, and so does any other value outside [0, G_src) (checked on the device, nothing is read out of bounds;
+ * hsad_env_fork logs code 4 for the same list).  The source is only read; source and destination must not overlap.
+ * HSAD_ERR_INVALID: H % 4 != 0, a size < 1, a null or not 16-byte aligned tensor. */
+int hsad_search_fork_state(const int32_t* src_index, int G_dst, int G_src, int P, int L, int H, const float* h_src, const float* c_src,
+                           float* h_dst, float* c_dst, void* h16_dst, void* stream);
+/* What act returned for all G * P rows of `env` (a_src / greedy_src int64 [G * P]) -> what hsad_env_step takes (a / greedy_a int64
+ * [G, P]; may be the same memory as the sources).  Every seat of a game that is finished or not started receives the noop uid A - 1
+ * in both outputs.  In a live game g with override[g] >= 0 (device int64 [G]) and player[g] (device int32 [G]) in [0, P):
+ * a[g, player[g]] = override[g]; greedy_a keeps greedy_src -- the agent's greedy action, what SAD shows the partner when the searcher
+ * deviates.  A player outside [0, P) means no override for that game; override == NULL means masking only (player may be NULL too). */
+int hsad_search_actions(const hsad_env* env, const int64_t* a_src, const int64_t* greedy_src, const int32_t* player,
+                        const int64_t* override_a, int64_t* a, int64_t* greedy_a, void* stream);
+/* Scores of the finished slots, reduced per job.  job device int32 [G]: the (root game, action) pair slot g works for; -1, or any
+ * value outside [0, n_job), skips the slot.  For every finished game (started and terminated) with a valid job: stats int64
+ * [n_job, 3] += (score, score^2, 1), where score is the score latched when the game ended -- HSAD_Q_SCORE of the final position
+ * (0 after the last life with bomb = 1).  It ACCUMULATES: the caller zeroes stats once per search and calls this once per chunk.
+ * Integer atomics: exact, order-free.  The "games still running" word of the host loop is hsad_seating_stats(env, G, ...)'s. */
+int hsad_search_job_stats(const hsad_env* env, const int32_t* job, int n_job, int64_t* stats, void* stream);
+
 /* ---- one-sided intra-node transport (dist.py ReplayLink(transport = "ipc")): landing buffers exported by IPC handle and written by the
  * SENDER with a device-to-device copy -- SDMA over xGMI, no kernel resident on either GPU while a peer has not answered (a posted RCCL
  * receive is one, and the learner's whole-chip persistent launches cannot start next to it).  Completion is announced by the sender's

@@ -1,0 +1,105 @@
+"""Records for DESIGN §3g, blueprint-policy search: seconds per search.policy_action_values call on one root batch of the full
+2-player game, jobs/s, env-steps/s of the search loop, the mean fraction of games still live per iteration (the case for or against
+compacting finished games out of the act batch), the three glue kernels' times, and the same call of mc_action_values (random
+playouts) as the yardstick.  Host clock around a device synchronise, median of the repeats.  One JSON line.
+
+    python tools/policy_search_probe.py [--roots 64] [--worlds 8] [--capacity 4096] [--hid 512] [--repeats 5]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from hanabi_sad_amd import BatchedHanabiEnv, _lib  # noqa: E402
+from hanabi_sad_amd.search import PolicySearch, mc_action_values  # noqa: E402
+
+
+def timed(fn, repeats):
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--roots", type=int, default=64)
+    ap.add_argument("--worlds", type=int, default=8)
+    ap.add_argument("--capacity", type=int, default=4096)
+    ap.add_argument("--hid", type=int, default=512)
+    ap.add_argument("--moves", type=int, default=10, help="lock-step greedy moves before the root position")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--sad", type=int, default=1)
+    args = ap.parse_args()
+    from hanabi_sad_amd.composite import CNet, CompositeAgent
+    from hanabi_sad_amd.eval import env_dims
+    from hanabi_sad_amd.selfplay import init_weights
+    dev, G, P = "cuda:0", args.roots, 2
+    F, A = env_dims(P, 5, bool(args.sad))
+    net = CNet(init_weights(F, args.hid, A, 5, 1), dev)          # a random net of the zoo's shape: timing does not ask for a trained one
+    agent = CompositeAgent(net, net, 1, 0.99)
+    root = BatchedHanabiEnv(G, players=P, seed=1, bomb=0, eps_list=[0.0], max_len=-1, sad=bool(args.sad), device=dev, track_deck_history=False)
+    root.reset()
+    hid = agent.get_h0(G * P)
+    for _ in range(args.moves):
+        obs = {"priv_s": root.priv_s.view(G * P, F), "legal_move": root.legal_move.view(G * P, A), "eps": root.eps.view(G * P)}
+        reply, hid = agent.act(obs, hid)
+        root.step(reply["a"].view(G, P).contiguous(), reply["greedy_a"].view(G, P).contiguous())
+    hid = {"h0": hid["h0"], "c0": hid["c0"]}
+    ps = PolicySearch(root, agent, args.capacity)
+    res = {"roots": G, "worlds": args.worlds, "capacity": args.capacity, "hid": args.hid, "sad": args.sad, "repeats": args.repeats}
+    sv = ps.search(root, hid, args.worlds, 0)                       # warm-up (first launch of each kernel)
+    jobs = int(sv.totals[..., 2].sum())
+    res["jobs"] = jobs
+    ms, steps, live, live_steps = [], [], [], []
+    for r in range(args.repeats):
+        ms += timed(lambda: ps.search(root, hid, args.worlds, 1 + r), 1)
+        steps.append(ps.iterations * args.capacity)                 # every slot is stepped every iteration, finished or not
+        live.append(sum(ps.open_games) / max(1, len(ps.open_games)) / args.capacity)
+        live_steps.append(sum(ps.open_games))                       # games still running after each step: the steps that moved a game
+    res["search_ms"], res["loop_iterations"] = ms, ps.iterations
+    res["jobs_per_s"] = [jobs / m * 1e3 for m in ms]
+    res["slot_steps_per_s"] = [s / m * 1e3 for s, m in zip(steps, ms)]
+    res["live_env_steps_per_s"] = [s / m * 1e3 for s, m in zip(live_steps, ms)]
+    res["live_fraction_per_iteration"] = live
+    res["mc_action_values_ms"] = timed(lambda: mc_action_values(root, args.worlds, 3, capacity=args.capacity), args.repeats)
+    # the three glue kernels alone, on the search env as the last chunk left it
+    env, lib, st = ps.env, ps.lib, ps.env._stream()
+    cap = args.capacity
+    src = torch.randint(0, G, (cap,), device=dev).to(torch.int32)
+    L, H = ps.h.shape[0], ps.h.shape[2]
+    h16 = ps.h16.data_ptr() if ps.h16 is not None else None
+    a = torch.zeros(cap * P, dtype=torch.int64, device=dev)
+    player = torch.zeros(cap, dtype=torch.int32, device=dev)
+    override = torch.zeros(cap, dtype=torch.int64, device=dev)
+    job = (torch.arange(cap, device=dev) // args.worlds).to(torch.int32)
+    n_job = int(job.max()) + 1
+    stats = torch.zeros(n_job, 3, dtype=torch.int64, device=dev)
+    calls = {
+        "fork_state_ms": lambda: _lib.check(lib.hsad_search_fork_state(src.data_ptr(), cap, G, P, L, H, hid["h0"].data_ptr(), hid["c0"].data_ptr(),
+                                                                       ps.h.data_ptr(), ps.c.data_ptr(), h16, st)),
+        "actions_ms": lambda: _lib.check(lib.hsad_search_actions(env.h, a.data_ptr(), a.data_ptr(), player.data_ptr(), override.data_ptr(),
+                                                                 env.a.data_ptr(), env.greedy_a.data_ptr(), st)),
+        "job_stats_ms": lambda: _lib.check(lib.hsad_search_job_stats(env.h, job.data_ptr(), n_job, stats.data_ptr(), st)),
+    }
+    for name, fn in calls.items():
+        fn()
+        res[name] = timed(fn, args.repeats)
+    for k in ("search_ms", "jobs_per_s", "slot_steps_per_s", "live_env_steps_per_s", "live_fraction_per_iteration", "mc_action_values_ms", "fork_state_ms", "actions_ms",
+              "job_stats_ms"):
+        res[k + "_median"] = statistics.median(res[k])
+    ps.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

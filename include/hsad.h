@@ -504,7 +504,8 @@ int hsad_gemm_timing_read(int M, int N, int K, double* avg_ms, int32_t* launches
 int hsad_lstm_sync_timed_out(const void* sync_scratch, int T, int Bn, int32_t* timed_out);
 /* Dueling head + masked argmax (r2d2.py:106-131): heads fp32 [M,ldh] = [advantage(A) | value(1) | ...],
  * legal fp32 [M,A], action int64 [M] (may be NULL) -> q [M,A], qa [M], greedy int64 [M] (may be NULL).
- * scratch: fp32 [2 + ceil(M/256)]. */
+ * scratch: fp32 [2 + ceil(M/256)].  On return scratch[1 + i] = min of q over rows [256 i, 256 i + 256) (what hsad_loss_tail folds);
+ * scratch[0] = the global minimum, written only when a greedy output is asked for (nobody reads it otherwise). */
 int hsad_q_head(const float* heads, int ldh, const float* legal, const int64_t* action, int M, int A, float* q,
                 float* qa, int64_t* greedy, float* scratch, void* stream);
 /* n-step double-DQN TD error, Huber loss, priorities (r2d2.py:403-428,472-478); all [T,B] fp32 except
@@ -558,8 +559,9 @@ int hsad_prepare_weight(const float* src, int R, int C, int ld_src, const int32_
                         void* dstT16, int ld_dstT, void* stream);
 /* out[i] = a[perm[i]] + b[perm[i]] (b / perm may be NULL): the gate bias b_ih + b_hh in gate-blocked order */
 int hsad_bias_sum_perm(const float* a, const float* b, const int32_t* perm, float* out, int n, void* stream);
-/* the same, batched: every operand of a net re-derived in ONE launch (hsad_r2d2_net_refresh uses it).  begin, then up to 12
- * hsad_prepare_weight jobs, then up to 8 hsad_bias_sum_perm jobs, then launch.  The job list is thread-local host state. */
+/* the same, batched: every operand of a net re-derived in ONE launch (hsad_r2d2_net_refresh uses it).  begin, then up to 20
+ * hsad_prepare_weight jobs, then up to 12 hsad_bias_sum_perm jobs (no weight job after a bias job), then launch.  The job list is
+ * thread-local host state. */
 int hsad_refresh_begin(void);
 int hsad_refresh_add_weight(const float* src, int R, int C, int ld_src, const int32_t* perm, void* dst16, int ld_dst, void* dstT16,
                             int ld_dstT);

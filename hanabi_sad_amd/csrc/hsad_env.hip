@@ -73,6 +73,8 @@ struct EnvParams {
   int g_begin, g_count;            // launch covers games [g_begin, g_begin + g_count); g_begin % 64 == 0
   unsigned long long policy_seed;  // MODE 2 (step with built-in random-legal policy)
   int n_iter;       // MODE 3: iterations this launch runs for its games (persistent rollout; 1 otherwise)
+  int delta;        // env_rollout_pipe_kernel: two copies of the observation bit rows in LDS; every stream of the launch but the first
+                    // stores only the lines of priv_s whose bits changed since the stream before (rollout_delta_active)
   int stagger_ticks;  // MODE 3, n_iter > 1: workgroup b starts (b % 8) * stagger_ticks (100 MHz) late, see env_kernel
   int stagger_mode;   // which workgroups start late (developer switch HSAD_ENV_STAGGER_MODE, see env_rollout_kernel)
   int64_t* a_out;                  // MODE 2: where the sampled actions are recorded ([G,P] each)
@@ -463,6 +465,8 @@ __device__ __forceinline__ uint32_t hand_match_mask(uint32_t hw, bool by_color, 
 //                              8 stream wave (thread 64): rows of `it - 1` streamed and cleared, 5 last record only: epilogue stream done,
 //                              6 / 7 as above
 //                              12 pacing: ticks by which the stream of this iteration's rows is delayed (pace_delay)
+//                              13 delta stream (EnvParams::delta): 128-byte lines of priv_s the stream wave stored for the rows of `it - 1`;
+//                              14 / 15 last record only: lines wave 0 / wave 1 stored in the epilogue stream
 //   both, trace layout:        9 HW_REG_HW_ID, 10 HW_REG_XCC_ID of the workgroup (written with slot 0)
 __device__ __forceinline__ void env_stamp(const EnvParams& ep, int it, int k, unsigned long long v) {
   const size_t blk = (size_t)(ep.g_begin / ep.gpw) + blockIdx.x;
@@ -710,6 +714,35 @@ __device__ __forceinline__ void stream_bits_f32_aligned(const uint32_t* bits, fl
   }
   const uint32_t done = nch << 2;
   if ((uint32_t)lane < n - done) out[done + lane] = get1(bits, done + lane) ? 1.f : 0.f;
+}
+
+// Same, but only where the bits changed: `old` holds the bit words this range of `out` was last written from.  Word w is the eight
+// float4 of chunks 8w .. 8w+7, one 128-byte line of `out` (the range starts on a line), so a line is stored iff its word differs and
+// no line is ever stored in part.  all: every line regardless (`old` is not read).  The tail floats (n & 3) are always stored.
+// Returns this lane's count of stored lines (count on).
+template <bool NT>
+__device__ __forceinline__ unsigned stream_bits_f32_delta(const uint32_t* bits, const uint32_t* old, bool all, float* out, uint32_t n,
+                                                          int lane, int nthreads, bool count) {
+  float4* o4 = reinterpret_cast<float4*>(out);
+  const uint32_t nch = n >> 2;
+  unsigned stored = 0;
+  for (uint32_t k = lane; k < nch; k += nthreads) {
+    const uint32_t w = bits[k >> 3];
+    if (all || w != old[k >> 3]) {
+      const float4 v = nib_to_f4((w >> ((k & 7u) * 4u)) & 15u);
+      if (NT) {
+        typedef float nt_f4 __attribute__((ext_vector_type(4)));
+        nt_f4 q = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(q, reinterpret_cast<nt_f4*>(o4 + k));
+      } else {
+        o4[k] = v;
+      }
+      if (count && (k & 7u) == 0u) ++stored;
+    }
+  }
+  const uint32_t done = nch << 2;
+  if ((uint32_t)lane < n - done) out[done + lane] = get1(bits, done + lane) ? 1.f : 0.f;
+  return stored;
 }
 
 __device__ __forceinline__ uint32_t perm_c(uint32_t pm, int c) { return (pm >> (3 * c)) & 7u; }
@@ -996,6 +1029,35 @@ __device__ __forceinline__ void stream_rows(const EnvParams& ep, const uint32_t*
   stream_rows_packed(ep, s_obs, 0, ng * P, (size_t)g0 * P, t, n);
   stream_bits_f32_aligned<false>(s_legal, ep.legal + (size_t)g0 * PA, (uint32_t)(ng * PA), t, n);
   stream_bits_f32_aligned<false>(s_own, ep.own + (size_t)g0 * PO, (uint32_t)(ng * PO), t, n);
+}
+
+// The same for the pipelined rollout, whose later streams of a launch reduce the float32 observation to the lines that changed
+// (EnvParams::delta).  s_old: the bit rows priv_s was last written from; all: every line (the first stream of a launch, and every
+// stream without delta).  The packed forms, legal moves and own hand go out in full from the current rows.  Returns this lane's
+// count of observation lines stored (count on: the trace).
+__device__ __forceinline__ unsigned stream_rows_delta(const EnvParams& ep, const uint32_t* s_obs, const uint32_t* s_old, bool all,
+                                                      const uint32_t* s_legal, const uint32_t* s_own, int g0, int ng, int P, int H,
+                                                      int t, int n, bool count) {
+  const size_t PF = (size_t)P * ep.F, PA = (size_t)P * ep.A, PO = (size_t)P * 3 * H;
+  unsigned stored = 0;
+  if (!ep.obs_f32) {
+    // device consumers only: no float32 observation leaves the chip
+  } else if (ep.nt_stores) {
+    stored = stream_bits_f32_delta<true>(s_obs, s_old, all, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t, n, count);
+  } else {
+    stored = stream_bits_f32_delta<false>(s_obs, s_old, all, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t, n, count);
+  }
+  stream_rows_packed(ep, s_obs, 0, ng * P, (size_t)g0 * P, t, n);
+  stream_bits_f32_aligned<false>(s_legal, ep.legal + (size_t)g0 * PA, (uint32_t)(ng * PA), t, n);
+  stream_bits_f32_aligned<false>(s_own, ep.own + (size_t)g0 * PO, (uint32_t)(ng * PO), t, n);
+  return stored;
+}
+
+// zero `nz` LDS words from p (16-byte aligned) by threads [t, t + n)
+__device__ __forceinline__ void clear_words(uint32_t* p, int nz, int t, int n) {
+  uint4* z4 = reinterpret_cast<uint4*>(p);
+  for (int k = t; k < (nz >> 2); k += n) z4[k] = make_uint4(0u, 0u, 0u, 0u);
+  for (int k = (nz & ~3) + t; k < nz; k += n) p[k] = 0u;
 }
 
 // zero the obs / legal / own bit rows (contiguous in LDS from s_obs) by threads [t, t + n)
@@ -1548,6 +1610,11 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
 // CU happen to be out of phase.  The state planes stay in LDS for the whole launch (loaded once, written back after the last
 // iteration: nothing else reads them while the launch runs).  Same arithmetic, draw order and values as env_rollout_kernel: only
 // which wave writes the rows, and when, differs.
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+  for (int o = kWave / 2; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, kWave);
+  return v;
+}
+
 template <int TP, int TH>
 __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void env_rollout_pipe_kernel(EnvParams ep) {
   rollout_stagger(ep);
@@ -1560,6 +1627,12 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
   uint32_t* s_grec = s_win + ep.win_words * kWave;
   float* s_eps = reinterpret_cast<float*>(s_grec + kWave);
   uint32_t* s_pace = s_grec + kWave + 128;   // one word: the delay (ticks) of the next stream, logic wave -> stream wave
+  // ep.delta: a second copy of the observation bit rows behind everything else.  The rows of iteration i are built in copy i & 1;
+  // while they are streamed the other copy still holds the rows of i - 1, which is what priv_s holds, so only the lines whose
+  // word differs are stored.  The first stream of a launch stores every line: nothing is assumed about priv_s before the launch.
+  // (the copy's address is worked out where it is used: as one more launch-long value it costs the generic instance a register it
+  // does not have)
+#define S_OBS1(z) (ep.delta ? s_pace + 4 + (z) : s_obs)
 
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
@@ -1627,8 +1700,21 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
         const unsigned d = (unsigned)__builtin_amdgcn_readfirstlane((int)s_pace[0]);
         if (d) pace_sleep(d);
       }
-      stream_rows(ep, s_obs, s_legal, s_own, g0, ng, P, H, lane, kWave);
-      clear_rows(ep, s_obs, lane, kWave);
+      // rows of iter - 1; with delta, against the copy this iteration builds in, which holds the rows of iter - 2: the last ones
+      // written (iter 1: nothing written yet, every line goes out)
+      uint32_t* s_obs1 = S_OBS1(zero);
+      uint32_t* rows = (iter & 1) ? s_obs : s_obs1;
+      uint32_t* prev = (iter & 1) ? s_obs1 : s_obs;
+      const bool dbg_lines = ep.dbg && ep.dbg_iters > 0;
+      int sl = lane;
+      asm volatile("" : "+v"(sl));   // opaque: the stream's per-lane addresses are worked out here, not kept in registers for the launch
+      unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || iter == 1, s_legal, s_own, g0, ng, P, H, sl, kWave, dbg_lines);
+      clear_words(prev, ep.obs_words, sl, kWave);
+      clear_words(s_legal, ep.legal_words + ep.own_words, sl, kWave);
+      if (dbg_lines) {
+        stored = wave_sum(stored);
+        if (lane == 0) env_stamp(ep, dbg_it, 13, stored);
+      }
       STAMP_T(8, kWave);
     }
     __syncthreads();
@@ -1636,7 +1722,7 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     // ---- phase B: both waves build the rows of `iter`; wave 0 finishes the look-ahead refill and writes the scalars ----
     Refill rf;
     refill_issue(rf, rng, valid && wave == 0);
-    if (valid) build_rows<TP, TH>(ep, s_st, lane, g, s_obs, s_legal, s_own, s_grec[lane], wave, 2);
+    if (valid) build_rows<TP, TH>(ep, s_st, lane, g, (iter & 1) ? S_OBS1(zero) : s_obs, s_legal, s_own, s_grec[lane], wave, 2);
     STAMP(3);
     if (valid && wave == 0) {
       refill_finish(rf, rng);
@@ -1659,9 +1745,20 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     STAMP(4);
   }
   // epilogue: both waves stream the last iteration's rows
-  stream_rows(ep, s_obs, s_legal, s_own, g0, ng, P, H, tid, ep.nthreads);
   const int dbg_it = ep.n_iter - 1;
+  {
+    const uint32_t* s_obs1 = S_OBS1(0);
+    const uint32_t* rows = (ep.n_iter & 1) ? s_obs : s_obs1;
+    const uint32_t* prev = (ep.n_iter & 1) ? s_obs1 : s_obs;
+    const bool dbg_lines = ep.dbg && ep.dbg_iters > 0;
+    unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || ep.n_iter == 1, s_legal, s_own, g0, ng, P, H, tid, ep.nthreads, dbg_lines);
+    if (dbg_lines) {
+      stored = wave_sum(stored);
+      if (lane == 0) env_stamp(ep, dbg_it, 14 + wave, stored);
+    }
+  }
   STAMP(5);
+#undef S_OBS1
 }
 
 // ---- init: zero planes, seed mt19937 (std::mt19937::seed: x0 = s; x_i = 1812433253*(x ^ x>>30) + i) ---
@@ -1865,6 +1962,11 @@ struct hsad_env {
   // pacing of persistent launches (pace_delay).  Only paced launches touch the word, and each adds exactly pace_blocks x n_iter
   // to it, so the host knows its value at the start of the next one without a memset: *d_pace == pace_base between launches
   int rollout_pace;               // hsad_env_set_rollout_pace; HSAD_ENV_PACE=0 at creation
+  // delta stream of the pipelined launches (EnvParams::delta).  Scope: one launch.  Nothing about priv_s is remembered between
+  // launches, so reset / step / fork or a caller writing into priv_s cannot make anything stale.
+  int rollout_delta;              // hsad_env_set_rollout_delta; HSAD_ENV_DELTA=0 at creation: every stream in full, for A/B
+  bool delta_fits;                // the second copy of the rows costs the pipelined kernel no resident workgroup per CU
+  size_t lds_bytes_delta;         // lds_bytes_reset + the second copy
   unsigned long long* d_pace;     // the progress word (allocated with the env, zero)
   unsigned long long pace_base;   // its value once everything launched so far has run
   long long pace_bias;            // hsad_env_debug_pace_bias: added to the base the kernels are told, never to pace_base
@@ -1926,6 +2028,11 @@ bool rollout_pipelined(const hsad_env* e) {
   return e->rollout_pipe && e->ep.nthreads == 2 * kWave && e->ep.kmode == 0 && !e->ep.variant;
 }
 
+// the delta stream needs the pipelined schedule, a float32 observation to skip lines of, and room for the second copy of the rows
+bool rollout_delta_active(const hsad_env* e) {
+  return e->rollout_delta && e->delta_fits && rollout_pipelined(e) && e->ep.obs_f32;
+}
+
 EnvRolloutFn pick_rollout_kernel(int P, int H, bool pipe, bool variant) {
   if (variant) return env_rollout_kernel<0, 0, true>;
 #define HSAD_ROLLOUT_SPECIALISE(PP, HH) \
@@ -1939,9 +2046,22 @@ EnvRolloutFn pick_rollout_kernel(int P, int H, bool pipe, bool variant) {
 }
 
 int configure_env_kernels(hsad_env* e) {
-  for (const bool pipe : {false, true})
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_rollout_kernel(e->ep.P, e->ep.H, pipe, e->ep.variant != 0)),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes_reset));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_rollout_kernel(e->ep.P, e->ep.H, false, e->ep.variant != 0)),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes_reset));
+  // the pipelined kernel with and without the second copy of the observation rows: the delta stream is used only where the copy
+  // leaves as many workgroups resident per CU as the kernel has without it (configs[1]: four)
+  e->delta_fits = false;
+  if (!e->ep.variant) {
+    const void* fn = reinterpret_cast<const void*>(pick_rollout_kernel(e->ep.P, e->ep.H, true, false));
+    const bool room = e->lds_bytes_delta <= 160 * 1024;
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(room ? e->lds_bytes_delta : e->lds_bytes_reset)));
+    if (room) {
+      int wg_full = 0, wg_delta = 0;
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_full, fn, 2 * kWave, e->lds_bytes_reset));
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_delta, fn, 2 * kWave, e->lds_bytes_delta));
+      e->delta_fits = wg_delta >= 1 && wg_delta >= wg_full;
+    }
+  }
   for (int mode = 0; mode < 4; ++mode) {
     const size_t lds = (mode == 1 || mode == 2) ? e->lds_bytes : e->lds_bytes_reset;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_env_kernel(mode, e->ep.P, e->ep.H, e->ep.variant != 0)),
@@ -1954,8 +2074,10 @@ int configure_env_kernels(hsad_env* e) {
 void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipStream_t stream, int g_begin,
                 int g_count, uint64_t policy_seed = 0, int64_t* a_out = nullptr, int64_t* g_out = nullptr, int part = -1,
                 unsigned long long tag = 0, unsigned long long first_tag = 0, int n_part = 1, int n_iter = 1) {
-  const size_t lds = (mode == 1 || mode == 2) ? e->lds_bytes : e->lds_bytes_reset;
+  size_t lds = (mode == 1 || mode == 2) ? e->lds_bytes : e->lds_bytes_reset;
   EnvParams ep = e->ep;
+  ep.delta = mode == 3 && n_iter > 1 && rollout_delta_active(e) ? 1 : 0;
+  if (ep.delta) lds = e->lds_bytes_delta;
   ep.phase = part >= 0 ? e->d_phase : nullptr;
   ep.part = part < 0 ? 0 : part;
   ep.lock_ticks = (int)(e->stagger_ns / 10);
@@ -2100,6 +2222,7 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   // + 4: the pacing word of the pipelined rollout behind the eps copy (kept a multiple of 16 bytes)
   e->lds_bytes = sizeof(uint32_t) * ((size_t)ep.npl * kWave + ep.obs_words + ep.legal_words + ep.own_words + kWave + 128 + 4);
   e->lds_bytes_reset = e->lds_bytes + sizeof(uint32_t) * (size_t)ep.win_words * kWave;
+  e->lds_bytes_delta = e->lds_bytes_reset + sizeof(uint32_t) * (size_t)ep.obs_words;
   e->device = cfg->device;
   e->bound = false;
   e->n_part = 0;
@@ -2112,6 +2235,8 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->rollout_chunk = 0;
   e->rollout_pipe = getenv("HSAD_ENV_PIPE") ? atoi(getenv("HSAD_ENV_PIPE")) != 0 : 1;
   e->rollout_pace = getenv("HSAD_ENV_PACE") ? atoi(getenv("HSAD_ENV_PACE")) != 0 : 1;
+  e->rollout_delta = getenv("HSAD_ENV_DELTA") ? atoi(getenv("HSAD_ENV_DELTA")) != 0 : 1;
+  e->delta_fits = false;
   e->d_pace = nullptr;
   e->pace_base = 0;
   e->pace_bias = 0;
@@ -2396,6 +2521,14 @@ int hsad_env_set_rollout_pace(hsad_env* e, int on) {
 
 int hsad_env_rollout_pace_cap_us(const hsad_env* e) { return e ? e->pace_cap_ticks / 100 : 0; }
 
+int hsad_env_set_rollout_delta(hsad_env* e, int on) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  e->rollout_delta = on != 0;
+  return HSAD_OK;
+}
+
+int hsad_env_rollout_delta_active(const hsad_env* e) { return e && rollout_delta_active(e) ? 1 : 0; }
+
 int hsad_env_debug_pace_bias(hsad_env* e, int64_t bias) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");
   e->pace_bias = (long long)bias;
@@ -2463,7 +2596,9 @@ int hsad_env_debug_trace(hsad_env* e, uint64_t* buf, int n_iters) {
   return HSAD_OK;
 }
 
-int64_t hsad_env_rollout_lds_bytes(const hsad_env* e) { return e ? (int64_t)e->lds_bytes_reset : 0; }
+int64_t hsad_env_rollout_lds_bytes(const hsad_env* e) {
+  return e ? (int64_t)(rollout_delta_active(e) ? e->lds_bytes_delta : e->lds_bytes_reset) : 0;
+}
 
 int hsad_env_error_count(hsad_env* e, int32_t* count, int32_t* first_game, int32_t* first_code) {
   if (!e || !count) return set_error(HSAD_ERR_INVALID, "null argument");

@@ -159,6 +159,15 @@ class BatchedHanabiEnv:
     def rollout_pace_cap_us(self):
         return int(self.lib.hsad_env_rollout_pace_cap_us(self.h))
 
+    def set_rollout_delta(self, on):
+        """persistent rollout: the streams of a launch after its first store only the observation lines that changed (default on;
+        results are identical, see include/hsad.h)"""
+        _lib.check(self.lib.hsad_env_set_rollout_delta(self.h, int(bool(on))))
+
+    def rollout_delta_active(self):
+        """whether persistent launches use the delta stream as the env stands"""
+        return bool(self.lib.hsad_env_rollout_delta_active(self.h))
+
     def debug_pace_bias(self, bias):
         """test seam: offset of the counter base the paced kernels are told"""
         _lib.check(self.lib.hsad_env_debug_pace_bias(self.h, int(bias)))

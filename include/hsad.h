@@ -167,6 +167,15 @@ int hsad_env_set_rollout_chunk(hsad_env* env, int iterations_per_launch);
 int hsad_env_set_rollout_pace(hsad_env* env, int on);
 /* longest delay of one iteration, microseconds */
 int hsad_env_rollout_pace_cap_us(const hsad_env* env);
+/* Delta stream of the pipelined persistent launches (on by default; HSAD_ENV_DELTA=0 when the env is created, or on = 0 here, gives
+ * the full stream, for A/B).  One move changes little of an observation, so within one launch every observation stream after the
+ * first stores only the 128-byte lines of priv_s whose bits differ from what the stream before wrote; the workgroup keeps those bits
+ * in a second copy of its LDS rows.  The first stream of every launch stores everything and nothing is carried between launches, so
+ * whatever happens to priv_s or the games between launches cannot matter.  Results are bit-identical.  The packed outputs, legal
+ * moves and own hand are streamed in full.  hsad_env_rollout_delta_active: whether persistent launches use it now -- not without the
+ * pipelined schedule or the float32 observation, and not where the second copy would cost a resident workgroup per CU. */
+int hsad_env_set_rollout_delta(hsad_env* env, int on);
+int hsad_env_rollout_delta_active(const hsad_env* env);
 /* Test seams of the pacing.  bias is added to the counter base every later persistent launch is told (not to the host's own
  * record), so that every workgroup's lead reads bias / workgroups iterations too high: all far ahead (bias > 0) or far behind (bias < 0); 0
  * restores the truth.  A lead no launch could produce (beyond its iteration count) switches the delay off.
@@ -212,7 +221,8 @@ int hsad_env_debug_timing(hsad_env* env, uint64_t* buf);
  * wall_clock64 stamps (100 MHz) of every iteration plus each workgroup's HW_ID / XCC_ID; slot map in csrc/hsad_env.hip (env_stamp).
  * buf == NULL switches the trace (and hsad_env_debug_timing) off. */
 int hsad_env_debug_trace(hsad_env* env, uint64_t* buf, int n_iters);
-/* Dynamic LDS bytes per workgroup of the reset / rollout kernels (what a persistent rollout launch requests). */
+/* Dynamic LDS bytes per workgroup of the reset / rollout kernels (what a persistent rollout launch requests: with the second copy
+ * of the observation rows while hsad_env_rollout_delta_active). */
 int64_t hsad_env_rollout_lds_bytes(const hsad_env* env);
 
 /* Number of games that hit an API-contract error (illegal move, step on a finished game) since

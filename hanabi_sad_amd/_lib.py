@@ -130,6 +130,9 @@ SIGNATURES = {
     "hsad_env_determinize": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "hsad_env_playout_random": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
     "hsad_env_playout_random_keyed": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P, _P]),
+    "hsad_env_rewind_scripted": (C.c_int, [_P, _P, _P, _P]),
+    "hsad_env_sad_section": (C.c_int, [_P, _P, _P]),
+    "hsad_env_observe_sad": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "hsad_aggregate_priority": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
     "hsad_replay_create": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(Field), C.c_int, C.POINTER(_P)]),
@@ -283,6 +286,8 @@ SIGNATURES = {
     "hsad_search_fork_state": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "hsad_search_actions": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "hsad_search_job_stats": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "hsad_search_world_script": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "hsad_search_replay_actions": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "hsad_ipc_handle_bytes": (C.c_int, []),
     "hsad_ipc_alloc": (C.c_int, [C.c_int64, C.POINTER(_P), _P, C.c_int]),
     "hsad_ipc_free": (C.c_int, [_P]),

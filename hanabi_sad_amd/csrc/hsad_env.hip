@@ -60,6 +60,7 @@ enum : int {
 // EPS(p) float bits;  PERM(p) colour perm 5x3b [0..14] | inverse perm [15..29]
 
 struct EnvParams {
+  static constexpr bool kScripted = false;
   int G, Gpad, P, H, A, F, F0, LAL, OB, OD, OL, OK, DECKW;
   int max_len, sad, shuffle_color, bomb, kmode, n_eps, track_dh, npl;
   int nthreads;    // workgroup size: 128 (wave 0 logic, wave 1 LDS clearing, both build + stream) or 256 (two more waves for clearing,
@@ -119,6 +120,19 @@ struct EnvParams {
   // (V = false) compile them in as constants.  variant = 0 for 5 colours, 5 ranks, 8 information and 3 life tokens.
   int nC, nR, max_info, max_life, deck_max, variant;
   unsigned long long deck_full;    // the full deck's 2-bit card counts, type colour*5+rank (unused types 0)
+};
+
+// deal script of an env (hsad_env_rewind_scripted): cards [Gpad, 52] card types in deal order, count [Gpad] scripted deals per game
+struct DealScript {
+  uint8_t* cards;
+  int32_t* count;
+};
+// What env_step_scripted_kernel takes instead of EnvParams.  The step path (env_body, env_logic, deal_one) is a template over its
+// parameter struct and reads the script only where kScripted says so: EnvParams, and with it every kernel of an env that never
+// received a script, is what it was before scripts existed.
+struct ScriptedParams : EnvParams {
+  static constexpr bool kScripted = true;
+  DealScript sc;
 };
 
 constexpr uint32_t kIdentityPerm = (0u) | (1u << 3) | (2u << 6) | (3u << 9) | (4u << 12);
@@ -568,14 +582,31 @@ __device__ __forceinline__ uint32_t advance_player(int P, int H, const uint32_t*
   return board;
 }
 
+// the next card type to deal.  ScriptedParams (the scripted step only): while the deal index is below the game's script length the
+// card is the script's and no generator draw is consumed; a scripted card the deck does not hold (a game forked over a script that
+// was validated for another) is logged as code 5 and dealt from the generator instead
+__device__ __forceinline__ void log_error(const EnvParams& ep, int g, int code);   // defined with the error log below
+template <class EP, class Ru>
+__device__ __forceinline__ int next_card(const EP& ep, uint64_t deck, int deck_size, Rng& rng, int g, const Ru& ru) {
+  if constexpr (EP::kScripted) {
+    const int di = ru.deck - deck_size;
+    if (di < ep.sc.count[g]) {
+      const int t = (int)ep.sc.cards[(size_t)g * 52 + di];
+      if (t < 25 && cnt2(deck, t) != 0u) return t;
+      log_error(ep, g, 5);
+    }
+  }
+  return deal_pick(ep.deal_mode, deck, deck_size, rng);
+}
+
 // deal one card to the first short hand (kDeal branch of HanabiState::ApplyMove + ApplyRandomChance)
-template <class Ru>
-__device__ __forceinline__ void deal_one(const EnvParams& ep, int P, int H, uint32_t* s_st, int lane, Rng& rng,
+template <class EP, class Ru>
+__device__ __forceinline__ void deal_one(const EP& ep, int P, int H, uint32_t* s_st, int lane, Rng& rng,
                                          int g, const Ru& ru) {
   uint64_t deck = (uint64_t)ST(PL_DECK_LO) | ((uint64_t)ST(PL_DECK_HI) << 32);
   uint32_t misc = ST(PL_MISC);
   int deck_size = (misc >> 8) & 63;
-  const int t = deal_pick(ep.deal_mode, deck, deck_size, rng);
+  const int t = next_card(ep, deck, deck_size, rng, g, ru);
   deck -= (uint64_t)1 << (2 * t);
   ST(PL_DECK_LO) = (uint32_t)deck;
   ST(PL_DECK_HI) = (uint32_t)(deck >> 32);
@@ -1070,8 +1101,8 @@ __device__ __forceinline__ void clear_rows(const EnvParams& ep, uint32_t* s_obs,
 
 // The game logic of one iteration for the 64 games of the logic wave (wave 0): reset-if-terminated (MODE 0 / 3), then the
 // policy (MODE 2 / 3) or the given actions (MODE 1) and the env step, all on the state planes staged in s_st.
-template <int MODE, int TP, int TH, bool V = false>
-__device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
+template <int MODE, int TP, int TH, bool V = false, class EP = EnvParams>
+__device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
                                           uint32_t* s_st, uint32_t* s_win, const float* s_eps, const int lane, const int g,
                                           const bool active, const bool do_reset, Rng& rng, uint32_t& greedy_rec, float& reward,
                                           bool& term, const int dbg_it = 0) {
@@ -1354,8 +1385,8 @@ __device__ __forceinline__ void env_logic(const EnvParams& ep, const int64_t* __
   }
 }
 
-template <int MODE, int TP, int TH, bool V = false>
-__device__ __forceinline__ void env_body(const EnvParams& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
+template <int MODE, int TP, int TH, bool V = false, class EP = EnvParams>
+__device__ __forceinline__ void env_body(const EP& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
                                          const int g_bias = 0, const int dbg_it = 0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* s_st = smem;
@@ -1510,6 +1541,14 @@ template <int MODE, int TP, int TH, bool V = false>
 __global__ __launch_bounds__(kEnvThreads) void env_kernel(EnvParams ep, const int64_t* __restrict__ a_in,
                                                           const int64_t* __restrict__ g_in) {
   env_body<MODE, TP, TH, V>(ep, a_in, g_in);
+}
+
+// the step (MODE 1) of an env that holds a deal script: next_card reads it.  A kernel of its own, so that env_kernel is compiled
+// from what it always was
+template <int TP, int TH, bool V = false>
+__global__ __launch_bounds__(kEnvThreads) void env_step_scripted_kernel(ScriptedParams ep, const int64_t* __restrict__ a_in,
+                                                                        const int64_t* __restrict__ g_in) {
+  env_body<1, TP, TH, V>(ep, a_in, g_in);
 }
 
 // Persistent rollout: games are independent, so a workgroup simply runs n_iter iterations (reset finished games + policy +
@@ -1977,6 +2016,10 @@ struct hsad_env {
   int last_rollout_iters, last_rollout_parts;
   hipEvent_t fork;
   int32_t* d_sel;     // [Gpad] which games hsad_env_determinize resampled (hsad_env_search.inc); allocated on first use
+  // deal script (hsad_env_rewind_scripted).  scripted: hsad_env_step launches env_step_scripted_kernel; set by the first rewind,
+  // cleared by hsad_env_reset / hsad_env_reseed.  The buffers are allocated on first use
+  bool scripted;
+  DealScript script;
 };
 
 namespace {
@@ -2014,6 +2057,17 @@ EnvKernelFn pick_env_kernel(int mode, int P, int H, bool variant) {
     case 2: return env_kernel<2, 0, 0>;
     default: return env_kernel<3, 0, 0>;
   }
+}
+
+// the step of an env that holds a deal script: the same (players, hand) choices as the plain step
+typedef void (*EnvScriptedStepFn)(ScriptedParams, const int64_t*, const int64_t*);
+EnvScriptedStepFn pick_scripted_step_kernel(int P, int H, bool variant) {
+  if (variant) return env_step_scripted_kernel<0, 0, true>;
+  if (P == 2 && H == 5) return env_step_scripted_kernel<2, 5>;
+  if (P == 5 && H == 4) return env_step_scripted_kernel<5, 4>;
+  if (P == 3 && H == 5) return env_step_scripted_kernel<3, 5>;
+  if (P == 4 && H == 4) return env_step_scripted_kernel<4, 4>;
+  return env_step_scripted_kernel<0, 0>;
 }
 
 typedef void (*EnvRolloutFn)(EnvParams);
@@ -2110,6 +2164,13 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
   }
   if (mode == 3 && n_iter > 1)
     hipLaunchKernelGGL(pick_rollout_kernel(ep.P, ep.H, rollout_pipelined(e), ep.variant != 0), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds, stream, ep);
+  else if (mode == 1 && e->scripted) {
+    ScriptedParams sp;
+    static_cast<EnvParams&>(sp) = ep;
+    sp.sc = e->script;
+    hipLaunchKernelGGL(pick_scripted_step_kernel(ep.P, ep.H, ep.variant != 0), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads),
+                       lds, stream, sp, a, g);
+  }
   else
     hipLaunchKernelGGL(pick_env_kernel(mode, ep.P, ep.H, ep.variant != 0), dim3((g_count + ep.gpw - 1) / ep.gpw), dim3(ep.nthreads), lds,
                        stream, ep, a, g);
@@ -2244,6 +2305,8 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->pace_cap_ticks = getenv("HSAD_ENV_PACE_CAP_US") ? std::min(1000, std::max(0, atoi(getenv("HSAD_ENV_PACE_CAP_US")))) * 100 : kPaceCapTicks;
   e->fork = nullptr;
   e->d_sel = nullptr;
+  e->scripted = false;
+  e->script = DealScript{nullptr, nullptr};
   if (e->lds_bytes_reset > 160 * 1024) {
     const size_t need = e->lds_bytes_reset;
     delete e;
@@ -2295,6 +2358,8 @@ void hsad_env_destroy(hsad_env* e) {
   if (e->d_phase) (void)hipFree(e->d_phase);
   if (e->d_pace) (void)hipFree(e->d_pace);
   if (e->d_sel) (void)hipFree(e->d_sel);
+  if (e->script.cards) (void)hipFree(e->script.cards);
+  if (e->script.count) (void)hipFree(e->script.count);
   if (e->ep.planes) (void)hipFree(e->ep.planes);
   if (e->ep.mt) (void)hipFree(e->ep.mt);
   if (e->ep.deck_hist) (void)hipFree(e->ep.deck_hist);
@@ -2374,6 +2439,7 @@ int hsad_env_bind_packed(hsad_env* e, uint64_t* priv_bits, uint64_t* legal_bits,
 int hsad_env_reset(hsad_env* e, void* stream) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");
   if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
+  e->scripted = false;   // every game deals from its generator again
   launch_env(e, 0, nullptr, nullptr, (hipStream_t)stream, 0, e->ep.Gpad);
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
@@ -2382,6 +2448,7 @@ int hsad_env_reset(hsad_env* e, void* stream) {
 int hsad_env_reseed(hsad_env* e, int32_t seed0, int32_t period, void* stream) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");
   e->ep.seed0 = seed0;
+  e->scripted = false;
   hipLaunchKernelGGL(reseed_kernel, dim3((e->ep.Gpad + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->ep, (int)seed0, (int)period);
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
@@ -2445,6 +2512,7 @@ int hsad_env_rollout_random(hsad_env* e, int n_iter, uint64_t policy_seed, int64
   if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
   if (!a) return set_error(HSAD_ERR_INVALID, "action tensor is null");
   if (e->ep.sad && !greedy_a) return set_error(HSAD_ERR_INVALID, "sad=1 requires greedy_a");
+  if (e->scripted) return set_error(HSAD_ERR_STATE, "hsad_env_rollout_random: the env holds a deal script (only hsad_env_step deals from it; hsad_env_reset clears it)");
   const int K = e->n_part_active;
   const int blocks = e->ep.Gpad / e->ep.gpw;
   if (e->rollout_chunk > 0) {   // persistent: one launch = rollout_chunk iterations of every game (the last one may be shorter)

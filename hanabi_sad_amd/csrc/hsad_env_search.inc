@@ -17,11 +17,13 @@ struct ObserveArgs {
   int sel_limit;
   const unsigned long long* sad_bits;  // [*, sad_pw64] or NULL
   int sad_pw64;
-  const float* sad_f32;                // [*, F] (used when sad_bits is NULL)
+  const float* sad_f32;                // [*, F] (used when sad_bits is NULL); both NULL: an all-zero section, as after a reset
+  const unsigned long long* sad_words; // [*] the section itself, one word per row (hsad_env_sad_section); wins over the other two
 };
 
 __device__ __forceinline__ uint64_t sad_section_of(const EnvParams& ep, const ObserveArgs& oa, size_t row) {
   const uint64_t mask = (1ull << ep.LAL) - 1ull;   // LAL <= 61
+  if (oa.sad_words) return oa.sad_words[row] & mask;
   if (oa.sad_bits) {
     const unsigned long long* r = oa.sad_bits + row * (size_t)oa.sad_pw64;
     const int w = ep.F0 >> 6, sh = ep.F0 & 63;
@@ -29,6 +31,7 @@ __device__ __forceinline__ uint64_t sad_section_of(const EnvParams& ep, const Ob
     if (sh && w + 1 < oa.sad_pw64) v |= r[w + 1] << (64 - sh);
     return v & mask;
   }
+  if (!oa.sad_f32) return 0ull;
   const float* r = oa.sad_f32 + row * (size_t)ep.F + ep.F0;
   uint64_t v = 0;
   for (int i = 0; i < ep.LAL; ++i) v |= (uint64_t)(r[i] != 0.f ? 1u : 0u) << i;
@@ -105,6 +108,13 @@ __global__ __launch_bounds__(kEnvThreads) void env_observe_kernel(EnvParams ep, 
     ep.terminal[g] = (uint8_t)((misc >> 14) & 1u);
   }
   if (ep.kmode == 1) v0_fixup<V>(ep, s_st, s_obs, mine, g0, lane);
+}
+
+// ---- the SAD section of the env's current rows, one word per (game, seat) row: what a log keeps of an observation ---------------
+__global__ void env_sad_section_kernel(EnvParams ep, ObserveArgs oa, unsigned long long* __restrict__ out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= ep.G * ep.P) return;
+  out[r] = ep.sad ? sad_section_of(ep, oa, (size_t)r) : 0ull;
 }
 
 // ---- fork: dst game j becomes src game src_index[j] -----------------------------------------------------------------------------
@@ -220,6 +230,69 @@ __global__ void env_determinize_kernel(EnvParams ep, const int32_t* __restrict__
   sel[g] = changed ? g : -1;
 }
 
+// ---- rewind: back to a fresh deal whose cards are the script's ----------------------------------------------------------------------
+// One thread per game.  A game with count > 0 that is started and whose script is a legal deal order (count in [P * H, deck], every
+// card a type the full deck still holds after the cards before it) is put back to what a reset leaves, with the hands dealt from
+// script[0 .. P * H) in deal_one's order (seat 0's H cards first); its script row and count move into the env's own buffers, which
+// the scripted step reads.  What reset drew from the generator stays: eps, colour permutations, generator words, draw counter,
+// look-ahead, last score, policy counter.  A bad script is logged (code 5) and the game left alone; sel[g] = g for the rewound
+// games (the observe pass that follows rewrites their rows), -1 otherwise.
+__global__ void env_rewind_kernel(EnvParams ep, DealScript own, const uint8_t* __restrict__ script, const int32_t* __restrict__ count,
+                                  int32_t* __restrict__ sel) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ep.G) return;
+  sel[g] = -1;
+  const int n = count[g];
+  if (n <= 0) return;
+  const int P = ep.P, H = ep.H;
+  const uint32_t misc = GP(PL_MISC);
+  if (!((misc >> 15) & 1u)) return;   // never started: reset has drawn no eps and no permutation to keep
+  const uint8_t* sc = script + (size_t)g * 52;
+  bool ok = n >= P * H && n <= ep.deck_max;
+  uint64_t pool = ep.deck_full, deck = ep.deck_full;
+  for (int i = 0; ok && i < n; ++i) {
+    const int t = sc[i];
+    if (t >= 25 || cnt2(pool, t) == 0u) {
+      ok = false;
+      break;
+    }
+    pool -= (uint64_t)1 << (2 * t);
+    if (i + 1 == P * H) deck = pool;
+  }
+  if (!ok) {
+    log_error(ep, g, 5);
+    return;
+  }
+  for (int i = 0; i < 52; ++i) own.cards[(size_t)g * 52 + i] = i < n ? sc[i] : (uint8_t)0;
+  own.count[g] = n;
+  if (ep.track_dh)
+    for (int i = 0; i < P * H; ++i) ep.deck_hist[(size_t)g * 52 + i] = sc[i];
+  const uint32_t cmask = (1u << ep.nC) - 1u, rmask = (1u << ep.nR) - 1u;
+  uint32_t full_kc = 0u, full_kr = 0u;
+  for (int i = 0; i < H; ++i) {
+    full_kc |= cmask << (5 * i);
+    full_kr |= rmask << (5 * i);
+  }
+  for (int p = 0; p < P; ++p) {
+    uint32_t hw = 0;
+    for (int i = 0; i < H; ++i) hw |= (uint32_t)sc[p * H + i] << (5 * i);
+    GP(PLH(p)) = hw | ((uint32_t)H << 25);
+    GP(PLKCP(p)) = full_kc;
+    GP(PLKRP(p)) = full_kr;
+    GP(PLKH(p)) = 0u;
+  }
+  GP(PL_DECK_LO) = (uint32_t)deck;
+  GP(PL_DECK_HI) = (uint32_t)(deck >> 32);
+  GP(PL_DISC_LO) = 0u;
+  GP(PL_DISC_HI) = 0u;
+  // the board of a reset after its deal: full tokens, no fireworks, P turns to play, seat 0 on turn, seat 1 % P next
+  GP(PL_BOARD) = ((uint32_t)ep.max_info << 15) | ((uint32_t)ep.max_life << 19) | ((uint32_t)P << 21) | (1u << 24) | ((uint32_t)(1 % P) << 27);
+  // step 0, deck size, not terminated, started; last score [16..21] and the look-ahead count [22..23] kept
+  GP(PL_MISC) = (misc & ((63u << 16) | (3u << 22))) | ((uint32_t)(ep.deck_max - P * H) << 8) | (1u << 15);
+  GP(PL_LASTMV) = 0u;
+  sel[g] = g;
+}
+
 // ---- playout: random-legal policy -> step until the games end, no restart, no observation rows ------------------------------------
 // One wave per 64 games; the planes stay in LDS and the generator context in registers for the whole launch.  Per iteration and live
 // game: the policy of policy_kernel on the legal masks of the state itself (the masks build_rows would have stored), then the step
@@ -320,6 +393,7 @@ int launch_observe(hsad_env* e, const ObserveArgs& oa, hipStream_t stream) {
 bool sad_source(const hsad_env* src, ObserveArgs* oa) {
   oa->sad_bits = nullptr;
   oa->sad_f32 = nullptr;
+  oa->sad_words = nullptr;
   oa->sad_pw64 = 0;
   if (src->ep.priv_bits) {
     oa->sad_bits = src->ep.priv_bits;
@@ -378,6 +452,81 @@ int hsad_env_determinize(hsad_env* e, const int32_t* viewer, const int64_t* key,
   return launch_observe(e, oa, (hipStream_t)stream);
 }
 
+int hsad_env_rewind_scripted(hsad_env* e, const uint8_t* script, const int32_t* count, void* stream) {
+  if (!e || !script || !count) return set_error(HSAD_ERR_INVALID, "null argument");
+  if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
+  const int Gpad = e->ep.Gpad;
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->d_sel) HIP_TRY(hipMalloc((void**)&e->d_sel, sizeof(int32_t) * (size_t)Gpad));
+  if (!e->script.cards) HIP_TRY(hipMalloc((void**)&e->script.cards, (size_t)Gpad * 52));
+  if (!e->script.count) HIP_TRY(hipMalloc((void**)&e->script.count, sizeof(int32_t) * (size_t)Gpad));
+  if (!e->scripted) {   // the first script since creation / reset: no game has one yet
+    HIP_TRY(hipMemsetAsync(e->script.cards, 0, (size_t)Gpad * 52, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(e->script.count, 0, sizeof(int32_t) * (size_t)Gpad, (hipStream_t)stream));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pick_scripted_step_kernel(e->ep.P, e->ep.H, e->ep.variant != 0)),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
+    e->scripted = true;
+  }
+  hipLaunchKernelGGL(env_rewind_kernel, dim3((e->ep.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->ep, e->script, script, count, e->d_sel);
+  HIP_TRY(hipGetLastError());
+  ObserveArgs oa;
+  oa.sel = e->d_sel;
+  oa.sel_limit = e->ep.G;
+  oa.sad_bits = nullptr;   // no move has been made: the SAD section of a rewound game is all-zero
+  oa.sad_f32 = nullptr;
+  oa.sad_words = nullptr;
+  oa.sad_pw64 = 0;
+  return launch_observe(e, oa, (hipStream_t)stream);
+}
+
+int hsad_env_sad_section(hsad_env* e, int64_t* out, void* stream) {
+  if (!e || !out) return set_error(HSAD_ERR_INVALID, "null argument");
+  if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
+  ObserveArgs oa;
+  oa.sel = nullptr;
+  oa.sel_limit = 0;
+  if (!sad_source(e, &oa) && e->ep.sad)
+    return set_error(HSAD_ERR_INVALID, "hsad_env_sad_section: sad = 1 needs the env's own observation rows (float32 or bit words)");
+  const int n = e->ep.G * e->ep.P;
+  hipLaunchKernelGGL(env_sad_section_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->ep, oa,
+                     reinterpret_cast<unsigned long long*>(out));
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_env_observe_sad(hsad_env* e, const int32_t* src_index, int G_src, const int64_t* sad, void* stream) {
+  if (!e || !src_index || !sad) return set_error(HSAD_ERR_INVALID, "null argument");
+  if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
+  if (G_src < 1) return set_error(HSAD_ERR_INVALID, "hsad_env_observe_sad: G_src must be >= 1");
+  if (!e->ep.sad) return HSAD_OK;   // the rows have no such section
+  ObserveArgs oa;
+  oa.sel = src_index;
+  oa.sel_limit = G_src;
+  oa.sad_bits = nullptr;
+  oa.sad_f32 = nullptr;
+  oa.sad_words = reinterpret_cast<const unsigned long long*>(sad);
+  oa.sad_pw64 = 0;
+  return launch_observe(e, oa, (hipStream_t)stream);
+}
+
+// shared with csrc/hsad_search.hip (not part of the public header): the hand planes hsad_search_world_script reads
+int hsad_internal_env_hands(const hsad_env* e, const uint32_t** hand0, int* G, int* Gpad, int* P, int* H) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  *hand0 = e->ep.planes + (size_t)PL_FIXED * e->ep.Gpad;   // plane PLH(p) = hand0 + p * Gpad
+  *G = e->ep.G;
+  *Gpad = e->ep.Gpad;
+  *P = e->ep.P;
+  *H = e->ep.H;
+  return HSAD_OK;
+}
+
+// shared with csrc/hsad_search.hip: the legal-move masks [G, P] (bit uid) of the rows the env wrote last
+int hsad_internal_env_legal_bits(const hsad_env* e, const unsigned long long** legal_bits) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  *legal_bits = e->ep.legal_bits;
+  return HSAD_OK;
+}
+
 int hsad_env_playout_random_keyed(hsad_env* e, int max_iter, uint64_t policy_seed, const int64_t* key, int64_t* a, int64_t* greedy_a,
                                   void* stream) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");
@@ -385,6 +534,8 @@ int hsad_env_playout_random_keyed(hsad_env* e, int max_iter, uint64_t policy_see
   if (!a) return set_error(HSAD_ERR_INVALID, "action tensor is null");
   if (e->ep.sad && !greedy_a) return set_error(HSAD_ERR_INVALID, "sad=1 requires greedy_a");
   if (max_iter < 0) return set_error(HSAD_ERR_INVALID, "max_iter must be >= 0");
+  if (e->scripted)
+    return set_error(HSAD_ERR_STATE, "hsad_env_playout_random: the env holds a deal script (only hsad_env_step deals from it; hsad_env_reset clears it)");
   if (max_iter == 0) return HSAD_OK;
   EnvParams ep = e->ep;
   ep.policy_seed = policy_seed;

@@ -10,7 +10,12 @@
 //               candidate action forced on the searcher's seat (first move only: the caller passes no override afterwards).
 //               greedy_a keeps the agent's greedy action -- what SAD shows the partner when the searcher deviates
 //   job_stats   the finished slots' scores summed per job (sum, sum of squares, count) with integer atomics: exact and order-free
-// All three are launch-only, one pass and HBM-bound.  The state rows move as 16-byte vectors (H % 4 == 0; with H % 8 == 0 the bf16
+// and, for the replay stage that rebuilds every sampled world's LSTM states from the game's history (PolicySearch(replay=True)):
+//   world_script    the root's deal order with the viewer's current cards replaced by the world's sampled hand: what
+//                   hsad_env_rewind_scripted takes, so that the world can be played again from its first move
+//   replay_actions  the root's logged moves as the a / greedy_a rows of the replay step, and the count of partner moves at which the
+//                   blueprint in this world would have shown another greedy action than the one observed
+// All are launch-only, one pass and HBM-bound.  The state rows move as 16-byte vectors (H % 4 == 0; with H % 8 == 0 the bf16
 // row is written as 16-byte vectors too).
 #include <hip/hip_runtime.h>
 
@@ -22,6 +27,8 @@
 
 extern "C" int hsad_internal_set_error(int code, const char* msg);
 extern "C" int hsad_internal_env_status(const hsad_env* e, const uint32_t** misc, int* G, int* P, int* A, int* perfect_score);
+extern "C" int hsad_internal_env_hands(const hsad_env* e, const uint32_t** hand0, int* G, int* Gpad, int* P, int* H);
+extern "C" int hsad_internal_env_legal_bits(const hsad_env* e, const unsigned long long** legal_bits);
 
 namespace {
 
@@ -137,6 +144,93 @@ __global__ __launch_bounds__(kThreads) void job_stats_kernel(const uint32_t* __r
   atomicAdd(s + 2, 1ull);
 }
 
+// one thread per world slot.  The env's move uids (HanabiGame::GetMove order): discard slot i = i, play slot i = H + i, hints above.
+// hand0: the world env's hand planes, word of seat p and game j at hand0[p * Gpad + j] = cards 5 x 5 bits | length [25..27]
+__global__ __launch_bounds__(kThreads) void world_script_kernel(const uint32_t* __restrict__ hand0, int G_w, int Gpad_w, int P, int H,
+                                                                const int32_t* __restrict__ src_index, const int32_t* __restrict__ viewer,
+                                                                const uint8_t* __restrict__ root_dh, const int32_t* __restrict__ root_count,
+                                                                int G_root, const int64_t* __restrict__ log_a, int n_moves,
+                                                                uint8_t* __restrict__ script_out, int32_t* __restrict__ count_out) {
+  const int j = blockIdx.x * kThreads + threadIdx.x;
+  if (j >= G_w) return;
+  uint8_t* out = script_out + (size_t)j * 52;
+  const int s = src_index[j], v = viewer[j];
+  int n = 0;
+  int slot[5] = {0, 0, 0, 0, 0}, len = 0;
+  bool ok = s >= 0 && s < G_root && v >= 0 && v < P;
+  if (ok) {
+    n = root_count[s];
+    ok = n >= P * H && n <= 50;
+  }
+  if (ok) {
+    len = H;
+    for (int i = 0; i < H; ++i) slot[i] = v * H + i;
+    int d = P * H;   // the running deal index
+    for (int t = 0; t < n_moves; ++t) {
+      const int m = t % P;
+      const int64_t uid = log_a[((size_t)t * G_root + s) * P + m];
+      if (uid < 0 || uid >= 2 * H) continue;   // a hint or the noop: no card moves
+      const int idx = (int)(uid < H ? uid : uid - H);
+      if (m == v) {
+        if (idx >= len) {
+          ok = false;
+          break;
+        }
+        for (int i = idx; i + 1 < len; ++i) slot[i] = slot[i + 1];
+        len -= 1;
+      }
+      if (d < n) {
+        if (m == v) slot[len++] = d;   // len < H here: a slot was just freed
+        d += 1;
+      }
+    }
+    // the log must lead to the hand the world holds
+    const uint32_t hw = hand0[(size_t)v * Gpad_w + j];
+    ok = ok && (int)((hw >> 25) & 7u) == len;
+    if (ok) {
+      const uint8_t* dh = root_dh + (size_t)s * 52;
+      for (int i = 0; i < 52; ++i) out[i] = i < n ? dh[i] : (uint8_t)0;
+      for (int k = 0; k < len; ++k) out[slot[k]] = (uint8_t)((hw >> (5 * k)) & 31u);   // slot[k] < d <= n <= 50
+    }
+  }
+  if (!ok) {
+    for (int i = 0; i < 52; ++i) out[i] = 0;
+    n = 0;
+  }
+  count_out[j] = n;
+}
+
+// one thread per slot of the replaying env; misc: its status plane (num_step [0..7]: movers rotate from seat 0); legal: its legal-move
+// masks [G, P], bit uid.  The logged MOVE is legal in every world the sampler can give (a hint that was made touched cards, and the
+// knowledge the sampler obeys says so); the logged GREEDY action is hypothetical and need not be -- a hint that touches no card of the
+// hand this world gave the viewer.  The step would refuse it (sad = 1), so the mover then shows its move instead; the world is
+// counted as a mismatch anyway, since act never returns an illegal greedy action.
+__global__ __launch_bounds__(kThreads) void replay_actions_kernel(const uint32_t* __restrict__ misc,
+                                                                  const unsigned long long* __restrict__ legal, int G, int P, int noop,
+                                                                  const int32_t* __restrict__ src_index, const int32_t* __restrict__ viewer,
+                                                                  const int64_t* __restrict__ log_a_t, const int64_t* __restrict__ log_g_t,
+                                                                  int G_root, const int64_t* __restrict__ greedy_src, int64_t* __restrict__ a,
+                                                                  int64_t* __restrict__ ga, int32_t* __restrict__ mismatch) {
+  const int g = blockIdx.x * kThreads + threadIdx.x;
+  if (g >= G) return;
+  const int s = src_index[g];
+  const uint32_t m = misc[g];
+  if (s < 0 || s >= G_root || !game_live(m)) {
+    for (int p = 0; p < P; ++p) a[(size_t)g * P + p] = ga[(size_t)g * P + p] = (int64_t)noop;
+    return;
+  }
+  const int mover = (int)(m & 255u) % P;
+  const int64_t shown = log_g_t[(size_t)s * P + mover];
+  const bool differs = mover != viewer[g] && greedy_src[(size_t)g * P + mover] != shown;   // read before a / ga (may alias) are written
+  const bool possible = shown >= 0 && shown < 64 && ((legal[(size_t)g * P + mover] >> shown) & 1ull);
+  for (int p = 0; p < P; ++p) {
+    const int64_t act = log_a_t[(size_t)s * P + p];
+    a[(size_t)g * P + p] = act;
+    ga[(size_t)g * P + p] = (p == mover && !possible) ? act : log_g_t[(size_t)s * P + p];
+  }
+  if (differs) mismatch[g] += 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -187,6 +281,39 @@ int hsad_search_job_stats(const hsad_env* env, const int32_t* job, int n_job, in
   CK(hsad_internal_env_status(env, &misc, &G, &P, &A, &perfect));
   hipLaunchKernelGGL(job_stats_kernel, dim3((G + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, misc, G, job, n_job,
                      reinterpret_cast<unsigned long long*>(stats));
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_search_world_script(const hsad_env* world_env, const int32_t* src_index, const int32_t* viewer, const uint8_t* root_deck_hist,
+                             const int32_t* root_count, int G_root, const int64_t* log_a, int n_moves, uint8_t* script_out,
+                             int32_t* count_out, void* stream) {
+  if (!src_index || !viewer || !root_deck_hist || !root_count || !script_out || !count_out)
+    return efail(HSAD_ERR_INVALID, "hsad_search_world_script: null argument");
+  if (G_root < 1 || n_moves < 0) return efail(HSAD_ERR_INVALID, "hsad_search_world_script: G_root must be >= 1 and n_moves >= 0");
+  if (n_moves > 0 && !log_a) return efail(HSAD_ERR_INVALID, "hsad_search_world_script: n_moves > 0 needs the move log");
+  const uint32_t* hand0;
+  int G, Gpad, P, H;
+  CK(hsad_internal_env_hands(world_env, &hand0, &G, &Gpad, &P, &H));
+  hipLaunchKernelGGL(world_script_kernel, dim3((G + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, hand0, G, Gpad, P, H,
+                     src_index, viewer, root_deck_hist, root_count, G_root, log_a, n_moves, script_out, count_out);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_search_replay_actions(const hsad_env* env, const int32_t* src_index, const int32_t* viewer, const int64_t* log_a_t,
+                               const int64_t* log_greedy_t, int G_root, const int64_t* greedy_src, int64_t* a, int64_t* greedy_a,
+                               int32_t* mismatch, void* stream) {
+  if (!src_index || !viewer || !log_a_t || !log_greedy_t || !greedy_src || !a || !greedy_a || !mismatch)
+    return efail(HSAD_ERR_INVALID, "hsad_search_replay_actions: null argument");
+  if (G_root < 1) return efail(HSAD_ERR_INVALID, "hsad_search_replay_actions: G_root must be >= 1");
+  const uint32_t* misc;
+  int G, P, A, perfect;
+  CK(hsad_internal_env_status(env, &misc, &G, &P, &A, &perfect));
+  const unsigned long long* legal;
+  CK(hsad_internal_env_legal_bits(env, &legal));
+  hipLaunchKernelGGL(replay_actions_kernel, dim3((G + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, misc, legal, G, P, A - 1,
+                     src_index, viewer, log_a_t, log_greedy_t, G_root, greedy_src, a, greedy_a, mismatch);
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
 }

@@ -222,6 +222,36 @@ class BatchedHanabiEnv:
                                                           self.greedy_a.data_ptr(), self._stream()))
         return self.a, self.greedy_a
 
+    def rewind_scripted(self, script, count):
+        """games with count[g] > 0 (int32 [G]) start again from a fresh deal whose cards are script[g] (uint8 [G, 52], or [G, 50]
+        as deck_history() returns it): the hands from its first P * H entries, every later deal of step() from the script until
+        count[g] cards are dealt, then from the generator.  eps, colour permutation and generator are kept; reset() / reseed()
+        clear the script.  See hsad_env_rewind_scripted."""
+        s = torch.as_tensor(script, device=self.device).to(torch.uint8)
+        if s.dim() == 2 and s.shape[1] == 50:
+            s = torch.nn.functional.pad(s, (0, 2))
+        s = s.contiguous()
+        assert s.shape == (self.G, 52), "expected a [%d, 52] script, got %s" % (self.G, tuple(s.shape))
+        c = self._i32(count, self.G)
+        _lib.check(self.lib.hsad_env_rewind_scripted(self.h, s.data_ptr(), c.data_ptr(), self._stream()))
+
+    def sad_section(self, out=None):
+        """int64 [G, P]: the SAD greedy-action section of the current rows, one word per row (zeros with sad = 0); what a GameLog
+        keeps of an observation.  See hsad_env_sad_section."""
+        if out is None:
+            out = torch.zeros(self.G, self.P, dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == self.G * self.P
+        _lib.check(self.lib.hsad_env_sad_section(self.h, out.data_ptr(), self._stream()))
+        return out
+
+    def observe_sad(self, src_index, sad):
+        """rewrites the rows of every game g with src_index[g] >= 0 from its state, the SAD section of seat p = sad[src_index[g], p]
+        (int64 [G_src, P]): a replayed world is shown what was seen, not what its own cards would have shown.  No-op with sad = 0."""
+        idx = self._i32(src_index, self.G)
+        s = torch.as_tensor(sad, device=self.device).to(torch.int64).contiguous()
+        assert s.dim() == 2 and s.shape[1] == self.P
+        _lib.check(self.lib.hsad_env_observe_sad(self.h, idx.data_ptr(), int(s.shape[0]), s.data_ptr(), self._stream()))
+
     def query(self):
         out = torch.zeros(self.G, 16, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.hsad_env_query(self.h, out.data_ptr(), self._stream()))
@@ -251,5 +281,5 @@ class BatchedHanabiEnv:
         _lib.check(self.lib.hsad_env_error_count(self.h, C.byref(n), C.byref(g), C.byref(c)))
         if n.value:
             what = {1: "illegal move", 2: "illegal greedy move", 3: "step on a finished game",
-                    4: "fork source index out of range"}.get(c.value, "?")
+                    4: "fork source index out of range", 5: "deal script names a card the deck does not hold"}.get(c.value, "?")
             raise _lib.HsadError("%d game(s) violated the env contract; first: game %d, %s" % (n.value, g.value, what))

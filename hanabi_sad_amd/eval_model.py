@@ -38,6 +38,10 @@ def parse_args(argv=None):
     p.add_argument("--search_worlds", default=0, type=int, help="> 0 with a single --idx: also play with blueprint-policy search "
                    "(search.play_with_search), this many sampled worlds per legal action")
     p.add_argument("--search_threshold", default=0.05, type=float, help="deviate from the blueprint only for a larger value gain")
+    p.add_argument("--search_replay", default=0, type=int, help="1: rebuild every sampled world's LSTM states by replaying the game's "
+                   "history (play_with_search(replay_history=True))")
+    p.add_argument("--search_consistent", default=0, type=int, help="1 (with --search_replay 1): count only the worlds in which the "
+                   "blueprint shows the partners' observed greedy actions")
     p.add_argument("--search_seat", default=None, type=int, help="the one seat that searches (default: every seat)")
     return p.parse_args(argv)
 
@@ -78,7 +82,8 @@ def search_report(args):
     kw = dict(precision=args.precision, device=args.device, threshold=args.search_threshold,
               searcher="all" if args.search_seat is None else args.search_seat)
     base = play_with_search(agent, n, 1, 0, sad, worlds=0, **kw)
-    res = play_with_search(agent, n, 1, 0, sad, worlds=args.search_worlds, **kw)
+    res = play_with_search(agent, n, 1, 0, sad, worlds=args.search_worlds, replay_history=bool(args.search_replay),
+                           consistent_only=bool(args.search_consistent), **kw)
     print("blueprint: %f +/- %f" % (base.mean, base.sem), "; perfect: ", base.perfect)
     print("blueprint + search (%d worlds): %f +/- %f" % (args.search_worlds, res.mean, res.sem), "; perfect: ", res.perfect,
           "; deviations per game: %f" % float(res.deviations.double().mean()))

@@ -6,7 +6,10 @@ batched in one search env, `capacity` games at a time.
 
 Two rollout policies: mc_action_values plays the worlds out with random legal moves (one launch, hsad_env_playout_random);
 policy_action_values / PolicySearch play them out with the blueprint itself -- the R2D2 agent acting greedily for every seat --
-which is what can improve on that agent (choose_action, play_with_search).  The glue kernels of the second are csrc/hsad_search.hip."""
+which is what can improve on that agent (choose_action, play_with_search).  The glue kernels of the second are csrc/hsad_search.hip.
+
+PolicySearch(replay=True) first plays every sampled world again from its first move (GameLog, hsad_search_world_script,
+hsad_env_rewind_scripted, hsad_search_replay_actions), so that each seat's LSTM state is the one that world's observations give."""
 import numpy as np
 import torch
 
@@ -106,11 +109,14 @@ class SearchValues:
     totals int64 [G, A, 3] = (sum score, sum score^2, worlds counted) per (root game, action) as hsad_search_job_stats reduced them;
     values float32 [G, A] = sum / worlds in float32 from those integers, NaN where nothing was counted (illegal actions, games that
     are not live, turns of a player who does not search); sem float32 [G, A] = population std / sqrt(worlds) from the integers;
-    blueprint_a int64 [G] = the agent's own greedy action at the root, -1 for games that were not searched."""
+    blueprint_a int64 [G] = the agent's own greedy action at the root, -1 for games that were not searched;
+    mismatch int32 [G, worlds] (replay only, else None) = per sampled world the number of past partner moves at which the blueprint,
+    replayed in that world, showed another greedy action than the logged one (0 for games that were not searched)."""
 
-    def __init__(self, totals, blueprint_a):
+    def __init__(self, totals, blueprint_a, mismatch=None):
         self.totals = totals = torch.as_tensor(totals).to(torch.int64)
         self.blueprint_a = torch.as_tensor(blueprint_a).to(torch.int64)
+        self.mismatch = mismatch
         s, sq, n = totals[..., 0], totals[..., 1], totals[..., 2]
         nan = torch.full(s.shape, float("nan"), dtype=torch.float32, device=totals.device)
         counted = n > 0
@@ -133,18 +139,67 @@ def _searched_games(searcher, cur, G):
     return m != 0
 
 
+class GameLog:
+    """The root's moves as stepped: a / greedy_a int64 [n_moves, G, P] on the device (views of a buffer that grows by doubling),
+    and sad int64 [n_moves, G, P]: the SAD greedy-action section every seat was shown after the move (zeros with sad = 0).
+    Once per root step: append() with the rows hsad_env_step is given, then observed(env) after the step."""
+
+    def __init__(self, G, P, device, room=128):
+        self.G, self.P, self.device, self.n_moves = int(G), int(P), torch.device(device), 0
+        self._a = torch.zeros(room, self.G, self.P, dtype=torch.int64, device=self.device)
+        self._g = torch.zeros_like(self._a)
+        self._s = torch.zeros_like(self._a)
+
+    def append(self, a, greedy_a=None):
+        if self.n_moves == self._a.shape[0]:
+            self._a = torch.cat([self._a, torch.zeros_like(self._a)])
+            self._g = torch.cat([self._g, torch.zeros_like(self._g)])
+            self._s = torch.cat([self._s, torch.zeros_like(self._s)])
+        self._a[self.n_moves].copy_(a.view(self.G, self.P))
+        self._g[self.n_moves].copy_((a if greedy_a is None else greedy_a).view(self.G, self.P))
+        self.n_moves += 1
+
+    def observed(self, env):
+        """after the step of the move just appended: keeps what the root's rows now show of the greedy action"""
+        if env.sad:
+            env.sad_section(self._s[self.n_moves - 1])
+
+    @property
+    def sad(self):
+        return self._s[:self.n_moves]
+
+    @property
+    def a(self):
+        return self._a[:self.n_moves]
+
+    @property
+    def greedy_a(self):
+        return self._g[:self.n_moves]
+
+
+class _WorldChunk:
+    """`capacity` world slots of the replay stage: their env and the agent's state after the replay"""
+
+    def __init__(self, env):
+        self.env, self.h, self.c = env, None, None
+
+
 class PolicySearch:
     """The search env of `capacity` slots, the agent's state buffers for its capacity * P rows and the host loop that plays one
-    chunk of jobs; search() may be called move after move (play_with_search does).  `like` is any env with the root's rules."""
+    chunk of jobs; search() may be called move after move (play_with_search does).  `like` is any env with the root's rules.
+    replay=True: search() takes the root's GameLog and rebuilds the LSTM states of every sampled world by replay (world envs of
+    `capacity` slots each, made when first needed and kept); consistent_only=True then counts only the worlds without a mismatch."""
 
-    def __init__(self, like, agent, capacity=4096, max_steps=200):
+    def __init__(self, like, agent, capacity=4096, max_steps=200, replay=False, consistent_only=False):
         self.agent, self.capacity, self.max_steps = agent, int(capacity), int(max_steps)
+        self.replay, self.consistent_only = bool(replay), bool(consistent_only)
+        if self.consistent_only and not self.replay:
+            raise ValueError("consistent_only needs replay=True: the mismatch count comes from the replay")
         self.device = dev = like.device
         self.bf16 = bool(getattr(agent, "accepts_bf16_obs", False))
-        self.env = env = BatchedHanabiEnv(self.capacity, seed=0, eps_list=(0.0,), device=str(dev), track_deck_history=False, **like.config)
+        self.env = env = self._make_env(like.config)
+        self.config, self.worlds_env = dict(like.config), []
         self.lib = env.lib
-        if self.bf16:     # a bf16 kernel agent reads the env's packed rows: the first GEMM's operand, written by the env itself
-            env.enable_packed(bf16_row_len=agent.online.Fp, keep_float32=False)
         env.reset()       # spare slots of a short chunk hold started games: they play on with the rest and are never counted
         N = self.capacity * env.P
         z = agent.get_h0(N)
@@ -158,11 +213,20 @@ class PolicySearch:
         self.iterations = 0        # env steps of the last search, over all its chunks
         self.open_games = []       # the "games still running" words the host read during the last search (one per step, one step late)
 
+    def _make_env(self, config):
+        env = BatchedHanabiEnv(self.capacity, seed=0, eps_list=(0.0,), device=str(self.device), track_deck_history=False, **config)
+        if self.bf16:     # a bf16 kernel agent reads the env's packed rows: the first GEMM's operand, written by the env itself
+            env.enable_packed(bf16_row_len=self.agent.online.Fp, keep_float32=False)
+        return env
+
     def close(self):
         self.env.close()
+        for w in self.worlds_env:
+            w.env.close()
+        self.worlds_env = []
 
-    def _obs(self):
-        env = self.env
+    def _obs(self, env=None):
+        env = self.env if env is None else env
         N = env.G * env.P
         if self.bf16:
             return {"priv_s_bf16": env.priv_s_bf16.view(N, -1), "legal_move": env.legal_move.view(N, env.A), "eps": self.eps}
@@ -201,9 +265,70 @@ class PolicySearch:
             raise RuntimeError("%d game(s) of the search env still running after %d steps" % (int(self.unfinished.cpu()[0]), self.max_steps))
         return bp
 
-    def search(self, root, hid, worlds, seed, searcher=None):
+    def _replay(self, root, log, games, cur, worlds, seed, seed_of):
+        """the replay stage: world slot i * worlds + w = world w of root game games[i], `capacity` slots per world env.  Per env: fork
+        the root with the world seeds, determinize, hsad_search_world_script, hsad_env_rewind_scripted, zero agent state, then per
+        logged move agent.act -> hsad_search_replay_actions -> step -> (sad = 1) hsad_env_observe_sad with the section the root's
+        rows showed after that move.  -> mismatch int32 [len(games) * worlds] on the device"""
+        from .eval import _drain_errors
+        if log is None or (log.G, log.P) != (root.G, root.P):
+            raise ValueError("replay=True needs log=, the GameLog of the root's %d x %d action rows" % (root.G, root.P))
+        cap, dev, lib, agent, G, P = self.capacity, self.device, self.lib, self.agent, root.G, root.P
+        nw = len(games) * worlds
+        n_chunk = (nw + cap - 1) // cap
+        while len(self.worlds_env) < n_chunk:
+            self.worlds_env.append(_WorldChunk(self._make_env(self.config)))
+        dh, cnt = root.deck_history()
+        if int(cnt.max()) == 0:
+            raise ValueError("replay=True needs a root env built with track_deck_history=True")
+        dh = torch.nn.functional.pad(dh, (0, 2)).contiguous()
+        n_moves = log.n_moves
+        la, lg = log.a, log.greedy_a
+        mismatch = torch.zeros(n_chunk * cap, dtype=torch.int32, device=dev)
+        script = torch.zeros(cap, 52, dtype=torch.uint8, device=dev)
+        count = torch.zeros(cap, dtype=torch.int32, device=dev)
+        for ci in range(n_chunk):
+            w = self.worlds_env[ci]
+            env = w.env
+            k = np.arange(ci * cap, (ci + 1) * cap)
+            valid = k < nw
+            kk = np.minimum(k, nw - 1)
+            g_c, w_c = games[kk // worlds], kk % worlds
+            src = torch.from_numpy(np.where(valid, g_c, -1).astype(np.int32)).to(dev)
+            seeds = torch.from_numpy(seed_of[g_c, w_c]).to(dev)
+            key = torch.from_numpy((g_c << 32) | w_c).to(dev)
+            viewer = torch.from_numpy(np.where(valid, cur[g_c], -1).astype(np.int32)).to(dev)
+            env.reseed(0)       # every slot "not started": the spare ones get the noop and never hold a world of an earlier search
+            env.fork_from(root, src, seeds)
+            env.determinize(viewer, key, seed)
+            _lib.check(lib.hsad_search_world_script(env.h, src.data_ptr(), viewer.data_ptr(), dh.data_ptr(), cnt.data_ptr(), G,
+                                                    la.data_ptr() if n_moves else None, n_moves, script.data_ptr(), count.data_ptr(),
+                                                    env._stream()))
+            env.rewind_scripted(script, count)
+            src = torch.where(count > 0, src, torch.full_like(src, -1))     # a slot whose script was refused replays nothing
+            z = agent.get_h0(cap * P)
+            hid = {"h0": torch.zeros_like(z["h0"]).contiguous(), "c0": torch.zeros_like(z["c0"]).contiguous()}
+            if self.h16 is not None:
+                hid["h0_16"] = torch.zeros_like(self.h16)
+            mm = mismatch[ci * cap:(ci + 1) * cap]
+            for t in range(n_moves):
+                reply, hid = agent.act(self._obs(env), hid)
+                g = reply["greedy_a"].contiguous()
+                _lib.check(lib.hsad_search_replay_actions(env.h, src.data_ptr(), viewer.data_ptr(), la[t].data_ptr(), lg[t].data_ptr(), G,
+                                                          g.data_ptr(), env.a.data_ptr(), env.greedy_a.data_ptr(), mm.data_ptr(),
+                                                          env._stream()))
+                env.step(env.a, env.greedy_a)
+                if env.sad:     # every seat saw the greedy action as the TRUE cards showed it, whatever hand this world holds
+                    env.observe_sad(src, log.sad[t])
+            w.h, w.c = hid["h0"].contiguous(), hid["c0"].contiguous()
+            n_err, g_err, code = _drain_errors(env)   # finished and spare slots were handed the noop: code 3 notes
+            if n_err and code != 3:
+                raise RuntimeError("replay: %d game(s) of the world env left their history; first: slot %d, code %d" % (n_err, g_err, code))
+        return mismatch[:nw]
+
+    def search(self, root, hid, worlds, seed, searcher=None, log=None):
         """-> SearchValues for the root env's games; root and hid ({"h0", "c0"}: [L, root.G * root.P, H], the agent's state entering
-        the root step) are only read.  See policy_action_values."""
+        the root step) are only read.  log: the root's GameLog (replay=True).  See policy_action_values."""
         from .eval import _drain_errors
         G, P, A, cap = root.G, root.P, root.A, self.capacity
         dev, env, lib = self.device, self.env, self.lib
@@ -220,7 +345,7 @@ class PolicySearch:
         if len(pairs):
             pairs = pairs[_searched_games(searcher, cur, G)[pairs[:, 0]]]
         if len(pairs) == 0 or worlds < 1:
-            return SearchValues(totals, blueprint)
+            return SearchValues(totals, blueprint, torch.zeros(G, max(worlds, 0), dtype=torch.int32, device=dev) if self.replay else None)
         n_job = len(pairs)
         n = n_job * worlds                                   # jobs in (game, action, world) order; job k works for pair k // worlds
         games, first_pair = np.unique(pairs[:, 0], return_index=True)
@@ -230,6 +355,16 @@ class PolicySearch:
         first_job = first_pair * worlds                      # world 0 of each game's first job: where the blueprint's own move is read
         stats = torch.zeros(n_job, 3, dtype=torch.int64, device=dev)
         L, H = self.h.shape[0], self.h.shape[2]
+        keep = mismatch = None
+        if self.replay:
+            mism = self._replay(root, log, games, cur, worlds, seed, seed_of).view(len(games), worlds)
+            mismatch = torch.zeros(G, worlds, dtype=torch.int32, device=dev)
+            mismatch[torch.from_numpy(games).to(dev)] = mism
+            if self.consistent_only:      # a game with no consistent world falls back to all of its worlds
+                keep = mism == 0
+                keep = torch.where(keep.any(dim=1, keepdim=True), keep, torch.ones_like(keep))
+            game_pos = np.zeros(G, dtype=np.int64)
+            game_pos[games] = np.arange(len(games))
         for c0 in range(0, n, cap):
             k = np.arange(c0, c0 + cap)
             valid = k < n
@@ -242,10 +377,25 @@ class PolicySearch:
             player = torch.from_numpy(np.where(valid, cur[g_c], -1).astype(np.int32)).to(dev)
             override = torch.from_numpy(np.where(valid, a_c, -1).astype(np.int64)).to(dev)
             job = torch.from_numpy(np.where(valid, pj, -1).astype(np.int32)).to(dev)
-            env.fork_from(root, src, seeds)
-            env.determinize(player, key, seed)
-            _lib.check(lib.hsad_search_fork_state(src.data_ptr(), cap, G, P, L, H, h_src.data_ptr(), c_src.data_ptr(), self.h.data_ptr(),
-                                                  self.c.data_ptr(), self.h16.data_ptr() if self.h16 is not None else None, env._stream()))
+            if not self.replay:
+                env.fork_from(root, src, seeds)
+                env.determinize(player, key, seed)
+                _lib.check(lib.hsad_search_fork_state(src.data_ptr(), cap, G, P, L, H, h_src.data_ptr(), c_src.data_ptr(), self.h.data_ptr(),
+                                                      self.c.data_ptr(), self.h16.data_ptr() if self.h16 is not None else None, env._stream()))
+            else:
+                # the worlds stand in the world envs, determinised and replayed: fork them and their rebuilt h / c, with the world
+                # seeds again (the generator a fork of the root would have)
+                ws = game_pos[g_c] * worlds + w_c
+                for wc in np.unique(ws[valid] // cap):
+                    w = self.worlds_env[int(wc)]
+                    src_w = torch.from_numpy(np.where(valid & (ws // cap == wc), ws % cap, -1).astype(np.int32)).to(dev)
+                    env.fork_from(w.env, src_w, seeds)
+                    _lib.check(lib.hsad_search_fork_state(src_w.data_ptr(), cap, cap, P, L, H, w.h.data_ptr(), w.c.data_ptr(), self.h.data_ptr(),
+                                                          self.c.data_ptr(), self.h16.data_ptr() if self.h16 is not None else None,
+                                                          env._stream()))
+                if keep is not None:
+                    kept = keep[torch.from_numpy(game_pos[g_c]).to(dev), torch.from_numpy(w_c).to(dev)]
+                    job = torch.where(kept, job, torch.full_like(job, -1))
             here = (first_job >= c0) & (first_job < c0 + cap)
             bp_rows = None
             if here.any():
@@ -257,10 +407,11 @@ class PolicySearch:
         _drain_errors(env)        # finished games were handed the noop: the "step on a finished game" notes
         pd = torch.from_numpy(pairs).to(dev)
         totals[pd[:, 0], pd[:, 1]] = stats
-        return SearchValues(totals, blueprint)
+        return SearchValues(totals, blueprint, mismatch)
 
 
-def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_steps=200, searcher=None):
+def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_steps=200, searcher=None, replay=False, log=None,
+                         consistent_only=False):
     """SearchValues: values[g, a] = mean final score (HSAD_Q_SCORE) over `worlds` sampled worlds when the player on turn of root game
     g plays a and EVERY player, the searcher included, then follows the blueprint `agent` greedily to the end of the game.
 
@@ -282,12 +433,20 @@ def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_step
     (net_step in csrc/hsad_agent.hip, CompositeAgent.act, R2D2Agent._fused), whose bf16 rounding differs.  capacity * P below 1,024
     and capacity * P from 1,024 up are two regimes.
 
-    Stated approximation: the partners' LSTM states are those of the TRUE world.  In a sampled world their observations differ in
-    the searcher's hand, so a full SPARTA would replay the history per world to rebuild them; here every seat of a fork starts from
-    the state its root game carries."""
-    ps = PolicySearch(root, agent, capacity, max_steps)
+    replay=False: every seat of a fork starts from the LSTM state its root game carries -- the partners' states are those of the TRUE
+    world, although in a sampled world their observations differed in the searcher's hand.  replay=True (needs log, the root's
+    GameLog, and a root that tracks its deck history) rebuilds them: before the act chunks, every world (root game, w) is forked,
+    determinised, rewound to its first deal with the sampled hand in the deal script (hsad_search_world_script,
+    hsad_env_rewind_scripted) and played again move by move from zero state with the logged actions forced
+    (hsad_search_replay_actions) and, with sad = 1, the greedy-action section of the rows forced to what the root's rows showed
+    (GameLog.sad, hsad_env_observe_sad: that section was computed from the true cards and seen by every seat, so a sampled world
+    must show it too -- which also keeps the searcher's own replayed state equal to the one it carries); the act chunks then fork the worlds and their h / c from the world envs.  A world's cards and
+    generator are the same either way.  SearchValues.mismatch counts, per world, the partner moves whose greedy action differs in
+    that world; consistent_only=True leaves worlds with a mismatch out of the totals (all worlds where none is consistent).  The
+    replay costs one act + step per logged move on all searched games x worlds slots."""
+    ps = PolicySearch(root, agent, capacity, max_steps, replay=replay, consistent_only=consistent_only)
     try:
-        return ps.search(root, hid, worlds, seed, searcher)
+        return ps.search(root, hid, worlds, seed, searcher, log=log)
     finally:
         ps.close()
 
@@ -326,23 +485,27 @@ class SearchPlay:
 
 def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05, search_seed=0, searcher="all", capacity=4096,
                      num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16", shuffle_color=False, colors=5, ranks=5,
-                     max_information_tokens=8, max_life_tokens=3):
+                     max_information_tokens=8, max_life_tokens=3, replay_history=False, consistent_only=False):
     """eval.evaluate's lock-step loop over the deals seed .. seed + num_game - 1 with search on top of the blueprint -> SearchPlay.
     Before each step: PolicySearch values for the games whose player on turn searches (searcher: "all" or a seat number),
     choose_action, then the root steps with a = the chosen action and greedy_a = the blueprint's greedy action; the carried state
     is advanced by the blueprint's act as usual.  The search seed of a move is move_seed(search_seed, move), so a run repeats
     exactly.  worlds = 0 takes no search path at all and returns evaluate's scores.  The search env has min(capacity, num_game x
-    (A - 1) x worlds) slots -- the most jobs a move can have -- and capacity x P decides the acting regime (policy_action_values)."""
+    (A - 1) x worlds) slots -- the most jobs a move can have -- and capacity x P decides the acting regime (policy_action_values).
+    replay_history=True: the root tracks its deck history, a GameLog keeps the rows it was stepped with and the search rebuilds
+    every world's LSTM states by replay (PolicySearch(replay=True)); consistent_only as there."""
     from .eval import _acting_agent, _drain_errors
     agent = _acting_agent(agent, precision, device)
     env = BatchedHanabiEnv(num_game, players=num_player, hand_size=hand_size, seed=seed, bomb=bomb, eps_list=[0.0], max_len=-1, sad=bool(sad),
-                           shuffle_color=bool(shuffle_color), device=device, track_deck_history=False, colors=colors, ranks=ranks,
+                           shuffle_color=bool(shuffle_color), device=device, track_deck_history=bool(replay_history), colors=colors, ranks=ranks,
                            max_information_tokens=max_information_tokens, max_life_tokens=max_life_tokens)
     seat = None if searcher == "all" else int(searcher)
     if seat is not None and not 0 <= seat < num_player:
         raise ValueError("searcher must be \"all\" or a seat in 0..%d" % (num_player - 1))
     # no move has more jobs than games x playable actions x worlds: a smaller batch needs no more slots than that
-    ps = PolicySearch(env, agent, min(int(capacity), num_game * (env.A - 1) * worlds), max_steps) if worlds > 0 else None
+    ps = PolicySearch(env, agent, min(int(capacity), num_game * (env.A - 1) * worlds), max_steps, replay=bool(replay_history),
+                      consistent_only=bool(consistent_only)) if worlds > 0 else None
+    log = GameLog(num_game, num_player, env.device) if ps is not None and replay_history else None
     N = num_game * num_player
     deviations = torch.zeros(num_game, dtype=torch.int64, device=env.device)
     trace = []
@@ -363,7 +526,7 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
                 a = torch.where(live, a.view(num_game, num_player), torch.full_like(a.view(num_game, num_player), noop)).contiguous()
                 env.step(a, a)
             else:
-                sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat)
+                sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat, log=log)
                 player = q[:, Q_CUR_PLAYER].contiguous()
                 # the blueprint's move is the root act's own greedy action (the search's first act gives the same one while both
                 # run in one acting regime; this one holds in any)
@@ -372,7 +535,11 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
                 chosen = choose_action(sv.values, blueprint, threshold).contiguous()
                 _lib.check(env.lib.hsad_search_actions(env.h, a.data_ptr(), g.data_ptr(), player.data_ptr(), chosen.data_ptr(),
                                                        env.a.data_ptr(), env.greedy_a.data_ptr(), env._stream()))
+                if log is not None:
+                    log.append(env.a, env.greedy_a)
                 env.step(env.a, env.greedy_a)
+                if log is not None:
+                    log.observed(env)
                 deviations += ((chosen >= 0) & (chosen != blueprint)).to(torch.int64)
                 trace.append((chosen.cpu(), blueprint.cpu()))
             hid = new_hid

@@ -227,7 +227,8 @@ int64_t hsad_env_rollout_lds_bytes(const hsad_env* env);
 
 /* Number of games that hit an API-contract error (illegal move, step on a finished game) since
  * the last call; synchronises the device.  first_game/first_code (may be NULL) describe the first.
- * Codes: 1 illegal move, 2 illegal greedy move, 3 step on a finished game, 4 hsad_env_fork source index out of range. */
+ * Codes: 1 illegal move, 2 illegal greedy move, 3 step on a finished game, 4 hsad_env_fork source index out of range, 5 a deal
+ * script names a card the deck does not hold (hsad_env_rewind_scripted). */
 int hsad_env_error_count(hsad_env* env, int32_t* count, int32_t* first_game, int32_t* first_code);
 
 /* ---- The env as a simulator for test-time search (determinised Monte Carlo, SPARTA-style single-agent search): branch a game,
@@ -273,6 +274,36 @@ int hsad_env_determinize(hsad_env* env, const int32_t* viewer, const int64_t* ke
 int hsad_env_playout_random(hsad_env* env, int max_iter, uint64_t policy_seed, int64_t* a, int64_t* greedy_a, void* stream);
 int hsad_env_playout_random_keyed(hsad_env* env, int max_iter, uint64_t policy_seed, const int64_t* key, int64_t* a, int64_t* greedy_a,
                                   void* stream);
+
+/* hsad_env_rewind_scripted: start games again from a deal somebody else chose.  script device uint8 [G, 52]: card types
+ * (colour * 5 + rank) in deal order, the layout of the deck history (hsad_env_deck_history rows padded to 52); count device int32
+ * [G]: how many deals of game g are scripted.  Every game with count[g] > 0 that is started goes back to what a fresh deal leaves --
+ * full deck counts less the hands, empty discards and fireworks, full tokens, step 0, not terminated, cleared knowledge and last
+ * move -- with the hands dealt from script[g, 0 .. P * H) in deal order (seat 0's H cards first).  What hsad_env_reset drew from the
+ * generator is kept: the eps choice, the colour permutations, the generator's words, draw counter and look-ahead; so are the policy
+ * counter and the last score.  Games with count[g] <= 0, and games that were never started, are left alone.  The rows of the rewound
+ * games are rewritten by the observe pass (SAD section all-zero, reward 0, terminal 0).  The script must be a legal deal order:
+ * P * H <= count[g] <= deck size, and every card a type the full deck still holds after the cards before it; otherwise the game is
+ * left alone and counted in the error log (code 5).  The env copies the script (the caller's buffers may be reused at once).
+ * From then on, while a game's deal index (deck size - cards left) is below count[g], hsad_env_step deals script[g, index] and
+ * consumes NO generator draw; past the script it deals from the generator as ever.  hsad_env_fork copies the deal index with the
+ * state; the script stays with the env it was given to (a game forked INTO a scripted env continues on that env's script; a scripted
+ * card its deck does not hold is logged as code 5 and dealt from the generator).  hsad_env_reset and hsad_env_reseed clear the
+ * script of every game.  An env that never received a script runs the very step, reset and rollout kernels it ran before this call
+ * existed: the scripted deal is a separate instantiation of the step kernel, selected only after this call.  While an env holds a
+ * script, hsad_env_rollout_random and hsad_env_playout_random are refused (HSAD_ERR_STATE).  Launch-only. */
+int hsad_env_rewind_scripted(hsad_env* env, const uint8_t* script, const int32_t* count, void* stream);
+
+/* The SAD greedy-action section of an observation as a value that can be logged and shown again.  It is no function of the state
+ * (hsad_env_fork) -- and in a replayed world it is no function of that world either: what every seat SAW of a greedy action was
+ * computed from the true cards (the card of a greedy play, the slots a greedy hint touches), whatever hand a sampled world holds.
+ * hsad_env_sad_section: out device int64 [G * P] = the section of the env's currently bound rows (float32 or bit words), bit i =
+ * column F - section length + i; all zero with sad = 0.
+ * hsad_env_observe_sad: the observe pass of hsad_env_fork for every game g with 0 <= src_index[g] < G_src (device int32 [G]): all
+ * bound rows of game g are rewritten from its state (reward = 0, terminal = the state's bit) with the section of seat p taken from
+ * sad[src_index[g] * P + p] (device int64 [G_src * P]).  Other games keep their rows.  A no-op with sad = 0.  Launch-only. */
+int hsad_env_sad_section(hsad_env* env, int64_t* out, void* stream);
+int hsad_env_observe_sad(hsad_env* env, const int32_t* src_index, int G_src, const int64_t* sad, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------
@@ -1112,6 +1143,41 @@ int hsad_search_actions(const hsad_env* env, const int64_t* a_src, const int64_t
  * (0 after the last life with bomb = 1).  It ACCUMULATES: the caller zeroes stats once per search and calls this once per chunk.
  * Integer atomics: exact, order-free.  The "games still running" word of the host loop is hsad_seating_stats(env, G, ...)'s. */
 int hsad_search_job_stats(const hsad_env* env, const int32_t* job, int n_job, int64_t* stats, void* stream);
+
+/* ---- replay stage of blueprint-policy search (PolicySearch(replay = True)): every sampled world is played again from its first
+ * move, so that each seat's LSTM state is the one that world's observations produce. ---- */
+/* The deal script of every world slot.  world_env: a determinised fork of the root (G_w slots); src_index device int32 [G_w]: the
+ * root game slot j was forked from; viewer device int32 [G_w]: the seat whose hand was resampled; root_deck_hist device uint8
+ * [G_root, 52] and root_count device int32 [G_root]: the root's deck history and the number of cards it has dealt; log_a device
+ * int64 [n_moves, G_root, P]: the action rows the root was stepped with, move after move.  Per slot j with s = src_index[j],
+ * v = viewer[j]:
+ *   slot list = deal indices v * H .. v * H + H - 1 (the initial deal gives seat p the indices p * H ..);  d = P * H;
+ *   for t = 0 .. n_moves - 1: mover m = t mod P (movers rotate from seat 0), uid = log_a[t, s, m]; uid in [0, H) discards and
+ *   uid in [H, 2H) plays hand slot i = uid mod H (the env's move-uid order); any other uid moves no card.  For a play or discard:
+ *   if m == v, entry i leaves the list and the later entries shift down;  then, if d < root_count[s], a card was dealt to the
+ *   mover: if m == v, d is appended to the list; d += 1.
+ *   script_out[j] = root_deck_hist[s] (entries [0, root_count[s]), zero beyond) with entry list[k] replaced by card k of the hand
+ *   world_env holds for seat v;  count_out[j] = root_count[s].
+ * s = -1 or outside [0, G_root), v outside [0, P), root_count[s] < P * H (never started) or a log that does not lead to the length
+ * of the hand world_env holds skip the slot: count_out[j] = 0 and an all-zero row, which hsad_env_rewind_scripted leaves alone
+ * (the convention of hsad_env_fork and hsad_search_fork_state).  script_out device uint8 [G_w, 52], count_out device int32 [G_w]. */
+int hsad_search_world_script(const hsad_env* world_env, const int32_t* src_index, const int32_t* viewer, const uint8_t* root_deck_hist,
+                             const int32_t* root_count, int G_root, const int64_t* log_a, int n_moves, uint8_t* script_out,
+                             int32_t* count_out, void* stream);
+/* One teacher-forced replay step.  log_a_t / log_greedy_t device int64 [G_root, P]: the rows of move t of the root's log;
+ * greedy_src device int64 [G * P]: the greedy actions act has just returned for env's rows.  For every slot g of env (G slots) with
+ * s = src_index[g] in [0, G_root) whose game is live: a[g] / greedy_a[g] (device int64 [G, P]) = row s of log_a_t / log_greedy_t, and
+ * mismatch[g] (device int32 [G]) += 1 when the mover -- seat (env's step count of game g) mod P -- is not viewer[g] and
+ * greedy_src[g * P + mover] != log_greedy_t[s, mover]: in this world the blueprint would have shown another greedy action than the
+ * one that was observed.  The logged greedy action is hypothetical and may be illegal in this world (a hint that touches no card of
+ * the hand the world gave the viewer; the logged move itself is legal in every world the sampler gives): greedy_a[g, mover] is then
+ * the logged move, so that the step accepts it, and the mismatch is counted all the same (act returns legal greedy actions only).
+ * Finished, never-started and skipped (s outside [0, G_root)) slots get the noop uid A - 1 in both outputs.
+ * mismatch ACCUMULATES: the caller zeroes it before move 0.  With sad = 1 the caller follows the step with hsad_env_observe_sad and
+ * the logged section of this move, so that the rows show the greedy action as it was seen. */
+int hsad_search_replay_actions(const hsad_env* env, const int32_t* src_index, const int32_t* viewer, const int64_t* log_a_t,
+                               const int64_t* log_greedy_t, int G_root, const int64_t* greedy_src, int64_t* a, int64_t* greedy_a,
+                               int32_t* mismatch, void* stream);
 
 /* ---- one-sided intra-node transport (dist.py ReplayLink(transport = "ipc")): landing buffers exported by IPC handle and written by the
  * SENDER with a device-to-device copy -- SDMA over xGMI, no kernel resident on either GPU while a peer has not answered (a posted RCCL

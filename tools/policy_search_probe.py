@@ -1,9 +1,11 @@
 """Records for DESIGN §3g, blueprint-policy search: seconds per search.policy_action_values call on one root batch of the full
 2-player game, jobs/s, env-steps/s of the search loop, the mean fraction of games still live per iteration (the case for or against
 compacting finished games out of the act batch), the three glue kernels' times, and the same call of mc_action_values (random
-playouts) as the yardstick.  Host clock around a device synchronise, median of the repeats.  One JSON line.
+playouts) as the yardstick.  --replay adds the replay stage (PolicySearch(replay=True)): its seconds alone at several move
+depths -- the cost grows with the move number -- and the whole search with it.  Host clock around a device synchronise, median of
+the repeats.  One JSON line.
 
-    python tools/policy_search_probe.py [--roots 64] [--worlds 8] [--capacity 4096] [--hid 512] [--repeats 5]
+    python tools/policy_search_probe.py [--roots 64] [--worlds 8] [--capacity 4096] [--hid 512] [--repeats 5] [--replay]
 """
 import argparse
 import json
@@ -12,11 +14,12 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hanabi_sad_amd import BatchedHanabiEnv, _lib  # noqa: E402
-from hanabi_sad_amd.search import PolicySearch, mc_action_values  # noqa: E402
+from hanabi_sad_amd.search import GameLog, PolicySearch, mc_action_values, search_jobs, world_seed  # noqa: E402
 
 
 def timed(fn, repeats):
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--moves", type=int, default=10, help="lock-step greedy moves before the root position")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sad", type=int, default=1)
+    ap.add_argument("--replay", action="store_true", help="also time the replay stage per move depth and the search with replay")
     args = ap.parse_args()
     from hanabi_sad_amd.composite import CNet, CompositeAgent
     from hanabi_sad_amd.eval import env_dims
@@ -47,13 +51,22 @@ def main():
     F, A = env_dims(P, 5, bool(args.sad))
     net = CNet(init_weights(F, args.hid, A, 5, 1), dev)          # a random net of the zoo's shape: timing does not ask for a trained one
     agent = CompositeAgent(net, net, 1, 0.99)
-    root = BatchedHanabiEnv(G, players=P, seed=1, bomb=0, eps_list=[0.0], max_len=-1, sad=bool(args.sad), device=dev, track_deck_history=False)
+    root = BatchedHanabiEnv(G, players=P, seed=1, bomb=0, eps_list=[0.0], max_len=-1, sad=bool(args.sad), device=dev, track_deck_history=bool(args.replay))
     root.reset()
     hid = agent.get_h0(G * P)
-    for _ in range(args.moves):
+    log = GameLog(G, P, dev)
+    depths = sorted({d for d in (args.moves // 4, args.moves // 2, args.moves) if d >= 1}) if args.replay else []
+    snaps = {}
+    for move in range(args.moves):
         obs = {"priv_s": root.priv_s.view(G * P, F), "legal_move": root.legal_move.view(G * P, A), "eps": root.eps.view(G * P)}
         reply, hid = agent.act(obs, hid)
+        log.append(reply["a"], reply["greedy_a"])
         root.step(reply["a"].view(G, P).contiguous(), reply["greedy_a"].view(G, P).contiguous())
+        if move + 1 in depths:
+            snaps[move + 1] = BatchedHanabiEnv(G, players=P, seed=1, bomb=0, eps_list=[0.0], max_len=-1, sad=bool(args.sad), device=dev,
+                                               track_deck_history=True)
+            snaps[move + 1].fork_from(root, torch.arange(G, dtype=torch.int32))
+        log.observed(root)
     hid = {"h0": hid["h0"], "c0": hid["c0"]}
     ps = PolicySearch(root, agent, args.capacity)
     res = {"roots": G, "worlds": args.worlds, "capacity": args.capacity, "hid": args.hid, "sad": args.sad, "repeats": args.repeats}
@@ -98,6 +111,28 @@ def main():
               "job_stats_ms"):
         res[k + "_median"] = statistics.median(res[k])
     ps.close()
+    if args.replay:
+        rp = PolicySearch(root, agent, args.capacity, replay=True)
+        rp.search(root, hid, args.worlds, 0, log=log)               # warm-up: builds the world envs
+        res["search_replay_ms"] = timed(lambda: rp.search(root, hid, args.worlds, 1, log=log), args.repeats)
+        res["search_replay_ms_median"] = statistics.median(res["search_replay_ms"])
+        # the replay stage alone at several move depths: forks of the root taken on the way, each with the log up to there
+        res["replay_ms_by_depth"], res["replay_ms_per_move"] = {}, {}
+        for depth, snap in sorted(snaps.items()):
+            part = GameLog(G, P, dev)
+            for t in range(depth):
+                part.append(log.a[t], log.greedy_a[t])
+                part._s[t].copy_(log.sad[t])
+            pairs, cur = search_jobs(snap)
+            games = np.unique(pairs[:, 0])
+            seed_of = np.zeros((G, args.worlds), dtype=np.int32)
+            for g in games:
+                seed_of[g] = [world_seed(1, int(g), w) for w in range(args.worlds)]
+            ms = timed(lambda: rp._replay(snap, part, games, cur, args.worlds, 1, seed_of), args.repeats)
+            res["replay_ms_by_depth"][str(depth)] = statistics.median(ms)
+            res["replay_ms_per_move"][str(depth)] = statistics.median(ms) / depth
+            snap.close()
+        rp.close()
     print(json.dumps(res))
 
 

@@ -128,6 +128,8 @@ SIGNATURES = {
     "hsad_env_error_count": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hsad_env_fork": (C.c_int, [_P, _P, _P, _P, _P]),
     "hsad_env_determinize": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
+    "hsad_env_hand_belief": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "hsad_env_determinize_exact": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_int, _P, _P, _P]),
     "hsad_env_playout_random": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
     "hsad_env_playout_random_keyed": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P, _P]),
     "hsad_env_rewind_scripted": (C.c_int, [_P, _P, _P, _P]),

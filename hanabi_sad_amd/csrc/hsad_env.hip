@@ -2684,3 +2684,6 @@ int hsad_env_error_count(hsad_env* e, int32_t* count, int32_t* first_game, int32
 
 // fork / determinise / observe / playout: the env as a simulator for test-time search
 #include "hsad_env_search.inc"
+
+// the exact belief over a hidden hand and the rejection-free sampler on top of it
+#include "hsad_env_belief.inc"

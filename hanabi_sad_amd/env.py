@@ -8,6 +8,29 @@ import torch
 from . import _lib
 
 
+class HandBelief:
+    """what BatchedHanabiEnv.hand_belief returns, on the env's device: total int64 [G] = N, the number of assignments of physical
+    unseen cards to the hand's slots that the card knowledge allows (0 for a skipped game); counts int64 [G, H, 25] = of those, the
+    ones with card type colour * 5 + rank in the slot; trinary int64 [G, H, 3] = counts summed into [playable, rank below the
+    firework, rank above it]."""
+
+    def __init__(self, total, counts, trinary):
+        self.total, self.counts, self.trinary = total, counts, trinary
+
+    def _over_total(self, x):
+        n = self.total.view(-1, 1, 1)
+        p = x.to(torch.float64) / torch.where(n > 0, n, torch.ones_like(n)).to(torch.float64)
+        return torch.where(n > 0, p, torch.zeros_like(p))
+
+    def probs(self):
+        """float64 [G, H, 25]: P(slot holds the type); zeros where total == 0"""
+        return self._over_total(self.counts)
+
+    def trinary_probs(self):
+        """float64 [G, H, 3]; zeros where total == 0"""
+        return self._over_total(self.trinary)
+
+
 class BatchedHanabiEnv:
     def __init__(self, num_games, players=2, hand_size=5, seed=1, bomb=0, eps_list=(0.0,), max_len=80, sad=False,
                  shuffle_obs=False, shuffle_color=False, knowledge_mode=0, device="cuda:0", track_deck_history=True,
@@ -208,6 +231,37 @@ class BatchedHanabiEnv:
         _lib.check(self.lib.hsad_env_determinize(self.h, v.data_ptr(), k.data_ptr(), int(seed) & (2 ** 64 - 1), tries.data_ptr(),
                                                  self._stream()))
         return tries
+
+    def hand_belief(self, viewer):
+        """the exact belief over the hidden hand of player viewer[g] (int32 [G]; -1 = skip): how many assignments of unseen
+        physical cards its card knowledge allows, and their per-slot marginals -> HandBelief.  Reads the state only.
+        See hsad_env_hand_belief."""
+        v = self._i32(viewer, self.G)
+        total = torch.zeros(self.G, dtype=torch.int64, device=self.device)
+        counts = torch.zeros(self.G, self.H, 25, dtype=torch.int64, device=self.device)
+        tri = torch.zeros(self.G, self.H, 3, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.hsad_env_hand_belief(self.h, v.data_ptr(), total.data_ptr(), counts.data_ptr(), tri.data_ptr(), self._stream()))
+        return HandBelief(total, counts, tri)
+
+    def determinize_exact(self, viewer, key, seed, stratum=None, n_strata=1, rank=None):
+        """determinize without rejection: the hand of player viewer[g] becomes hand number r of the N its card knowledge allows
+        (counted with the weight of the physical cards).  rank (int64 [G]) gives r itself; otherwise r is drawn from stratum
+        stratum[g] (int32 [G], None = 0) of n_strata equal parts of [0, N) with the hash of (seed, key[g]): the worlds
+        stratum = 0 .. n_strata - 1 of a game cover its belief evenly, n_strata = 1 is a plain exact draw.  Returns rank_out
+        (int64 [G]: the rank used, -1 for a game left alone -- skipped, rank or stratum out of range).  See hsad_env_determinize_exact."""
+        v = self._i32(viewer, self.G)
+        k = torch.as_tensor(key, device=self.device).to(torch.int64).contiguous()
+        assert k.shape == (self.G,)
+        st = self._i32(stratum, self.G) if stratum is not None else None
+        rk = None
+        if rank is not None:
+            rk = torch.as_tensor(rank, device=self.device).to(torch.int64).contiguous()
+            assert rk.shape == (self.G,)
+        out = torch.zeros(self.G, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.hsad_env_determinize_exact(self.h, v.data_ptr(), k.data_ptr(), int(seed) & (2 ** 64 - 1),
+                                                       st.data_ptr() if st is not None else None, int(n_strata),
+                                                       rk.data_ptr() if rk is not None else None, out.data_ptr(), self._stream()))
+        return out
 
     def playout_random(self, max_iter, policy_seed, key=None):
         """random-legal policy -> step until every live game has ended (at most max_iter iterations), finished games left alone.

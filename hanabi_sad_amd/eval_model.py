@@ -43,6 +43,9 @@ def parse_args(argv=None):
     p.add_argument("--search_consistent", default=0, type=int, help="1 (with --search_replay 1): count only the worlds in which the "
                    "blueprint shows the partners' observed greedy actions")
     p.add_argument("--search_seat", default=None, type=int, help="the one seat that searches (default: every seat)")
+    p.add_argument("--search_sampler", default="rejection", type=str, choices=["rejection", "stratified"],
+                   help="how the sampled worlds' hidden hands are drawn: hsad_env_determinize, or hsad_env_determinize_exact with the "
+                   "worlds of a game stratified over its exact belief")
     return p.parse_args(argv)
 
 
@@ -83,7 +86,7 @@ def search_report(args):
               searcher="all" if args.search_seat is None else args.search_seat)
     base = play_with_search(agent, n, 1, 0, sad, worlds=0, **kw)
     res = play_with_search(agent, n, 1, 0, sad, worlds=args.search_worlds, replay_history=bool(args.search_replay),
-                           consistent_only=bool(args.search_consistent), **kw)
+                           consistent_only=bool(args.search_consistent), sampler=args.search_sampler, **kw)
     print("blueprint: %f +/- %f" % (base.mean, base.sem), "; perfect: ", base.perfect)
     print("blueprint + search (%d worlds): %f +/- %f" % (args.search_worlds, res.mean, res.sem), "; perfect: ", res.perfect,
           "; deviations per game: %f" % float(res.deviations.double().mean()))

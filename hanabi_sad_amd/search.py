@@ -38,6 +38,24 @@ def world_key(g, w):
     return (int(g) << 32) | int(w)
 
 
+SAMPLERS = ("rejection", "stratified")
+
+
+def _check_sampler(sampler):
+    if sampler not in SAMPLERS:
+        raise ValueError("sampler must be one of %s; got %r" % (", ".join(SAMPLERS), sampler))
+    return sampler
+
+
+def _sample_hands(env, sampler, viewer, key, seed, world, worlds):
+    """the hidden hands of the slots' worlds: "rejection" = determinize, independent draws per world; "stratified" =
+    determinize_exact with world w of a game drawing from the w-th of `worlds` equal parts of that game's exact belief"""
+    if sampler == "rejection":
+        env.determinize(viewer, key, seed)
+    else:
+        env.determinize_exact(viewer, key, seed, stratum=world, n_strata=worlds)
+
+
 def search_jobs(root):
     """(game, action) pairs to evaluate: every legal action of the player on turn of every live root game, in (game, action) order;
     also that player per game.  Reads the root's legal_move rows."""
@@ -49,11 +67,14 @@ def search_jobs(root):
     return np.asarray(pairs, dtype=np.int64).reshape(-1, 2), cur
 
 
-def mc_action_values(root, worlds, seed, capacity=4096, max_iter=None):
+def mc_action_values(root, worlds, seed, capacity=4096, max_iter=None, sampler="rejection"):
     """float32 [G, A] on the root's device: values[g, a] = mean final score (HSAD_Q_SCORE: honours `bomb`) over `worlds` random
     playouts of action a by the player on turn of root game g; NaN for illegal actions and for games that are not live.  The root
     env is only read.  The result does not depend on `capacity` (jobs are keyed by (game, world), never by the slot they run in).
-    A world whose sampler gave up (32 rejected tries: not seen in practice) keeps the true hand."""
+    A world whose sampler gave up (32 rejected tries: not seen in practice) keeps the true hand.  sampler="stratified" draws the
+    hands with determinize_exact instead: never gives up, and the worlds of a game cover its exact belief evenly (world w takes the
+    w-th of `worlds` equal parts); keys, seeds and everything after the draw are the same."""
+    _check_sampler(sampler)
     G, P, A = root.G, root.P, root.A
     dev = root.device
     values = np.full((G, A), np.nan, dtype=np.float32)
@@ -79,7 +100,7 @@ def mc_action_values(root, worlds, seed, capacity=4096, max_iter=None):
             key = torch.from_numpy((g_c << 32) | w_c).to(dev)
             p_c = torch.from_numpy(cur[g_c]).to(dev)
             senv.fork_from(root, torch.from_numpy(g_c.astype(np.int32)), torch.from_numpy(seeds))
-            senv.determinize(p_c, key, seed)
+            _sample_hands(senv, sampler, p_c, key, seed, torch.from_numpy(w_c.astype(np.int32)), worlds)
             act = torch.full((capacity, P), A - 1, dtype=torch.int64, device=dev)   # the noop for the players not on turn
             act[slot, p_c] = torch.from_numpy(a_c).to(dev)
             senv.step(act, act)
@@ -188,10 +209,13 @@ class PolicySearch:
     """The search env of `capacity` slots, the agent's state buffers for its capacity * P rows and the host loop that plays one
     chunk of jobs; search() may be called move after move (play_with_search does).  `like` is any env with the root's rules.
     replay=True: search() takes the root's GameLog and rebuilds the LSTM states of every sampled world by replay (world envs of
-    `capacity` slots each, made when first needed and kept); consistent_only=True then counts only the worlds without a mismatch."""
+    `capacity` slots each, made when first needed and kept); consistent_only=True then counts only the worlds without a mismatch.
+    sampler: "rejection" (determinize) or "stratified" (determinize_exact, world w of a game in stratum w of `worlds`), for the
+    act chunks and the world envs of the replay stage alike."""
 
-    def __init__(self, like, agent, capacity=4096, max_steps=200, replay=False, consistent_only=False):
+    def __init__(self, like, agent, capacity=4096, max_steps=200, replay=False, consistent_only=False, sampler="rejection"):
         self.agent, self.capacity, self.max_steps = agent, int(capacity), int(max_steps)
+        self.sampler = _check_sampler(sampler)
         self.replay, self.consistent_only = bool(replay), bool(consistent_only)
         if self.consistent_only and not self.replay:
             raise ValueError("consistent_only needs replay=True: the mismatch count comes from the replay")
@@ -300,7 +324,7 @@ class PolicySearch:
             viewer = torch.from_numpy(np.where(valid, cur[g_c], -1).astype(np.int32)).to(dev)
             env.reseed(0)       # every slot "not started": the spare ones get the noop and never hold a world of an earlier search
             env.fork_from(root, src, seeds)
-            env.determinize(viewer, key, seed)
+            _sample_hands(env, self.sampler, viewer, key, seed, torch.from_numpy(w_c.astype(np.int32)), worlds)
             _lib.check(lib.hsad_search_world_script(env.h, src.data_ptr(), viewer.data_ptr(), dh.data_ptr(), cnt.data_ptr(), G,
                                                     la.data_ptr() if n_moves else None, n_moves, script.data_ptr(), count.data_ptr(),
                                                     env._stream()))
@@ -379,7 +403,7 @@ class PolicySearch:
             job = torch.from_numpy(np.where(valid, pj, -1).astype(np.int32)).to(dev)
             if not self.replay:
                 env.fork_from(root, src, seeds)
-                env.determinize(player, key, seed)
+                _sample_hands(env, self.sampler, player, key, seed, torch.from_numpy(w_c.astype(np.int32)), worlds)
                 _lib.check(lib.hsad_search_fork_state(src.data_ptr(), cap, G, P, L, H, h_src.data_ptr(), c_src.data_ptr(), self.h.data_ptr(),
                                                       self.c.data_ptr(), self.h16.data_ptr() if self.h16 is not None else None, env._stream()))
             else:
@@ -411,7 +435,7 @@ class PolicySearch:
 
 
 def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_steps=200, searcher=None, replay=False, log=None,
-                         consistent_only=False):
+                         consistent_only=False, sampler="rejection"):
     """SearchValues: values[g, a] = mean final score (HSAD_Q_SCORE) over `worlds` sampled worlds when the player on turn of root game
     g plays a and EVERY player, the searcher included, then follows the blueprint `agent` greedily to the end of the game.
 
@@ -443,8 +467,11 @@ def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_step
     must show it too -- which also keeps the searcher's own replayed state equal to the one it carries); the act chunks then fork the worlds and their h / c from the world envs.  A world's cards and
     generator are the same either way.  SearchValues.mismatch counts, per world, the partner moves whose greedy action differs in
     that world; consistent_only=True leaves worlds with a mismatch out of the totals (all worlds where none is consistent).  The
-    replay costs one act + step per logged move on all searched games x worlds slots."""
-    ps = PolicySearch(root, agent, capacity, max_steps, replay=replay, consistent_only=consistent_only)
+    replay costs one act + step per logged move on all searched games x worlds slots.
+
+    sampler="stratified": the hands come from determinize_exact(stratum = world, n_strata = worlds) wherever determinize is named
+    above, the world envs of the replay included (see mc_action_values)."""
+    ps = PolicySearch(root, agent, capacity, max_steps, replay=replay, consistent_only=consistent_only, sampler=sampler)
     try:
         return ps.search(root, hid, worlds, seed, searcher, log=log)
     finally:
@@ -485,7 +512,7 @@ class SearchPlay:
 
 def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05, search_seed=0, searcher="all", capacity=4096,
                      num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16", shuffle_color=False, colors=5, ranks=5,
-                     max_information_tokens=8, max_life_tokens=3, replay_history=False, consistent_only=False):
+                     max_information_tokens=8, max_life_tokens=3, replay_history=False, consistent_only=False, sampler="rejection"):
     """eval.evaluate's lock-step loop over the deals seed .. seed + num_game - 1 with search on top of the blueprint -> SearchPlay.
     Before each step: PolicySearch values for the games whose player on turn searches (searcher: "all" or a seat number),
     choose_action, then the root steps with a = the chosen action and greedy_a = the blueprint's greedy action; the carried state
@@ -493,7 +520,8 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
     exactly.  worlds = 0 takes no search path at all and returns evaluate's scores.  The search env has min(capacity, num_game x
     (A - 1) x worlds) slots -- the most jobs a move can have -- and capacity x P decides the acting regime (policy_action_values).
     replay_history=True: the root tracks its deck history, a GameLog keeps the rows it was stepped with and the search rebuilds
-    every world's LSTM states by replay (PolicySearch(replay=True)); consistent_only as there."""
+    every world's LSTM states by replay (PolicySearch(replay=True)); consistent_only and sampler as there."""
+    _check_sampler(sampler)
     from .eval import _acting_agent, _drain_errors
     agent = _acting_agent(agent, precision, device)
     env = BatchedHanabiEnv(num_game, players=num_player, hand_size=hand_size, seed=seed, bomb=bomb, eps_list=[0.0], max_len=-1, sad=bool(sad),
@@ -504,7 +532,7 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
         raise ValueError("searcher must be \"all\" or a seat in 0..%d" % (num_player - 1))
     # no move has more jobs than games x playable actions x worlds: a smaller batch needs no more slots than that
     ps = PolicySearch(env, agent, min(int(capacity), num_game * (env.A - 1) * worlds), max_steps, replay=bool(replay_history),
-                      consistent_only=bool(consistent_only)) if worlds > 0 else None
+                      consistent_only=bool(consistent_only), sampler=sampler) if worlds > 0 else None
     log = GameLog(num_game, num_player, env.device) if ps is not None and replay_history else None
     N = num_game * num_player
     deviations = torch.zeros(num_game, dtype=torch.int64, device=env.device)

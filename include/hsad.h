@@ -263,6 +263,40 @@ int hsad_env_fork(hsad_env* dst, hsad_env* src, const int32_t* src_index, const 
  * resampled games are then rewritten by the observe pass (SAD section kept from the env's own rows).  Launch-only. */
 int hsad_env_determinize(hsad_env* env, const int32_t* viewer, const int64_t* key, uint64_t seed, int32_t* tries_out, void* stream);
 
+/* The exact belief over the viewer's hidden hand, and a sampler without rejection on top of it.  Notation as above: card type
+ * t = colour * 5 + rank, pool[t] = deck count + copies in the viewer's hand, occupied slots i = 0 .. n-1 (n <= 5) in slot order,
+ * compat_i[t] = colour(t) and rank(t) both plausible for slot i.  The belief is the distribution hsad_env_determinize samples:
+ * uniform over the injective assignments of PHYSICAL unseen cards to the slots that agree with compat.  For a set of slots B let
+ * s_B(q) = sum_t q[t] prod_{i in B} compat_i[t] (the cards plausible for every slot of B).  The number of assignments for slots S:
+ *   C({}, q) = 1;   C(S, q) = sum over B subset of S with min(S) in B of (-1)^(|B|-1) (|B|-1)! s_B(q) C(S \ B, q)
+ * (inclusion-exclusion over which slots were given the same card: Moebius inversion on the lattice of set partitions), exact in
+ * int64 (every term < 2^35, N = C(all slots, pool) < 2^28).  Marginals: num[i][t] = pool[t] compat_i[t] C(all \ {i}, pool - e_t),
+ * sum_t num[i][t] = N, P(slot i holds type t) = num[i][t] / N.  Unrank, r in [0, N), q = pool: for slot i = 0 .. n-1, for t
+ * ascending with q[t] compat_i[t] != 0: c = C({i+1 .. n-1}, q - e_t), w = q[t] c; r < w: slot i holds t, q[t] -= 1, r = r mod c,
+ * next slot; else r -= w.  Exactly prod of the falling counts ranks arrive at each hand: its weight in the belief.
+ *
+ * hsad_env_hand_belief: viewer device int32 [G]; a game with viewer -1 or out of range, never started or finished is skipped.
+ * total_out device int64 [G] = N (0 if skipped); counts_out device int64 [G, H, 25] = num (empty slots and skipped games all zero);
+ * trinary_out device int64 [G, H, 3] or NULL = num summed by the classes of EncodeOwnHandTrinary against the firework fw of the
+ * card's colour: [rank == fw (playable), rank < fw, rank > fw].  Reads the state only: no bound output is needed or touched (it
+ * works on a sad = 1 env with no observation rows).  Launch-only.
+ *
+ * hsad_env_determinize_exact: hsad_env_determinize's in-place counterpart with the same skip rules: the hand of viewer[g] becomes
+ * unrank(r) in slot order, the deck counts the q it leaves; everything else in the state is unchanged.  rank_in device int64 [G]:
+ * r = rank_in[g] (key, seed and stratum are ignored, key may be NULL).  rank_in NULL: the stratified rank of world w = stratum[g]
+ * (device int32 [G], NULL = 0) of W = n_strata:
+ *   lo = (w N) / W, hi = ((w + 1) N) / W, u = (hash(seed, key[g], 0, 65) << 32) | hash(seed, key[g], 1, 65),
+ *   r = lo + ((u * (hi - lo)) >> 64)   (r = lo for an empty stratum)
+ * with hash the policy's hash, stream 65 (hsad_env_determinize uses 64).  The W worlds of a game thus cover [0, N) evenly; W = 1 is
+ * a plain exact draw.  There is no try count and no giving up.  A game is LEFT ALONE -- state and rows -- when it is skipped, when
+ * rank_in[g] is outside [0, N), when stratum[g] is outside [0, W) or when N = 0 (a live game's true hand is consistent, so N >= 1).
+ * rank_out device int64 [G] or NULL: the rank used, -1 for every game left alone.  The rows of the resampled games are rewritten by
+ * the observe pass, SAD section kept from the env's own rows: the precondition and error of hsad_env_determinize with sad = 1.
+ * HSAD_ERR_INVALID when n_strata < 1 or > 2^20.  Launch-only. */
+int hsad_env_hand_belief(hsad_env* env, const int32_t* viewer, int64_t* total_out, int64_t* counts_out, int64_t* trinary_out, void* stream);
+int hsad_env_determinize_exact(hsad_env* env, const int32_t* viewer, const int64_t* key, uint64_t seed, const int32_t* stratum, int n_strata,
+                               const int64_t* rank_in, int64_t* rank_out, void* stream);
+
 /* hsad_env_playout_random: up to max_iter iterations of random-legal policy -> step for every game that is started and not
  * finished, in one launch.  A finished game is left alone (no restart, no error, no counter advance); a live game's trajectory --
  * actions in a / greedy_a, state, draws -- is that of hsad_env_policy_random + hsad_env_step.  NO observation rows are written

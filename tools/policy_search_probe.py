@@ -3,9 +3,12 @@
 compacting finished games out of the act batch), the three glue kernels' times, and the same call of mc_action_values (random
 playouts) as the yardstick.  --replay adds the replay stage (PolicySearch(replay=True)): its seconds alone at several move
 depths -- the cost grows with the move number -- and the whole search with it.  Host clock around a device synchronise, median of
-the repeats.  One JSON line.
+the repeats.  --sampler chooses how the worlds' hands are drawn in every search timed here (rejection: hsad_env_determinize;
+stratified: hsad_env_determinize_exact); the determinise call of both samplers and hsad_env_hand_belief are also timed alone on the
+search env.  One JSON line.
 
     python tools/policy_search_probe.py [--roots 64] [--worlds 8] [--capacity 4096] [--hid 512] [--repeats 5] [--replay]
+                                        [--sampler rejection|stratified]
 """
 import argparse
 import json
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sad", type=int, default=1)
     ap.add_argument("--replay", action="store_true", help="also time the replay stage per move depth and the search with replay")
+    ap.add_argument("--sampler", choices=["rejection", "stratified"], default="rejection")
     args = ap.parse_args()
     from hanabi_sad_amd.composite import CNet, CompositeAgent
     from hanabi_sad_amd.eval import env_dims
@@ -68,8 +72,9 @@ def main():
             snaps[move + 1].fork_from(root, torch.arange(G, dtype=torch.int32))
         log.observed(root)
     hid = {"h0": hid["h0"], "c0": hid["c0"]}
-    ps = PolicySearch(root, agent, args.capacity)
-    res = {"roots": G, "worlds": args.worlds, "capacity": args.capacity, "hid": args.hid, "sad": args.sad, "repeats": args.repeats}
+    ps = PolicySearch(root, agent, args.capacity, sampler=args.sampler)
+    res = {"roots": G, "worlds": args.worlds, "capacity": args.capacity, "hid": args.hid, "sad": args.sad, "repeats": args.repeats,
+           "sampler": args.sampler}
     sv = ps.search(root, hid, args.worlds, 0)                       # warm-up (first launch of each kernel)
     jobs = int(sv.totals[..., 2].sum())
     res["jobs"] = jobs
@@ -84,7 +89,7 @@ def main():
     res["slot_steps_per_s"] = [s / m * 1e3 for s, m in zip(steps, ms)]
     res["live_env_steps_per_s"] = [s / m * 1e3 for s, m in zip(live_steps, ms)]
     res["live_fraction_per_iteration"] = live
-    res["mc_action_values_ms"] = timed(lambda: mc_action_values(root, args.worlds, 3, capacity=args.capacity), args.repeats)
+    res["mc_action_values_ms"] = timed(lambda: mc_action_values(root, args.worlds, 3, capacity=args.capacity, sampler=args.sampler), args.repeats)
     # the three glue kernels alone, on the search env as the last chunk left it
     env, lib, st = ps.env, ps.lib, ps.env._stream()
     cap = args.capacity
@@ -107,12 +112,29 @@ def main():
     for name, fn in calls.items():
         fn()
         res[name] = timed(fn, args.repeats)
+    # the determinise call of both samplers and the belief kernel, on forks of the root in the search env (every slot a world)
+    q = root.query()
+    cur = torch.where(q[:, 0] == 0, q[:, 1], torch.full_like(q[:, 1], -1)).to(torch.int32)
+    viewer = cur[src.to(torch.int64)].contiguous()
+    wkey = torch.arange(cap, device=dev, dtype=torch.int64)
+    stratum = (torch.arange(cap, device=dev) % args.worlds).to(torch.int32)
+    det = {"determinize_observe_ms": lambda: env.determinize(viewer, wkey, 7),
+           "determinize_exact_observe_ms": lambda: env.determinize_exact(viewer, wkey, 7, stratum=stratum, n_strata=args.worlds),
+           "hand_belief_ms": lambda: env.hand_belief(viewer)}
+    for name, fn in det.items():
+        ms = []
+        for r in range(args.repeats + 1):
+            env.fork_from(root, src)
+            ms += timed(fn, 1)
+        res[name] = ms[1:]                                          # the first call is the warm-up
+        res[name + "_median"] = statistics.median(res[name])
+    res["chosen_determinize_ms_median"] = res["determinize_exact_observe_ms_median" if args.sampler == "stratified" else "determinize_observe_ms_median"]
     for k in ("search_ms", "jobs_per_s", "slot_steps_per_s", "live_env_steps_per_s", "live_fraction_per_iteration", "mc_action_values_ms", "fork_state_ms", "actions_ms",
               "job_stats_ms"):
         res[k + "_median"] = statistics.median(res[k])
     ps.close()
     if args.replay:
-        rp = PolicySearch(root, agent, args.capacity, replay=True)
+        rp = PolicySearch(root, agent, args.capacity, replay=True, sampler=args.sampler)
         rp.search(root, hid, args.worlds, 0, log=log)               # warm-up: builds the world envs
         res["search_replay_ms"] = timed(lambda: rp.search(root, hid, args.worlds, 1, log=log), args.repeats)
         res["search_replay_ms_median"] = statistics.median(res["search_replay_ms"])

@@ -1,7 +1,8 @@
 """Records for DESIGN §3g: fork + observe time, the playout's env-steps/s without the observation stream, the sampler's mean tries,
-next to hsad_env_step on the same games.  One JSON line.
+next to hsad_env_step on the same games; with --sampler stratified also the time of hsad_env_determinize_exact + observe on the same
+states (8 strata), and in either case the time of hsad_env_hand_belief.  One JSON line.
 
-    python tools/search_probe.py [--games 65536] [--repeats 5]
+    python tools/search_probe.py [--games 65536] [--repeats 5] [--sampler rejection|stratified]
 """
 import argparse
 import json
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--games", type=int, default=65536)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sad", type=int, default=1)
+    ap.add_argument("--sampler", choices=["rejection", "stratified"], default="rejection")
     args = ap.parse_args()
     G, dev = args.games, "cuda:0"
     kw = dict(players=2, hand_size=5, sad=bool(args.sad), eps_list=(0.0,), device=dev)
@@ -40,7 +42,7 @@ def main():
     src.rollout_random(12, 3)
     idx = torch.randperm(G, device=dev, generator=torch.Generator(device=dev).manual_seed(0)).to(torch.int32)
     seeds = torch.arange(G, device=dev, dtype=torch.int32)
-    res = {"games": G, "sad": args.sad, "repeats": args.repeats}
+    res = {"games": G, "sad": args.sad, "repeats": args.repeats, "sampler": args.sampler}
     dst.fork_from(src, idx)   # warm-up (first launch of each kernel)
     res["fork_observe_ms"] = timed(lambda: dst.fork_from(src, idx), args.repeats)
     res["fork_observe_reseed_ms"] = timed(lambda: dst.fork_from(src, idx, seeds), args.repeats)
@@ -66,6 +68,24 @@ def main():
         tries_mean.append(float(done.mean()))
         gave_up += int((tries < 0).sum())
     res["determinize_observe_ms"], res["mean_tries"], res["gave_up"] = det_ms, tries_mean, gave_up
+    medians = []
+    if args.sampler == "stratified":   # the chosen sampler's call on the same states, next to the rejection sampler's
+        stratum = (torch.arange(G, device=dev, dtype=torch.int32) % 8).contiguous()
+        exact_ms, left_alone = [], 0
+        for r in range(args.repeats):
+            dst.fork_from(src, torch.arange(G, device=dev, dtype=torch.int32))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rank = dst.determinize_exact(viewer, key, 100 + r, stratum=stratum, n_strata=8)
+            torch.cuda.synchronize()
+            exact_ms.append((time.perf_counter() - t0) * 1e3)
+            left_alone += int(((rank < 0) & (viewer >= 0)).sum())
+        res["determinize_exact_observe_ms"], res["exact_left_alone"] = exact_ms, left_alone
+        medians.append("determinize_exact_observe_ms")
+    dst.fork_from(src, torch.arange(G, device=dev, dtype=torch.int32))
+    dst.hand_belief(viewer)   # warm-up
+    res["hand_belief_ms"] = timed(lambda: dst.hand_belief(viewer), args.repeats)
+    medians.append("hand_belief_ms")
     # playout: every game from where the fork left it to its end
     rates, play_ms = [], []
     for r in range(args.repeats):
@@ -79,7 +99,7 @@ def main():
         rates.append(steps / ms * 1e3)
     dst.check_errors()
     res["playout_ms"], res["playout_env_steps_per_s"] = play_ms, rates
-    for k in ("fork_observe_ms", "fork_observe_reseed_ms", "env_step_ms", "determinize_observe_ms", "playout_ms", "playout_env_steps_per_s"):
+    for k in ("fork_observe_ms", "fork_observe_reseed_ms", "env_step_ms", "determinize_observe_ms", "playout_ms", "playout_env_steps_per_s", *medians):
         res[k + "_median"] = statistics.median(res[k])
     print(json.dumps(res))
 

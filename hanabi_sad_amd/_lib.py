@@ -288,6 +288,8 @@ SIGNATURES = {
     "hsad_search_fork_state": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "hsad_search_actions": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "hsad_search_job_stats": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "hsad_search_world_scores": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "hsad_search_round": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "hsad_search_world_script": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
     "hsad_search_replay_actions": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "hsad_ipc_handle_bytes": (C.c_int, []),

@@ -1,5 +1,5 @@
 // hsad_search.hip — the glue kernels of blueprint-policy search (include/hsad.h: hsad_search_fork_state / hsad_search_actions /
-// hsad_search_job_stats; search.PolicySearch drives them).
+// hsad_search_job_stats / hsad_search_world_scores / hsad_search_round; search.PolicySearch drives them).
 //
 // What they serve: SPARTA-style single-agent search.  A search env holds `capacity` slots; slot j plays one (root game, candidate
 // action, sampled world) job: hsad_env_fork + hsad_env_determinize put the world there, the R2D2 agent acts for every seat of every
@@ -15,6 +15,10 @@
 //                   hsad_env_rewind_scripted takes, so that the world can be played again from its first move
 //   replay_actions  the root's logged moves as the a / greedy_a rows of the replay step, and the count of partner moves at which the
 //                   blueprint in this world would have shown another greedy action than the one observed
+// and, for the search in rounds (PolicySearch.search(rounds = ...)), which compares actions world by world and drops hopeless ones:
+//   world_scores    the finished slots' scores, one byte per (pair, world)
+//   round           per searched game: raw sums, the leader, paired sums against the leader's and the blueprint's row, pruning --
+//                   one workgroup per game, integer arithmetic only, no atomics
 // All are launch-only, one pass and HBM-bound.  The state rows move as 16-byte vectors (H % 4 == 0; with H % 8 == 0 the bf16
 // row is written as 16-byte vectors too).
 #include <hip/hip_runtime.h>
@@ -231,6 +235,143 @@ __global__ __launch_bounds__(kThreads) void replay_actions_kernel(const uint32_t
   if (differs) mismatch[g] += 1;
 }
 
+// one thread per slot; one byte store per finished slot with a valid (pair, world): a (pair, world) is played at most once, so no
+// two slots of a launch name the same byte
+__global__ __launch_bounds__(kThreads) void world_scores_kernel(const uint32_t* __restrict__ misc, int G, const int32_t* __restrict__ pair,
+                                                                const int32_t* __restrict__ world, int n_pair, int worlds,
+                                                                uint8_t* __restrict__ scores) {
+  const int g = blockIdx.x * kThreads + threadIdx.x;
+  if (g >= G) return;
+  const int p = pair[g], w = world[g];
+  if (p < 0 || p >= n_pair || w < 0 || w >= worlds) return;
+  const uint32_t m = misc[g];
+  if (!game_finished(m)) return;
+  scores[(size_t)p * worlds + w] = (uint8_t)(((m >> 16) & 63u) - 1u);   // the score job_stats_kernel sums, 0..25
+}
+
+constexpr int kRoundWorlds = 4096;     // the longest row hsad_search_round takes: with it every product below stays under 2^56
+constexpr int kRoundLdsPairs = 32;     // raw sums of a game's first pairs are kept in LDS; later pairs are read back from raw_out
+constexpr uint8_t kAbsent = 0xFF;
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// is the raw mean (s_a / n_a) of pair a ahead of that of pair b?  n = 0 is behind everything; ties go to the lower pair index
+__device__ __forceinline__ bool leads(int s_a, int n_a, int i_a, int s_b, int n_b, int i_b) {
+  if (n_a == 0 || n_b == 0) return n_a != 0 || (n_b == 0 && i_a < i_b);
+  const long long l = (long long)s_a * n_b, r = (long long)s_b * n_a;
+  return l > r || (l == r && i_a < i_b);
+}
+
+// one workgroup of four waves per searched game; waves take the game's pairs round-robin, the lanes of a wave stride over the worlds
+// of a row (byte loads from consecutive addresses).  Per-lane and per-wave sums fit int32: |d| <= 25, d^2 <= 625, worlds <= 4096.
+__global__ __launch_bounds__(kThreads) void search_round_kernel(const uint8_t* __restrict__ scores, int n_pair, int worlds,
+                                                                const int32_t* __restrict__ first_pair, const int32_t* __restrict__ bp_pair,
+                                                                long long z2_num, long long z2_den, int min_n, uint8_t* __restrict__ alive,
+                                                                int32_t* __restrict__ leader_out, long long* __restrict__ raw_out,
+                                                                long long* __restrict__ paired_ref_out,
+                                                                long long* __restrict__ paired_bp_out) {
+  __shared__ int raw_s[kRoundLdsPairs], raw_n[kRoundLdsPairs];
+  __shared__ uint8_t ref_row[kRoundWorlds], bp_row[kRoundWorlds];
+  __shared__ int leader_sh;
+  const int k = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int p0 = first_pair[k], p1 = first_pair[k + 1];
+  if (p0 < 0 || p1 > n_pair || p0 >= p1) {      // no pairs, or a list that leaves the tables: nothing of this game is read or written
+    if (threadIdx.x == 0) leader_out[k] = -1;
+    return;
+  }
+  int bp = bp_pair[k];
+  if (bp < p0 || bp >= p1) bp = -1;             // no blueprint pair: its table stays (0, 0, 0), and nothing is exempt on its account
+  // phase 1: raw sums
+  for (int p = p0 + wave; p < p1; p += 4) {
+    const uint8_t* row = scores + (size_t)p * worlds;
+    int s = 0, n = 0;
+    for (int w = lane; w < worlds; w += 64) {
+      const uint8_t v = row[w];
+      if (v != kAbsent) {
+        s += v;
+        n += 1;
+      }
+    }
+    s = wave_sum(s);
+    n = wave_sum(n);
+    if (lane == 0) {
+      raw_out[(size_t)p * 2 + 0] = s;
+      raw_out[(size_t)p * 2 + 1] = n;
+      if (p - p0 < kRoundLdsPairs) {
+        raw_s[p - p0] = s;
+        raw_n[p - p0] = n;
+      }
+    }
+  }
+  __syncthreads();      // the raw sums of every pair, in LDS and (workgroup scope) in raw_out
+  // the leader: wave 0, every lane the best of its pairs, then a butterfly over (sum, n, index)
+  if (wave == 0) {
+    int bs = 0, bn = 0, bi = 0x7fffffff;
+    for (int p = p0 + lane; p < p1; p += 64) {
+      if (alive[p] == 0) continue;
+      const int i = p - p0;
+      const int s = i < kRoundLdsPairs ? raw_s[i] : (int)raw_out[(size_t)p * 2 + 0];
+      const int n = i < kRoundLdsPairs ? raw_n[i] : (int)raw_out[(size_t)p * 2 + 1];
+      if (n > 0 && leads(s, n, p, bs, bn, bi)) bs = s, bn = n, bi = p;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int os = __shfl_xor(bs, o, 64), on = __shfl_xor(bn, o, 64), oi = __shfl_xor(bi, o, 64);
+      if (leads(os, on, oi, bs, bn, bi)) bs = os, bn = on, bi = oi;
+    }
+    if (lane == 0) {
+      leader_sh = bn > 0 ? bi : bp;
+      leader_out[k] = leader_sh;
+    }
+  }
+  __syncthreads();
+  const int leader = leader_sh;
+  // the two reference rows into LDS: every pair of the game is compared with them
+  for (int w = threadIdx.x; w < worlds; w += kThreads) {
+    ref_row[w] = leader >= 0 ? scores[(size_t)leader * worlds + w] : kAbsent;
+    bp_row[w] = bp >= 0 ? scores[(size_t)bp * worlds + w] : kAbsent;
+  }
+  __syncthreads();
+  // phase 2: paired sums against both rows, and the pruning rule on the leader's
+  for (int p = p0 + wave; p < p1; p += 4) {
+    const uint8_t* row = scores + (size_t)p * worlds;
+    int D = 0, Q = 0, n = 0, Db = 0, Qb = 0, nb = 0;
+    for (int w = lane; w < worlds; w += 64) {
+      const uint8_t v = row[w], r = ref_row[w], b = bp_row[w];
+      if (v != kAbsent && r != kAbsent) {
+        const int d = (int)v - (int)r;
+        D += d;
+        Q += d * d;
+        n += 1;
+      }
+      if (v != kAbsent && b != kAbsent) {
+        const int d = (int)v - (int)b;
+        Db += d;
+        Qb += d * d;
+        nb += 1;
+      }
+    }
+    D = wave_sum(D), Q = wave_sum(Q), n = wave_sum(n);
+    Db = wave_sum(Db), Qb = wave_sum(Qb), nb = wave_sum(nb);
+    if (lane == 0) {
+      long long* o = paired_ref_out + (size_t)p * 3;
+      o[0] = D, o[1] = Q, o[2] = n;
+      o = paired_bp_out + (size_t)p * 3;
+      o[0] = Db, o[1] = Qb, o[2] = nb;
+      if (alive[p] != 0 && p != leader && p != bp && n >= min_n && D < 0) {
+        // mean + z * sem < 0 with mean = D / n, sem^2 = (n Q - D^2) / n^3 and D < 0  <=>  D^2 n > z^2 (n Q - D^2)
+        const long long D2 = (long long)D * D;
+        if (D2 * n * z2_den > z2_num * ((long long)n * Q - D2)) alive[p] = 0;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -314,6 +455,37 @@ int hsad_search_replay_actions(const hsad_env* env, const int32_t* src_index, co
   CK(hsad_internal_env_legal_bits(env, &legal));
   hipLaunchKernelGGL(replay_actions_kernel, dim3((G + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, misc, legal, G, P, A - 1,
                      src_index, viewer, log_a_t, log_greedy_t, G_root, greedy_src, a, greedy_a, mismatch);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_search_world_scores(const hsad_env* env, const int32_t* pair, const int32_t* world, int n_pair, int worlds, uint8_t* scores,
+                             void* stream) {
+  if (!pair || !world || !scores) return efail(HSAD_ERR_INVALID, "hsad_search_world_scores: null argument");
+  if (n_pair < 1 || worlds < 1) return efail(HSAD_ERR_INVALID, "hsad_search_world_scores: n_pair and worlds must be >= 1");
+  const uint32_t* misc;
+  int G, P, A, perfect;
+  CK(hsad_internal_env_status(env, &misc, &G, &P, &A, &perfect));
+  hipLaunchKernelGGL(world_scores_kernel, dim3((G + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, misc, G, pair, world,
+                     n_pair, worlds, scores);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_search_round(const uint8_t* scores, int n_pair, int worlds, const int32_t* first_pair, int n_game, const int32_t* bp_pair,
+                      int z2_num, int z2_den, int min_n, uint8_t* alive, int32_t* leader_out, int64_t* raw_out, int64_t* paired_ref_out,
+                      int64_t* paired_bp_out, void* stream) {
+  if (!scores || !first_pair || !bp_pair || !alive || !leader_out || !raw_out || !paired_ref_out || !paired_bp_out)
+    return efail(HSAD_ERR_INVALID, "hsad_search_round: null argument");
+  if (n_pair < 1 || n_game < 1) return efail(HSAD_ERR_INVALID, "hsad_search_round: n_pair and n_game must be >= 1");
+  if (worlds < 1 || worlds > kRoundWorlds)
+    return efail(HSAD_ERR_INVALID, "hsad_search_round: worlds = %d is outside [1, %d]", worlds, kRoundWorlds);
+  if (z2_den < 1 || z2_den > 1024 || z2_num < 0 || z2_num > 16384)
+    return efail(HSAD_ERR_INVALID, "hsad_search_round: z^2 = %d / %d is outside [0, 16384] / [1, 1024] (the int64 bounds)", z2_num, z2_den);
+  if (min_n < 1) return efail(HSAD_ERR_INVALID, "hsad_search_round: min_n must be >= 1");
+  hipLaunchKernelGGL(search_round_kernel, dim3(n_game), dim3(kThreads), 0, (hipStream_t)stream, scores, n_pair, worlds, first_pair, bp_pair,
+                     (long long)z2_num, (long long)z2_den, min_n, alive, leader_out, reinterpret_cast<long long*>(raw_out),
+                     reinterpret_cast<long long*>(paired_ref_out), reinterpret_cast<long long*>(paired_bp_out));
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
 }

@@ -9,6 +9,7 @@ layout.
   --paper op  --method sad --idx 0 3 6 9 --cross_play   the 4 x 4 matrix
   --paper sad --weight a.pthw b.pthw c.pthw --cross_play
   --paper op  --method sad --idx 0 --search_worlds 8    M0 in self-play, blueprint only and blueprint + search over the same deals
+  ... --search_worlds 32 --search_rounds 8,8,16         the same with the search in rounds (paired statistics, pruning)
 
 As in the reference the deals are seeds 1 .. num_game * num_run, bombing out keeps the score (bomb 0) and everyone acts greedily.
 Whether the env appends SAD's greedy-action section is read off the models' input width (838 vs 783 features in the 2-player
@@ -46,6 +47,13 @@ def parse_args(argv=None):
     p.add_argument("--search_sampler", default="rejection", type=str, choices=["rejection", "stratified"],
                    help="how the sampled worlds' hidden hands are drawn: hsad_env_determinize, or hsad_env_determinize_exact with the "
                    "worlds of a game stratified over its exact belief")
+    p.add_argument("--search_rounds", default=None, type=lambda s: tuple(int(x) for x in s.split(",")),
+                   help="world counts per round, e.g. 8,8,16 (their sum must be --search_worlds): search in rounds, dropping hopeless "
+                   "actions in between, and choose by the paired statistics (search.choose_action_paired)")
+    p.add_argument("--search_prune_z", default=2.0, type=float, help="with --search_rounds: drop an action whose paired mean lies more "
+                   "than this many paired standard errors below the round's leader")
+    p.add_argument("--search_deviate_z", default=0.0, type=float, help="with --search_rounds: deviate only where the paired gain over "
+                   "the blueprint's action also exceeds this many of its standard errors")
     return p.parse_args(argv)
 
 
@@ -85,6 +93,8 @@ def search_report(args):
     kw = dict(precision=args.precision, device=args.device, threshold=args.search_threshold,
               searcher="all" if args.search_seat is None else args.search_seat)
     base = play_with_search(agent, n, 1, 0, sad, worlds=0, **kw)
+    if args.search_rounds is not None:
+        kw.update(rounds=args.search_rounds, prune_z=args.search_prune_z, deviate_z=args.search_deviate_z)
     res = play_with_search(agent, n, 1, 0, sad, worlds=args.search_worlds, replay_history=bool(args.search_replay),
                            consistent_only=bool(args.search_consistent), sampler=args.search_sampler, **kw)
     print("blueprint: %f +/- %f" % (base.mean, base.sem), "; perfect: ", base.perfect)

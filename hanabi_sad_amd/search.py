@@ -9,7 +9,13 @@ policy_action_values / PolicySearch play them out with the blueprint itself -- t
 which is what can improve on that agent (choose_action, play_with_search).  The glue kernels of the second are csrc/hsad_search.hip.
 
 PolicySearch(replay=True) first plays every sampled world again from its first move (GameLog, hsad_search_world_script,
-hsad_env_rewind_scripted, hsad_search_replay_actions), so that each seat's LSTM state is the one that world's observations give."""
+hsad_env_rewind_scripted, hsad_search_replay_actions), so that each seat's LSTM state is the one that world's observations give.
+
+search(rounds=(n0, n1, ...)) plays the worlds in rounds: the per-world scores are kept (hsad_search_world_scores), and after each
+round hsad_search_round compares every action with the round's leader world by world -- the actions of a game meet the same worlds
+-- and drops those that are already hopeless (round_world_order, SearchValues.paired / pruned_round, choose_action_paired)."""
+from fractions import Fraction
+
 import numpy as np
 import torch
 
@@ -125,6 +131,35 @@ def mc_greedy_action(values):
 # ---------------------------------------------------------------------------------------------------------
 # blueprint-policy search: the sampled worlds are played out by the agent itself
 # ---------------------------------------------------------------------------------------------------------
+MAX_ROUND_WORLDS, MAX_Z2_DEN, MAX_Z2_NUM = 4096, 1024, 16384     # the int64 bounds of hsad_search_round (include/hsad.h)
+
+
+def round_world_order(worlds):
+    """the order in which a search in rounds plays a game's worlds: the indices 0 .. worlds - 1 sorted by their bit-reversed value
+    over (worlds - 1).bit_length() bits -- 8 -> [0, 4, 2, 6, 1, 5, 3, 7].  Every prefix is spread over [0, worlds): with the stratified
+    sampler world w is stratum w of the belief in rank order, so an early round does not sit in one corner of it.  World 0 is first."""
+    bits = max(int(worlds) - 1, 0).bit_length()
+    return sorted(range(int(worlds)), key=lambda w: int(format(w, "0%db" % bits)[::-1], 2) if bits else 0)
+
+
+def _check_rounds(rounds, worlds, prune_z, min_n):
+    """-> (rounds as a tuple of ints, z2_num, z2_den): prune_z^2 as the fraction hsad_search_round takes"""
+    try:
+        rounds = tuple(int(r) for r in rounds)
+    except TypeError:
+        raise ValueError("rounds must be a tuple of positive world counts; got %r" % (rounds,))
+    if not rounds or any(r < 1 for r in rounds) or sum(rounds) != worlds:
+        raise ValueError("rounds must be positive world counts that sum to worlds = %d; got %r" % (worlds, rounds))
+    if worlds > MAX_ROUND_WORLDS:
+        raise ValueError("a search in rounds takes at most %d worlds; got %d" % (MAX_ROUND_WORLDS, worlds))
+    if not prune_z >= 0 or int(min_n) < 1:
+        raise ValueError("prune_z must be >= 0 and min_n >= 1; got %r, %r" % (prune_z, min_n))
+    z2 = Fraction(prune_z * prune_z).limit_denominator(MAX_Z2_DEN)
+    if z2.numerator > MAX_Z2_NUM:
+        raise ValueError("prune_z = %r: z^2 = %s has a numerator above %d" % (prune_z, z2, MAX_Z2_NUM))
+    return rounds, z2.numerator, z2.denominator
+
+
 class SearchValues:
     """what PolicySearch.search returns, all on the device of `totals`:
     totals int64 [G, A, 3] = (sum score, sum score^2, worlds counted) per (root game, action) as hsad_search_job_stats reduced them;
@@ -132,9 +167,13 @@ class SearchValues:
     are not live, turns of a player who does not search); sem float32 [G, A] = population std / sqrt(worlds) from the integers;
     blueprint_a int64 [G] = the agent's own greedy action at the root, -1 for games that were not searched;
     mismatch int32 [G, worlds] (replay only, else None) = per sampled world the number of past partner moves at which the blueprint,
-    replayed in that world, showed another greedy action than the logged one (0 for games that were not searched)."""
+    replayed in that world, showed another greedy action than the logged one (0 for games that were not searched).
+    A search in rounds (search(rounds=...), else all None) adds: paired int64 [G, A, 3] = (sum d, sum d^2, worlds) of d = the action's
+    score minus the blueprint action's in the same world, over the worlds both were played in; paired_mean / paired_sem float32
+    [G, A] from those integers as values / sem are (NaN where no world is shared); pruned_round int32 [G, A] = the round after which
+    the action was dropped, -1 if never; world_scores uint8 [G, A, worlds] = the score per world, 0xFF where not played."""
 
-    def __init__(self, totals, blueprint_a, mismatch=None):
+    def __init__(self, totals, blueprint_a, mismatch=None, paired=None, pruned_round=None, world_scores=None):
         self.totals = totals = torch.as_tensor(totals).to(torch.int64)
         self.blueprint_a = torch.as_tensor(blueprint_a).to(torch.int64)
         self.mismatch = mismatch
@@ -146,6 +185,17 @@ class SearchValues:
         var_n2 = (nf * sq - s * s).clamp(min=0).to(torch.float64)        # n^2 * population variance, exact in int64
         nd = nf.to(torch.float64)
         self.sem = torch.where(counted, (torch.sqrt(var_n2) / nd / torch.sqrt(nd)).to(torch.float32), nan)
+        self.paired, self.pruned_round, self.world_scores = paired, pruned_round, world_scores
+        self.paired_mean = self.paired_sem = None
+        if paired is not None:
+            self.paired = paired = torch.as_tensor(paired).to(torch.int64)
+            d, dq, dn = paired[..., 0], paired[..., 1], paired[..., 2]
+            shared = dn > 0
+            nf = torch.where(shared, dn, torch.ones_like(dn))
+            self.paired_mean = torch.where(shared, d.to(torch.float32) / nf.to(torch.float32), nan)
+            var_n2 = (nf * dq - d * d).clamp(min=0).to(torch.float64)
+            nd = nf.to(torch.float64)
+            self.paired_sem = torch.where(shared, (torch.sqrt(var_n2) / nd / torch.sqrt(nd)).to(torch.float32), nan)
 
 
 def _searched_games(searcher, cur, G):
@@ -236,6 +286,7 @@ class PolicySearch:
         self.copied = [torch.cuda.Event() for _ in range(2)]
         self.iterations = 0        # env steps of the last search, over all its chunks
         self.open_games = []       # the "games still running" words the host read during the last search (one per step, one step late)
+        self.round_jobs = []       # jobs played per round of the last search in rounds
 
     def _make_env(self, config):
         env = BatchedHanabiEnv(self.capacity, seed=0, eps_list=(0.0,), device=str(self.device), track_deck_history=False, **config)
@@ -350,10 +401,65 @@ class PolicySearch:
                 raise RuntimeError("replay: %d game(s) of the world env left their history; first: slot %d, code %d" % (n_err, g_err, code))
         return mismatch[:nw]
 
-    def search(self, root, hid, worlds, seed, searcher=None, log=None):
+    def _rounds(self, play, rounds, z2, min_n, scores, pairs, games, first_pair, blueprint):
+        """the round loop of search(rounds=...).  Round r plays the next rounds[r] worlds of round_world_order for every pair still
+        alive, jobs in (pair, world-order) order and chunked by capacity like the flat search; then hsad_search_round names each game's
+        leader, fills the paired tables and prunes, and `alive` comes to the host: the one synchronisation of the round.  The job lists
+        stay host-built numpy: per chunk a few thousand entries against tens of act steps.
+        -> (paired against the blueprint's action int64 [n_pair, 3] on the device, pruned_round int32 [n_pair] numpy)"""
+        cap, dev, lib, env = self.capacity, self.device, self.lib, self.env
+        n_pair, worlds = scores.shape
+        n_game = len(games)
+        order = np.asarray(round_world_order(worlds), dtype=np.int64)
+        first_d = torch.from_numpy(np.append(first_pair, n_pair).astype(np.int32)).to(dev)
+        pair_of = torch.full((int(games[-1]) + 1, env.A), -1, dtype=torch.int32, device=dev)      # (game, action) -> pair
+        pd = torch.from_numpy(pairs).to(dev)
+        pair_of[pd[:, 0], pd[:, 1]] = torch.arange(n_pair, dtype=torch.int32, device=dev)
+        games_d = torch.from_numpy(games).to(dev)
+        alive_d = torch.ones(n_pair, dtype=torch.uint8, device=dev)
+        leader = torch.zeros(n_game, dtype=torch.int32, device=dev)
+        raw = torch.zeros(n_pair, 2, dtype=torch.int64, device=dev)
+        paired_ref, paired_bp = torch.zeros(n_pair, 3, dtype=torch.int64, device=dev), torch.zeros(n_pair, 3, dtype=torch.int64, device=dev)
+        alive = np.ones(n_pair, dtype=bool)
+        pruned_round = np.full(n_pair, -1, dtype=np.int32)
+        game_of_pair = np.searchsorted(first_pair, np.arange(n_pair), side="right") - 1
+        bp_pair, off = None, 0
+        for r, n_w in enumerate(rounds):
+            ws = order[off:off + n_w]
+            off += n_w
+            # a game down to one alive pair -- necessarily the blueprint's -- has nothing left to compare
+            left = np.bincount(game_of_pair[alive], minlength=n_game)
+            ap = np.nonzero(alive & (left[game_of_pair] > 1))[0] if r else np.arange(n_pair)
+            n = len(ap) * n_w
+            self.round_jobs.append(n)
+            if n == 0:
+                break
+            # round 0 holds every pair, world 0 first: the first job of each game's first pair is where the blueprint's move is read
+            first_job = first_pair * n_w
+            for c0 in range(0, n, cap):
+                k = np.arange(c0, c0 + cap)
+                kk = np.minimum(k, n - 1)
+                here = (first_job >= c0) & (first_job < c0 + cap) if r == 0 else np.zeros(n_game, dtype=bool)
+                play(ap[kk // n_w], ws[kk % n_w], k < n, first_job - c0, here)
+            if bp_pair is None:
+                bp_a = blueprint[games_d]
+                bp_pair = torch.where(bp_a >= 0, pair_of[games_d, bp_a.clamp(min=0)], torch.full_like(leader, -1)).contiguous()
+            _lib.check(lib.hsad_search_round(scores.data_ptr(), n_pair, worlds, first_d.data_ptr(), n_game, bp_pair.data_ptr(), z2[0], z2[1],
+                                             int(min_n), alive_d.data_ptr(), leader.data_ptr(), raw.data_ptr(), paired_ref.data_ptr(),
+                                             paired_bp.data_ptr(), env._stream()))
+            now = alive_d.cpu().numpy() != 0
+            pruned_round[alive & ~now] = r
+            alive = now
+        return paired_bp, pruned_round
+
+    def search(self, root, hid, worlds, seed, searcher=None, log=None, rounds=None, prune_z=2.0, min_n=2):
         """-> SearchValues for the root env's games; root and hid ({"h0", "c0"}: [L, root.G * root.P, H], the agent's state entering
-        the root step) are only read.  log: the root's GameLog (replay=True).  See policy_action_values."""
+        the root step) are only read.  log: the root's GameLog (replay=True).  rounds: None, or world counts per round (their sum is
+        `worlds`) for the search in rounds with pruning at prune_z paired standard errors.  See policy_action_values."""
         from .eval import _drain_errors
+        z2 = None
+        if rounds is not None:
+            rounds, *z2 = _check_rounds(rounds, worlds, prune_z, min_n)
         G, P, A, cap = root.G, root.P, root.A, self.capacity
         dev, env, lib = self.device, self.env, self.lib
         if (P, A) != (env.P, env.A):
@@ -362,14 +468,20 @@ class PolicySearch:
         if tuple(h_src.shape) != (self.h.shape[0], G * P, self.h.shape[2]) or h_src.shape != c_src.shape:
             raise ValueError("hid must hold h0 / c0 of shape [%d, %d, %d]; got %s" % (self.h.shape[0], G * P, self.h.shape[2], tuple(h_src.shape)))
         h_src, c_src = h_src.contiguous(), c_src.contiguous()
-        self.iterations, self.open_games = 0, []
+        self.iterations, self.open_games, self.round_jobs = 0, [], []
         totals = torch.zeros(G, A, 3, dtype=torch.int64, device=dev)
         blueprint = torch.full((G,), -1, dtype=torch.int64, device=dev)
         pairs, cur = search_jobs(root)
         if len(pairs):
             pairs = pairs[_searched_games(searcher, cur, G)[pairs[:, 0]]]
         if len(pairs) == 0 or worlds < 1:
-            return SearchValues(totals, blueprint, torch.zeros(G, max(worlds, 0), dtype=torch.int32, device=dev) if self.replay else None)
+            extra = {}
+            if rounds is not None:
+                extra = dict(paired=torch.zeros(G, A, 3, dtype=torch.int64, device=dev),
+                             pruned_round=torch.full((G, A), -1, dtype=torch.int32, device=dev),
+                             world_scores=torch.full((G, A, worlds), 0xFF, dtype=torch.uint8, device=dev))
+            return SearchValues(totals, blueprint, torch.zeros(G, max(worlds, 0), dtype=torch.int32, device=dev) if self.replay else None,
+                                **extra)
         n_job = len(pairs)
         n = n_job * worlds                                   # jobs in (game, action, world) order; job k works for pair k // worlds
         games, first_pair = np.unique(pairs[:, 0], return_index=True)
@@ -389,11 +501,11 @@ class PolicySearch:
                 keep = torch.where(keep.any(dim=1, keepdim=True), keep, torch.ones_like(keep))
             game_pos = np.zeros(G, dtype=np.int64)
             game_pos[games] = np.arange(len(games))
-        for c0 in range(0, n, cap):
-            k = np.arange(c0, c0 + cap)
-            valid = k < n
-            kk = np.minimum(k, n - 1)
-            pj, w_c = kk // worlds, kk % worlds
+        scores = None if rounds is None else torch.full((n_job, worlds), 0xFF, dtype=torch.uint8, device=dev)
+
+        def play(pj, w_c, valid, bp_slot, here):
+            """one chunk: slot i plays world w_c[i] of pair pj[i] where valid[i]; bp_slot[here] are the slots whose first act is the
+            blueprint's own move of the games games[here]"""
             g_c, a_c = pairs[pj, 0], pairs[pj, 1]
             src = torch.from_numpy(np.where(valid, g_c, -1).astype(np.int32)).to(dev)      # spare slots: no fork, no job
             seeds = torch.from_numpy(seed_of[g_c, w_c]).to(dev)
@@ -420,22 +532,41 @@ class PolicySearch:
                 if keep is not None:
                     kept = keep[torch.from_numpy(game_pos[g_c]).to(dev), torch.from_numpy(w_c).to(dev)]
                     job = torch.where(kept, job, torch.full_like(job, -1))
-            here = (first_job >= c0) & (first_job < c0 + cap)
             bp_rows = None
             if here.any():
-                bp_rows = torch.from_numpy((first_job[here] - c0) * P + cur[games[here]]).to(dev)
+                bp_rows = torch.from_numpy(bp_slot[here] * P + cur[games[here]]).to(dev)
             bp = self._play_chunk(player, override, bp_rows)
             if bp is not None:
                 blueprint[torch.from_numpy(games[here]).to(dev)] = bp
             _lib.check(lib.hsad_search_job_stats(env.h, job.data_ptr(), n_job, stats.data_ptr(), env._stream()))
+            if scores is not None:
+                world_d = torch.from_numpy(w_c.astype(np.int32)).to(dev)
+                _lib.check(lib.hsad_search_world_scores(env.h, job.data_ptr(), world_d.data_ptr(), n_job, worlds, scores.data_ptr(),
+                                                        env._stream()))
+
+        if rounds is None:
+            for c0 in range(0, n, cap):
+                k = np.arange(c0, c0 + cap)
+                kk = np.minimum(k, n - 1)
+                play(kk // worlds, kk % worlds, k < n, first_job - c0, (first_job >= c0) & (first_job < c0 + cap))
+        else:
+            extra = self._rounds(play, rounds, z2, min_n, scores, pairs, games, first_pair, blueprint)
         _drain_errors(env)        # finished games were handed the noop: the "step on a finished game" notes
         pd = torch.from_numpy(pairs).to(dev)
         totals[pd[:, 0], pd[:, 1]] = stats
-        return SearchValues(totals, blueprint, mismatch)
+        if rounds is None:
+            return SearchValues(totals, blueprint, mismatch)
+        paired = torch.zeros(G, A, 3, dtype=torch.int64, device=dev)
+        pruned = torch.full((G, A), -1, dtype=torch.int32, device=dev)
+        table = torch.full((G, A, worlds), 0xFF, dtype=torch.uint8, device=dev)
+        paired[pd[:, 0], pd[:, 1]] = extra[0]
+        pruned[pd[:, 0], pd[:, 1]] = torch.from_numpy(extra[1]).to(dev)
+        table[pd[:, 0], pd[:, 1]] = scores
+        return SearchValues(totals, blueprint, mismatch, paired=paired, pruned_round=pruned, world_scores=table)
 
 
 def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_steps=200, searcher=None, replay=False, log=None,
-                         consistent_only=False, sampler="rejection"):
+                         consistent_only=False, sampler="rejection", rounds=None, prune_z=2.0, min_n=2):
     """SearchValues: values[g, a] = mean final score (HSAD_Q_SCORE) over `worlds` sampled worlds when the player on turn of root game
     g plays a and EVERY player, the searcher included, then follows the blueprint `agent` greedily to the end of the game.
 
@@ -470,10 +601,22 @@ def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_step
     replay costs one act + step per logged move on all searched games x worlds slots.
 
     sampler="stratified": the hands come from determinize_exact(stratum = world, n_strata = worlds) wherever determinize is named
-    above, the world envs of the replay included (see mc_action_values)."""
+    above, the world envs of the replay included (see mc_action_values).
+
+    rounds=(n0, n1, ...) (positive, summing to `worlds` <= 4,096; None = the flat search above, untouched): the worlds are played in
+    rounds and actions that are already hopeless are dropped in between.  A game's worlds are taken in round_world_order; round r
+    plays its next rounds[r] worlds for every action still alive (jobs in (action, world-order) order, chunked as above -- a (game,
+    action, world) job is the very job of the flat search: same stratum, seed and key, whenever it runs).  Each chunk also stores its
+    scores per world (hsad_search_world_scores), and after each round hsad_search_round picks the game's leader (largest raw mean
+    among the alive actions, exact, lowest action on ties), sums d = score - leader's score world by world and drops an action iff it
+    was played in >= min_n shared worlds and its paired mean lies more than prune_z paired standard errors below zero (prune_z^2 as
+    Fraction(z * z).limit_denominator(1024), numerator <= 16,384; equality keeps the action).  The leader and the blueprint's own
+    action are never dropped; a game down to one action plays no more.  The host reads `alive` once per round.  The replay stage is
+    not split: it replays all worlds up front.  SearchValues then carries paired / paired_mean / paired_sem (against the blueprint's
+    action), pruned_round and world_scores; totals / values count the worlds each action was played in."""
     ps = PolicySearch(root, agent, capacity, max_steps, replay=replay, consistent_only=consistent_only, sampler=sampler)
     try:
-        return ps.search(root, hid, worlds, seed, searcher, log=log)
+        return ps.search(root, hid, worlds, seed, searcher, log=log, rounds=rounds, prune_z=prune_z, min_n=min_n)
     finally:
         ps.close()
 
@@ -488,6 +631,23 @@ def choose_action(values, blueprint_a, threshold=0.05):
     v_best = filled.gather(1, best.unsqueeze(1)).squeeze(1)
     v_bp = filled.gather(1, bp.clamp(min=0).unsqueeze(1)).squeeze(1)
     deviate = (v_best - v_bp) > threshold            # NaN (nothing to compare) is False
+    return torch.where(bp < 0, torch.full_like(bp, -1), torch.where(deviate, best, bp))
+
+
+def choose_action_paired(sv, threshold=0.05, z=0.0):
+    """int64 [G] from the SearchValues of a search in rounds: among the actions never pruned -- all played in the same worlds -- the
+    one with the largest paired_mean (the mean gain over the blueprint's action, world by world; lowest uid on ties), where that mean
+    is > threshold and > z * its paired_sem; else blueprint_a.  -1 where blueprint_a is -1.  Pure tensor code (CPU tensors work)."""
+    if sv.paired is None:
+        raise ValueError("choose_action_paired needs the SearchValues of a search in rounds (search(rounds=...))")
+    pm, ps = sv.paired_mean, sv.paired_sem
+    bp = torch.as_tensor(sv.blueprint_a).to(torch.int64)
+    out = torch.isnan(pm) | (torch.as_tensor(sv.pruned_round) >= 0)
+    filled = torch.where(out, torch.full_like(pm, -float("inf")), pm)
+    best = filled.argmax(dim=1)
+    m_best = filled.gather(1, best.unsqueeze(1)).squeeze(1)
+    s_best = torch.nan_to_num(ps.gather(1, best.unsqueeze(1)).squeeze(1), nan=0.0)
+    deviate = (m_best > threshold) & (m_best > z * s_best)     # -inf (no candidate) is False
     return torch.where(bp < 0, torch.full_like(bp, -1), torch.where(deviate, best, bp))
 
 
@@ -512,7 +672,8 @@ class SearchPlay:
 
 def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05, search_seed=0, searcher="all", capacity=4096,
                      num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16", shuffle_color=False, colors=5, ranks=5,
-                     max_information_tokens=8, max_life_tokens=3, replay_history=False, consistent_only=False, sampler="rejection"):
+                     max_information_tokens=8, max_life_tokens=3, replay_history=False, consistent_only=False, sampler="rejection",
+                     rounds=None, prune_z=2.0, deviate_z=0.0):
     """eval.evaluate's lock-step loop over the deals seed .. seed + num_game - 1 with search on top of the blueprint -> SearchPlay.
     Before each step: PolicySearch values for the games whose player on turn searches (searcher: "all" or a seat number),
     choose_action, then the root steps with a = the chosen action and greedy_a = the blueprint's greedy action; the carried state
@@ -520,8 +681,12 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
     exactly.  worlds = 0 takes no search path at all and returns evaluate's scores.  The search env has min(capacity, num_game x
     (A - 1) x worlds) slots -- the most jobs a move can have -- and capacity x P decides the acting regime (policy_action_values).
     replay_history=True: the root tracks its deck history, a GameLog keeps the rows it was stepped with and the search rebuilds
-    every world's LSTM states by replay (PolicySearch(replay=True)); consistent_only and sampler as there."""
+    every world's LSTM states by replay (PolicySearch(replay=True)); consistent_only and sampler as there.
+    rounds=(n0, n1, ...): every search runs in rounds with pruning at prune_z (policy_action_values) and the move is
+    choose_action_paired(sv, threshold, deviate_z) instead of choose_action."""
     _check_sampler(sampler)
+    if rounds is not None and worlds > 0:
+        _check_rounds(rounds, worlds, prune_z, 2)
     from .eval import _acting_agent, _drain_errors
     agent = _acting_agent(agent, precision, device)
     env = BatchedHanabiEnv(num_game, players=num_player, hand_size=hand_size, seed=seed, bomb=bomb, eps_list=[0.0], max_len=-1, sad=bool(sad),
@@ -554,13 +719,18 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
                 a = torch.where(live, a.view(num_game, num_player), torch.full_like(a.view(num_game, num_player), noop)).contiguous()
                 env.step(a, a)
             else:
-                sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat, log=log)
+                sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat, log=log, rounds=rounds, prune_z=prune_z)
                 player = q[:, Q_CUR_PLAYER].contiguous()
                 # the blueprint's move is the root act's own greedy action (the search's first act gives the same one while both
                 # run in one acting regime; this one holds in any)
                 own = g.view(num_game, num_player).gather(1, player.to(torch.int64).clamp(0, num_player - 1).unsqueeze(1)).squeeze(1)
                 blueprint = torch.where(sv.blueprint_a >= 0, own, sv.blueprint_a)
-                chosen = choose_action(sv.values, blueprint, threshold).contiguous()
+                if rounds is None:
+                    chosen = choose_action(sv.values, blueprint, threshold)
+                else:       # the paired statistics are against the search's blueprint_a: "no deviation" is the root act's own move
+                    chosen = choose_action_paired(sv, threshold, deviate_z)
+                    chosen = torch.where(chosen == sv.blueprint_a, blueprint, chosen)
+                chosen = chosen.contiguous()
                 _lib.check(env.lib.hsad_search_actions(env.h, a.data_ptr(), g.data_ptr(), player.data_ptr(), chosen.data_ptr(),
                                                        env.a.data_ptr(), env.greedy_a.data_ptr(), env._stream()))
                 if log is not None:

@@ -1178,6 +1178,38 @@ int hsad_search_actions(const hsad_env* env, const int64_t* a_src, const int64_t
  * Integer atomics: exact, order-free.  The "games still running" word of the host loop is hsad_seating_stats(env, G, ...)'s. */
 int hsad_search_job_stats(const hsad_env* env, const int32_t* job, int n_job, int64_t* stats, void* stream);
 
+/* ---- round-wise search (PolicySearch.search(rounds = ...)): the per-world scores are kept, so that actions can be compared world
+ * by world (common random numbers: every action of a game meets the same worlds) and hopeless ones dropped between rounds. ---- */
+/* The finished slots' scores, one byte each.  pair / world device int32 [G]: the (root game, action) pair and the world slot g
+ * played.  For every finished game (started and terminated) with pair[g] in [0, n_pair) and world[g] in [0, worlds):
+ * scores[pair[g] * worlds + world[g]] = the score hsad_search_job_stats sums, 0..25.  scores device uint8 [n_pair, worlds]; the
+ * caller fills it with 0xFF ("not evaluated") once per search.  Every other slot stores nothing.  Plain byte stores, no atomics: a
+ * (pair, world) is played at most once, and two slots of one call that named the same entry would race.
+ * HSAD_ERR_INVALID: n_pair < 1, worlds < 1, a null argument. */
+int hsad_search_world_scores(const hsad_env* env, const int32_t* pair, const int32_t* world, int n_pair, int worlds, uint8_t* scores,
+                             void* stream);
+/* One round's decision on the score table of hsad_search_world_scores.  Searched game k (one workgroup each) owns the pairs
+ * first_pair[k] .. first_pair[k + 1] - 1 (device int32 [n_game + 1], ascending); bp_pair[k] (device int32 [n_game]) is the pair of
+ * the blueprint's own action.  0xFF entries are absent.  All arithmetic is integer and no atomics are used: the outputs are the same
+ * bits run to run.
+ *   raw_out int64 [n_pair, 2] = (sum s, n) over the present entries of the row.
+ *   leader_out int32 [n_game] = among the pairs with alive != 0 and n > 0 the one with the largest raw mean, compared exactly
+ *     (sum_p * n_q > sum_q * n_p), ties to the lowest pair index; bp_pair[k] when there is no such pair.
+ *   paired_ref_out / paired_bp_out int64 [n_pair, 3] = (D, Q, n) = (sum d, sum d^2, count) over the worlds present in both the pair's
+ *     row and the leader's / the blueprint pair's row, d = s - s_ref.
+ *   alive device uint8 [n_pair], read and written in place: a pair that is alive, is neither the leader nor bp_pair[k], is set to 0
+ *     iff, with (D, Q, n) against the leader, n >= min_n, D < 0 and D^2 * n * z2_den > z2_num * (n * Q - D^2) -- its paired mean lies
+ *     more than z standard errors (of the paired mean, population variance) below the leader's, z^2 = z2_num / z2_den.  Equality
+ *     does not prune; z2_num = 0 prunes every negative D.
+ * Bounds that keep every product in int64 (scores <= 25): worlds <= 4096, 1 <= z2_den <= 1024, 0 <= z2_num <= 16384, so that
+ * D^2 * n * z2_den <= (25 * 2^12)^2 * 2^12 * 2^10 < 2^56.  HSAD_ERR_INVALID outside them, for min_n < 1, n_pair < 1, n_game < 1 and
+ * null arguments.  Checked on the device: a game whose pair range is empty or leaves [0, n_pair) gets leader -1 and nothing else read
+ * or written; a bp_pair[k] outside its game's range counts as "no blueprint pair": paired_bp_out is (0, 0, 0) for the game's pairs,
+ * no pair is exempt on its account and the leader's fall-back is -1. */
+int hsad_search_round(const uint8_t* scores, int n_pair, int worlds, const int32_t* first_pair, int n_game, const int32_t* bp_pair,
+                      int z2_num, int z2_den, int min_n, uint8_t* alive, int32_t* leader_out, int64_t* raw_out, int64_t* paired_ref_out,
+                      int64_t* paired_bp_out, void* stream);
+
 /* ---- replay stage of blueprint-policy search (PolicySearch(replay = True)): every sampled world is played again from its first
  * move, so that each seat's LSTM state is the one that world's observations produce. ---- */
 /* The deal script of every world slot.  world_env: a determinised fork of the root (G_w slots); src_index device int32 [G_w]: the

@@ -5,13 +5,16 @@ playouts) as the yardstick.  --replay adds the replay stage (PolicySearch(replay
 depths -- the cost grows with the move number -- and the whole search with it.  Host clock around a device synchronise, median of
 the repeats.  --sampler chooses how the worlds' hands are drawn in every search timed here (rejection: hsad_env_determinize;
 stratified: hsad_env_determinize_exact); the determinise call of both samplers and hsad_env_hand_belief are also timed alone on the
-search env.  One JSON line.
+search env.  --rounds a,b,c (summing to --worlds) adds the search in rounds on the same root in the same process: the jobs it
+played per round against pairs x worlds, its seconds per search next to the flat search's, and the time of one hsad_search_round
+call on the search's own score table.  One JSON line.
 
     python tools/policy_search_probe.py [--roots 64] [--worlds 8] [--capacity 4096] [--hid 512] [--repeats 5] [--replay]
-                                        [--sampler rejection|stratified]
+                                        [--sampler rejection|stratified] [--rounds 2,2,4] [--prune_z 2.0]
 """
 import argparse
 import json
+from fractions import Fraction
 import os
 import statistics
 import sys
@@ -47,6 +50,9 @@ def main():
     ap.add_argument("--sad", type=int, default=1)
     ap.add_argument("--replay", action="store_true", help="also time the replay stage per move depth and the search with replay")
     ap.add_argument("--sampler", choices=["rejection", "stratified"], default="rejection")
+    ap.add_argument("--rounds", type=lambda s: tuple(int(x) for x in s.split(",")), default=None,
+                    help="world counts per round (sum = --worlds): also time the search in rounds against the flat search")
+    ap.add_argument("--prune_z", type=float, default=2.0)
     args = ap.parse_args()
     from hanabi_sad_amd.composite import CNet, CompositeAgent
     from hanabi_sad_amd.eval import env_dims
@@ -89,6 +95,32 @@ def main():
     res["slot_steps_per_s"] = [s / m * 1e3 for s, m in zip(steps, ms)]
     res["live_env_steps_per_s"] = [s / m * 1e3 for s, m in zip(live_steps, ms)]
     res["live_fraction_per_iteration"] = live
+    if args.rounds is not None:
+        rkw = dict(rounds=args.rounds, prune_z=args.prune_z)
+        sv = ps.search(root, hid, args.worlds, 0, **rkw)            # warm-up
+        rms, rjobs = [], []
+        for r in range(args.repeats):                               # the seeds of the flat searches timed above
+            rms += timed(lambda: ps.search(root, hid, args.worlds, 1 + r, **rkw), 1)
+            rjobs.append(list(ps.round_jobs))
+        res["rounds"], res["prune_z"], res["rounds_flat_jobs"] = list(args.rounds), args.prune_z, jobs
+        res["rounds_jobs"], res["rounds_jobs_total"] = rjobs, [sum(j) for j in rjobs]
+        res["rounds_search_ms"], res["rounds_search_ms_median"] = rms, statistics.median(rms)
+        # one hsad_search_round call on the last search's table: every (game, action) a pair, illegal actions all-absent rows
+        A_ = root.A
+        table = sv.world_scores.reshape(G * A_, args.worlds).contiguous()
+        first = (torch.arange(G + 1, device=dev) * A_).to(torch.int32)
+        bp_pair = (torch.arange(G, device=dev) * A_ + sv.blueprint_a.clamp(min=0)).to(torch.int32)
+        alive = torch.ones(G * A_, dtype=torch.uint8, device=dev)
+        leader = torch.zeros(G, dtype=torch.int32, device=dev)
+        raw = torch.zeros(G * A_, 2, dtype=torch.int64, device=dev)
+        pr, pb = torch.zeros(G * A_, 3, dtype=torch.int64, device=dev), torch.zeros(G * A_, 3, dtype=torch.int64, device=dev)
+        z2 = Fraction(args.prune_z * args.prune_z).limit_denominator(1024)
+        call = lambda: _lib.check(ps.lib.hsad_search_round(table.data_ptr(), G * A_, args.worlds, first.data_ptr(), G, bp_pair.data_ptr(),
+                                                           z2.numerator, z2.denominator, 2, alive.data_ptr(), leader.data_ptr(), raw.data_ptr(),
+                                                           pr.data_ptr(), pb.data_ptr(), ps.env._stream()))
+        call()
+        res["round_kernel_ms"] = timed(call, args.repeats)
+        res["round_kernel_ms_median"] = statistics.median(res["round_kernel_ms"])
     res["mc_action_values_ms"] = timed(lambda: mc_action_values(root, args.worlds, 3, capacity=args.capacity, sampler=args.sampler), args.repeats)
     # the three glue kernels alone, on the search env as the last chunk left it
     env, lib, st = ps.env, ps.lib, ps.env._stream()

@@ -125,6 +125,7 @@ SIGNATURES = {
     "hsad_env_debug_timing": (C.c_int, [_P, _P]),
     "hsad_env_debug_trace": (C.c_int, [_P, _P, C.c_int]),
     "hsad_env_rollout_lds_bytes": (C.c_int64, [_P]),
+    "hsad_env_rollout_resident_workgroups": (C.c_int, [_P]),
     "hsad_env_error_count": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hsad_env_fork": (C.c_int, [_P, _P, _P, _P, _P]),
     "hsad_env_determinize": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),

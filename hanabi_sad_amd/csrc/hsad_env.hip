@@ -852,7 +852,7 @@ __device__ __forceinline__ uint64_t legal_mask_of(int P, int H, int A, const uin
 template <int TP, int TH, bool V = false>
 __device__ __forceinline__ void build_rows(const EnvParams& ep, const uint32_t* s_st, int lane, int g, uint32_t* s_obs,
                                            uint32_t* s_legal, uint32_t* s_own, uint32_t greedy_rec, int p_begin,
-                                           int p_step) {
+                                           int p_step, uint32_t* s_lmask = nullptr) {
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
   const auto ru = RulesOf<V>::make(ep);
   const uint32_t CR = (uint32_t)ru.CR, RR = (uint32_t)ru.R;
@@ -928,6 +928,10 @@ __device__ __forceinline__ void build_rows(const EnvParams& ep, const uint32_t* 
     or_bits64(s_legal, (uint32_t)(lane * P + p) * (uint32_t)ep.A, lm);
     ep.legal_bits[(size_t)g * P + p] = lm;
     if (ep.legal_out) ep.legal_out[(size_t)g * P + p] = lm;
+    if (s_lmask) {   // env_rollout_pipe_kernel: where the logic wave's policy reads it in the next iteration (LogicCarry)
+      s_lmask[(2 * p) * kWave + lane] = (uint32_t)lm;
+      s_lmask[(2 * p + 1) * kWave + lane] = (uint32_t)(lm >> 32);
+    }
 
     // own hand trinary [playable, discardable, other] (EncodeOwnHandTrinary)
     {
@@ -1099,13 +1103,28 @@ __device__ __forceinline__ void clear_rows(const EnvParams& ep, uint32_t* s_obs,
   for (int k = (nz & ~3) + t; k < nz; k += n) s_obs[k] = 0u;
 }
 
+// What env_rollout_pipe_kernel holds on to from one iteration of a launch to the next instead of going through global memory for
+// it (env_logic<..., CARRY = true>; every other caller passes none and compiles the statements it always had: counter and masks
+// are read from, and the counter written to, global memory every time).
+//   counter: this lane's act counter (EnvParams::act_count), loaded in the launch's prologue and stored after its last iteration.
+//   s_lmask: the legal masks build_rows left in LDS in phase B of the previous iteration, mask of (lane, p) as two words at
+//            [(2p) * kWave + lane] and [(2p + 1) * kWave + lane] of the lane's own column of the mt19937 prefetch window.  A lane
+//            uses that column only in an iteration in which its game restarts, and then recomputes its masks from the fresh state,
+//            so the two never meet; the words cost no LDS.  The launch's prologue fills them from EnvParams::legal_bits: nothing is
+//            assumed about what ran before the launch.  (Every window holds 2PH + P + 2 words or more per lane, hsad_env_create.)
+struct LogicCarry {
+  uint32_t* counter;
+  const uint32_t* s_lmask;
+};
+typedef __attribute__((address_space(3))) const uint32_t* LdsWordPtr;   // a load through it is an LDS instruction, never a flat one
+
 // The game logic of one iteration for the 64 games of the logic wave (wave 0): reset-if-terminated (MODE 0 / 3), then the
 // policy (MODE 2 / 3) or the given actions (MODE 1) and the env step, all on the state planes staged in s_st.
-template <int MODE, int TP, int TH, bool V = false, class EP = EnvParams>
+template <int MODE, int TP, int TH, bool V = false, class EP = EnvParams, bool CARRY = false>
 __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
                                           uint32_t* s_st, uint32_t* s_win, const float* s_eps, const int lane, const int g,
                                           const bool active, const bool do_reset, Rng& rng, uint32_t& greedy_rec, float& reward,
-                                          bool& term, const int dbg_it = 0) {
+                                          bool& term, const int dbg_it = 0, const LogicCarry carry = {nullptr, nullptr}) {
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
   const auto ru = RulesOf<V>::make(ep);
   if (MODE == 0 || MODE == 3) {
@@ -1195,7 +1214,18 @@ __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restric
       STAMP(7);
       for (int p = 0; p < P; ++p) {
         const uint32_t r = rng_next(rng) % (uint32_t)ep.n_eps;
-        ST(PLEPS(p)) = __float_as_uint(r < 128u ? s_eps[r] : ep.eps_list[r]);
+        // (CARRY: the staged list through an LDS pointer and the rest behind a branch; the select of the two addresses is a
+        // flat load, which is waited for on the vector-memory counter as well, i.e. behind the wave's stores)
+        if (!CARRY) {
+          ST(PLEPS(p)) = __float_as_uint(r < 128u ? s_eps[r] : ep.eps_list[r]);
+        } else {
+          uint32_t e;
+          if (r < 128u)
+            e = ((LdsWordPtr)reinterpret_cast<const uint32_t*>(s_eps))[r];
+          else
+            e = __float_as_uint(ep.eps_list[r]);
+          ST(PLEPS(p)) = e;
+        }
       }
       if (ep.shuffle_color) {
         const int fix = (int)(rng_next(rng) % (uint32_t)P);
@@ -1258,15 +1288,31 @@ __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restric
       } else {
         int uid, guid = 0;
         if (MODE >= 2) {
-          const uint32_t counter = ep.act_count[g];
-          ep.act_count[g] = counter + 1u;
+          uint32_t counter;
+          if (CARRY) {
+            counter = *carry.counter;
+            *carry.counter = counter + 1u;
+          } else {
+            counter = ep.act_count[g];
+            ep.act_count[g] = counter + 1u;
+          }
           uid = guid = 0;
           for (int p = 0; p < P; ++p) {
-            // legal bits of the state the policy acts on: the stored side output, or (MODE 3, game restarted a
-            // moment ago in this very launch) recomputed from the fresh state
-            const uint64_t mask = do_reset ? legal_mask_of<TH>(P, H, ep.A, s_st, lane, p,
-                                                               ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru)
-                                           : ep.legal_bits[(size_t)g * P + p];
+            // legal bits of the state the policy acts on: the stored side output (global memory, or the copy build_rows left
+            // in LDS: LogicCarry), or (MODE 3, game restarted a moment ago in this very launch) recomputed from the fresh state
+            uint64_t mask;
+            if (CARRY) {   // (a compile-time choice: chosen at run time, the global load and its vmcnt(0) at the join stay in the loop)
+              if (do_reset) {
+                mask = legal_mask_of<TH>(P, H, ep.A, s_st, lane, p, ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru);
+              } else {
+                const LdsWordPtr lm = (LdsWordPtr)carry.s_lmask;
+                mask = (uint64_t)lm[(2 * p) * kWave + lane] | ((uint64_t)lm[(2 * p + 1) * kWave + lane] << 32);
+              }
+            } else {
+              mask = do_reset ? legal_mask_of<TH>(P, H, ep.A, s_st, lane, p,
+                                                  ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru)
+                              : ep.legal_bits[(size_t)g * P + p];
+            }
             const int pa = policy_pick(ep.policy_seed, (uint64_t)g, (uint64_t)counter, p, 0, mask);
             const int pg = policy_pick(ep.policy_seed, (uint64_t)g, (uint64_t)counter, p, 1, mask);
             ep.a_out[(size_t)g * P + p] = pa;
@@ -1681,9 +1727,18 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
   if (ng <= 0) return;
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
 
-  // prologue: the logic wave stages the state planes, the stream wave clears the rows and copies the eps list
+  // prologue: the logic wave stages the state planes and its act counters, the stream wave clears the rows and copies the eps list
+  uint32_t act_counter = 0u;   // this lane's EnvParams::act_count, carried in a register for the launch (LogicCarry)
   if (wave == 0) {
     const int g = g0 + lane;
+    if (lane < ng) {
+      act_counter = ep.act_count[g];
+      for (int p = 0; p < P; ++p) {   // the masks the previous launch, step or reset left: where build_rows leaves them from now on
+        const uint64_t lm = ep.legal_bits[(size_t)g * P + p];
+        s_win[(2 * p) * kWave + lane] = (uint32_t)lm;
+        s_win[(2 * p + 1) * kWave + lane] = (uint32_t)(lm >> 32);
+      }
+    }
     for (int pl0 = 0; pl0 < ep.npl; pl0 += 8) {
       uint32_t v[8];
 #pragma unroll
@@ -1731,7 +1786,9 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       rng.la_n = (int)((misc0 >> 22) & 3u);
       rng.spos = (rng.draws + (uint32_t)rng.la_n) % (uint32_t)kMtN;
       uint32_t greedy_rec = 0;
-      env_logic<3, TP, TH>(ep, nullptr, nullptr, s_st, s_win, s_eps, lane, g, valid, do_reset, rng, greedy_rec, reward, term, dbg_it);
+      const LogicCarry carry = {&act_counter, s_win};
+      env_logic<3, TP, TH, false, EnvParams, true>(ep, nullptr, nullptr, s_st, s_win, s_eps, lane, g, valid, do_reset, rng, greedy_rec, reward,
+                                                   term, dbg_it, carry);
       s_grec[lane] = greedy_rec;
       STAMP(11);
     } else if (iter > 0) {
@@ -1761,7 +1818,7 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     // ---- phase B: both waves build the rows of `iter`; wave 0 finishes the look-ahead refill and writes the scalars ----
     Refill rf;
     refill_issue(rf, rng, valid && wave == 0);
-    if (valid) build_rows<TP, TH>(ep, s_st, lane, g, (iter & 1) ? S_OBS1(zero) : s_obs, s_legal, s_own, s_grec[lane], wave, 2);
+    if (valid) build_rows<TP, TH>(ep, s_st, lane, g, (iter & 1) ? S_OBS1(zero) : s_obs, s_legal, s_own, s_grec[lane], wave, 2, s_win);
     STAMP(3);
     if (valid && wave == 0) {
       refill_finish(rf, rng);
@@ -1772,8 +1829,10 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       for (int p = 0; p < P; ++p) ep.eps[(size_t)g * P + p] = __uint_as_float(ST(PLEPS(p)));
       ep.reward[g] = reward;
       ep.terminal[g] = term ? 1 : 0;
-      if (iter == ep.n_iter - 1)
+      if (iter == ep.n_iter - 1) {
         for (int pl = 0; pl < ep.npl; ++pl) ep.planes[(size_t)pl * ep.Gpad + g] = ST(pl);
+        ep.act_count[g] = act_counter;
+      }
       if (ep.pace && lane == 0) {   // the delay of the stream of these rows (phase A of iter + 1), read after the barrier below
         const unsigned d = iter > 0 ? pace_delay(ep, pace_s, iter, pace_t_own) : 0u;
         s_pace[0] = d;
@@ -2666,6 +2725,14 @@ int hsad_env_debug_trace(hsad_env* e, uint64_t* buf, int n_iters) {
 
 int64_t hsad_env_rollout_lds_bytes(const hsad_env* e) {
   return e ? (int64_t)(rollout_delta_active(e) ? e->lds_bytes_delta : e->lds_bytes_reset) : 0;
+}
+
+int hsad_env_rollout_resident_workgroups(const hsad_env* e) {
+  if (!e) return 0;
+  const void* fn = reinterpret_cast<const void*>(pick_rollout_kernel(e->ep.P, e->ep.H, rollout_pipelined(e), e->ep.variant != 0));
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, e->ep.nthreads, (size_t)hsad_env_rollout_lds_bytes(e)) != hipSuccess) return -1;
+  return n;
 }
 
 int hsad_env_error_count(hsad_env* e, int32_t* count, int32_t* first_game, int32_t* first_code) {

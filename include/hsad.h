@@ -224,6 +224,9 @@ int hsad_env_debug_trace(hsad_env* env, uint64_t* buf, int n_iters);
 /* Dynamic LDS bytes per workgroup of the reset / rollout kernels (what a persistent rollout launch requests: with the second copy
  * of the observation rows while hsad_env_rollout_delta_active). */
 int64_t hsad_env_rollout_lds_bytes(const hsad_env* env);
+/* Workgroups of the persistent rollout kernel this env launches (pipelined or single-phase, its workgroup size, the LDS bytes
+ * above) that one CU holds at a time: hipOccupancyMaxActiveBlocksPerMultiprocessor.  -1 if the query fails. */
+int hsad_env_rollout_resident_workgroups(const hsad_env* env);
 
 /* Number of games that hit an API-contract error (illegal move, step on a finished game) since
  * the last call; synchronises the device.  first_game/first_code (may be NULL) describe the first.

@@ -114,6 +114,8 @@ SIGNATURES = {
     "hsad_env_rollout_pace_cap_us": (C.c_int, [_P]),
     "hsad_env_set_rollout_delta": (C.c_int, [_P, C.c_int]),
     "hsad_env_rollout_delta_active": (C.c_int, [_P]),
+    "hsad_env_set_rollout_compact": (C.c_int, [_P, C.c_int]),
+    "hsad_env_rollout_compact_active": (C.c_int, [_P]),
     "hsad_env_debug_pace_bias": (C.c_int, [_P, C.c_int64]),
     "hsad_env_debug_pace_word": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hsad_env_last_rollout_ms": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),

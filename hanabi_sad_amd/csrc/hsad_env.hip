@@ -76,6 +76,7 @@ struct EnvParams {
   int n_iter;       // MODE 3: iterations this launch runs for its games (persistent rollout; 1 otherwise)
   int delta;        // env_rollout_pipe_kernel: two copies of the observation bit rows in LDS; every stream of the launch but the first
                     // stores only the lines of priv_s whose bits changed since the stream before (rollout_delta_active)
+  int compact;      // with delta: the stream wave lists the changed lines first and stores from the list (stream_bits_f32_compact)
   int stagger_ticks;  // MODE 3, n_iter > 1: workgroup b starts (b % 8) * stagger_ticks (100 MHz) late, see env_kernel
   int stagger_mode;   // which workgroups start late (developer switch HSAD_ENV_STAGGER_MODE, see env_rollout_kernel)
   int64_t* a_out;                  // MODE 2: where the sampled actions are recorded ([G,P] each)
@@ -776,6 +777,95 @@ __device__ __forceinline__ unsigned stream_bits_f32_delta(const uint32_t* bits, 
   return stored;
 }
 
+// The compacted form of the same (EnvParams::compact), for one wave and a stream that is not an `all` stream: first a scan that
+// lists the changed words, then a store loop over the list only, eight whole lines per wave-store, without a predicate and with
+// several groups of LDS reads in flight.  Stores exactly the lines the direct form stores.  Returns the number of lines stored in
+// lane 0 and 0 in every other lane (the direct form's per-lane counts sum to the same).
+//
+// The list costs no LDS: entry r (a word index, 32 bits) is written in place to list[r], where list is `old` itself.  Invariant:
+// scan step s reads positions [64s, 64s + 64) and lane l's entry goes to position base_s + rank <= 64s + l, base_s being the
+// number of changed words before step s and rank the number of changed lanes below l.  So a write of step s lands only on a
+// position that step s or an earlier one has read, and every later step reads only positions >= 64(s + 1): no read of `old` ever
+// sees a list entry.  Within a step the compare -> ballot -> rank dependence puts the step's reads before its writes.  The scan
+// below takes kScanSteps steps' reads together ahead of their writes, which keeps the invariant: those writes land below
+// 64(s + kScanSteps) at most, all read by then.  A partial last word (n / 4 not a multiple of 8) is not listed: its position is
+// beyond every entry, and the lanes of its chunks store it in the direct form.  The caller clears `old`, list included, afterwards.
+constexpr int kScanSteps = 4;    // scan steps whose LDS reads are issued together
+constexpr int kStoreGroups = 4;  // store groups (eight lines each) whose LDS reads are issued together
+
+template <bool NT>
+__device__ __forceinline__ void store_chunk(float4* p, const float4 v) {
+  if (NT) {
+    typedef float nt_f4 __attribute__((ext_vector_type(4)));
+    nt_f4 q = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(q, reinterpret_cast<nt_f4*>(p));
+  } else {
+    *p = v;
+  }
+}
+
+template <bool NT>
+__device__ __forceinline__ unsigned stream_bits_f32_compact(const uint32_t* bits, uint32_t* list, float* out, uint32_t n, int lane) {
+  float4* o4 = reinterpret_cast<float4*>(out);
+  const uint32_t nch = n >> 2;
+  const uint32_t nfull = nch >> 3;   // words that own eight chunks
+  // scan: count is wave-uniform
+  uint32_t count = 0;
+  for (uint32_t w0 = 0; w0 < nfull; w0 += 64u * kScanSteps) {
+    uint32_t b[kScanSteps], o[kScanSteps];
+#pragma unroll
+    for (int u = 0; u < kScanSteps; ++u) {
+      const uint32_t w = min(w0 + 64u * u + (uint32_t)lane, nfull - 1u);
+      b[u] = bits[w];
+      o[u] = list[w];
+    }
+#pragma unroll
+    for (int u = 0; u < kScanSteps; ++u) {
+      const uint32_t w = w0 + 64u * u + (uint32_t)lane;
+      const bool changed = w < nfull && b[u] != o[u];
+      const unsigned long long m = __ballot(changed);
+      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      if (changed) list[count + rank] = w;
+      count += (uint32_t)__popcll(m);
+    }
+  }
+  // the partial last word, read before anything else is done (no entry reaches its position)
+  const uint32_t kp = 8u * nfull + (uint32_t)lane;
+  const bool part = kp < nch;   // lanes 0 .. (nch & 7) - 1
+  uint32_t wp = 0u;
+  bool part_changed = false;
+  if (part) {
+    wp = bits[nfull];
+    part_changed = wp != list[nfull];
+  }
+  // store: lane l serves entry 8j + (l >> 3) of group j, chunk l & 7 of its line
+  const uint32_t sub = (uint32_t)lane >> 3, c = (uint32_t)lane & 7u;
+  uint32_t e0 = 0;
+  for (; e0 + 8u * kStoreGroups <= count; e0 += 8u * kStoreGroups) {
+    uint32_t idx[kStoreGroups], word[kStoreGroups];
+#pragma unroll
+    for (int u = 0; u < kStoreGroups; ++u) idx[u] = list[e0 + 8u * u + sub];
+#pragma unroll
+    for (int u = 0; u < kStoreGroups; ++u) word[u] = bits[idx[u]];
+#pragma unroll
+    for (int u = 0; u < kStoreGroups; ++u) store_chunk<NT>(o4 + 8u * idx[u] + c, nib_to_f4((word[u] >> (4u * c)) & 15u));
+  }
+  if (e0 < count) {   // the last, partial block of groups: the lanes of entries >= count are off
+    uint32_t idx[kStoreGroups], word[kStoreGroups];
+#pragma unroll
+    for (int u = 0; u < kStoreGroups; ++u) idx[u] = list[min(e0 + 8u * u + sub, count - 1u)];
+#pragma unroll
+    for (int u = 0; u < kStoreGroups; ++u) word[u] = bits[idx[u]];
+#pragma unroll
+    for (int u = 0; u < kStoreGroups; ++u)
+      if (e0 + 8u * u + sub < count) store_chunk<NT>(o4 + 8u * idx[u] + c, nib_to_f4((word[u] >> (4u * c)) & 15u));
+  }
+  if (part_changed) store_chunk<NT>(o4 + kp, nib_to_f4((wp >> (4u * c)) & 15u));
+  const uint32_t done = nch << 2;
+  if ((uint32_t)lane < n - done) out[done + lane] = get1(bits, done + lane) ? 1.f : 0.f;
+  return lane == 0 ? count + (part_changed ? 1u : 0u) : 0u;
+}
+
 __device__ __forceinline__ uint32_t perm_c(uint32_t pm, int c) { return (pm >> (3 * c)) & 7u; }
 
 template <class Ru>
@@ -1069,14 +1159,22 @@ __device__ __forceinline__ void stream_rows(const EnvParams& ep, const uint32_t*
 // The same for the pipelined rollout, whose later streams of a launch reduce the float32 observation to the lines that changed
 // (EnvParams::delta).  s_old: the bit rows priv_s was last written from; all: every line (the first stream of a launch, and every
 // stream without delta).  The packed forms, legal moves and own hand go out in full from the current rows.  Returns this lane's
-// count of observation lines stored (count on: the trace).
-__device__ __forceinline__ unsigned stream_rows_delta(const EnvParams& ep, const uint32_t* s_obs, const uint32_t* s_old, bool all,
+// count of observation lines stored (count on: the trace).  compact: one wave streams (t its lane, n == kWave) and takes the
+// compacted form where the stream is not an `all` stream; that form writes its list of changed lines into s_old, which the caller
+// clears afterwards anyway.  The choice is wave-uniform and made once per stream.
+__device__ __forceinline__ unsigned stream_rows_delta(const EnvParams& ep, const uint32_t* s_obs, uint32_t* s_old, bool all,
                                                       const uint32_t* s_legal, const uint32_t* s_own, int g0, int ng, int P, int H,
-                                                      int t, int n, bool count) {
+                                                      int t, int n, bool count, bool compact) {
   const size_t PF = (size_t)P * ep.F, PA = (size_t)P * ep.A, PO = (size_t)P * 3 * H;
   unsigned stored = 0;
   if (!ep.obs_f32) {
     // device consumers only: no float32 observation leaves the chip
+  } else if (compact && !all) {
+    if (ep.nt_stores) {
+      stored = stream_bits_f32_compact<true>(s_obs, s_old, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t);
+    } else {
+      stored = stream_bits_f32_compact<false>(s_obs, s_old, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t);
+    }
   } else if (ep.nt_stores) {
     stored = stream_bits_f32_delta<true>(s_obs, s_old, all, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t, n, count);
   } else {
@@ -1804,7 +1902,8 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       const bool dbg_lines = ep.dbg && ep.dbg_iters > 0;
       int sl = lane;
       asm volatile("" : "+v"(sl));   // opaque: the stream's per-lane addresses are worked out here, not kept in registers for the launch
-      unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || iter == 1, s_legal, s_own, g0, ng, P, H, sl, kWave, dbg_lines);
+      unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || iter == 1, s_legal, s_own, g0, ng, P, H, sl, kWave, dbg_lines,
+                                          ep.compact != 0);
       clear_words(prev, ep.obs_words, sl, kWave);
       clear_words(s_legal, ep.legal_words + ep.own_words, sl, kWave);
       if (dbg_lines) {
@@ -1842,14 +1941,16 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     __syncthreads();   // rows complete before wave 1 streams them; wave 1 done reading s_st before wave 0 changes it
     STAMP(4);
   }
-  // epilogue: both waves stream the last iteration's rows
+  // epilogue: both waves stream the last iteration's rows, in the direct form (one stream of a launch: the compacted form's list
+  // would have to be split between the waves for about 1 % of a 50-iteration launch)
   const int dbg_it = ep.n_iter - 1;
   {
-    const uint32_t* s_obs1 = S_OBS1(0);
+    uint32_t* s_obs1 = S_OBS1(0);
     const uint32_t* rows = (ep.n_iter & 1) ? s_obs : s_obs1;
-    const uint32_t* prev = (ep.n_iter & 1) ? s_obs1 : s_obs;
+    uint32_t* prev = (ep.n_iter & 1) ? s_obs1 : s_obs;
     const bool dbg_lines = ep.dbg && ep.dbg_iters > 0;
-    unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || ep.n_iter == 1, s_legal, s_own, g0, ng, P, H, tid, ep.nthreads, dbg_lines);
+    unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || ep.n_iter == 1, s_legal, s_own, g0, ng, P, H, tid, ep.nthreads, dbg_lines,
+                                        false);
     if (dbg_lines) {
       stored = wave_sum(stored);
       if (lane == 0) env_stamp(ep, dbg_it, 14 + wave, stored);
@@ -2063,6 +2164,7 @@ struct hsad_env {
   // delta stream of the pipelined launches (EnvParams::delta).  Scope: one launch.  Nothing about priv_s is remembered between
   // launches, so reset / step / fork or a caller writing into priv_s cannot make anything stale.
   int rollout_delta;              // hsad_env_set_rollout_delta; HSAD_ENV_DELTA=0 at creation: every stream in full, for A/B
+  int rollout_compact;            // hsad_env_set_rollout_compact; HSAD_ENV_COMPACT=0 at creation: the direct form of the delta stream
   bool delta_fits;                // the second copy of the rows costs the pipelined kernel no resident workgroup per CU
   size_t lds_bytes_delta;         // lds_bytes_reset + the second copy
   unsigned long long* d_pace;     // the progress word (allocated with the env, zero)
@@ -2190,6 +2292,7 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
   size_t lds = (mode == 1 || mode == 2) ? e->lds_bytes : e->lds_bytes_reset;
   EnvParams ep = e->ep;
   ep.delta = mode == 3 && n_iter > 1 && rollout_delta_active(e) ? 1 : 0;
+  ep.compact = ep.delta && e->rollout_compact ? 1 : 0;
   if (ep.delta) lds = e->lds_bytes_delta;
   ep.phase = part >= 0 ? e->d_phase : nullptr;
   ep.part = part < 0 ? 0 : part;
@@ -2356,6 +2459,7 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->rollout_pipe = getenv("HSAD_ENV_PIPE") ? atoi(getenv("HSAD_ENV_PIPE")) != 0 : 1;
   e->rollout_pace = getenv("HSAD_ENV_PACE") ? atoi(getenv("HSAD_ENV_PACE")) != 0 : 1;
   e->rollout_delta = getenv("HSAD_ENV_DELTA") ? atoi(getenv("HSAD_ENV_DELTA")) != 0 : 1;
+  e->rollout_compact = getenv("HSAD_ENV_COMPACT") ? atoi(getenv("HSAD_ENV_COMPACT")) != 0 : 1;
   e->delta_fits = false;
   e->d_pace = nullptr;
   e->pace_base = 0;
@@ -2655,6 +2759,14 @@ int hsad_env_set_rollout_delta(hsad_env* e, int on) {
 }
 
 int hsad_env_rollout_delta_active(const hsad_env* e) { return e && rollout_delta_active(e) ? 1 : 0; }
+
+int hsad_env_set_rollout_compact(hsad_env* e, int on) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  e->rollout_compact = on != 0;
+  return HSAD_OK;
+}
+
+int hsad_env_rollout_compact_active(const hsad_env* e) { return e && e->rollout_compact && rollout_delta_active(e) ? 1 : 0; }
 
 int hsad_env_debug_pace_bias(hsad_env* e, int64_t bias) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");

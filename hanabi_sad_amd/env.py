@@ -191,6 +191,15 @@ class BatchedHanabiEnv:
         """whether persistent launches use the delta stream as the env stands"""
         return bool(self.lib.hsad_env_rollout_delta_active(self.h))
 
+    def set_rollout_compact(self, on):
+        """delta stream: list the changed lines first and store from the list (default on; results are identical, see
+        include/hsad.h)"""
+        _lib.check(self.lib.hsad_env_set_rollout_compact(self.h, int(bool(on))))
+
+    def rollout_compact_active(self):
+        """whether persistent launches use the compacted form of the delta stream as the env stands"""
+        return bool(self.lib.hsad_env_rollout_compact_active(self.h))
+
     def debug_pace_bias(self, bias):
         """test seam: offset of the counter base the paced kernels are told"""
         _lib.check(self.lib.hsad_env_debug_pace_bias(self.h, int(bias)))

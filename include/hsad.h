@@ -176,6 +176,12 @@ int hsad_env_rollout_pace_cap_us(const hsad_env* env);
  * pipelined schedule or the float32 observation, and not where the second copy would cost a resident workgroup per CU. */
 int hsad_env_set_rollout_delta(hsad_env* env, int on);
 int hsad_env_rollout_delta_active(const hsad_env* env);
+/* Compacted form of the delta stream (on by default wherever the delta stream is active; HSAD_ENV_COMPACT=0 when the env is created,
+ * or on = 0 here, gives the direct form, for A/B).  The stream wave first lists the lines that changed, in place in the LDS copy it
+ * has just compared, and then stores from the list, eight whole lines per wave-store.  The same lines are stored either way: results
+ * are bit-identical.  hsad_env_rollout_compact_active: true only where hsad_env_rollout_delta_active is. */
+int hsad_env_set_rollout_compact(hsad_env* env, int on);
+int hsad_env_rollout_compact_active(const hsad_env* env);
 /* Test seams of the pacing.  bias is added to the counter base every later persistent launch is told (not to the host's own
  * record), so that every workgroup's lead reads bias / workgroups iterations too high: all far ahead (bias > 0) or far behind (bias < 0); 0
  * restores the truth.  A lead no launch could produce (beyond its iteration count) switches the delay off.

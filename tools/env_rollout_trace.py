@@ -1,7 +1,7 @@
 """Per-iteration trace of one persistent rollout launch at configs[1] (65,536 two-player games): where each workgroup's time goes,
 and how many workgroups stream observations on each CU and on the chip over time.
 
-  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--delta on|off] [--json OUT]
+  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--delta on|off] [--compact on|off] [--json OUT]
 
 The driver's shape is --warmup 5 --iters 20 (one 5-iteration launch, then the traced 20-iteration launch).  --schedule single runs
 env_rollout_kernel (HSAD_ENV_PIPE=0), pipe the default env_rollout_pipe_kernel.  Stamps are wall_clock64 (100 MHz, 10 ns) of
@@ -13,7 +13,8 @@ where the workgroup runs (XCC; SE; SH; CU = the four co-resident workgroups) and
 position of its rows in the output buffers); per grouping the spread between the group means is set against the spread inside the
 groups (`share_of_variance_between_groups` is the usual eta squared).  --pace off traces the unpaced launch (HSAD_ENV_PACE=0); with
 pacing on, `pace` says how many iterations delayed their stream and by how much (--l0-q8 / --cap-us: the developer switches
-HSAD_ENV_PACE_L0_Q8 / HSAD_ENV_PACE_CAP_US).  --delta off traces the full observation stream (HSAD_ENV_DELTA=0).
+HSAD_ENV_PACE_L0_Q8 / HSAD_ENV_PACE_CAP_US).  --delta off traces the full observation stream (HSAD_ENV_DELTA=0),
+--compact off the direct form of the delta stream (HSAD_ENV_COMPACT=0).
 
 `reset_iterations` splits the logic wave's time in the workgroup-iterations whose lane 0 restarted its game (the only ones that carry
 the reset stamps 6 / 7): the wait for the mt19937 window, the deal, and the rest (eps, colour shuffle, policy and step)."""
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--schedule", choices=("pipe", "single"), default="pipe")
     ap.add_argument("--pace", choices=("on", "off"), default="on")
     ap.add_argument("--delta", choices=("on", "off"), default="on")
+    ap.add_argument("--compact", choices=("on", "off"), default="on")
     ap.add_argument("--l0-q8", type=int, default=None)
     ap.add_argument("--cap-us", type=int, default=None)
     ap.add_argument("--json", default=None)
@@ -44,6 +46,7 @@ def main():
     os.environ["HSAD_ENV_PIPE"] = "1" if args.schedule == "pipe" else "0"
     os.environ["HSAD_ENV_PACE"] = "1" if args.pace == "on" else "0"
     os.environ["HSAD_ENV_DELTA"] = "1" if args.delta == "on" else "0"
+    os.environ["HSAD_ENV_COMPACT"] = "1" if args.compact == "on" else "0"
     if args.l0_q8 is not None:
         os.environ["HSAD_ENV_PACE_L0_Q8"] = str(args.l0_q8)
     if args.cap_us is not None:
@@ -67,6 +70,7 @@ def main():
     s = buf.view(nwg, args.iters, 16).cpu().numpy().astype(np.int64)
     rec = analyse(s, args.schedule == "pipe", args)
     rec["delta_stream_active"] = bool(env.rollout_delta_active())
+    rec["compact_stream_active"] = bool(env.rollout_compact_active())
     rec["pace"] = dict(rec.get("pace", {}), on=args.pace == "on", cap_us=env.rollout_pace_cap_us(),
                        l0_q8=args.l0_q8 if args.l0_q8 is not None else "default")
     print(json.dumps(rec, indent=1))

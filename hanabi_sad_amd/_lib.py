@@ -138,6 +138,10 @@ SIGNATURES = {
     "hsad_env_rewind_scripted": (C.c_int, [_P, _P, _P, _P]),
     "hsad_env_sad_section": (C.c_int, [_P, _P, _P]),
     "hsad_env_observe_sad": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "hsad_env_import_state": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "hsad_env_snapshot_record_bytes": (C.c_int64, [_P]),
+    "hsad_env_snapshot": (C.c_int, [_P, _P, _P]),
+    "hsad_env_restore": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "hsad_aggregate_priority": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
     "hsad_replay_create": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(Field), C.c_int, C.POINTER(_P)]),

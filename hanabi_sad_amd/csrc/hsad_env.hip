@@ -2181,6 +2181,7 @@ struct hsad_env {
   // cleared by hsad_env_reset / hsad_env_reseed.  The buffers are allocated on first use
   bool scripted;
   DealScript script;
+  unsigned long long* d_sad;   // [Gpad * P] the SAD sections hsad_env_restore hands to the observe pass (hsad_env_position.inc); allocated on first use
 };
 
 namespace {
@@ -2470,6 +2471,7 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->d_sel = nullptr;
   e->scripted = false;
   e->script = DealScript{nullptr, nullptr};
+  e->d_sad = nullptr;
   if (e->lds_bytes_reset > 160 * 1024) {
     const size_t need = e->lds_bytes_reset;
     delete e;
@@ -2523,6 +2525,7 @@ void hsad_env_destroy(hsad_env* e) {
   if (e->d_sel) (void)hipFree(e->d_sel);
   if (e->script.cards) (void)hipFree(e->script.cards);
   if (e->script.count) (void)hipFree(e->script.count);
+  if (e->d_sad) (void)hipFree(e->d_sad);
   if (e->ep.planes) (void)hipFree(e->ep.planes);
   if (e->ep.mt) (void)hipFree(e->ep.mt);
   if (e->ep.deck_hist) (void)hipFree(e->ep.deck_hist);
@@ -2866,3 +2869,6 @@ int hsad_env_error_count(hsad_env* e, int32_t* count, int32_t* first_game, int32
 
 // the exact belief over a hidden hand and the rejection-free sampler on top of it
 #include "hsad_env_belief.inc"
+
+// positions in and out: import of the canonical record, snapshot and restore of whole games
+#include "hsad_env_position.inc"

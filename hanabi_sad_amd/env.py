@@ -55,6 +55,10 @@ class BatchedHanabiEnv:
         self.config = dict(players=players, hand_size=hand_size, bomb=int(bomb), max_len=int(max_len), sad=bool(sad),
                            shuffle_color=bool(shuffle_color), knowledge_mode=int(knowledge_mode), colors=int(colors), ranks=int(ranks),
                            max_information_tokens=int(max_information_tokens), max_life_tokens=int(max_life_tokens))
+        # everything load() needs to build this env again (save / load)
+        self._full_config = dict(self.config, num_games=int(num_games), seed=int(seed), eps_list=[float(e) for e in eps_list],
+                                 track_deck_history=bool(track_deck_history), deal_mode=int(deal_mode),
+                                 games_per_workgroup=int(games_per_workgroup))
         self.G, self.P, self.H = num_games, players, hand_size
         self.colors, self.ranks = int(colors), int(ranks)
         self.max_information_tokens, self.max_life_tokens = int(max_information_tokens), int(max_life_tokens)
@@ -315,6 +319,107 @@ class BatchedHanabiEnv:
         assert s.dim() == 2 and s.shape[1] == self.P
         _lib.check(self.lib.hsad_env_observe_sad(self.h, idx.data_ptr(), int(s.shape[0]), s.data_ptr(), self._stream()))
 
+    # -- positions in and out (include/hsad.h: hsad_env_import_state / _snapshot / _restore; hanabi_sad_amd/position.py) --
+    def import_state(self, states, games=None, seeds=None, eps=None):
+        """the games listed in `games` (list or tensor of indices; None: all G in order) become the positions `states` (int32, one
+        canonical record per entry: export_state's layout, position.Position.to_record).  seeds (one int32 per entry) reseeds
+        each game's generator, None keeps it; eps (float [entries, P]) sets its eps row, None keeps it.  Returns status int32
+        [G]: -1 not listed, 0 imported, else the HSAD_POS_* flags of a refused record (position.explain; the game is untouched
+        and check_errors() reports it).
+        The cards of an imported position have no deal order: the game's deck-history row is cleared, but deck_history() still
+        counts deck size minus cards left for it, so it returns that many cards of type 0 until the next reset deals afresh.
+        Do not feed such a history to rewind_scripted (the deck does not hold those cards: error code 5)."""
+        W = self.lib.hsad_env_state_words(self.h)
+        st = torch.as_tensor(states, device=self.device).to(torch.int32)
+        if st.dim() == 1:
+            st = st.view(1, -1)
+        idx = torch.arange(self.G, device=self.device) if games is None else torch.as_tensor(games, device=self.device).to(torch.int64).view(-1)
+        n = idx.numel()
+        assert st.shape == (n, W), "expected %d records of %d words, got %s" % (n, W, tuple(st.shape))
+        if n and (int(idx.min()) < 0 or int(idx.max()) >= self.G or idx.unique().numel() != n):
+            raise ValueError("import_state: games must be distinct indices in [0, %d)" % self.G)
+        full = torch.zeros(self.G, W, dtype=torch.int32, device=self.device)
+        full[idx] = st
+        take = torch.zeros(self.G, dtype=torch.uint8, device=self.device)
+        take[idx] = 1
+        sd = ep = None
+        if seeds is not None:
+            sd = torch.zeros(self.G, dtype=torch.int32, device=self.device)
+            sd[idx] = torch.as_tensor(seeds, device=self.device).to(torch.int32).view(n)
+        if eps is not None:
+            ep = torch.zeros(self.G, self.P, dtype=torch.float32, device=self.device)
+            ep[idx] = torch.as_tensor(eps, device=self.device).to(torch.float32).view(n, self.P)
+        status = torch.zeros(self.G, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.hsad_env_import_state(self.h, full.data_ptr(), take.data_ptr(), sd.data_ptr() if sd is not None else None,
+                                                  ep.data_ptr() if ep is not None else None, status.data_ptr(), self._stream()))
+        return status
+
+    def snapshot_record_bytes(self):
+        return int(self.lib.hsad_env_snapshot_record_bytes(self.h))
+
+    def snapshot(self):
+        """uint8 [G, record_bytes]: every game complete -- state, generator, policy counter, deck history, deal script, the SAD
+        section of its rows.  Opaque and exact; restore() of it continues bit for bit."""
+        out = torch.zeros(self.G, self.snapshot_record_bytes(), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.hsad_env_snapshot(self.h, out.data_ptr(), self._stream()))
+        return out
+
+    def restore(self, snap, src_index=None):
+        """game j becomes record src_index[j] of snap (int32 [G]; None: record j, and snap must hold G records; -1 leaves game j
+        alone) and its rows are rewritten as they were.  Returns status int32 [G]: 0 restored, -1 left alone, else the
+        HSAD_POS_* flags of a refused record (game untouched; check_errors() reports it)."""
+        assert snap.dtype == torch.uint8 and snap.dim() == 2, "expected a uint8 [G_src, record_bytes] snapshot"
+        snap = snap.to(self.device).contiguous()
+        idx = self._i32(src_index, self.G) if src_index is not None else None
+        status = torch.zeros(self.G, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.hsad_env_restore(self.h, snap.data_ptr(), int(snap.shape[1]), int(snap.shape[0]),
+                                             idx.data_ptr() if idx is not None else None, status.data_ptr(), self._stream()))
+        return status
+
+    SAVE_VERSION = 1
+
+    @staticmethod
+    def _record_bytes(players, track_deck_history, script):
+        """hsad_env_snapshot_record_bytes, from the configuration alone (include/hsad.h gives the layout)"""
+        return 4 * (10 + 6 * players + 1 + 624 + (13 if track_deck_history else 0) + (14 if script else 0) + 2 * players)
+
+    def save(self, path):
+        """one torch.save dict: format version, the env's full configuration, record_bytes, the snapshot"""
+        snap = self.snapshot()
+        cfg = dict(self._full_config)
+        script = int(snap.shape[1]) != self._record_bytes(cfg["players"], cfg["track_deck_history"], False)
+        # `layout`: what the records were made for, apart from the configuration they are saved with
+        torch.save(dict(version=self.SAVE_VERSION, config=cfg, record_bytes=int(snap.shape[1]),
+                        layout=dict(players=cfg["players"], hand_size=cfg["hand_size"], track_deck_history=cfg["track_deck_history"],
+                                    script=bool(script)), snapshot=snap.cpu()), path)
+
+    @classmethod
+    def load(cls, path, device="cuda:0"):
+        """the env save() wrote, on `device`, its games where they were.  ValueError, before anything is launched on the games, for
+        another format version, a record size that is not this configuration's or a snapshot of another length; HsadError if the
+        device refuses a record.  The record size does not depend on the hand size, so the hand-size check rests on the file
+        saying it twice (`config` and `layout`): a file in which both were changed together gets as far as the device, whose
+        position check then refuses the records (HsadError)."""
+        d = torch.load(path, map_location="cpu")
+        if not isinstance(d, dict) or d.get("version") != cls.SAVE_VERSION:
+            raise ValueError("%s: not a saved env of format version %d" % (path, cls.SAVE_VERSION))
+        cfg, snap, rb, lay = dict(d["config"]), d["snapshot"], int(d["record_bytes"]), dict(d["layout"])
+        for k in ("players", "hand_size", "track_deck_history"):
+            if lay[k] != cfg[k]:
+                raise ValueError("%s: the records were made for %s = %s, the configuration says %s" % (path, k, lay[k], cfg[k]))
+        want = cls._record_bytes(cfg["players"], cfg["track_deck_history"], lay["script"])
+        if rb != want:
+            raise ValueError("%s: records of %d bytes, this configuration's are %d" % (path, rb, want))
+        if snap.dtype != torch.uint8 or snap.dim() != 2 or tuple(snap.shape) != (int(cfg["num_games"]), rb):
+            raise ValueError("%s: the snapshot is not %d records of %d bytes" % (path, int(cfg["num_games"]), rb))
+        env = cls(device=device, **cfg)
+        status = env.restore(snap)
+        if bool((status != 0).any()):
+            bad = int((status != 0).nonzero()[0])
+            env.close()
+            raise _lib.HsadError("%s: record %d was refused (flags %d)" % (path, bad, int(status[bad])))
+        return env
+
     def query(self):
         out = torch.zeros(self.G, 16, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.hsad_env_query(self.h, out.data_ptr(), self._stream()))
@@ -344,5 +449,6 @@ class BatchedHanabiEnv:
         _lib.check(self.lib.hsad_env_error_count(self.h, C.byref(n), C.byref(g), C.byref(c)))
         if n.value:
             what = {1: "illegal move", 2: "illegal greedy move", 3: "step on a finished game",
-                    4: "fork source index out of range", 5: "deal script names a card the deck does not hold"}.get(c.value, "?")
+                    4: "fork source index out of range", 5: "deal script names a card the deck does not hold",
+                    6: "position refused (import_state / restore; see the call's status)"}.get(c.value, "?")
             raise _lib.HsadError("%d game(s) violated the env contract; first: game %d, %s" % (n.value, g.value, what))

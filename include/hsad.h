@@ -236,8 +236,9 @@ int hsad_env_rollout_resident_workgroups(const hsad_env* env);
 
 /* Number of games that hit an API-contract error (illegal move, step on a finished game) since
  * the last call; synchronises the device.  first_game/first_code (may be NULL) describe the first.
- * Codes: 1 illegal move, 2 illegal greedy move, 3 step on a finished game, 4 hsad_env_fork source index out of range, 5 a deal
- * script names a card the deck does not hold (hsad_env_rewind_scripted). */
+ * Codes: 1 illegal move, 2 illegal greedy move, 3 step on a finished game, 4 hsad_env_fork / hsad_env_restore source index out of
+ * range, 5 a deal script names a card the deck does not hold (hsad_env_rewind_scripted), 6 hsad_env_import_state / hsad_env_restore
+ * refused a position (the call's status word holds the HSAD_POS_* flags that say why). */
 int hsad_env_error_count(hsad_env* env, int32_t* count, int32_t* first_game, int32_t* first_code);
 
 /* ---- The env as a simulator for test-time search (determinised Monte Carlo, SPARTA-style single-agent search): branch a game,
@@ -347,6 +348,86 @@ int hsad_env_rewind_scripted(hsad_env* env, const uint8_t* script, const int32_t
  * sad[src_index[g] * P + p] (device int64 [G_src * P]).  Other games keep their rows.  A no-op with sad = 0.  Launch-only. */
 int hsad_env_sad_section(hsad_env* env, int64_t* out, void* stream);
 int hsad_env_observe_sad(hsad_env* env, const int32_t* src_index, int G_src, const int64_t* sad, void* stream);
+
+/* ---- Positions in and out of an env: set one up, save the games, take them back.  Both directions below are launch-only, act per
+ * game, and check on the device before they write: a game whose input is refused is left alone -- state, generator, rows -- gets
+ * the reason in its status word and is counted in the error log (code 6).  Nothing below changes what any earlier call computes.
+ *
+ * Why a position is refused, as bits of the status word.  The first eight are position_valid (csrc/hsad_position.h), the check both
+ * calls share: it admits exactly the positions from which the step, the row builder, the legal-move masks, the deal, the belief
+ * kernels and the playout index in range and keep every card accounted for. */
+enum {
+  HSAD_POS_CONSERVATION = 1,  /* for some card type: deck + discards + copies in hands + (its colour's firework > its rank) differs
+                                 from the full deck's count; the deck-size field is not the sum of the deck counts; a card, a count
+                                 or a firework sits in a colour >= colors or a rank >= ranks */
+  HSAD_POS_BOARD = 2,         /* a firework > ranks; info > max_information_tokens; life > max_life_tokens; cur_player outside
+                                 [0, P); next_non_chance_player != (cur_player + 1) % P; turns_to_play > P, or != P while the deck
+                                 holds a card */
+  HSAD_POS_HANDS = 4,         /* occupied slots not contiguous from 0; a length other than H, or H - 1 on an empty deck; more
+                                 short hands than P - turns_to_play (each move on an empty deck takes one turn) */
+  HSAD_POS_KNOWLEDGE = 8,     /* a plausible-colour / -rank mask that is empty, leaves the rules' colours / ranks or excludes the
+                                 card's own; a hinted colour / rank (>= 0) that is not the card's or whose mask is not that one bit */
+  HSAD_POS_LASTMOVE = 16,     /* last move: type outside 0..4, player >= P, target offset outside 1..P-1 (hints), colour >= colors,
+                                 rank >= ranks, card index >= H, reveal mask >= 2^H.  Only what the encoder indexes with: whether
+                                 the move fits the rest of the position is not checked and cannot be */
+  HSAD_POS_STEP = 32,         /* num_step > 255, or > max_len when max_len > 0 */
+  HSAD_POS_PERM = 64,         /* a colour permutation that is none of 0..4, moves a colour >= colors, whose inverse is not its
+                                 inverse, or that is not the identity with shuffle_color off */
+  HSAD_POS_TERMINAL = 128,    /* the position is finished: life < 1, every firework complete, turns_to_play < 1, or num_step ==
+                                 max_len > 0.  A finished position is held to what a final move leaves, which no deal follows: the
+                                 mover's hand may be short over a non-empty deck, and then cur_player is -1 and
+                                 next_non_chance_player the seat after the mover */
+  HSAD_POS_FIELD = 256,       /* import: a record word does not fit the bit field that holds it (reported alone: the record is not
+                                 looked at further) */
+  HSAD_POS_NO_GENERATOR = 512,/* import with seeds == NULL into a game that was never started: it has no generator to keep */
+  HSAD_POS_LOOKAHEAD = 1024,  /* restore: look-ahead count > 2 */
+  HSAD_POS_HISTORY = 2048,    /* restore: a deck-history or script card >= 25; a script count outside {0} and [P * H, deck size] */
+  HSAD_POS_SCRIPT = 4096,     /* restore: the script's remaining deals name a card the record's deck does not hold */
+  HSAD_POS_RECORD = 8192      /* restore: the record's terminated bit disagrees with its position */
+};
+
+/* hsad_env_import_state: game g with take[g] != 0 (device uint8 [G]) becomes the position states[g] (device int32
+ * [G, hsad_env_state_words()], the layout hsad_env_export_state writes), live: started, not terminated, last score from word 74.
+ * status (device int32 [G] or NULL): -1 for take[g] == 0 (game untouched), 0 imported, else the HSAD_POS_* flags (game untouched,
+ * error log code 6).  A finished position is refused with HSAD_POS_TERMINAL.  Record fields the last move's type does not use,
+ * the knowledge words of empty slots (card -1) and word 73 are ignored.
+ * Generator: seeds (device int32 [G]) gives game g std::mt19937(seeds[g]) with no draw consumed and an empty look-ahead, exactly
+ * hsad_env_fork's seeding; seeds == NULL keeps the game's generator, draw counter and look-ahead (HSAD_POS_NO_GENERATOR for a game
+ * that was never started).  eps (device float [G, P]) sets the eps plane; NULL keeps it (0 for a never-started game).  The policy
+ * counter is kept.  The cards of an imported position have no deal order: the game's deck-history row is cleared (the cards
+ * hsad_env_deck_history returns for it are 0 until the next reset deals afresh) and, while the env holds a deal script, the game's
+ * script is dropped -- the scripted-env rules apply unchanged to the other games.  The rows of the imported games are rewritten by
+ * the observe pass as after hsad_env_rewind_scripted: SAD section all-zero, reward 0, terminal 0.  Launch-only. */
+int hsad_env_import_state(hsad_env* env, const int32_t* states, const uint8_t* take, const int32_t* seeds, const float* eps,
+                          int32_t* status, void* stream);
+
+/* A snapshot is G fixed-size records in device memory, one per game, holding everything that decides what the game does and shows
+ * next.  Record of 32-bit words, with npl = 10 + 6 P:
+ *   [0, npl)            the state planes (board, hands, knowledge, eps, colour permutations, draw counter, look-ahead)
+ *   [npl]               the policy counter
+ *   [npl + 1, npl + 625) the 624 generator words
+ *   then 13 words       the deck-history row (52 bytes)              -- only if the env tracks the deck history
+ *   then 13 + 1 words   the deal-script row (52 bytes) and its count -- only if the env holds a deal script
+ *   then 2 P words      the SAD section of each seat's current row (low word first; hsad_env_sad_section's value)
+ * Size and offsets depend on (P, track_deck_history, script held) only; hsad_env_snapshot_record_bytes gives the size as the env
+ * stands.  Pacing, timing and trace state is not game state and is not recorded; no rollout launch carries a per-game word into
+ * the next that is not derived from the planes and the rows.  The records are opaque and exact: bytes may be copied, stored and
+ * loaded by another process.  hsad_env_snapshot needs the env's observation rows (float32 or bit words) with sad = 1.
+ * hsad_env_restore: dst game j becomes record src_index[j] (device int32 [G]) of `in` (G_src records of record_bytes each);
+ * src_index == NULL is the identity and needs G_src == G; -1 leaves game j alone (status -1); another value outside [0, G_src)
+ * too, counted as code 4.  record_bytes must be this env's record size with or without a deal script (HSAD_ERR_INVALID otherwise,
+ * before anything is launched): records with a script make the env hold one (as hsad_env_rewind_scripted does), records without
+ * clear the restored games' scripts.  Each record is read once and checked before a word of its game is written: a started record
+ * must pass position_valid (a finished game is part of an env: HSAD_POS_TERMINAL is allowed, and must agree with the record's
+ * terminated bit) and the HSAD_POS_LOOKAHEAD / _HISTORY / _SCRIPT checks; a never-started record is restored as it is.  Every
+ * generator index is derived from the draw counter modulo 624, so any counter is in range.  A refused record leaves its game
+ * alone: status = its flags, code 6.  The rows of the restored games are rewritten by the observe pass with the recorded SAD
+ * section: every bound row, legal moves, own hand and eps are what the env showed when the snapshot was taken, bit for bit (given
+ * that its rows were current then: hsad_env_playout_random leaves them stale); reward = 0, terminal = the state's bit. */
+int64_t hsad_env_snapshot_record_bytes(const hsad_env* env);
+int hsad_env_snapshot(hsad_env* env, void* out, void* stream);
+int hsad_env_restore(hsad_env* env, const void* in, int64_t record_bytes, int G_src, const int32_t* src_index, int32_t* status,
+                     void* stream);
 
 
 /* ------------------------------------------------------------------------------------------

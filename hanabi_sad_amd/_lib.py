@@ -135,6 +135,8 @@ SIGNATURES = {
     "hsad_env_determinize_exact": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_int, _P, _P, _P]),
     "hsad_env_playout_random": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
     "hsad_env_playout_random_keyed": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P, _P]),
+    "hsad_env_policy_rule": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_uint64, _P, _P, _P, _P]),
+    "hsad_env_playout_rule": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_uint64, _P, _P, _P, _P]),
     "hsad_env_rewind_scripted": (C.c_int, [_P, _P, _P, _P]),
     "hsad_env_sad_section": (C.c_int, [_P, _P, _P]),
     "hsad_env_observe_sad": (C.c_int, [_P, _P, C.c_int, _P, _P]),

@@ -2872,3 +2872,6 @@ int hsad_env_error_count(hsad_env* e, int32_t* count, int32_t* first_game, int32
 
 // positions in and out: import of the canonical record, snapshot and restore of whole games
 #include "hsad_env_position.inc"
+
+// rule-list bots as a policy: one call on the planes, and whole playouts in one launch
+#include "hsad_env_rulebot.inc"

@@ -289,6 +289,52 @@ class BatchedHanabiEnv:
                                                           self.greedy_a.data_ptr(), self._stream()))
         return self.a, self.greedy_a
 
+    # -- rule-list bots (include/hsad.h: HSAD_RULE_*, hsad_env_policy_rule / _playout_rule; hanabi_sad_amd/rulebot.py) --
+    def _key64(self, key):
+        if key is None:
+            return None
+        k = torch.as_tensor(key, device=self.device).to(torch.int64).contiguous()
+        assert k.shape == (self.G,)
+        return k
+
+    def policy_rule(self, bots, seat_bot=None, seed=0, key=None):
+        """one policy call of rule bots on the current state: row (g, p) of a / greedy_a gets the move of bots[seat_bot[g, p]] (the
+        noop when seat p is not on turn).  bots: a RuleBot or a list of at most 8; seat_bot: int32 [G, P], or [P] for the same
+        seating in every game, None = bot 0 everywhere; -1 leaves the row untouched, and a game with no bot at all keeps its policy
+        counter.  key (int64 [G]) replaces the game index in the hash of the *_RANDOM rules.  Returns (a, greedy_a)."""
+        from . import rulebot
+        bots = [bots] if isinstance(bots, rulebot.RuleBot) else list(bots)
+        rules, n_rules, n_bot = rulebot.pack(bots)
+        if seat_bot is None:
+            sb = torch.zeros(self.G, self.P, dtype=torch.int32, device=self.device)
+        else:
+            sb = torch.as_tensor(seat_bot, device=self.device).to(torch.int32)
+            if sb.dim() == 1:
+                sb = sb.view(1, self.P).expand(self.G, self.P)
+            sb = sb.contiguous()
+            assert sb.shape == (self.G, self.P), "seat_bot must be [G, P] or [P], got %s" % (tuple(sb.shape),)
+        k = self._key64(key)
+        _lib.check(self.lib.hsad_env_policy_rule(self.h, rules, n_rules, n_bot, sb.data_ptr(), int(seed) & (2 ** 64 - 1),
+                                                 k.data_ptr() if k is not None else None, self.a.data_ptr(), self.greedy_a.data_ptr(),
+                                                 self._stream()))
+        return self.a, self.greedy_a
+
+    def playout_rule(self, max_iter, bots, seats=None, seed=0, key=None):
+        """playout_random with rule bots in place of the random pick: bot -> step until every live game has ended (at most max_iter
+        iterations) in one launch, finished games left alone, observation rows NOT rewritten.  bots: a RuleBot or a list of at most
+        8; seats: per seat the index of its bot (None = bot 0 on every seat).  A live game's trajectory is that of policy_rule +
+        step.  Returns (a, greedy_a)."""
+        from . import rulebot
+        bots = [bots] if isinstance(bots, rulebot.RuleBot) else list(bots)
+        rules, n_rules, n_bot = rulebot.pack(bots)
+        seats = [0] * self.P if seats is None else [int(s) for s in seats]
+        assert len(seats) == self.P, "one bot index per seat"
+        k = self._key64(key)
+        _lib.check(self.lib.hsad_env_playout_rule(self.h, int(max_iter), rules, n_rules, n_bot, (C.c_int32 * self.P)(*seats),
+                                                  int(seed) & (2 ** 64 - 1), k.data_ptr() if k is not None else None,
+                                                  self.a.data_ptr(), self.greedy_a.data_ptr(), self._stream()))
+        return self.a, self.greedy_a
+
     def rewind_scripted(self, script, count):
         """games with count[g] > 0 (int32 [G]) start again from a fresh deal whose cards are script[g] (uint8 [G, 52], or [G, 50]
         as deck_history() returns it): the hands from its first P * H entries, every later deal of step() from the script until
@@ -450,5 +496,6 @@ class BatchedHanabiEnv:
         if n.value:
             what = {1: "illegal move", 2: "illegal greedy move", 3: "step on a finished game",
                     4: "fork source index out of range", 5: "deal script names a card the deck does not hold",
-                    6: "position refused (import_state / restore; see the call's status)"}.get(c.value, "?")
+                    6: "position refused (import_state / restore; see the call's status)",
+                    7: "policy_rule: a seat_bot entry names no bot"}.get(c.value, "?")
             raise _lib.HsadError("%d game(s) violated the env contract; first: game %d, %s" % (n.value, g.value, what))

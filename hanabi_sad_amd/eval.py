@@ -11,6 +11,7 @@ import torch
 from . import _lib
 from .env import BatchedHanabiEnv
 from .r2d2 import R2D2Agent, R2D2NetKernels
+from .rulebot import RuleBot
 
 
 def evaluate(weights, num_game, seed, bomb, sad, *, num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16",
@@ -118,6 +119,9 @@ def _check_pool(agents, seatings, num_player, F, A):
         raise ValueError("seating %d seat %d names model %d; the pool has models 0..%d" % (s, p, seatings[s, p], K - 1))
     models = []
     for k, x in enumerate(agents):
+        if isinstance(x, RuleBot):           # no net: nothing to hold against the env's dimensions
+            models.append(x)
+            continue
         if isinstance(x, (str, bytes)) or hasattr(x, "__fspath__"):
             x = load_weights(x)
         dims = _model_dims(x)
@@ -179,14 +183,24 @@ class _SeatedModel:
 class _TournamentBatch:
     """one env object of S x n games (seating-major) and the pool seated on it; play(seed) runs one chunk of n deals"""
 
-    def __init__(self, agents, seatings, n, env_kw, device):
+    def __init__(self, agents, seatings, n, env_kw, device, bot_seed=0):
         S, P = seatings.shape
         self.n, self.S = n, S
         self.env = env = BatchedHanabiEnv(S * n, players=P, seed=0, eps_list=[0.0], max_len=-1, device=device, track_deck_history=False,
                                           **env_kw)
         self.lib, self.device = env.lib, env.device
+        owned = seating_rows(seatings, n, len(agents))
         self.models = [_SeatedModel(ag, rows, env, self.device)
-                       for ag, rows in zip(agents, seating_rows(seatings, n, len(agents))) if len(rows)]
+                       for ag, rows in zip(agents, owned) if len(rows) and not isinstance(ag, RuleBot)]
+        # the rule bots of the pool own no _SeatedModel: one policy_rule call per step serves all their rows
+        seated_bots = [k for k, ag in enumerate(agents) if isinstance(ag, RuleBot) and len(owned[k])]
+        self.bots, self.bot_seed = [agents[k] for k in seated_bots], int(bot_seed)
+        if self.bots:
+            sb = np.full(S * n * P, -1, dtype=np.int32)
+            for b, k in enumerate(seated_bots):
+                sb[owned[k]] = b
+            self.seat_bot = torch.from_numpy(sb).view(S * n, P).to(self.device)
+            self.deal = (torch.arange(S * n, dtype=torch.int64) % n).to(self.device)   # game s * n + d plays deal d
         widths = {m.Kp for m in self.models if m.bf16}
         if len(widths) > 1:
             raise _lib.HsadError("the pool's bf16 nets pad the observation to different row lengths: %s" % sorted(widths))
@@ -219,6 +233,8 @@ class _TournamentBatch:
         for t in range(max_steps):
             for m in self.models:
                 self._act(m)
+            if self.bots:     # the hash of a *_RANDOM rule is keyed by the deal's seed: a deal plays the same in every chunking
+                env.policy_rule(self.bots, self.seat_bot, seed=self.bot_seed, key=self.deal + int(seed))
             env.step(env.a, env.greedy_a)
             _lib.check(self.lib.hsad_seating_stats(env.h, self.n, self.stats.data_ptr(), self.unfinished.data_ptr(), env._stream()))
             # the host looks at ONE word, and one step late: it never waits for the step it has just enqueued (the extra step
@@ -239,11 +255,13 @@ class _TournamentBatch:
 
 
 def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_launch=1 << 18, precision="bf16", device="cuda:0",
-                  hand_size=5, shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3, max_steps=200):
+                  hand_size=5, shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3, max_steps=200,
+                  bot_seed=0):
     """Every seating of a model pool over the SAME deals, in one batched run -> SeatingScores.
 
     agents: the pool -- whatever `evaluate` accepts (weight dicts, kernel agents / nets, any object with act / get_h0 such as
-    obl.OBLAgent or rela.ContractAgent) or `.pthw` paths.  seatings: int [S, P], the model index on each seat.  Seating s plays the
+    obl.OBLAgent or rela.ContractAgent), `.pthw` paths, or rulebot.RuleBot members (at most 8: hand-coded partners, served by one
+    BatchedHanabiEnv.policy_rule call per step; bot_seed seeds their *_RANDOM rules, keyed by the deal).  seatings: int [S, P], the model index on each seat.  Seating s plays the
     deals seed .. seed + num_game - 1, the ones evaluate(..., seed) plays; every player acts greedily (max_len -1, eps 0).
 
     One env object holds S x n games, seating-major, reseeded with period n (BatchedHanabiEnv.reseed); per step each model acts ONCE
@@ -265,7 +283,7 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
         raise ValueError("num_game must be >= 1")
     models, seatings = _check_pool(agents, seatings, P, F, A)
     S = seatings.shape[0]
-    acting = [_acting_agent(x, precision, device) for x in models]
+    acting = [x if isinstance(x, RuleBot) else _acting_agent(x, precision, device) for x in models]
     env_kw = dict(hand_size=hand_size, bomb=bomb, sad=bool(sad), shuffle_color=bool(shuffle_color), **rules)
     per = max(1, min(int(num_game), int(games_per_launch) // S))
     scores = np.zeros((S, num_game), dtype=np.int64)
@@ -274,7 +292,7 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
     for start in range(0, num_game, per):
         n = min(per, num_game - start)
         if n not in batches:
-            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device)
+            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device, bot_seed)
             if (batches[n].env.F, batches[n].env.A) != (F, A):
                 raise _lib.HsadError("env_dims gives (%d, %d), the library (%d, %d)" % (F, A, batches[n].env.F, batches[n].env.A))
         sc, tt = batches[n].play(seed + start, max_steps)

@@ -8,6 +8,7 @@ layout.
   --paper obl --obl_path obl.pthw                       self-play of an OBL model
   --paper op  --method sad --idx 0 3 6 9 --cross_play   the 4 x 4 matrix
   --paper sad --weight a.pthw b.pthw c.pthw --cross_play
+  --paper op  --method sad --idx 0 3 --cross_play --bots cautious piers    the matrix with rule-bot partners (rulebot.PRESETS)
   --paper op  --method sad --idx 0 --search_worlds 8    M0 in self-play, blueprint only and blueprint + search over the same deals
   ... --search_worlds 32 --search_rounds 8,8,16         the same with the search in rounds (paired statistics, pruning)
 
@@ -18,6 +19,7 @@ import argparse
 import os
 
 from .eval import cross_play, env_dims, format_cross_play_table, play_seatings
+from .rulebot import PRESETS
 
 
 def parse_args(argv=None):
@@ -34,6 +36,8 @@ def parse_args(argv=None):
     p.add_argument("--obl_path", default=None, type=str)
     p.add_argument("--cross_play", action="store_true", help="print the score matrix of the pool (--idx / several --weight)")
     p.add_argument("--idx", default=None, type=int, nargs="+", help="--paper op --cross_play: the zoo models of the pool")
+    p.add_argument("--bots", default=[], type=str, nargs="+", choices=sorted(PRESETS),
+                   help="--cross_play: rule-bot presets appended to the pool (hand-coded partners; rulebot.PRESETS)")
     p.add_argument("--root", default=None, type=str, help="folder that holds models/op/<method>/M{idx}.pthw (default: the repository)")
     p.add_argument("--precision", default="bf16", type=str, choices=["bf16", "fp32"])
     p.add_argument("--search_worlds", default=0, type=int, help="> 0 with a single --idx: also play with blueprint-policy search "
@@ -111,7 +115,10 @@ def main(argv=None):
     net = agents[0].online
     n, kw = args.num_game * args.num_run, dict(precision=args.precision, device=args.device, hand_size=5 if P <= 3 else 4)
     sad = args.paper == "obl" or getattr(net, "F", None) == env_dims(P, kw["hand_size"], sad=True)[0]
+    if args.bots and not args.cross_play:
+        raise SystemExit("--bots needs --cross_play (the bots join the pool of the matrix)")
     if args.cross_play:
+        agents, names = agents + [PRESETS[b] for b in args.bots], names + list(args.bots)
         if P != 2:
             raise SystemExit("--cross_play is the two-player matrix")
         res = cross_play(agents, n, 1, 0, sad, **kw)

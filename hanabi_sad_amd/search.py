@@ -4,9 +4,10 @@ hands its card knowledge allows, the deck reshuffled -- and each world is played
 primitives (BatchedHanabiEnv.fork_from / determinize / step / playout_random); the rollouts of all (game, action, world) jobs run
 batched in one search env, `capacity` games at a time.
 
-Two rollout policies: mc_action_values plays the worlds out with random legal moves (one launch, hsad_env_playout_random);
+Rollout policies: mc_action_values plays the worlds out with random legal moves (one launch, hsad_env_playout_random) or, with
+playout=<rulebot.RuleBot>, with a rule-list bot on every seat (one launch as well, hsad_env_playout_rule);
 policy_action_values / PolicySearch play them out with the blueprint itself -- the R2D2 agent acting greedily for every seat --
-which is what can improve on that agent (choose_action, play_with_search).  The glue kernels of the second are csrc/hsad_search.hip.
+which is what can improve on that agent (choose_action, play_with_search).  The glue kernels of the latter are csrc/hsad_search.hip.
 
 PolicySearch(replay=True) first plays every sampled world again from its first move (GameLog, hsad_search_world_script,
 hsad_env_rewind_scripted, hsad_search_replay_actions), so that each seat's LSTM state is the one that world's observations give.
@@ -73,14 +74,20 @@ def search_jobs(root):
     return np.asarray(pairs, dtype=np.int64).reshape(-1, 2), cur
 
 
-def mc_action_values(root, worlds, seed, capacity=4096, max_iter=None, sampler="rejection"):
+def mc_action_values(root, worlds, seed, capacity=4096, max_iter=None, sampler="rejection", playout=None):
     """float32 [G, A] on the root's device: values[g, a] = mean final score (HSAD_Q_SCORE: honours `bomb`) over `worlds` random
     playouts of action a by the player on turn of root game g; NaN for illegal actions and for games that are not live.  The root
     env is only read.  The result does not depend on `capacity` (jobs are keyed by (game, world), never by the slot they run in).
     A world whose sampler gave up (32 rejected tries: not seen in practice) keeps the true hand.  sampler="stratified" draws the
     hands with determinize_exact instead: never gives up, and the worlds of a game cover its exact belief evenly (world w takes the
-    w-th of `worlds` equal parts); keys, seeds and everything after the draw are the same."""
+    w-th of `worlds` equal parts); keys, seeds and everything after the draw are the same.  playout: None plays the worlds out with
+    random legal moves; a rulebot.RuleBot plays them out with that bot on every seat (playout_rule in place of playout_random:
+    jobs, keys, seeds and samplers are unchanged)."""
     _check_sampler(sampler)
+    if playout is not None:
+        from .rulebot import RuleBot
+        if not isinstance(playout, RuleBot):
+            raise ValueError("playout must be None or a rulebot.RuleBot; got %r" % (playout,))
     G, P, A = root.G, root.P, root.A
     dev = root.device
     values = np.full((G, A), np.nan, dtype=np.float32)
@@ -110,7 +117,10 @@ def mc_action_values(root, worlds, seed, capacity=4096, max_iter=None, sampler="
             act = torch.full((capacity, P), A - 1, dtype=torch.int64, device=dev)   # the noop for the players not on turn
             act[slot, p_c] = torch.from_numpy(a_c).to(dev)
             senv.step(act, act)
-            senv.playout_random(max_iter, seed, key=key)
+            if playout is None:
+                senv.playout_random(max_iter, seed, key=key)
+            else:
+                senv.playout_rule(max_iter, playout, seed=seed, key=key)
             scores[c0:c0 + m] = senv.query()[:m, Q_SCORE].cpu().numpy()
         senv.check_errors()
     finally:

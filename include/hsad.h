@@ -238,7 +238,8 @@ int hsad_env_rollout_resident_workgroups(const hsad_env* env);
  * the last call; synchronises the device.  first_game/first_code (may be NULL) describe the first.
  * Codes: 1 illegal move, 2 illegal greedy move, 3 step on a finished game, 4 hsad_env_fork / hsad_env_restore source index out of
  * range, 5 a deal script names a card the deck does not hold (hsad_env_rewind_scripted), 6 hsad_env_import_state / hsad_env_restore
- * refused a position (the call's status word holds the HSAD_POS_* flags that say why). */
+ * refused a position (the call's status word holds the HSAD_POS_* flags that say why), 7 a hsad_env_policy_rule seat_bot entry names
+ * no bot. */
 int hsad_env_error_count(hsad_env* env, int32_t* count, int32_t* first_game, int32_t* first_code);
 
 /* ---- The env as a simulator for test-time search (determinised Monte Carlo, SPARTA-style single-agent search): branch a game,
@@ -318,6 +319,88 @@ int hsad_env_determinize_exact(hsad_env* env, const int32_t* viewer, const int64
 int hsad_env_playout_random(hsad_env* env, int max_iter, uint64_t policy_seed, int64_t* a, int64_t* greedy_a, void* stream);
 int hsad_env_playout_random_keyed(hsad_env* env, int max_iter, uint64_t policy_seed, const int64_t* key, int64_t* a, int64_t* greedy_a,
                                   void* stream);
+
+/* ---- Rule-list bots: a hand-coded Hanabi policy evaluated on the state planes on the device.  A bot is an ordered list of at most
+ * HSAD_RULE_MAX_RULES rules; the first rule that fires gives the action, and if none fires the action is the lowest set bit of the
+ * seat's legal mask.  Pure integer logic: every result is exact.  This text is the specification (csrc/hsad_rulebot.h follows it,
+ * tests/rulebot_ref.py restates it); the rule names echo rule-based agents of the Hanabi literature, but no fidelity to any published
+ * bot is claimed.
+ *
+ * The bot of seat p reads only what p may see: full[t] (copies of card type t = colour * 5 + rank under the env's rules, 0 outside
+ * them), fireworks fw[c], discards, info, life, deck size, the other seats' cards with their knowledge words, and for its own slots
+ * only the plausible-colour / plausible-rank masks and the hinted flags -- never its own cards.  Definitions:
+ *   pool[t]   = deck count + copies in p's own hand (the pool of hsad_env_determinize);
+ *   compat_i  = colour(t) and rank(t) both plausible for own slot i;   n_i = sum_t pool[t] compat_i[t]  (>= 1 in a valid position);
+ *   playable(t): rank == fw[c];   dead(t): rank < fw[c], or some rank r' with fw[c] <= r' < rank has discards[c*5+r'] == full[c*5+r'];
+ *   play_i, dead_i = the sum of n_i restricted to playable / dead types;
+ *   a card in another hand is PUBLICLY KNOWN X when every type with full[t] > 0 in that slot's compat mask is X;
+ *   scans over the partners' cards go by target offset 1 .. P-1, then by slot ascending, and the first hit wins;
+ *   THE HINT FOR a card: the rank hint if that slot's plausible-rank mask has more than one bit, otherwise the colour hint if its
+ *   plausible-colour mask has more than one bit; if both masks are singletons the card does not qualify and the scan goes on;
+ *   every hint rule needs info > 0, every discard rule needs info < max_information_tokens;
+ *   ratios are compared by integer cross-multiplication: x_i / n_i reaches k % iff x_i * 100 >= k * n_i, the best slot has the largest
+ *   x_i / n_i (slot j beats slot b iff x_j * n_b > x_b * n_j), ties go to the lowest slot.
+ * Rules (code, fires when -> action):
+ *    1 PLAY_CERTAIN             lowest own slot with play_i == n_i -> play it
+ *    2 PLAY_PROBABLE(k)         life > 1 and the best slot by play_i / n_i reaches k % -> play it
+ *    3 PLAY_PROBABLE_ENDGAME(k) as 2, and the deck is empty
+ *    4 HINT_PLAYABLE            first partner card that is playable and not publicly known playable (and qualifies) -> the hint for it
+ *    5 HINT_USEFUL              first partner card that is not dead and qualifies -> the hint for it
+ *    6 HINT_DEAD                first partner card that is dead and not publicly known dead (and qualifies) -> the hint for it
+ *    7 HINT_RANDOM              hash pick among the hint bits of the legal mask (there is one)
+ *    8 DISCARD_CERTAIN_DEAD     lowest own slot with dead_i == n_i -> discard it
+ *    9 DISCARD_PROBABLE_DEAD(k) the best slot by dead_i / n_i reaches k % -> discard it
+ *   10 DISCARD_UNHINTED_OLDEST  lowest own slot with neither hinted flag set -> discard it
+ *   11 DISCARD_OLDEST           -> discard slot 0 (new cards are appended: slot 0 is the oldest)
+ *   12 DISCARD_RANDOM           hash pick among the discard bits of the legal mask
+ *   13 LEGAL_RANDOM             hash pick over the whole legal mask
+ * k is 0 .. 100 for codes 2, 3 and 9 and must be 0 for every other code.  Action uids are those of the legal_move row: discard slot i
+ * = i, play slot i = H + i, colour hint = 2H + (o-1) C + colour, rank hint = 2H + (P-1) C + (o-1) R + rank (o the target offset), noop
+ * = A - 1; with shuffle_color a colour hint names the colour through the ACTOR's permutation, as its legal_move row does.  A seat that
+ * is not on turn gets the noop.  greedy_a = a.  A hash pick is hsad_env_policy_random's: the k-th set bit, k = h % popcount, with
+ *   h = hash(seed, key, counter, 128 + 16 p + j),   j = the rule's index in the list
+ * (the random policy owns streams 0 .. 2P-1, the samplers 64 and 65); counter is the game's policy counter, read once and
+ * incremented once per policy call, as hsad_env_policy_random does; key is key[g], or g when key == NULL.
+ *
+ * hsad_env_policy_rule: one policy call on the env's current state.  rules: HOST array [n_bot][HSAD_RULE_MAX_RULES] (bot b's list is
+ * rules[b * 8 .. b * 8 + n_rules[b])); n_rules HOST int32 [n_bot].  seat_bot DEVICE int32 [G * P]: the bot that plays row g * P + p;
+ * -1 leaves that row of a / greedy_a untouched.  A game whose P entries are all -1 is not touched at all (its counter included);
+ * every other game's counter advances by one.  An entry below -1 or >= n_bot leaves the row alone and is counted in the env's error
+ * log (code 7).  greedy_a may be NULL.  Reads the state planes only (no bound output is needed beyond hsad_env_bind_outputs).
+ *
+ * hsad_env_playout_rule: hsad_env_playout_random with the bots in place of the random pick: up to max_iter iterations of policy ->
+ * step for every live game in one launch, finished games left alone (no counter advance), no observation rows written, `terminal`,
+ * hsad_env_query and the legal masks current afterwards.  seat_bot_of_seat HOST int32 [P]: the bot of each seat, the same in every
+ * game.  A live game's trajectory is that of hsad_env_policy_rule + hsad_env_step.  Refused while the env holds a deal script.
+ *
+ * Both return HSAD_ERR_INVALID with a message, before anything is launched, for: n_bot outside 1 .. HSAD_RULE_MAX_BOTS, an n_rules
+ * entry outside 1 .. HSAD_RULE_MAX_RULES, an unknown rule code, k out of range, a seat_bot_of_seat entry outside 0 .. n_bot-1, more
+ * than 5 players.  Launch-only. */
+enum {
+  HSAD_RULE_PLAY_CERTAIN = 1,
+  HSAD_RULE_PLAY_PROBABLE = 2,
+  HSAD_RULE_PLAY_PROBABLE_ENDGAME = 3,
+  HSAD_RULE_HINT_PLAYABLE = 4,
+  HSAD_RULE_HINT_USEFUL = 5,
+  HSAD_RULE_HINT_DEAD = 6,
+  HSAD_RULE_HINT_RANDOM = 7,
+  HSAD_RULE_DISCARD_CERTAIN_DEAD = 8,
+  HSAD_RULE_DISCARD_PROBABLE_DEAD = 9,
+  HSAD_RULE_DISCARD_UNHINTED_OLDEST = 10,
+  HSAD_RULE_DISCARD_OLDEST = 11,
+  HSAD_RULE_DISCARD_RANDOM = 12,
+  HSAD_RULE_LEGAL_RANDOM = 13,
+  HSAD_RULE_MAX_RULES = 8,
+  HSAD_RULE_MAX_BOTS = 8
+};
+typedef struct hsad_rule {
+  int32_t code;
+  int32_t k;
+} hsad_rule;
+int hsad_env_policy_rule(hsad_env* env, const hsad_rule* rules, const int32_t* n_rules, int n_bot, const int32_t* seat_bot, uint64_t seed,
+                         const int64_t* key, int64_t* a, int64_t* greedy_a, void* stream);
+int hsad_env_playout_rule(hsad_env* env, int max_iter, const hsad_rule* rules, const int32_t* n_rules, int n_bot,
+                          const int32_t* seat_bot_of_seat, uint64_t seed, const int64_t* key, int64_t* a, int64_t* greedy_a, void* stream);
 
 /* hsad_env_rewind_scripted: start games again from a deal somebody else chose.  script device uint8 [G, 52]: card types
  * (colour * 5 + rank) in deal order, the layout of the deck history (hsad_env_deck_history rows padded to 52); count device int32

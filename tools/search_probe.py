@@ -1,8 +1,9 @@
 """Records for DESIGN §3g: fork + observe time, the playout's env-steps/s without the observation stream, the sampler's mean tries,
 next to hsad_env_step on the same games; with --sampler stratified also the time of hsad_env_determinize_exact + observe on the same
-states (8 strata), and in either case the time of hsad_env_hand_belief.  One JSON line.
+states (8 strata), and in either case the time of hsad_env_hand_belief; with --playout NAME (a preset of hanabi_sad_amd.rulebot) the
+env-steps/s of hsad_env_playout_rule next to hsad_env_playout_random's from the same states.  One JSON line.
 
-    python tools/search_probe.py [--games 65536] [--repeats 5] [--sampler rejection|stratified]
+    python tools/search_probe.py [--games 65536] [--repeats 5] [--sampler rejection|stratified] [--playout cautious|piers|flawed|random]
 """
 import argparse
 import json
@@ -15,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hanabi_sad_amd import BatchedHanabiEnv  # noqa: E402
+from hanabi_sad_amd.rulebot import PRESETS  # noqa: E402
 
 
 def timed(fn, repeats):
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sad", type=int, default=1)
     ap.add_argument("--sampler", choices=["rejection", "stratified"], default="rejection")
+    ap.add_argument("--playout", choices=sorted(PRESETS), default=None)
     args = ap.parse_args()
     G, dev = args.games, "cuda:0"
     kw = dict(players=2, hand_size=5, sad=bool(args.sad), eps_list=(0.0,), device=dev)
@@ -99,6 +102,21 @@ def main():
         rates.append(steps / ms * 1e3)
     dst.check_errors()
     res["playout_ms"], res["playout_env_steps_per_s"] = play_ms, rates
+    if args.playout:   # the same states, the same reseeded generators, the bot in place of the random pick
+        bot, rule_rates, rule_ms, rule_score = PRESETS[args.playout], [], [], []
+        for r in range(args.repeats):
+            dst.fork_from(src, torch.arange(G, device=dev, dtype=torch.int32), seeds)
+            n0 = dst.query()[:, 6].sum().item()
+            ms = timed(lambda: dst.playout_rule(100, bot, seed=9 + r), 1)[0]
+            qq = dst.query()
+            assert bool((qq[:, 0] == 1).all())
+            rule_ms.append(ms)
+            rule_rates.append((qq[:, 6].sum().item() - n0) / ms * 1e3)
+            rule_score.append(float(qq[:, 5].double().mean()))
+        dst.check_errors()
+        res["playout_rule"], res["playout_rule_ms"], res["playout_rule_env_steps_per_s"] = args.playout, rule_ms, rule_rates
+        res["playout_rule_mean_score"] = rule_score
+        medians += ["playout_rule_ms", "playout_rule_env_steps_per_s"]
     for k in ("fork_observe_ms", "fork_observe_reseed_ms", "env_step_ms", "determinize_observe_ms", "playout_ms", "playout_env_steps_per_s", *medians):
         res[k + "_median"] = statistics.median(res[k])
     print(json.dumps(res))

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "hsad.h"
+#include "hsad_deal_fast.h"
 
 namespace {
 
@@ -346,16 +347,7 @@ __device__ __forceinline__ int deal_pick(int deal_mode, uint64_t deck, int deck_
     const uint64_t lo = S * (uint64_t)deck_size;
     const uint64_t hi = __umul64hi(S, (uint64_t)deck_size);
     if (lo >= (1ull << 28) && lo <= 0ull - (1ull << 28)) {
-      const uint32_t need = (uint32_t)hi + 1u;
-      const uint32_t dlo = (uint32_t)deck, dhi = (uint32_t)(deck >> 32);
-      uint32_t acc = 0;
-      int pick = -1;
-#pragma unroll
-      for (int t = 0; t < 25; ++t) {
-        acc += (t < 16) ? ((dlo >> (2 * t)) & 3u) : ((dhi >> (2 * (t - 16))) & 3u);
-        if (pick < 0 && acc >= need) pick = t;
-      }
-      return pick;
+      return df_pick(deck, (uint32_t)hi + 1u);   // hi < deck_size: 1 <= need <= cards in the deck
     }
   }
   return deal_pick_exact(deck, deck_size, u1, u2);
@@ -1120,10 +1112,17 @@ __device__ __forceinline__ uint32_t policy_hash(uint64_t seed, uint64_t game, ui
 __device__ __forceinline__ int policy_pick(uint64_t seed, uint64_t game, uint64_t counter, int p, int stream,
                                            uint64_t mask) {
   const uint32_t h = policy_hash(seed, game, counter, (uint64_t)(p * 2 + stream));
-  int k = (int)(h % (uint32_t)__popcll(mask));
-  uint64_t m = mask;
-  while (k-- > 0) m &= m - 1;
-  return (int)__builtin_ctzll(m);
+  return df_select(mask, h % (uint32_t)__popcll(mask));
+}
+// The same pick from the hash's inner key, which depends on launch constants only (seed, game, player, stream): a launch that
+// keeps its games computes the keys once (env_rollout_pipe_kernel, LogicCarry) and pays one mix64 per pick instead of three.
+// nbits: bound on the mask's width (df_select).
+__device__ __forceinline__ uint64_t policy_key(uint64_t seed, uint64_t game, int p, int stream) {
+  return mix64(seed ^ mix64(game * 0xD1342543DE82EF95ull + (uint64_t)(p * 2 + stream)));
+}
+__device__ __forceinline__ int policy_pick_keyed(uint64_t key, uint64_t counter, uint64_t mask, int nbits) {
+  const uint32_t h = (uint32_t)(mix64(key + counter) >> 32);
+  return df_select(mask, h % (uint32_t)__popcll(mask), nbits);
 }
 
 // =================================================================================================
@@ -1210,10 +1209,24 @@ __device__ __forceinline__ void clear_rows(const EnvParams& ep, uint32_t* s_obs,
 //            uses that column only in an iteration in which its game restarts, and then recomputes its masks from the fresh state,
 //            so the two never meet; the words cost no LDS.  The launch's prologue fills them from EnvParams::legal_bits: nothing is
 //            assumed about what ran before the launch.  (Every window holds 2PH + P + 2 words or more per lane, hsad_env_create.)
+//   pkey:    this lane's policy keys (policy_key of player p, stream s at [2p + s]), computed in the launch's prologue: game, seed,
+//            player and stream do not change during a launch.  Only in the instances kPolicyKeys names (two registers per key; the
+//            others have none to spare without scratch) -- elsewhere nullptr and never read.
 struct LogicCarry {
   uint32_t* counter;
   const uint32_t* s_lmask;
+  const uint64_t* pkey;
 };
+template <int TP, int TH>
+constexpr bool kPolicyKeys = (TP == 2 && TH == 5);
+// key i of N: constant indices only, so the keys stay in registers whether or not the loop over the players is unrolled
+template <int N>
+__device__ __forceinline__ uint64_t carried_key(const uint64_t* k, int i) {
+  uint64_t v = k[0];
+#pragma unroll
+  for (int j = 1; j < N; ++j) v = (i == j) ? k[j] : v;
+  return v;
+}
 typedef __attribute__((address_space(3))) const uint32_t* LdsWordPtr;   // a load through it is an LDS instruction, never a flat one
 
 // The game logic of one iteration for the 64 games of the logic wave (wave 0): reset-if-terminated (MODE 0 / 3), then the
@@ -1222,26 +1235,35 @@ template <int MODE, int TP, int TH, bool V = false, class EP = EnvParams, bool C
 __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restrict__ a_in, const int64_t* __restrict__ g_in,
                                           uint32_t* s_st, uint32_t* s_win, const float* s_eps, const int lane, const int g,
                                           const bool active, const bool do_reset, Rng& rng, uint32_t& greedy_rec, float& reward,
-                                          bool& term, const int dbg_it = 0, const LogicCarry carry = {nullptr, nullptr}) {
+                                          bool& term, const int dbg_it = 0, const LogicCarry carry = {nullptr, nullptr, nullptr}) {
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
   const auto ru = RulesOf<V>::make(ep);
   if (MODE == 0 || MODE == 3) {
     // ---- prefetch window: every mt19937 word this reset will regenerate, in one round trip ----
     const int W = ep.win_w;
+    // what hsad_env_create can set W to in this instance: 2PH + P + 2 draws of a reset, with shuffle_color 1 + 2 (P - 1) more, 64 at most
+    constexpr int kWmin = (TP && !V) ? (2 * TP * TH + TP + 2 < 64 ? 2 * TP * TH + TP + 2 : 64) : 0;
+    constexpr int kWmax = (TP && !V) ? (kWmin + 1 + 2 * (TP - 1) < 64 ? kWmin + 1 + 2 * (TP - 1) : 64) : 64;
+    constexpr int kNB = kWmax <= 32 ? kWmax : 32;   // words of the one-batch form
     uint32_t* winA = s_win + lane;                   // x[wbase + k],       k in [0, W]   (W > 32 only)
     uint32_t* winB = s_win + (W <= 32 ? 0 : (W + 1) * kWave) + lane;  // x[wbase + k + 397], k in [0, W) -> new words
     const uint32_t wbase = rng.spos;
     if (do_reset) {
-      if (W <= 32) {
-        // one batch: all 2W+1 words in flight together, regenerated in registers, only the new words go to LDS
-        uint32_t va[33], vb[32];
+      if (kWmax <= 32 || (kWmin <= 32 && W <= 32)) {
+        // one batch: all 2 kNB + 1 words in flight together, regenerated in registers, only the new words go to LDS.  wbase < 624
+        // and j + 397 < 624, so an index wraps at most once: the lane's base pointer or the one 624 words below it, and the
+        // word's offset in the instruction (words past W are real state words, loaded and left unused)
+        const uint32_t* pw = rng.mt + wbase;
+        const uint32_t* pw_wrapped = pw - kMtN;
+        const int n0 = kMtN - (int)wbase;   // the first j for which wbase + j wraps
+        uint32_t va[kNB + 1], vb[kNB];
 #pragma unroll
-        for (int j = 0; j < 33; ++j) va[j] = rng.mt[(wbase + (uint32_t)min(j, W)) % (uint32_t)kMtN];
+        for (int j = 0; j <= kNB; ++j) va[j] = (j >= n0 ? pw_wrapped : pw)[j];
 #pragma unroll
-        for (int j = 0; j < 32; ++j) vb[j] = rng.mt[(wbase + (uint32_t)min(j, W) + kMtM) % (uint32_t)kMtN];
+        for (int j = 0; j < kNB; ++j) vb[j] = (j >= n0 - kMtM ? pw_wrapped : pw)[j + kMtM];
 #pragma unroll
-        for (int j = 0; j < 32; ++j)
-          if (j < W) winB[j * kWave] = mt_twist(va[j], va[j + 1], vb[j]);
+        for (int j = 0; j < kNB; ++j)
+          if (j < kWmin || j < W) winB[j * kWave] = mt_twist(va[j], va[j + 1], vb[j]);
       } else {
         for (int k0 = 0; k0 <= W; k0 += 16) {
           uint32_t va[16], vb[16];
@@ -1263,7 +1285,7 @@ __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restric
       STAMP(6);
       rng.win = winB;
       rng.w_n = W;
-      rng.spos = (wbase + (uint32_t)W) % (uint32_t)kMtN;
+      rng.spos = df_wrap624(wbase, (uint32_t)W);
 
       // HanabiEnv::reset (cpp/hanabi_env.cc:9-47): fresh HanabiState, deal until no chance node
       const uint64_t deck = ru.full;
@@ -1289,19 +1311,64 @@ __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restric
             full_kr |= ru.rmask << (5 * i);
           }
         }
-        for (int p = 0; p < P; ++p) {
-          uint32_t hw = 0;
-          for (int i = 0; i < H; ++i) {
-            const int t = deal_pick(ep.deal_mode, dk, dsize, rng);
-            dk -= (uint64_t)1 << (2 * t);
-            if (ep.track_dh) ep.deck_hist[(size_t)g * 52 + (ru.deck - dsize)] = (uint8_t)t;
-            dsize -= 1;
-            hw |= (uint32_t)t << (5 * i);
+        if constexpr (TP > 0 && !V) {
+          // The full deck keeps two card types or more while these P H <= 20 cards leave it, so the deal takes exactly 2 P H
+          // draws, and they are known in advance: the buffered look-ahead outputs first (la_n of them), then the window's words
+          // in order (it holds 2PH + P + 2 or more).  No generator call, no branch on where a draw comes from; card k leaves a
+          // deck of 50 - k.  The pick is deal_pick's: the bounded search inside the band, the literal restatement outside it and
+          // under deal_mode 1.  The generator's bookkeeping is set afterwards to what 2 P H calls of rng_next leave.
+          const int la_start = rng.la_n;
+          int wpos = -la_start;   // window word of the next draw (below 0: a look-ahead output)
+          uint32_t dleft = (uint32_t)ru.deck;
+#pragma clang loop unroll(disable)
+          for (int p = 0; p < P; ++p) {
+            uint32_t hw = 0;
+#pragma clang loop unroll(disable)
+            for (int i = 0; i < H; ++i) {
+              uint32_t u1 = mt_temper(winB[max(wpos, 0) * kWave]);
+              uint32_t u2 = mt_temper(winB[max(wpos + 1, 0) * kWave]);
+              if (wpos < 0) {   // the first card only
+                u1 = rng.la0;
+                if (wpos < -1) u2 = rng.la1;
+              }
+              wpos += 2;
+              const uint64_t p0 = (uint64_t)u1 * dleft, p1 = (uint64_t)u2 * dleft + (p0 >> 32);   // (u1 + 2^32 u2) dleft, 96 bits
+              const uint64_t lo = (uint64_t)(uint32_t)p0 | (p1 << 32);
+              int t;
+              if (ep.deal_mode == 0 && lo >= (1ull << 28) && lo <= 0ull - (1ull << 28))
+                t = df_pick(dk, (uint32_t)(p1 >> 32) + 1u);
+              else
+                t = deal_pick_exact(dk, (int)dleft, u1, u2);
+              dk -= (uint64_t)1 << (2 * t);
+              if (ep.track_dh) ep.deck_hist[(size_t)g * 52 + (ru.deck - (int)dleft)] = (uint8_t)t;
+              dleft -= 1u;
+              hw |= (uint32_t)t << (5 * i);
+            }
+            ST(PLH(p)) = hw | ((uint32_t)H << 25);
+            ST(PLKCP(p)) = full_kc;
+            ST(PLKRP(p)) = full_kr;
+            ST(PLKH(p)) = 0;
           }
-          ST(PLH(p)) = hw | ((uint32_t)H << 25);
-          ST(PLKCP(p)) = full_kc;
-          ST(PLKRP(p)) = full_kr;
-          ST(PLKH(p)) = 0;
+          dsize = (int)dleft;
+          rng.draws += (uint32_t)(2 * P * H);
+          if (la_start > 0) rng.la0 = rng.la1;
+          rng.la_n = 0;
+          rng.w_c = 2 * P * H - la_start;
+        } else {
+          for (int p = 0; p < P; ++p) {
+            uint32_t hw = 0;
+            for (int i = 0; i < H; ++i) {
+              const int t = deal_pick(ep.deal_mode, dk, dsize, rng);
+              dk -= (uint64_t)1 << (2 * t);
+              if (ep.track_dh) ep.deck_hist[(size_t)g * 52 + (ru.deck - dsize)] = (uint8_t)t;
+              dsize -= 1;
+              hw |= (uint32_t)t << (5 * i);
+            }
+            ST(PLH(p)) = hw | ((uint32_t)H << 25);
+            ST(PLKCP(p)) = full_kc;
+            ST(PLKRP(p)) = full_kr;
+            ST(PLKH(p)) = 0;
+          }
         }
         ST(PL_DECK_LO) = (uint32_t)dk;
         ST(PL_DECK_HI) = (uint32_t)(dk >> 32);
@@ -1369,8 +1436,12 @@ __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restric
         la_push(rng, mt_temper(winB[rng.w_c * kWave]));
         rng.w_c += 1;
       }
-      for (int k = 0; k < rng.w_c; ++k) rng.mt[(wbase + (uint32_t)k) % (uint32_t)kMtN] = winB[k * kWave];
-      if (rng.w_c < rng.w_n) rng.spos = (wbase + (uint32_t)rng.w_c) % (uint32_t)kMtN;
+      uint32_t wi = wbase;
+      for (int k = 0; k < rng.w_c; ++k) {
+        rng.mt[wi] = winB[k * kWave];
+        wi = wrap624(wi + 1u);
+      }
+      if (rng.w_c < rng.w_n) rng.spos = df_wrap624(wbase, (uint32_t)rng.w_c);
       rng.w_n = rng.w_c;
     }
   }
@@ -1395,6 +1466,9 @@ __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restric
             ep.act_count[g] = counter + 1u;
           }
           uid = guid = 0;
+          // the greedy stream's pick is read by the SAD step and by a caller that asked for it; nobody else pays for it
+          const bool need_g = ep.sad || ep.g_out != nullptr;
+          constexpr int kABits = (TP && !V) ? 2 * TH + (TP - 1) * 10 + 1 : 64;   // A of the full game: no legal bit at or above it
           for (int p = 0; p < P; ++p) {
             // legal bits of the state the policy acts on: the stored side output (global memory, or the copy build_rows left
             // in LDS: LogicCarry), or (MODE 3, game restarted a moment ago in this very launch) recomputed from the fresh state
@@ -1411,8 +1485,14 @@ __device__ __forceinline__ void env_logic(const EP& ep, const int64_t* __restric
                                                   ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru)
                               : ep.legal_bits[(size_t)g * P + p];
             }
-            const int pa = policy_pick(ep.policy_seed, (uint64_t)g, (uint64_t)counter, p, 0, mask);
-            const int pg = policy_pick(ep.policy_seed, (uint64_t)g, (uint64_t)counter, p, 1, mask);
+            int pa, pg = 0;
+            if constexpr (CARRY && kPolicyKeys<TP, TH>) {
+              pa = policy_pick_keyed(carried_key<2 * TP>(carry.pkey, 2 * p), (uint64_t)counter, mask, kABits);
+              if (need_g) pg = policy_pick_keyed(carried_key<2 * TP>(carry.pkey, 2 * p + 1), (uint64_t)counter, mask, kABits);
+            } else {
+              pa = policy_pick(ep.policy_seed, (uint64_t)g, (uint64_t)counter, p, 0, mask);
+              if (need_g) pg = policy_pick(ep.policy_seed, (uint64_t)g, (uint64_t)counter, p, 1, mask);
+            }
             ep.a_out[(size_t)g * P + p] = pa;
             if (ep.g_out) ep.g_out[(size_t)g * P + p] = pg;
             if (p == cur) {
@@ -1827,10 +1907,15 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
 
   // prologue: the logic wave stages the state planes and its act counters, the stream wave clears the rows and copies the eps list
   uint32_t act_counter = 0u;   // this lane's EnvParams::act_count, carried in a register for the launch (LogicCarry)
+  uint64_t pkey[kPolicyKeys<TP, TH> ? 2 * TP : 1] = {};   // and its policy keys, where the instance has the registers
   if (wave == 0) {
     const int g = g0 + lane;
     if (lane < ng) {
       act_counter = ep.act_count[g];
+      if constexpr (kPolicyKeys<TP, TH>) {
+#pragma unroll
+        for (int k = 0; k < 2 * TP; ++k) pkey[k] = policy_key(ep.policy_seed, (uint64_t)g, k >> 1, k & 1);
+      }
       for (int p = 0; p < P; ++p) {   // the masks the previous launch, step or reset left: where build_rows leaves them from now on
         const uint64_t lm = ep.legal_bits[(size_t)g * P + p];
         s_win[(2 * p) * kWave + lane] = (uint32_t)lm;
@@ -1884,7 +1969,7 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       rng.la_n = (int)((misc0 >> 22) & 3u);
       rng.spos = (rng.draws + (uint32_t)rng.la_n) % (uint32_t)kMtN;
       uint32_t greedy_rec = 0;
-      const LogicCarry carry = {&act_counter, s_win};
+      const LogicCarry carry = {&act_counter, s_win, pkey};
       env_logic<3, TP, TH, false, EnvParams, true>(ep, nullptr, nullptr, s_st, s_win, s_eps, lane, g, valid, do_reset, rng, greedy_rec, reward,
                                                    term, dbg_it, carry);
       s_grec[lane] = greedy_rec;

@@ -62,6 +62,12 @@ class ActorIO(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("legal_move", "own_hand", "eps", "reward", "terminal", "priv_bits", "legal_bits", "own_bits", "priv_s_bf16")]
 
 
+class ActorPartners(C.Structure):
+    """hsad_actor_partners (include/hsad.h): host arrays"""
+    _fields_ = [("rows", C.c_void_p), ("M", C.c_int32), ("rules", C.c_void_p), ("n_rules", C.c_void_p), ("n_bot", C.c_int32),
+                ("seat_bot", C.c_void_p), ("bot_seed", C.c_uint64)]
+
+
 class LstmFusedBwdRec(C.Structure):
     """hsad_lstm_fused_bwd_rec (include/hsad.h)"""
     _fields_ = [("WhhT_blocked", C.c_void_p), ("WihT_above_blocked", C.c_void_p), ("gates", C.c_void_p), ("cseq", C.c_void_p),
@@ -252,6 +258,8 @@ SIGNATURES = {
     "hsad_gemm_f32": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int,
                                 C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "hsad_actor_create": (C.c_int, [_P, _P, _P, _P, C.POINTER(ActorConfig), C.POINTER(ActorIO), C.POINTER(_P)]),
+    "hsad_actor_create_partnered": (C.c_int, [_P, _P, _P, _P, C.POINTER(ActorConfig), C.POINTER(ActorIO), C.POINTER(ActorPartners),
+                                              C.POINTER(_P)]),
     "hsad_actor_destroy": (None, [_P]),
     "hsad_actor_step": (C.c_int, [_P, _P]),
     "hsad_actor_set_run_ahead": (C.c_int, [_P, C.c_int]),

@@ -27,12 +27,135 @@ def transition_fields(env, vdn=False):
             ("own_hand", m * 3 * env.H, binary), ("a", m, torch.int64), ("greedy_a", m, torch.int64)]
 
 
+class PartnerSeatsError(ValueError):
+    """a seat layout hsad_actor_create_partnered refuses; .verdict = (code, index, value)"""
+
+    def __init__(self, text, verdict):
+        super().__init__(text)
+        self.verdict = verdict
+
+
+class PartnerSeats:
+    """Who sits where when the learner trains next to fixed partners (include/hsad.h, hsad_actor_partners): `rows` int32 [M], the
+    learner's rows g * P + p, strictly ascending; `seat_bot` int32 [G * P], -1 on exactly those rows and an index into `bots`
+    (rulebot.RuleBot, at most 8) on every other row.  `verdict` / `check` restate the library's check (csrc/hsad_partner.h), refusal
+    for refusal and in its order, so that a layout can be judged without a device."""
+    OK, VDN, PLAYERS, NUM_ROWS, ROW_RANGE, ROW_ORDER, N_BOT, N_RULES, RULE_CODE, RULE_K, LEARNER_BOT, PARTNER_BOT = range(12)
+
+    def __init__(self, bots, rows, seat_bot, bot_seed=0):
+        import numpy as np
+        from . import rulebot
+        self.bots = [bots] if isinstance(bots, rulebot.RuleBot) else list(bots)
+        self.rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1).astype(np.int32))
+        self.seat_bot = np.ascontiguousarray(np.asarray(seat_bot, dtype=np.int64).reshape(-1).astype(np.int32))
+        self.bot_seed = int(bot_seed)
+
+    @property
+    def M(self):
+        return int(self.rows.shape[0])
+
+    @classmethod
+    def alternate(cls, G, P, bots, bot_seed=0):
+        """the learner sits on seat g % P of game g and every other seat of that game gets bot (g // P) % len(bots): seats and
+        partners are balanced over the batch"""
+        import numpy as np
+        from . import rulebot
+        bots = [bots] if isinstance(bots, rulebot.RuleBot) else list(bots)
+        g = np.arange(G)
+        return cls._one_learner_seat(G, P, g % P, (g // P) % max(len(bots), 1), bots, bot_seed)
+
+    @classmethod
+    def fixed_seat(cls, G, P, seat, bots, bot_seed=0):
+        """the learner sits on `seat` in every game; the other seats of game g get bot g % len(bots)"""
+        import numpy as np
+        from . import rulebot
+        bots = [bots] if isinstance(bots, rulebot.RuleBot) else list(bots)
+        if not 0 <= int(seat) < P:
+            raise PartnerSeatsError("fixed_seat: seat = %d, must be 0..%d" % (seat, P - 1), (cls.ROW_RANGE, 0, int(seat)))
+        g = np.arange(G)
+        return cls._one_learner_seat(G, P, np.full(G, int(seat)), g % max(len(bots), 1), bots, bot_seed)
+
+    @classmethod
+    def _one_learner_seat(cls, G, P, seat_of_game, bot_of_game, bots, bot_seed):
+        import numpy as np
+        seat_bot = np.repeat(bot_of_game.astype(np.int32), P).reshape(G, P)
+        seat_bot[np.arange(G), seat_of_game] = -1
+        return cls(bots, np.arange(G) * P + seat_of_game, seat_bot, bot_seed)
+
+    def verdict(self, G, P, hand_size=5, vdn=False):
+        """(code, index, value) of partner_layout_verdict (csrc/hsad_partner.h): (0, 0, 0) for a layout the library runs"""
+        from . import rulebot
+        N, M, n_bot = G * P, self.M, len(self.bots)
+        rows, sb = self.rows.tolist(), self.seat_bot.tolist()
+        if vdn:
+            return (self.VDN, 0, int(vdn))
+        if P > 5 or hand_size > 5:
+            return (self.PLAYERS, 0, P)
+        if M < 1 or M > N:
+            return (self.NUM_ROWS, 0, M)
+        for i, r in enumerate(rows):
+            if r < 0 or r >= N:
+                return (self.ROW_RANGE, i, r)
+            if i > 0 and r <= rows[i - 1]:
+                return (self.ROW_ORDER, i, r)
+        if n_bot > rulebot.MAX_BOTS or (n_bot == 0 and M != N):
+            return (self.N_BOT, 0, n_bot)
+        for b, bot in enumerate(self.bots):
+            if not 1 <= len(bot.rules) <= rulebot.MAX_RULES:
+                return (self.N_RULES, b, len(bot.rules))
+            for code, k in bot.rules:      # rb_rules_invalid: per rule, the code first, then k
+                if not rulebot.PLAY_CERTAIN <= code <= rulebot.LEGAL_RANDOM:
+                    return (self.RULE_CODE, b, 0)
+                if (not 0 <= k <= 100) if code in rulebot._WITH_K else (k != 0):
+                    return (self.RULE_K, b, 0)
+        if len(sb) != N:
+            raise PartnerSeatsError("seat_bot has %d entries, the env has %d rows" % (len(sb), N), (self.PARTNER_BOT, len(sb), 0))
+        learner = set(rows)
+        for r in range(N):
+            if r in learner:
+                if sb[r] != -1:
+                    return (self.LEARNER_BOT, r, sb[r])
+            elif sb[r] < 0 or sb[r] >= n_bot:
+                return (self.PARTNER_BOT, r, sb[r])
+        return (self.OK, 0, 0)
+
+    def explain(self, verdict, G, P):
+        """the text of a refusal (partner_verdict_text); it names the offending entry"""
+        from . import rulebot
+        code, i, v = verdict
+        n_bot = len(self.bots)
+        return {self.OK: "ok",
+                self.VDN: "cfg->vdn = %d: a partnered actor is an IQL actor (one transition per learner row)" % v,
+                self.PLAYERS: "more than 5 players or 5 cards a hand (players = %d)" % v,
+                self.NUM_ROWS: "M = %d learner rows, must be 1..%d" % (v, G * P),
+                self.ROW_RANGE: "rows[%d] = %d, must be 0..%d" % (i, v, G * P - 1),
+                self.ROW_ORDER: "rows[%d] = %d is not above rows[%d]: rows must be strictly ascending" % (i, v, i - 1),
+                self.N_BOT: "n_bot = %d, must be 1..%d (0 only when every row is the learner's)" % (v, rulebot.MAX_BOTS),
+                self.N_RULES: "bot %d has %d rules, must be 1..%d" % (i, v, rulebot.MAX_RULES),
+                self.RULE_CODE: "bot %d names an unknown rule code" % i,
+                self.RULE_K: "bot %d: k must be 0..100 for the PROBABLE rules and 0 for every other" % i,
+                self.LEARNER_BOT: "seat_bot[%d] = %d on a learner row, must be -1" % (i, v),
+                self.PARTNER_BOT: "seat_bot[%d] = %d on a partner row, must be 0..%d" % (i, v, n_bot - 1)}[code]
+
+    def check(self, G, P, hand_size=5, vdn=False):
+        v = self.verdict(G, P, hand_size, vdn)
+        if v[0] != self.OK:
+            raise PartnerSeatsError("PartnerSeats: " + self.explain(v, G, P), v)
+        return self
+
+
 class DeviceActor:
     def __init__(self, env: BatchedHanabiEnv, agent: R2D2Agent, replay: DeviceReplay, multi_step, gamma, eta, seq_len,
-                 vdn=False, packed_obs=None, native=None):
+                 vdn=False, packed_obs=None, native=None, partners=None):
         self.env, self.agent, self.replay = env, agent, replay
         self.G, self.P = env.G, env.P
-        self.N = self.G * self.P              # agent rows (hidden state [L, N, H]) in both layouts
+        self.partners = partners
+        if partners is not None:
+            if native is not None and not native:
+                self._refuse_python_partners()
+            partners.check(self.G, self.P, env.H, vdn)
+        # agent rows (hidden state [L, N, H]) in both layouts; with partners (PartnerSeats): the learner's rows only
+        self.N = self.G * self.P if partners is None else partners.M
         self.vdn = bool(vdn)
         self.E = self.G if self.vdn else self.N   # transitions per step
         self.eta = float(eta)
@@ -67,8 +190,16 @@ class DeviceActor:
         self.c_actor = None
         if native is None:
             native = self.packed_obs and hasattr(agent, "online") and hasattr(agent.online, "h") and hasattr(agent, "lib") and not getattr(agent.online, "skip", False)
+        if partners is not None and not native:
+            self._refuse_python_partners()
         if native:
             self._make_native(multi_step, gamma, seq_len)
+
+    @staticmethod
+    def _refuse_python_partners():
+        from . import _lib
+        raise _lib.HsadError("PartnerSeats need the library's loop body (hsad_actor_create_partnered): the Python actor path runs the "
+                             "agent on every row; use the composite bf16 agent with the packed observation path and native != False")
 
     @property
     def verify_cached_priority(self):
@@ -94,7 +225,16 @@ class DeviceActor:
         io = _lib.ActorIO(env.legal_move.data_ptr(), env.own_hand.data_ptr(), env.eps.data_ptr(), env.reward.data_ptr(), env.terminal.data_ptr(),
                           env.priv_bits.data_ptr(), env.legal_bits.data_ptr(), env.own_bits.data_ptr(), env.priv_s_bf16.data_ptr())
         h = C.c_void_p()
-        _lib.check(agent.lib.hsad_actor_create(env.h, agent.online.h, agent.target.h, self.replay.h, C.byref(cfg), C.byref(io), C.byref(h)))
+        if self.partners is not None:
+            from . import rulebot
+            pt = self.partners
+            rules, n_rules, n_bot = rulebot.pack(pt.bots)
+            part = _lib.ActorPartners(pt.rows.ctypes.data, pt.M, C.addressof(rules), C.addressof(n_rules), n_bot, pt.seat_bot.ctypes.data,
+                                      pt.bot_seed)
+            _lib.check(agent.lib.hsad_actor_create_partnered(env.h, agent.online.h, agent.target.h, self.replay.h, C.byref(cfg), C.byref(io),
+                                                             C.byref(part), C.byref(h)))
+        else:
+            _lib.check(agent.lib.hsad_actor_create(env.h, agent.online.h, agent.target.h, self.replay.h, C.byref(cfg), C.byref(io), C.byref(h)))
         self.c_actor, self._lib = h, agent.lib
         nf = agent.lib.hsad_actor_n_finished_dev(h)
         from .composite import _view
@@ -113,12 +253,24 @@ class DeviceActor:
 
     @property
     def last_reply(self):
-        """{a, greedy_a} int64 [N] of the last step (native loop: views of the library's buffers)"""
+        """{a, greedy_a} int64 [G * P] of the last step (native loop: views of the library's buffers)"""
         import ctypes as C
         from .composite import _view
         g = C.c_void_p()
         a = self._lib.hsad_actor_last_actions(self.c_actor, C.byref(g))
-        return {"a": _view(a, self.N, self.env.device, self, dtype=torch.int64), "greedy_a": _view(g.value, self.N, self.env.device, self, dtype=torch.int64)}
+        n = self.G * self.P
+        return {"a": _view(a, n, self.env.device, self, dtype=torch.int64), "greedy_a": _view(g.value, n, self.env.device, self, dtype=torch.int64)}
+
+    @property
+    def state(self):
+        """(h, c) fp32 [L, N, H]: the carried state entering the next step (native loop: views of the library's buffers)"""
+        import ctypes as C
+        from . import _lib
+        from .composite import _view
+        h, c = C.c_void_p(), C.c_void_p()
+        _lib.check(self._lib.hsad_actor_state(self.c_actor, C.byref(h), C.byref(c)))
+        n = self.agent.online.L * self.N * self.agent.online.H
+        return _view(h.value, n, self.env.device, self), _view(c.value, n, self.env.device, self)
 
     @property
     def last_priority(self):

@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <thread>
 #include <vector>
 
@@ -107,12 +108,23 @@ struct hsad_actor {
   hipEvent_t ev_main = nullptr, ev_reset = nullptr, ev_flush = nullptr;
   bool fuse_tail = getenv("HSAD_ACTOR_FUSE_TAIL") ? atoi(getenv("HSAD_ACTOR_FUSE_TAIL")) != 0 : true;      // developer switch (A/B)
   RunAheadT<HipRunAheadRuntime, 8> ahead;      // hsad_run_ahead.h (the bound's ring of events; also compiled under the TSAN model)
+  struct PartnerSeats* partner = nullptr;      // hsad_actor_create_partnered (hsad_actor_partner.inc): N = E = the learner's rows
 };
 
-extern "C" {
+namespace {
+int actor_create_rows(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay, const hsad_actor_config* cfg,
+                      const hsad_actor_io* io, int rows, hsad_actor** out);
+int actor_tail(hsad_actor* ac, void* stream, int nxt, const float* reward, const uint8_t* terminal, int rows_per_flag);
+}  // namespace
 
-int hsad_actor_create(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay, const hsad_actor_config* cfg,
-                      const hsad_actor_io* io, hsad_actor** out) {
+#include "hsad_actor_partner.inc"
+
+namespace {
+
+// hsad_actor_create for `rows` agent rows (0: every row g * P + p of the env, which is what hsad_actor_create asks for; a partnered
+// actor: its M learner rows): state rings, Q ring, arena and sequence writer are sized by that count
+int actor_create_rows(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay, const hsad_actor_config* cfg,
+                      const hsad_actor_io* io, int rows, hsad_actor** out) {
   if (!env || !online || !target || !replay || !cfg || !io || !out) return xfail(HSAD_ERR_INVALID, "actor_create: null argument");
   if (!io->legal_move || !io->own_hand || !io->eps || !io->reward || !io->terminal || !io->priv_bits || !io->legal_bits || !io->own_bits ||
       !io->priv_s_bf16)
@@ -131,7 +143,7 @@ int hsad_actor_create(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* targe
   ac->io = *io;
   ac->G = hsad_env_num_games(env);
   ac->P = hsad_env_num_players(env);
-  ac->N = ac->G * ac->P;
+  ac->N = rows ? rows : ac->G * ac->P;
   ac->vdn = cfg->vdn != 0;
   ac->E = ac->vdn ? ac->G : ac->N;
   ac->F = hsad_env_feature_size(env);
@@ -199,10 +211,95 @@ int hsad_actor_create(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* targe
   return 0;
 }
 
+// The rest of an iteration behind the env step, for the actor's N agent rows.  reward / terminal: one entry per `rows_per_flag` agent
+// rows (hsad_actor_step: the env's per-game outputs, P rows each; a partnered actor: its gathered per-row copies, 1).
+int actor_tail(hsad_actor* ac, void* stream, int nxt, const float* reward, const uint8_t* terminal, int rows_per_flag) {
+  hipStream_t s = (hipStream_t)stream;
+  const int N = ac->N, P = ac->P, L = ac->L, Hd = ac->Hd, n = ac->multi_step;
+  const int rep = ac->vdn ? 1 : rows_per_flag;
+  // the per-env tail of the iteration -- reward / terminal push, n-step pop, priority from the cached Q-values, sequence push -- is ONE launch
+  // (hsad_seqwriter_step_tail) whenever the window is full, the cached Q_online is current and no sum over players is needed; the four
+  // separate entry points below remain for the first n steps, VDN, and the step after a weight sync
+  const int old_slot = (nxt + ac->nslot - 1 - n) % ac->nslot;       // the slot that entered act() n steps ago
+  const bool one_launch = ac->fuse_tail && !(ac->vdn && P > 1) && hsad_seqwriter_step_tail_ready(ac->writer) &&
+                          ac->qversion[old_slot] == hsad_r2d2_net_version(ac->online);
+  if (one_launch) {
+    CK(hsad_seqwriter_step_tail(ac->writer, reward, terminal, rep, ac->qring[old_slot], ac->tq, n, (double)ac->gamma, ac->prio,
+                                ac->rew, ac->boot, stream));
+    CK(hsad_zero_state_rows(ac->h[nxt], ac->c[nxt], ac->fused_state ? ac->h16[nxt] : nullptr, terminal, L, N, Hd, rows_per_flag, stream));
+    ac->cur = nxt;
+    ac->pushed = true;
+    HIP_TRY(hipEventRecord(ac->ev_flush, s));
+    HIP_TRY(hipStreamWaitEvent(ac->side_flush, ac->ev_flush, 0));
+    CK(hsad_seqwriter_flush_to_replay(ac->writer, ac->replay, ac->eta, ac->n_finished, (void*)ac->side_flush));
+    HIP_TRY(hipStreamWaitEvent(s, ac->ev_reset, 0));
+    if (ac->ahead.mark(s)) return xfail(HSAD_ERR_HIP, "actor_step: hipEventRecord failed");
+    return 0;
+  }
+  CK(hsad_seqwriter_push_reward_terminal_rep(ac->writer, reward, terminal, rep, stream));
+  CK(hsad_zero_state_rows(ac->h[nxt], ac->c[nxt], ac->fused_state ? ac->h16[nxt] : nullptr, terminal, L, N, Hd, rows_per_flag, stream));
+  ac->cur = nxt;
+  ac->pushed = false;
+  if (hsad_seqwriter_can_pop(ac->writer)) {
+    ac->pushed = true;
+    const int old = (nxt + ac->nslot - 1 - n) % ac->nslot;       // the slot that entered act() n steps ago
+    const float* qa = ac->qring[old];
+    const bool stale = ac->qversion[old] != hsad_r2d2_net_version(ac->online);
+    if (stale) {
+      // the online weights were synced since step t - n: the reference evaluates Q_online(s_{t-n}, a) with the NEW weights
+      // (compute_priority runs when the transition leaves the window) -- redo exactly that pass on the unpacked transition
+      const size_t E = ac->E;
+      const int m = ac->vdn ? P : 1;
+      if (!ac->u_priv) {
+        if (hipMalloc((void**)&ac->u_priv, E * m * ac->F * 4) != hipSuccess || hipMalloc((void**)&ac->u_legal, E * m * ac->A * 4) != hipSuccess ||
+            hipMalloc((void**)&ac->u_eps, E * m * 4) != hipSuccess || hipMalloc((void**)&ac->u_own, E * m * ac->H3 * 4) != hipSuccess ||
+            hipMalloc((void**)&ac->u_a, E * m * 8) != hipSuccess || hipMalloc((void**)&ac->u_g, E * m * 8) != hipSuccess)
+          return xfail(HSAD_ERR_NOMEM, "actor_step: buffers for the unpacked transition");
+      }
+      void* outf[6] = {ac->u_priv, ac->u_legal, ac->u_eps, ac->u_own, ac->u_a, ac->u_g};
+      CK(hsad_seqwriter_pop_transition(ac->writer, outf, nullptr, ac->rew, ac->term, ac->boot, stream));
+      CK(hsad_r2d2_q_of(ac->online, N, ac->u_priv, ac->u_legal, ac->u_a, ac->h[old], ac->c[old], ac->qa_redo, stream));
+      qa = ac->qa_redo;
+      ac->n_redo += 1;
+    } else {
+      CK(hsad_seqwriter_pop_transition(ac->writer, nullptr, nullptr, ac->rew, ac->term, ac->boot, stream));
+    }
+    const float* tq = ac->tq;
+    int n_out = N;
+    if (ac->vdn && P > 1) {      // VDN: Q summed over the players of a game (r2d2.py:341-345)
+      n_out = ac->G;
+      hipLaunchKernelGGL(sum_players2_kernel, dim3((n_out + 255) / 256), dim3(256), 0, s, qa, tq, n_out, P, ac->qa_sum, ac->tq_sum);
+      HIP_TRY(hipGetLastError());
+      qa = ac->qa_sum;
+      tq = ac->tq_sum;
+    }
+    CK(hsad_nstep_priority(qa, tq, ac->rew, ac->boot, n, (double)ac->gamma, n_out, ac->prio, stream));
+    CK(hsad_seqwriter_push_sequence(ac->writer, ac->prio, stream));
+    // finished sequences -> replay on a side stream: five small launches, three of them single-workgroup scans, next to the following
+    // step's network passes; the library's StreamFence orders whoever touches the writer or the replay next behind it
+    HIP_TRY(hipEventRecord(ac->ev_flush, s));
+    HIP_TRY(hipStreamWaitEvent(ac->side_flush, ac->ev_flush, 0));
+    CK(hsad_seqwriter_flush_to_replay(ac->writer, ac->replay, ac->eta, ac->n_finished, (void*)ac->side_flush));
+  }
+  HIP_TRY(hipStreamWaitEvent(s, ac->ev_reset, 0));      // nothing outside a step ever runs next to the reset
+  if (ac->ahead.mark(s)) return xfail(HSAD_ERR_HIP, "actor_step: hipEventRecord failed");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hsad_actor_create(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay, const hsad_actor_config* cfg,
+                      const hsad_actor_io* io, hsad_actor** out) {
+  return actor_create_rows(env, online, target, replay, cfg, io, 0, out);
+}
+
 void hsad_actor_destroy(hsad_actor* ac) {
   if (!ac) return;
   (void)hipDeviceSynchronize();
   if (ac->writer) hsad_seqwriter_destroy(ac->writer);
+  partner_free(ac->partner);
   for (void* q : {(void*)ac->arena, (void*)ac->u_priv, (void*)ac->u_legal, (void*)ac->u_eps, (void*)ac->u_own, (void*)ac->u_a, (void*)ac->u_g})
     if (q) (void)hipFree(q);
   if (ac->side_reset) (void)hipStreamDestroy(ac->side_reset);
@@ -250,7 +347,8 @@ int hsad_actor_step(hsad_actor* ac, void* stream) {
   // the host at most `bound` steps ahead of the device (hsad_run_ahead.h; polling: hipEventSynchronize has been seen to return only with
   // the stream's NEWEST work)
   if (const int q = ac->ahead.admit()) return xfail(HSAD_ERR_HIP, "actor_step: hipEventQuery failed: %s", hipGetErrorString((hipError_t)q));
-  const int N = ac->N, P = ac->P, L = ac->L, Hd = ac->Hd, n = ac->multi_step;
+  if (ac->partner) return partner_step(ac, stream);      // hsad_actor_create_partnered: the same iteration on the learner's rows
+  const int N = ac->N, P = ac->P;
   const int cur = ac->cur, nxt = (cur + 1) % ac->nslot;
   // `if (terminated) reset` (thread_loop.h:46-52): issued behind the previous env step on a side stream and joined at the end of
   // that iteration -- latency-bound deck shuffles next to the bookkeeping
@@ -272,73 +370,7 @@ int hsad_actor_step(hsad_actor* ac, void* stream) {
   ac->reset_pending = true;
   ac->num_act += N;
   ac->step_no += 1;
-  // the per-env tail of the iteration -- reward / terminal push, n-step pop, priority from the cached Q-values, sequence push -- is ONE launch
-  // (hsad_seqwriter_step_tail) whenever the window is full, the cached Q_online is current and no sum over players is needed; the four
-  // separate entry points below remain for the first n steps, VDN, and the step after a weight sync
-  const int old_slot = (nxt + ac->nslot - 1 - n) % ac->nslot;       // the slot that entered act() n steps ago
-  const bool one_launch = ac->fuse_tail && !(ac->vdn && P > 1) && hsad_seqwriter_step_tail_ready(ac->writer) &&
-                          ac->qversion[old_slot] == hsad_r2d2_net_version(ac->online);
-  if (one_launch) {
-    CK(hsad_seqwriter_step_tail(ac->writer, ac->io.reward, ac->io.terminal, ac->vdn ? 1 : P, ac->qring[old_slot], ac->tq, n, (double)ac->gamma, ac->prio,
-                                ac->rew, ac->boot, stream));
-    CK(hsad_zero_state_rows(ac->h[nxt], ac->c[nxt], ac->fused_state ? ac->h16[nxt] : nullptr, ac->io.terminal, L, N, Hd, P, stream));
-    ac->cur = nxt;
-    ac->pushed = true;
-    HIP_TRY(hipEventRecord(ac->ev_flush, s));
-    HIP_TRY(hipStreamWaitEvent(ac->side_flush, ac->ev_flush, 0));
-    CK(hsad_seqwriter_flush_to_replay(ac->writer, ac->replay, ac->eta, ac->n_finished, (void*)ac->side_flush));
-    HIP_TRY(hipStreamWaitEvent(s, ac->ev_reset, 0));
-    if (ac->ahead.mark(s)) return xfail(HSAD_ERR_HIP, "actor_step: hipEventRecord failed");
-    return 0;
-  }
-  CK(hsad_seqwriter_push_reward_terminal_rep(ac->writer, ac->io.reward, ac->io.terminal, ac->vdn ? 1 : P, stream));
-  CK(hsad_zero_state_rows(ac->h[nxt], ac->c[nxt], ac->fused_state ? ac->h16[nxt] : nullptr, ac->io.terminal, L, N, Hd, P, stream));
-  ac->cur = nxt;
-  ac->pushed = false;
-  if (hsad_seqwriter_can_pop(ac->writer)) {
-    ac->pushed = true;
-    const int old = (nxt + ac->nslot - 1 - n) % ac->nslot;       // the slot that entered act() n steps ago
-    const float* qa = ac->qring[old];
-    const bool stale = ac->qversion[old] != hsad_r2d2_net_version(ac->online);
-    if (stale) {
-      // the online weights were synced since step t - n: the reference evaluates Q_online(s_{t-n}, a) with the NEW weights
-      // (compute_priority runs when the transition leaves the window) -- redo exactly that pass on the unpacked transition
-      const size_t E = ac->E;
-      const int m = ac->vdn ? P : 1;
-      if (!ac->u_priv) {
-        if (hipMalloc((void**)&ac->u_priv, E * m * ac->F * 4) != hipSuccess || hipMalloc((void**)&ac->u_legal, E * m * ac->A * 4) != hipSuccess ||
-            hipMalloc((void**)&ac->u_eps, E * m * 4) != hipSuccess || hipMalloc((void**)&ac->u_own, E * m * ac->H3 * 4) != hipSuccess ||
-            hipMalloc((void**)&ac->u_a, E * m * 8) != hipSuccess || hipMalloc((void**)&ac->u_g, E * m * 8) != hipSuccess)
-          return xfail(HSAD_ERR_NOMEM, "actor_step: buffers for the unpacked transition");
-      }
-      void* outf[6] = {ac->u_priv, ac->u_legal, ac->u_eps, ac->u_own, ac->u_a, ac->u_g};
-      CK(hsad_seqwriter_pop_transition(ac->writer, outf, nullptr, ac->rew, ac->term, ac->boot, stream));
-      CK(hsad_r2d2_q_of(ac->online, N, ac->u_priv, ac->u_legal, ac->u_a, ac->h[old], ac->c[old], ac->qa_redo, stream));
-      qa = ac->qa_redo;
-      ac->n_redo += 1;
-    } else {
-      CK(hsad_seqwriter_pop_transition(ac->writer, nullptr, nullptr, ac->rew, ac->term, ac->boot, stream));
-    }
-    const float* tq = ac->tq;
-    int n_out = N;
-    if (ac->vdn && P > 1) {      // VDN: Q summed over the players of a game (r2d2.py:341-345)
-      n_out = ac->G;
-      hipLaunchKernelGGL(sum_players2_kernel, dim3((n_out + 255) / 256), dim3(256), 0, s, qa, tq, n_out, P, ac->qa_sum, ac->tq_sum);
-      HIP_TRY(hipGetLastError());
-      qa = ac->qa_sum;
-      tq = ac->tq_sum;
-    }
-    CK(hsad_nstep_priority(qa, tq, ac->rew, ac->boot, n, (double)ac->gamma, n_out, ac->prio, stream));
-    CK(hsad_seqwriter_push_sequence(ac->writer, ac->prio, stream));
-    // finished sequences -> replay on a side stream: five small launches, three of them single-workgroup scans, next to the following
-    // step's network passes; the library's StreamFence orders whoever touches the writer or the replay next behind it
-    HIP_TRY(hipEventRecord(ac->ev_flush, s));
-    HIP_TRY(hipStreamWaitEvent(ac->side_flush, ac->ev_flush, 0));
-    CK(hsad_seqwriter_flush_to_replay(ac->writer, ac->replay, ac->eta, ac->n_finished, (void*)ac->side_flush));
-  }
-  HIP_TRY(hipStreamWaitEvent(s, ac->ev_reset, 0));      // nothing outside a step ever runs next to the reset
-  if (ac->ahead.mark(s)) return xfail(HSAD_ERR_HIP, "actor_step: hipEventRecord failed");
-  return 0;
+  return actor_tail(ac, stream, nxt, ac->io.reward, ac->io.terminal, P);
 }
 
 }  // extern "C"

@@ -1,0 +1,307 @@
+// hsad_actor_partner.inc — the partnered actor (include/hsad.h: hsad_actor_create_partnered): in every game some rows g * P + p belong
+// to the learner and the rest to rule-list bots (hsad_rulebot.h).  The network runs on the learner's M rows only, and only those rows
+// reach the sequence writer and the replay.  Textually part of hsad_actor.hip (included behind struct hsad_actor: it uses the actor's
+// state rings, its side streams and its tail as they are).
+//
+// Nothing here is reached by an actor of hsad_actor_create: hsad_actor_step branches on `partner` once.  Two kernels are on the
+// step's path, both plain loads and vector stores, no atomics, no LDS beyond the staged bot table:
+//   partner_gather_kernel<0>  one launch in front of act: everything act and the sequence writer read of the learner's rows, compact
+//   partner_gather_kernel<1>  the same kernel's second pass behind the env step: reward and terminal of each learner row's game
+//   partner_merge_kernel      one thread per game, between act and the env step: the full a / greedy_a [G, P] -- the learner's rows
+//                             from the compact act output, the partners' from their bots on the state planes (policy_rule_kernel's
+//                             sibling: the same rb_act, hash streams, default key and counter rule)
+#include "hsad_partner.h"
+
+// csrc/hsad_env_rulebot.inc
+extern "C" int hsad_internal_env_rulebot_view(const hsad_env* e, const uint32_t** planes, uint32_t** act_count, int* G, int* Gpad, RbRules* ru);
+
+namespace {
+
+constexpr int kPartnerGatherThreads = 192;   // 896 bf16 + 14 bit words + 21 floats + 3 words of a row are 143 pieces: one pass
+constexpr int kPartnerBotWords = RB_TABLE_WORDS;
+
+// the pieces of one row, in the order the threads of a workgroup take them: obs vectors, bit-row pieces, legal pieces, three words
+struct PartnerGather {
+  const int32_t* rows;             // [M] learner rows g * P + p
+  int M, P;
+  // sources: the env's outputs (hsad_actor_io)
+  const uint4* obs16;              // [G*P][Fp] bf16 as 16-byte vectors
+  const float* legal;              // [G*P][A]
+  const float* eps;                // [G*P]
+  const unsigned long long* priv_bits;    // [G*P][pw64]
+  const unsigned long long* legal_bits;   // [G*P]
+  const unsigned long long* own_bits;     // [G*P]
+  const float* reward;             // [G]
+  const uint8_t* terminal;         // [G]
+  // destinations, compact [M]
+  uint4* c_obs16;
+  float* c_legal;
+  float* c_eps;
+  unsigned long long* c_priv_bits;
+  unsigned long long* c_legal_bits;
+  unsigned long long* c_own_bits;
+  float* c_reward;
+  uint8_t* c_terminal;
+  int n_obs;                       // Fp / 8 vectors of a row
+  int pw64, pb_vec, n_pb;          // bit row: pw64 words; as n_pb = pw64 / 2 vectors when the width is even, else as pw64 words
+  int A, lg_vec, n_lg;             // legal row: as n_lg = A / 4 vectors when 4 | A, else as A floats
+};
+
+// PASS 0: one workgroup per learner row.  PASS 1: one thread per learner row.
+template <int PASS>
+__global__ __launch_bounds__(kPartnerGatherThreads) void partner_gather_kernel(PartnerGather g) {
+  if (PASS == 1) {
+    const int e = blockIdx.x * kPartnerGatherThreads + threadIdx.x;
+    if (e >= g.M) return;
+    const int game = g.rows[e] / g.P;
+    g.c_reward[e] = g.reward[game];
+    g.c_terminal[e] = g.terminal[game];
+    return;
+  }
+  const int e = blockIdx.x;   // < M: the grid is M workgroups
+  const size_t r = (size_t)g.rows[e];
+  const int total = g.n_obs + g.n_pb + g.n_lg + 3;
+  for (int k = threadIdx.x; k < total; k += kPartnerGatherThreads) {
+    int j = k;
+    if (j < g.n_obs) {
+      g.c_obs16[(size_t)e * g.n_obs + j] = g.obs16[r * g.n_obs + j];
+      continue;
+    }
+    j -= g.n_obs;
+    if (j < g.n_pb) {
+      if (g.pb_vec)
+        reinterpret_cast<uint4*>(g.c_priv_bits)[(size_t)e * g.n_pb + j] = reinterpret_cast<const uint4*>(g.priv_bits)[r * g.n_pb + j];
+      else
+        g.c_priv_bits[(size_t)e * g.pw64 + j] = g.priv_bits[r * g.pw64 + j];
+      continue;
+    }
+    j -= g.n_pb;
+    if (j < g.n_lg) {
+      if (g.lg_vec)
+        reinterpret_cast<float4*>(g.c_legal)[(size_t)e * g.n_lg + j] = reinterpret_cast<const float4*>(g.legal)[r * g.n_lg + j];
+      else
+        g.c_legal[(size_t)e * g.A + j] = g.legal[r * g.A + j];
+      continue;
+    }
+    j -= g.n_lg;
+    if (j == 0) g.c_eps[e] = g.eps[r];
+    else if (j == 1) g.c_legal_bits[e] = g.legal_bits[r];
+    else g.c_own_bits[e] = g.own_bits[r];
+  }
+}
+
+// the bots of a launch as a kernel argument (288 bytes): the packed rule table of hsad_rulebot.h
+struct PartnerBots {
+  uint32_t table[RB_TABLE_WORDS];
+};
+
+struct PartnerPlanes {
+  const uint32_t* planes;
+  size_t Gpad;
+  int g;
+  __device__ __forceinline__ uint32_t operator()(int pl) const { return planes[(size_t)pl * Gpad + g]; }
+};
+
+// seat [G * P]: the bot b >= 0 of a partner row, or -(e + 1) for the learner row whose compact index is e.  A learner row of a game
+// that is not live gets the noop, as hsad_seat_scatter gives it; a partner row gets what hsad_env_policy_rule gives it.
+__global__ __launch_bounds__(256) void partner_merge_kernel(const uint32_t* __restrict__ planes, uint32_t* __restrict__ act_count, int G, int Gpad,
+                                                            RbRules ru, PartnerBots rb, const int32_t* __restrict__ seat, uint64_t seed,
+                                                            const int64_t* __restrict__ a_c, const int64_t* __restrict__ g_c,
+                                                            int64_t* __restrict__ a, int64_t* __restrict__ ga) {
+  __shared__ uint32_t s_rb[kPartnerBotWords];
+  for (int k = threadIdx.x; k < kPartnerBotWords; k += blockDim.x) s_rb[k] = rb.table[k];
+  __syncthreads();
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= G) return;
+  const int P = ru.P;
+  int32_t st[5];   // P <= 5 (refused otherwise)
+  bool any = false;
+#pragma unroll
+  for (int p = 0; p < 5; ++p) {
+    st[p] = p < P ? seat[(size_t)g * P + p] : -1;
+    any |= p < P && st[p] >= 0;
+  }
+  const PartnerPlanes w = {planes, (size_t)Gpad, g};
+  const uint32_t misc = w(RB_PL_MISC);
+  const bool live = ((misc >> 15) & 1u) && !((misc >> 14) & 1u);
+  uint32_t counter = 0u;
+  if (any) {   // the policy counter: read once, advanced once per call in every game that has a bot
+    counter = act_count[g];
+    act_count[g] = counter + 1u;
+  }
+#pragma unroll
+  for (int p = 0; p < 5; ++p) {
+    if (p >= P) break;
+    const size_t r = (size_t)g * P + p;
+    if (st[p] >= 0) {
+      const int uid = rb_act(w, ru, p, s_rb, st[p], seed, (uint64_t)g, (uint64_t)counter, nullptr);
+      a[r] = uid;
+      ga[r] = uid;
+    } else {
+      const int e = -st[p] - 1;
+      a[r] = live ? a_c[e] : (int64_t)(ru.A - 1);
+      ga[r] = live ? g_c[e] : (int64_t)(ru.A - 1);
+    }
+  }
+}
+
+}  // namespace
+
+// what a partnered actor holds on top of hsad_actor
+struct PartnerSeats {
+  char* arena = nullptr;
+  PartnerGather g;                 // both passes' argument
+  PartnerBots bots;
+  RbRules ru;
+  const uint32_t* planes = nullptr;
+  uint32_t* act_count = nullptr;
+  int Gpad = 0;
+  int32_t* seat = nullptr;         // [G * P], see partner_merge_kernel
+  int64_t *a_c = nullptr, *g_c = nullptr;   // compact act output [M]
+  uint64_t bot_seed = 0;
+};
+
+namespace {
+
+void partner_free(PartnerSeats* pt) {
+  if (!pt) return;
+  if (pt->arena) (void)hipFree(pt->arena);
+  delete pt;
+}
+
+// hsad_actor_step of a partnered actor: hsad_actor_step's iteration with the gather in front of act, the merge behind it, and the
+// tail on the gathered reward / terminal
+int partner_step(hsad_actor* ac, void* stream) {
+  PartnerSeats* pt = ac->partner;
+  hipStream_t s = (hipStream_t)stream;
+  const int M = ac->N;
+  const int cur = ac->cur, nxt = (cur + 1) % ac->nslot;
+  if (ac->reset_pending) ac->reset_pending = false;
+  else CK(hsad_env_reset(ac->env, stream));
+  hipLaunchKernelGGL(partner_gather_kernel<0>, dim3(M), dim3(kPartnerGatherThreads), 0, s, pt->g);
+  HIP_TRY(hipGetLastError());
+  const uint64_t v_on = hsad_r2d2_net_version(ac->online);
+  CK(hsad_r2d2_act(ac->online, ac->target, M, nullptr, pt->g.c_obs16, pt->g.c_legal, pt->g.c_eps, ac->h[cur], ac->c[cur],
+                   ac->fused_state ? ac->h16[cur] : nullptr, ac->seed, ac->counter++, pt->a_c, pt->g_c, ac->h[nxt], ac->c[nxt],
+                   ac->fused_state ? ac->h16[nxt] : nullptr, ac->qring[cur], ac->tq, stream));
+  ac->qversion[cur] = v_on;
+  hipLaunchKernelGGL(partner_merge_kernel, dim3((ac->G + 255) / 256), dim3(256), 0, s, pt->planes, pt->act_count, ac->G, pt->Gpad, pt->ru, pt->bots,
+                     pt->seat, pt->bot_seed, pt->a_c, pt->g_c, ac->a, ac->greedy);
+  HIP_TRY(hipGetLastError());
+  const void* fields[6] = {pt->g.c_priv_bits, pt->g.c_legal_bits, pt->g.c_eps, pt->g.c_own_bits, pt->a_c, pt->g_c};
+  CK(hsad_seqwriter_push_obs_action(ac->writer, fields, stream));
+  CK(hsad_env_step(ac->env, ac->a, ac->greedy, stream));
+  HIP_TRY(hipEventRecord(ac->ev_main, s));
+  HIP_TRY(hipStreamWaitEvent(ac->side_reset, ac->ev_main, 0));
+  CK(hsad_env_reset(ac->env, (void*)ac->side_reset));
+  HIP_TRY(hipEventRecord(ac->ev_reset, ac->side_reset));
+  ac->reset_pending = true;
+  hipLaunchKernelGGL(partner_gather_kernel<1>, dim3((M + kPartnerGatherThreads - 1) / kPartnerGatherThreads), dim3(kPartnerGatherThreads), 0, s, pt->g);
+  HIP_TRY(hipGetLastError());
+  ac->num_act += M;
+  ac->step_no += 1;
+  return actor_tail(ac, stream, nxt, pt->g.c_reward, pt->g.c_terminal, 1);
+}
+
+}  // namespace
+
+extern "C" int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay,
+                                           const hsad_actor_config* cfg, const hsad_actor_io* io, const hsad_actor_partners* partners,
+                                           hsad_actor** out) {
+  if (!env || !cfg || !partners || !out) return xfail(HSAD_ERR_INVALID, "actor_create_partnered: null argument");
+  if (!partners->rows || !partners->seat_bot || (partners->n_bot > 0 && (!partners->rules || !partners->n_rules)))
+    return xfail(HSAD_ERR_INVALID, "actor_create_partnered: null array in hsad_actor_partners");
+  const int G = hsad_env_num_games(env), P = hsad_env_num_players(env), M = partners->M;
+  const PartnerVerdict v = partner_layout_verdict(G, P, cfg->hand_size, cfg->vdn, partners->rows, M, partners->rules, partners->n_rules,
+                                                  partners->n_bot, partners->seat_bot);
+  if (v.code != PT_OK) {
+    char why[256];
+    partner_verdict_text(v, G, P, partners->n_bot, why, sizeof(why));
+    return xfail(HSAD_ERR_INVALID, "actor_create_partnered: %s", why);
+  }
+  auto* pt = new PartnerSeats();
+  int G_env = 0;
+  int rc = hsad_internal_env_rulebot_view(env, &pt->planes, &pt->act_count, &G_env, &pt->Gpad, &pt->ru);
+  hsad_actor* ac = nullptr;
+  if (!rc) rc = actor_create_rows(env, online, target, replay, cfg, io, M, &ac);   // the other refusals of hsad_actor_create
+  if (rc) {
+    partner_free(pt);
+    return rc;
+  }
+  ac->partner = pt;   // from here on hsad_actor_destroy frees pt
+  const int Fp = ac->Fp, A = ac->A, pw64 = (ac->F + 63) / 64;
+  const size_t N = (size_t)G * P;
+  if ((Fp & 7) || ((uintptr_t)io->priv_s_bf16 & 15u)) {
+    hsad_actor_destroy(ac);
+    return xfail(HSAD_ERR_INVALID, "actor_create_partnered: the bf16 observation rows must be 16-byte aligned and a multiple of 8 values long");
+  }
+  memset(&pt->bots, 0, sizeof(pt->bots));
+  for (int b = 0; b < partners->n_bot; ++b) {
+    const hsad_rule* r = partners->rules + (size_t)b * HSAD_RULE_MAX_RULES;
+    for (int j = 0; j < partners->n_rules[b]; ++j) pt->bots.table[b * HSAD_RULE_MAX_RULES + j] = rb_pack(r[j].code, r[j].k);
+    pt->bots.table[HSAD_RULE_MAX_BOTS * HSAD_RULE_MAX_RULES + b] = (uint32_t)partners->n_rules[b];
+  }
+  pt->bot_seed = partners->bot_seed;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t total = up(M * 4) + up(N * 4) + up((size_t)M * Fp * 2) + up((size_t)M * A * 4) + up(M * 4) + up((size_t)M * pw64 * 8) +
+                       2 * up(M * 8) + up(M * 4) + up(M) + 2 * up(N * 8);
+  if (hipMalloc((void**)&pt->arena, total) != hipSuccess) {
+    hsad_actor_destroy(ac);
+    return xfail(HSAD_ERR_NOMEM, "actor_create_partnered: hipMalloc of %zu bytes failed", total);
+  }
+  (void)hipMemset(pt->arena, 0, total);
+  char* p = pt->arena;
+  auto take = [&](size_t b) {
+    char* r = p;
+    p += up(b);
+    return r;
+  };
+  PartnerGather& g = pt->g;
+  int32_t* d_rows = (int32_t*)take(M * 4);
+  pt->seat = (int32_t*)take(N * 4);
+  g.rows = d_rows;
+  g.M = M;
+  g.P = P;
+  g.obs16 = (const uint4*)io->priv_s_bf16;
+  g.legal = io->legal_move;
+  g.eps = io->eps;
+  g.priv_bits = (const unsigned long long*)io->priv_bits;
+  g.legal_bits = (const unsigned long long*)io->legal_bits;
+  g.own_bits = (const unsigned long long*)io->own_bits;
+  g.reward = io->reward;
+  g.terminal = io->terminal;
+  g.c_obs16 = (uint4*)take((size_t)M * Fp * 2);
+  g.c_legal = (float*)take((size_t)M * A * 4);
+  g.c_eps = (float*)take(M * 4);
+  g.c_priv_bits = (unsigned long long*)take((size_t)M * pw64 * 8);
+  g.c_legal_bits = (unsigned long long*)take(M * 8);
+  g.c_own_bits = (unsigned long long*)take(M * 8);
+  g.c_reward = (float*)take(M * 4);
+  g.c_terminal = (uint8_t*)take(M);
+  g.n_obs = Fp / 8;
+  g.pw64 = pw64;
+  g.pb_vec = (pw64 % 2 == 0) && !((uintptr_t)io->priv_bits & 15u);
+  g.n_pb = g.pb_vec ? pw64 / 2 : pw64;
+  g.A = A;
+  g.lg_vec = (A % 4 == 0) && !((uintptr_t)io->legal_move & 15u);
+  g.n_lg = g.lg_vec ? A / 4 : A;
+  // the arena of hsad_actor_create holds a / greedy for the agent's rows: here the compact act output; the full [G, P] pair the env
+  // steps with (hsad_actor_last_actions) lives in this arena
+  pt->a_c = ac->a;
+  pt->g_c = ac->greedy;
+  ac->a = (int64_t*)take(N * 8);
+  ac->greedy = (int64_t*)take(N * 8);
+  std::vector<int32_t> seat(N);
+  int next = 0;
+  for (size_t r = 0; r < N; ++r) {
+    if (next < M && (size_t)partners->rows[next] == r) seat[r] = -(next++ + 1);
+    else seat[r] = partners->seat_bot[r];
+  }
+  if (hipMemcpy(d_rows, partners->rows, (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(pt->seat, seat.data(), N * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    hsad_actor_destroy(ac);
+    return xfail(HSAD_ERR_HIP, "actor_create_partnered: copying the seat layout to the device failed");
+  }
+  *out = ac;
+  return 0;
+}

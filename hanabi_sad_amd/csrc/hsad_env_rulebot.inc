@@ -198,6 +198,20 @@ int hsad_env_policy_rule(hsad_env* e, const hsad_rule* rules, const int32_t* n_r
   return HSAD_OK;
 }
 
+// shared with csrc/hsad_actor.hip (not part of the public header): what a rule bot outside this file needs of an env -- the state
+// planes [npl][Gpad], the policy counters [Gpad] and the rules rb_act takes, as policy_rule_kernel sees them
+int hsad_internal_env_rulebot_view(const hsad_env* e, const uint32_t** planes, uint32_t** act_count, int* G, int* Gpad, RbRules* ru) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
+  *planes = e->ep.planes;
+  *act_count = e->ep.act_count;
+  *G = e->ep.G;
+  *Gpad = e->ep.Gpad;
+  const EnvParams& ep = e->ep;
+  *ru = RbRules{ep.P, ep.H, ep.nC, ep.nR, ep.max_info, ep.A, ep.shuffle_color, ep.deck_full};   // rb_rules_of, on the host
+  return HSAD_OK;
+}
+
 int hsad_env_playout_rule(hsad_env* e, int max_iter, const hsad_rule* rules, const int32_t* n_rules, int n_bot,
                           const int32_t* seat_bot_of_seat, uint64_t seed, const int64_t* key, int64_t* a, int64_t* greedy_a, void* stream) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");

@@ -1,7 +1,7 @@
 """Rule-list Hanabi bots for the device env: an ordered list of at most 8 rules, the first that fires gives the move (include/hsad.h,
 HSAD_RULE_* and hsad_env_policy_rule, is the specification).  `RuleBot` is the list as data; `BatchedHanabiEnv.policy_rule` /
 `playout_rule` run it, `search.mc_action_values(playout=bot)` plays sampled worlds out with it and `eval.play_seatings` seats it next
-to networks.  The presets are this project's own restatements, named after the published rule-based agents they resemble (Walton-Rivers
+to networks; `actor.PartnerSeats` seats it next to the learner in the training actor (`selfplay --partner NAME`).  The presets are this project's own restatements, named after the published rule-based agents they resemble (Walton-Rivers
 et al. 2017); no fidelity to any published bot is claimed.  No torch, no device."""
 import ctypes as C
 

@@ -16,7 +16,7 @@ import time
 import numpy as np
 import torch
 
-from .actor import DeviceActor, transition_fields
+from .actor import DeviceActor, PartnerSeats, transition_fields
 from .env import BatchedHanabiEnv
 from .r2d2 import PARAM_ORDER, R2D2Agent, R2D2Learner, R2D2NetKernels, arch_of, check_sync, param_order
 from .replay import DeviceReplay, aggregate_priority
@@ -55,6 +55,38 @@ def init_weights(in_dim, hid_dim, out_dim, hand_size, seed, num_lstm_layer=2, nu
 def game_rules(args):
     """the rule keywords of BatchedHanabiEnv / evaluate from the command line (absent in older argument namespaces: the full game)"""
     return {k: int(getattr(args, k, d)) for k, d in (("colors", 5), ("ranks", 5), ("max_information_tokens", 8), ("max_life_tokens", 3))}
+
+
+def partner_bots(args):
+    """the rule bots of --partner (presets of rulebot.py), in the order given"""
+    from .rulebot import PRESETS
+    return [PRESETS[name] for name in getattr(args, "partner", None) or []]
+
+
+def partner_seats(args, num_game):
+    """--partner / --partner_seats -> actor.PartnerSeats for an env of num_game games; None without --partner"""
+    bots = partner_bots(args)
+    if not bots:
+        return None
+    if args.partner_seats == "alternate":
+        return PartnerSeats.alternate(num_game, args.num_player, bots, bot_seed=args.seed)
+    return PartnerSeats.fixed_seat(num_game, args.num_player, int(args.partner_seats), bots, bot_seed=args.seed)
+
+
+def print_partner_scores(args, weights, num_game, seed, device):
+    """one line per --partner bot: the score of `weights` seated with that bot through play_seatings, every bot on the same deals
+    (seating s puts the net on seat s and the bot on every other seat; the line is the mean over the P seatings)"""
+    from .eval import play_seatings
+    bots, P = partner_bots(args), args.num_player
+    seatings = [[0 if p == seat else k for p in range(P)] for k in range(1, len(bots) + 1) for seat in range(P)]
+    xp = play_seatings([weights] + bots, seatings, num_game, seed, args.eval_bomb, args.sad, hand_size=args.hand_size, device=str(device),
+                       shuffle_color=bool(args.shuffle_color), bot_seed=args.seed, **game_rules(args))
+    scores = []
+    for k, bot in enumerate(bots):
+        m = xp.mean[k * P:(k + 1) * P]
+        scores.append(float(m.mean()))
+        print("partner %s: score %.4f (%s)" % (bot.name, scores[-1], ", ".join("as seat %d: %.4f" % (q, float(m[q])) for q in range(P))))
+    return scores
 
 
 class Trainer:
@@ -102,7 +134,8 @@ class Trainer:
         from .dist import ShardedReplay
         self.sharded = ShardedReplay(self.replay, args.priority_weight, device, learner_rank=0) if world == 1 else None
         self.actor = DeviceActor(self.env, self.agent, self.replay, args.multi_step, args.gamma, args.eta, args.max_len,
-                                 vdn=self.vdn, native=None if getattr(args, "native_actor", 1) else False) if self.acting else None
+                                 vdn=self.vdn, native=None if getattr(args, "native_actor", 1) else False,
+                                 partners=partner_seats(args, self.env.G)) if self.acting else None
         self.num_update = 0
         self._drawn = None           # the batch of the next update, drawn ahead (--draw_ahead)
         self._drawn_ev = None        # ... and the event behind that draw when it was issued on the draw stream
@@ -298,6 +331,11 @@ def parse_args(argv=None):
     p.add_argument("--num_eval_game", type=int, default=1000)
     p.add_argument("--eval_partner", type=str, nargs="+", default=[], help="weight files of fixed partners: after each epoch's self-play "
                    "evaluation the online net plays --num_eval_game deals with each of them, in both seat orders (one batched run)")
+    p.add_argument("--partner", type=str, nargs="+", default=[], help="train next to fixed partners: rule-bot presets of rulebot.py (cautious, "
+                   "piers, flawed, random).  The net acts and learns on one seat per game, the bots play the others (actor.PartnerSeats); after "
+                   "each evaluation one line per partner gives the score of the current weights seated with that bot")
+    p.add_argument("--partner_seats", type=str, default="alternate", help="with --partner: alternate = the learner's seat is g %% P and the "
+                   "bots take turns over the games; 0, 1, ... = the learner keeps that seat in every game")
     p.add_argument("--early_draw", type=int, default=1, help="with --draw_ahead and the composite learner: priority write-back and the next draw are "
                    "issued between the forward half and the BPTT of an update on a stream of their own (0: behind the optimizer step on the caller's stream)")
     p.add_argument("--draw_ahead", type=int, default=1, help="1: the batch of update u + 1 is drawn at the end of update u (behind its priority "
@@ -320,6 +358,19 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.num_thread > 0 and args.num_game_per_thread > 0:
         args.num_game = args.num_thread * args.num_game_per_thread
+    if args.partner:
+        from .rulebot import MAX_BOTS, PRESETS
+        unknown = [n for n in args.partner if n not in PRESETS]
+        if unknown:
+            raise SystemExit("--partner: no rule-bot preset named %s (have: %s)" % (", ".join(unknown), ", ".join(sorted(PRESETS))))
+        if len(args.partner) > MAX_BOTS:
+            raise SystemExit("--partner: at most %d bots" % MAX_BOTS)
+        if args.method == "vdn":
+            raise SystemExit("--partner needs --method iql: a VDN transition holds every player's row, and the partners' rows are not the learner's")
+        if args.partner_seats != "alternate" and not (args.partner_seats.isdigit() and int(args.partner_seats) < args.num_player):
+            raise SystemExit("--partner_seats: alternate, or a seat 0..%d" % (args.num_player - 1))
+        if not getattr(args, "native_actor", 1):
+            raise SystemExit("--partner needs --native_actor 1: the Python loop body runs the agent on every row")
     if args.shuffle_obs:
         raise SystemExit("--shuffle_obs is not supported (selfplay.py:175 asserts it off)")
     if not 1 <= args.num_lstm_layer <= 3:
@@ -514,6 +565,8 @@ def run_epochs(tr, args, rank=0, link=None):
             sd = {k: tr.learner.online.w[k].detach().cpu().clone() for k in tr.param_names}
             saved = saver.save(None, sd, score, force_save_name=force)
         print("epoch %d, eval score: %.4f, perfect: %.2f, model saved: %s" % (epoch, score, perfect * 100, saved))
+        if getattr(args, "partner", None):
+            print_partner_scores(args, tr.learner.online.w, args.num_eval_game, eval_seed, tr.device)
         if partners:
             # cross-play against the fixed partners: seating (online, partner, ..) and (partner, online, partner, ..) per partner
             seatings = [[0 if p == seat else k for p in range(args.num_player)] for k in range(1, len(partners) + 1) for seat in (0, 1)]
@@ -618,6 +671,8 @@ def main(argv=None):
     # Tachometer definitions (pyhanabi/utils.py:229-240)
     print("Speed: train: %.1f, act: %.1f, buffer_size: %d" % (args.num_update * args.batchsize / dt,
                                                              (tr.actor.num_act - acts0) / dt, tr.replay.size()))
+    if args.partner and tr.learner is not None:      # the plain loop has no epochs: the partner lines once, for the final weights
+        print_partner_scores(args, tr.learner.online.w, args.num_eval_game, (9917 + args.seed) % 7777777, tr.device)
 
 
 if __name__ == "__main__":

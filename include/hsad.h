@@ -1305,6 +1305,54 @@ const int64_t* hsad_actor_last_actions(const hsad_actor* actor, const int64_t** 
  * filling the n-step window */
 const float* hsad_actor_last_priority(const hsad_actor* actor, int32_t* n);
 
+/* ---- The partnered actor: train next to fixed partners.  In every game some rows g * P + p belong to the learner and the rest to
+ * rule-list bots (HSAD_RULE_*, above); the network runs on the learner's rows only, and only those rows reach the replay.
+ *
+ * hsad_actor_partners: every array is a HOST array; the actor copies what it needs to the device itself.
+ *   rows      int32 [M]: the learner's rows g * P + p, strictly ascending, 1 <= M <= G * P.
+ *   rules, n_rules, n_bot: the rule table exactly as hsad_env_policy_rule takes it (rules [n_bot][HSAD_RULE_MAX_RULES], n_rules
+ *             [n_bot], 1 <= n_bot <= HSAD_RULE_MAX_BOTS); n_bot = 0 (rules and n_rules may then be NULL) only when M == G * P.
+ *   seat_bot  int32 [G * P]: -1 on exactly the learner's rows, a bot index 0 .. n_bot - 1 on every other row.
+ *   bot_seed  the seed of the bots' *_RANDOM rules (the `seed` of hsad_env_policy_rule).
+ *
+ * hsad_actor_create_partnered: an actor that behaves like an IQL actor of hsad_actor_create with E = M environments:
+ *   - the LSTM state rings, the Q ring and the arena are sized by M; hsad_actor_state returns fp32 [L, M, H];
+ *   - hsad_r2d2_act is called with N = M on compact rows in `rows` order (compact row e is row rows[e] of the env's outputs), so a
+ *     row's index in the eps-greedy hash is its compact index e, not its row id;
+ *   - the sequence writer has M envs; its fields are the learner rows' observation bits, legal bits, eps, own-hand bits, a and
+ *     greedy_a (the transition layout of hsad_actor_io with m = 1: the replay is created as for an IQL actor);
+ *   - reward and terminal of env e are those of game rows[e] / P; the carried state rows of env e are zeroed on that game's terminal;
+ *   - both tail paths work on M envs: the one-launch tail hsad_seqwriter_step_tail, and the four entry points with the redo of
+ *     Q_online(s_{t-n}, a) on M rows after a weight sync; hsad_actor_last_priority returns float32 [M];
+ *   - every partner row gets the move of its bot as hsad_env_policy_rule(rules, n_rules, n_bot, seat_bot, bot_seed, key = NULL)
+ *     defines it on the state the step starts from: the same hash streams 128 + 16 p + j, the game index as the key, the game's
+ *     policy counter read once and advanced once per step in every game that has a bot (a game with no bot keeps its counter), the
+ *     noop for a seat that is not on turn, greedy_a = a;
+ *   - a learner row receives what hsad_seat_scatter would write: the agent's a / greedy_a (the noop in a game that is not live);
+ *   - hsad_actor_num_act counts M per step; hsad_actor_last_actions returns the full int64 [G, P] arrays the env stepped with.
+ * With rows = every row and n_bot = 0 the actor computes, bit for bit, what an actor of hsad_actor_create computes.
+ * One step adds three launches to hsad_actor_step's: the row gather in front of act (bf16 observation row, float legal row, eps and
+ * the three bit rows of the M rows into compact buffers), the action merge behind it (one thread per game), and the gather's second
+ * pass behind the env step (reward / terminal per learner row).
+ *
+ * HSAD_ERR_INVALID with a message that names the offending entry, before anything is allocated or launched: cfg->vdn != 0; more
+ * than 5 players; M outside 1 .. G * P; a rows entry out of range, or not above the entry before it (unsorted or duplicated);
+ * n_bot outside 0 .. HSAD_RULE_MAX_BOTS, or 0 with partner rows; an n_rules entry outside 1 .. HSAD_RULE_MAX_RULES; an unknown rule
+ * code; k out of range; a learner row whose seat_bot entry is not -1; a partner row whose entry is outside 0 .. n_bot - 1; and what
+ * hsad_actor_create refuses (a skip_connect net, a missing buffer).  The check is csrc/hsad_partner.h. */
+typedef struct hsad_actor_partners {
+  const int32_t* rows;
+  int32_t M;
+  const hsad_rule* rules;
+  const int32_t* n_rules;
+  int32_t n_bot;
+  const int32_t* seat_bot;
+  uint64_t bot_seed;
+} hsad_actor_partners;
+int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay,
+                                const hsad_actor_config* cfg, const hsad_actor_io* io, const hsad_actor_partners* partners,
+                                hsad_actor** out);
+
 /* ---- seat kernels of a tournament batch (eval.play_seatings): one env object holds every seating of a model pool over the same
  * deals (hsad_env_reseed with period = deals); a model acts once per step on the rows it owns, listed as flat row ids g * P + p.
  * All three are HBM-bound, one pass, launch-only. ---- */

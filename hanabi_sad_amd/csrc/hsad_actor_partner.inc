@@ -18,7 +18,6 @@ extern "C" int hsad_internal_env_rulebot_view(const hsad_env* e, const uint32_t*
 namespace {
 
 constexpr int kPartnerGatherThreads = 192;   // 896 bf16 + 14 bit words + 21 floats + 3 words of a row are 143 pieces: one pass
-constexpr int kPartnerBotWords = RB_TABLE_WORDS;
 
 // the pieces of one row, in the order the threads of a workgroup take them: obs vectors, bit-row pieces, legal pieces, three words
 struct PartnerGather {
@@ -90,27 +89,14 @@ __global__ __launch_bounds__(kPartnerGatherThreads) void partner_gather_kernel(P
   }
 }
 
-// the bots of a launch as a kernel argument (288 bytes): the packed rule table of hsad_rulebot.h
-struct PartnerBots {
-  uint32_t table[RB_TABLE_WORDS];
-};
-
-struct PartnerPlanes {
-  const uint32_t* planes;
-  size_t Gpad;
-  int g;
-  __device__ __forceinline__ uint32_t operator()(int pl) const { return planes[(size_t)pl * Gpad + g]; }
-};
-
 // seat [G * P]: the bot b >= 0 of a partner row, or -(e + 1) for the learner row whose compact index is e.  A learner row of a game
 // that is not live gets the noop, as hsad_seat_scatter gives it; a partner row gets what hsad_env_policy_rule gives it.
 __global__ __launch_bounds__(256) void partner_merge_kernel(const uint32_t* __restrict__ planes, uint32_t* __restrict__ act_count, int G, int Gpad,
-                                                            RbRules ru, PartnerBots rb, const int32_t* __restrict__ seat, uint64_t seed,
+                                                            RbRules ru, RuleBots rb, const int32_t* __restrict__ seat, uint64_t seed,
                                                             const int64_t* __restrict__ a_c, const int64_t* __restrict__ g_c,
                                                             int64_t* __restrict__ a, int64_t* __restrict__ ga) {
-  __shared__ uint32_t s_rb[kPartnerBotWords];
-  for (int k = threadIdx.x; k < kPartnerBotWords; k += blockDim.x) s_rb[k] = rb.table[k];
-  __syncthreads();
+  __shared__ uint32_t s_rb[kRuleBotWords];
+  stage_bots(rb, s_rb, threadIdx.x, blockDim.x);   // (the seat words of rb are zero here and never read: seats are per row, `seat`)
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= G) return;
   const int P = ru.P;
@@ -121,9 +107,8 @@ __global__ __launch_bounds__(256) void partner_merge_kernel(const uint32_t* __re
     st[p] = p < P ? seat[(size_t)g * P + p] : -1;
     any |= p < P && st[p] >= 0;
   }
-  const PartnerPlanes w = {planes, (size_t)Gpad, g};
-  const uint32_t misc = w(RB_PL_MISC);
-  const bool live = ((misc >> 15) & 1u) && !((misc >> 14) & 1u);
+  const GlobalPlanes w = {planes, (size_t)Gpad, g};
+  const bool live = misc_live(w(PL_MISC));
   uint32_t counter = 0u;
   if (any) {   // the policy counter: read once, advanced once per call in every game that has a bot
     counter = act_count[g];
@@ -151,7 +136,7 @@ __global__ __launch_bounds__(256) void partner_merge_kernel(const uint32_t* __re
 struct PartnerSeats {
   char* arena = nullptr;
   PartnerGather g;                 // both passes' argument
-  PartnerBots bots;
+  RuleBots bots;                   // the packed rule table; the seats are per row (`seat` below), not per launch
   RbRules ru;
   const uint32_t* planes = nullptr;
   uint32_t* act_count = nullptr;
@@ -241,6 +226,7 @@ extern "C" int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online,
     for (int j = 0; j < partners->n_rules[b]; ++j) pt->bots.table[b * HSAD_RULE_MAX_RULES + j] = rb_pack(r[j].code, r[j].k);
     pt->bots.table[HSAD_RULE_MAX_BOTS * HSAD_RULE_MAX_RULES + b] = (uint32_t)partners->n_rules[b];
   }
+  pt->bots.n_bot = partners->n_bot;
   pt->bot_seed = partners->bot_seed;
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t total = up(M * 4) + up(N * 4) + up((size_t)M * Fp * 2) + up((size_t)M * A * 4) + up(M * 4) + up((size_t)M * pw64 * 8) +

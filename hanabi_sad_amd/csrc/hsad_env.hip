@@ -8,7 +8,7 @@
 //
 //  * State lives in HBM as struct-of-arrays *planes* of packed u32 bit-fields, game index
 //    fastest ([plane][G]) so a wavefront's 64 lanes (= 64 games) load/store each plane with one
-//    coalesced 256-B access.  The per-game std::mt19937 is kept as 624 words per game and advanced
+//    coalesced 256-B access (which plane holds what, and the fields of every word: hsad_planes.h).  The per-game std::mt19937 is kept as 624 words per game and advanced
 //    incrementally (one word regenerated per draw), so there is never a 624-word twist stall.
 //  * One wavefront = 64 games.  State planes are staged in LDS ([plane][lane], conflict-free) so
 //    the game logic can index hands/knowledge by a run-time seat without scratch spills.
@@ -31,34 +31,13 @@
 
 #include "hsad.h"
 #include "hsad_deal_fast.h"
+#include "hsad_planes.h"
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kMtN = 624;
 constexpr int kMtM = 397;
-
-// ---- state planes ---------------------------------------------------------------------------
-enum : int {
-  PL_DECK_LO = 0,  // deck counts, 2 bits per card type (colour*5+rank), types 0..15
-  PL_DECK_HI = 1,  // types 16..24
-  PL_DISC_LO = 2,  // discard counts, same packing
-  PL_DISC_HI = 3,
-  PL_BOARD = 4,   // fireworks 5x3b [0..14] | info [15..18] | life [19..20] | turns_to_play [21..23]
-                  // | cur_player+1 [24..26] | next_non_chance_player [27..29]
-  PL_MISC = 5,    // num_step [0..7] | deck_size [8..13] | term [14] | started [15] | last_score+1 [16..21]
-                  // | la_n [22..23] = number of buffered look-ahead RNG outputs
-  PL_LASTMV = 6,  // newest non-deal move: type[0..2] player[3..5] target_off[6..8] colour[9..11]
-                  // rank[12..14] card_index[15..17] reveal_mask[18..22] card_colour[23..25]
-                  // card_rank[26..28] scored[29] info_token[30]
-  PL_DRAWS = 7,   // raw mt19937 draws consumed so far (logical; memory is la_n draws ahead)
-  PL_LA0 = 8,     // look-ahead: the next two tempered mt19937 outputs, regenerated off the critical path
-  PL_LA1 = 9,
-  PL_FIXED = 10
-};
-// then per player p: HAND(p) cards 5x5b [0..24] | len [25..27];  KCP(p) colour-plausible 5x5b;
-// KRP(p) rank-plausible 5x5b;  KH(p) hints 5x6b (hinted colour+1 [0..2], hinted rank+1 [3..5]);
-// EPS(p) float bits;  PERM(p) colour perm 5x3b [0..14] | inverse perm [15..29]
 
 struct EnvParams {
   static constexpr bool kScripted = false;
@@ -294,8 +273,6 @@ __device__ __forceinline__ uint32_t uniform_below(uint32_t range, Rng& r) {
   return (uint32_t)(product >> 32);
 }
 
-__device__ __forceinline__ uint32_t cnt2(uint64_t bits, int t) { return (uint32_t)(bits >> (2 * t)) & 3u; }
-
 // Literal restatement of std::discrete_distribution<>(probs)(rng) with probs = count/deck_size
 // (libstdc++ random.tcc: normalise by the sequential sum, partial sums, last := 1.0,
 // p = generate_canonical<double,53> = (u1 + u2*2^32)/2^64, index = lower_bound(cp, p)).
@@ -360,19 +337,6 @@ __device__ __forceinline__ uint32_t remove_field(uint32_t x, int i, int w, int n
   const uint32_t low = body & ((1u << (i * w)) - 1u);
   const uint32_t high = ((i + 1) * w >= 32) ? 0u : (body >> ((i + 1) * w));
   return (x & ~total_mask) | low | (high << (i * w));
-}
-
-__device__ __forceinline__ int board_fw(uint32_t b, int c) { return (b >> (3 * c)) & 7; }
-__device__ __forceinline__ int board_fw_sum(uint32_t b) {
-  return board_fw(b, 0) + board_fw(b, 1) + board_fw(b, 2) + board_fw(b, 3) + board_fw(b, 4);
-}
-__device__ __forceinline__ int board_info(uint32_t b) { return (b >> 15) & 15; }
-__device__ __forceinline__ int board_life(uint32_t b) { return (b >> 19) & 3; }
-__device__ __forceinline__ int board_turns(uint32_t b) { return (b >> 21) & 7; }
-__device__ __forceinline__ int board_cur(uint32_t b) { return (int)((b >> 24) & 7) - 1; }
-__device__ __forceinline__ int board_next(uint32_t b) { return (b >> 27) & 7; }
-__device__ __forceinline__ uint32_t board_set(uint32_t b, int shift, uint32_t mask, uint32_t v) {
-  return (b & ~(mask << shift)) | (v << shift);
 }
 
 struct MoveDec {
@@ -501,12 +465,44 @@ __device__ __forceinline__ void env_stamp(const EnvParams& ep, int it, int k, un
       }                                                                                                 \
     }                                                                                                   \
   } while (0)
-#define PLH(p) (PL_FIXED + (p))
-#define PLKCP(p) (PL_FIXED + P + (p))
-#define PLKRP(p) (PL_FIXED + 2 * P + (p))
-#define PLKH(p) (PL_FIXED + 3 * P + (p))
-#define PLEPS(p) (PL_FIXED + 4 * P + (p))
-#define PLPERM(p) (PL_FIXED + 5 * P + (p))
+
+// ---- the planes of a wave's 64 games between global memory and LDS, and the generator context that lives in them ---------------
+// Used by the playout body and env_observe_kernel.  NOT by env_body and env_rollout_pipe_kernel, which spell the same sequences out:
+// calling these helpers there changes the register allocation and instruction order of every env_kernel, scripted-step and rollout
+// instance (measured when the helpers were introduced, tools/isa_compare.py: env_rollout_pipe_kernel<2,5> 213 -> 212 VGPRs and
+// 436 bytes shorter, <4,4> 1,276 bytes longer), and those kernels are what bench.py times.  Leave them spelled out.
+//
+// all npl planes of game g -> s_st (loads issued in batches of 8 so they overlap)
+__device__ __forceinline__ void stage_planes(const EnvParams& ep, uint32_t* s_st, int lane, int g) {
+  for (int pl0 = 0; pl0 < ep.npl; pl0 += 8) {
+    uint32_t v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = ep.planes[(size_t)min(pl0 + j, ep.npl - 1) * ep.Gpad + g];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (pl0 + j < ep.npl) ST(pl0 + j) = v[j];
+  }
+}
+// game g's generator as the staged planes describe it (no prefetch window); misc: the game's PL_MISC word, which every caller holds
+__device__ __forceinline__ Rng rng_open(const EnvParams& ep, const uint32_t* s_st, int lane, int g, uint32_t misc) {
+  Rng rng;
+  rng.mt = ep.mt + (size_t)g * kMtN;
+  rng.draws = ST(PL_DRAWS);
+  rng.la0 = ST(PL_LA0);
+  rng.la1 = ST(PL_LA1);
+  rng.la_n = misc_la_n(misc);
+  rng.spos = (rng.draws + (uint32_t)rng.la_n) % (uint32_t)kMtN;
+  rng.win = nullptr;
+  rng.w_c = rng.w_n = 0;
+  return rng;
+}
+// ... and back into the staged planes
+__device__ __forceinline__ void rng_close(const Rng& rng, uint32_t* s_st, int lane) {
+  ST(PL_DRAWS) = rng.draws;
+  ST(PL_LA0) = rng.la0;
+  ST(PL_LA1) = rng.la1;
+  ST(PL_MISC) = (ST(PL_MISC) & ~(3u << 22)) | ((uint32_t)rng.la_n << 22);
+}
 
 template <class Ru>
 __device__ __forceinline__ bool move_is_legal(int P, const uint32_t* s_st, int lane, const MoveDec& m, const Ru& ru) {
@@ -1097,17 +1093,7 @@ __device__ __forceinline__ void log_error(const EnvParams& ep, int g, int code) 
 }
 
 // ---- counter-based random-legal policy ---------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ uint32_t policy_hash(uint64_t seed, uint64_t game, uint64_t counter, uint64_t stream) {
-  const uint64_t k = mix64(seed ^ mix64(game * 0xD1342543DE82EF95ull + stream));
-  return (uint32_t)(mix64(k + counter) >> 32);
-}
-
+// (mix64 and policy_hash: hsad_planes.h)
 // k-th set bit of the legal mask, k = hash % popcount (same specification as oracle orc_policy_random)
 __device__ __forceinline__ int policy_pick(uint64_t seed, uint64_t game, uint64_t counter, int p, int stream,
                                            uint64_t mask) {
@@ -2089,16 +2075,16 @@ __global__ void query_kernel(EnvParams ep, int32_t* __restrict__ out) {
   if (g >= ep.G) return;
   const uint32_t board = GP(PL_BOARD), misc = GP(PL_MISC);
   int32_t* o = out + (size_t)g * HSAD_QUERY_WORDS;
-  const bool started = (misc >> 15) & 1u;
-  o[HSAD_Q_TERMINATED] = (!started || ((misc >> 14) & 1u)) ? 1 : 0;
+  const bool started = misc_started(misc);
+  o[HSAD_Q_TERMINATED] = misc_live(misc) ? 0 : 1;
   o[HSAD_Q_CUR_PLAYER] = board_cur(board);
   const int life = board_life(board);
   o[HSAD_Q_SCORE] = (life <= 0 && ep.bomb) ? 0 : board_fw_sum(board);
   o[HSAD_Q_LIFE] = life;
   o[HSAD_Q_INFO] = board_info(board);
-  o[HSAD_Q_LAST_SCORE] = (int)((misc >> 16) & 63u) - 1;
-  o[HSAD_Q_NUM_STEP] = misc & 255u;
-  o[HSAD_Q_DECK_SIZE] = (misc >> 8) & 63u;
+  o[HSAD_Q_LAST_SCORE] = misc_last_score(misc);
+  o[HSAD_Q_NUM_STEP] = misc_num_step(misc);
+  o[HSAD_Q_DECK_SIZE] = misc_deck_size(misc);
   for (int c = 0; c < 5; ++c) o[HSAD_Q_FIREWORKS + c] = board_fw(board, c);
   o[HSAD_Q_RNG_DRAWS] = (int32_t)(GP(PL_DRAWS) & 0x7fffffffu);
   o[HSAD_Q_STARTED] = started ? 1 : 0;
@@ -2129,7 +2115,7 @@ __global__ void deck_history_kernel(EnvParams ep, uint8_t* __restrict__ out, int
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ep.G) return;
   const uint32_t misc = GP(PL_MISC);
-  const int n = ((misc >> 15) & 1u) ? ep.deck_max - (int)((misc >> 8) & 63u) : 0;
+  const int n = misc_started(misc) ? ep.deck_max - misc_deck_size(misc) : 0;
   count[g] = ep.track_dh ? n : 0;
   for (int i = 0; i < 50; ++i) out[(size_t)g * 50 + i] = (ep.track_dh && i < n) ? ep.deck_hist[(size_t)g * 52 + i] : 0;
 }
@@ -2153,8 +2139,8 @@ __global__ void export_state_kernel(EnvParams ep, int32_t* __restrict__ out, int
   o[57] = board_cur(board);
   o[58] = board_next(board);
   o[59] = board_turns(board);
-  o[60] = misc & 255u;
-  o[61] = (misc >> 8) & 63u;
+  o[60] = misc_num_step(misc);
+  o[61] = misc_deck_size(misc);
   const int type = rec & 7;
   o[62] = type;
   o[63] = -1;
@@ -2175,7 +2161,7 @@ __global__ void export_state_kernel(EnvParams ep, int32_t* __restrict__ out, int
     }
   }
   o[73] = (int32_t)(GP(PL_DRAWS) & 0x7fffffffu);
-  o[74] = (int)((misc >> 16) & 63u) - 1;
+  o[74] = misc_last_score(misc);
   int base = 80;
   for (int p = 0; p < ep.P; ++p) {
     const uint32_t hw = GP(PLH(p)), kcp = GP(PLKCP(p)), krp = GP(PLKRP(p)), kh = GP(PLKH(p));
@@ -2196,7 +2182,7 @@ __global__ void export_state_kernel(EnvParams ep, int32_t* __restrict__ out, int
   }
   base += ep.P * ep.H * 6;
   for (int p = 0; p < ep.P; ++p) {
-    const uint32_t pw = ((misc >> 15) & 1u) ? GP(PLPERM(p)) : kIdentityPermBoth;
+    const uint32_t pw = misc_started(misc) ? GP(PLPERM(p)) : kIdentityPermBoth;
     for (int c = 0; c < 5; ++c) {
       o[base + p * 5 + c] = perm_c(pw & 0x7fffu, c);
       o[base + ep.P * 5 + p * 5 + c] = perm_c(pw >> 15, c);

@@ -20,7 +20,7 @@ struct HandKnowledge {
 __device__ __forceinline__ bool hand_knowledge(const EnvParams& ep, int g, int p, HandKnowledge* k) {
   const int P = ep.P;
   const uint32_t misc = GP(PL_MISC);
-  if (p < 0 || p >= P || !((misc >> 15) & 1u) || ((misc >> 14) & 1u)) return false;
+  if (p < 0 || p >= P || !misc_live(misc)) return false;
   const uint32_t hw = GP(PLH(p)), kcp = GP(PLKCP(p)), krp = GP(PLKRP(p));
   const int L = min((int)((hw >> 25) & 7u), HC_MAX_SLOTS);
   uint64_t pool = (uint64_t)GP(PL_DECK_LO) | ((uint64_t)GP(PL_DECK_HI) << 32);

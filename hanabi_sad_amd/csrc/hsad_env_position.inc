@@ -9,10 +9,6 @@
 
 namespace {
 
-static_assert(POS_PL_DECK == PL_DECK_LO && POS_PL_DISC == PL_DISC_LO && POS_PL_BOARD == PL_BOARD && POS_PL_MISC == PL_MISC &&
-                  POS_PL_LASTMV == PL_LASTMV && POS_PL_FIXED == PL_FIXED,
-              "hsad_position.h restates the plane numbers of hsad_env.hip");
-
 __host__ __device__ inline PosRules pos_rules_of(const EnvParams& ep) {
   return PosRules{ep.P, ep.H, ep.nC, ep.nR, ep.max_info, ep.max_life, ep.max_len, ep.shuffle_color, ep.deck_full};
 }
@@ -44,7 +40,7 @@ __global__ void env_import_kernel(EnvParams ep, DealScript own, const int32_t* _
   uint32_t w[POS_MAX_PLANES];
   uint32_t flags = pos_decode_record(states + (size_t)g * words, r, w);
   const uint32_t misc0 = GP(PL_MISC);
-  const bool started = (misc0 >> 15) & 1u;
+  const bool started = misc_started(misc0);
   if (!(flags & (HSAD_POS_FIELD | HSAD_POS_HANDS))) flags |= position_valid(w, r);
   if (!seeds && !started) flags |= HSAD_POS_NO_GENERATOR;
   if (status) status[g] = (int32_t)flags;
@@ -132,7 +128,7 @@ __global__ void env_snapshot_kernel(EnvParams ep, DealScript own, ObserveArgs oa
 __device__ uint32_t snapshot_record_valid(const EnvParams& ep, const SnapLayout& l, const uint32_t* rec) {
   const uint32_t misc = rec[PL_MISC];
   uint32_t f = 0;
-  if (((misc >> 22) & 3u) > 2u) f |= HSAD_POS_LOOKAHEAD;
+  if (misc_la_n(misc) > 2) f |= HSAD_POS_LOOKAHEAD;
   // the history and the script are written with the game whatever its state: their ranges hold for every record
   if (l.has_dh) {
     const uint8_t* dh = reinterpret_cast<const uint8_t*>(rec + l.off_dh);
@@ -151,16 +147,16 @@ __device__ uint32_t snapshot_record_valid(const EnvParams& ep, const SnapLayout&
       if (!script_ok) f |= HSAD_POS_HISTORY;
     }
   }
-  if (!((misc >> 15) & 1u)) return f;   // never started: its planes are restored as they are (a reset overwrites every one it reads)
+  if (!misc_started(misc)) return f;   // never started: its planes are restored as they are (a reset overwrites every one it reads)
   const PosRules r = pos_rules_of(ep);
   const uint32_t pv = position_valid(rec, r);
   f |= pv & ~(uint32_t)HSAD_POS_TERMINAL;
-  const bool term = (misc >> 14) & 1u;
+  const bool term = misc_term(misc);
   if (term != ((pv & HSAD_POS_TERMINAL) != 0u)) f |= HSAD_POS_RECORD;   // the terminated bit is what the position says
   if (script_ok && !term && !(f & HSAD_POS_CONSERVATION)) {
     // the deals still to come from the script, on the deck the record holds
     uint64_t pool = (uint64_t)rec[PL_DECK_LO] | ((uint64_t)rec[PL_DECK_HI] << 32);
-    for (int i = ep.deck_max - (int)((misc >> 8) & 63u); i < n; ++i) {
+    for (int i = ep.deck_max - misc_deck_size(misc); i < n; ++i) {
       const int t = sc[i];
       if (cnt2(pool, t) == 0u) {
         f |= HSAD_POS_SCRIPT;

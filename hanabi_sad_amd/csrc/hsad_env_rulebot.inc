@@ -1,47 +1,16 @@
 // hsad_env_rulebot.inc — rule-list bots (hsad_rulebot.h) as a policy of the env: one policy call on the planes in global memory, and
 // whole playouts in one launch with the planes in LDS.  Textually part of hsad_env.hip (included at its end: the kernels below use
-// its state planes, its game logic and env_playout_kernel's prologue and epilogue as they are).
+// its state planes, its game logic and the playout body of hsad_env_search.inc as they are).
 //
-// Nothing here is reached by reset / step / rollout / playout_random: the two kernels are separate launches, EnvParams is what it
-// was, and every existing kernel is compiled from unchanged code.  Plain loads and vector stores only; the one atomic is log_error's.
+// Nothing here is reached by reset / step / rollout: the two kernels are separate launches and EnvParams is what it was.  The
+// playout kernel shares playout_body with env_playout_kernel (playout_random); the step and rollout kernels are compiled from
+// unchanged code.  Plain loads and vector stores only; the one atomic is log_error's.
 
 #include "hsad_rulebot.h"
 
 namespace {
 
-static_assert(RB_PL_DECK == PL_DECK_LO && RB_PL_DISC == PL_DISC_LO && RB_PL_BOARD == PL_BOARD && RB_PL_MISC == PL_MISC &&
-                  RB_PL_FIXED == PL_FIXED,
-              "hsad_rulebot.h restates the plane numbers of hsad_env.hip");
-
-// the bots of a launch, as a kernel argument (296 bytes): the packed rule table of hsad_rulebot.h, then the bot of each seat
-// (hsad_env_playout_rule).  The kernels copy it to LDS once: which row a lane reads depends on its game.
-struct RuleBots {
-  uint32_t table[RB_TABLE_WORDS];
-  int32_t seat[8];
-  int n_bot;
-};
-constexpr int kRuleBotWords = RB_TABLE_WORDS + 8;
-
-__device__ __forceinline__ RbRules rb_rules_of(const EnvParams& ep) {
-  return RbRules{ep.P, ep.H, ep.nC, ep.nR, ep.max_info, ep.A, ep.shuffle_color, ep.deck_full};
-}
-
-__device__ __forceinline__ void stage_bots(const RuleBots& rb, uint32_t* s_rb, int tid, int nthreads) {
-  for (int k = tid; k < kRuleBotWords; k += nthreads) s_rb[k] = k < RB_TABLE_WORDS ? rb.table[k] : (uint32_t)rb.seat[k - RB_TABLE_WORDS];
-  __syncthreads();
-}
-
-struct GlobalPlanes {
-  const uint32_t* planes;
-  size_t Gpad;
-  int g;
-  __device__ __forceinline__ uint32_t operator()(int pl) const { return planes[(size_t)pl * Gpad + g]; }
-};
-struct LdsPlanes {
-  const uint32_t* s_st;
-  int lane;
-  __device__ __forceinline__ uint32_t operator()(int pl) const { return s_st[pl * kWave + lane]; }
-};
+static_assert(kRbPlaneStride == kWave, "LdsPlanes (hsad_rulebot.h) indexes the planes as the kernels stage them: [npl][kWave]");
 
 // ---- one policy call: one thread per game on the planes in global memory, the shape of policy_kernel ----------------------------------
 __global__ __launch_bounds__(256) void policy_rule_kernel(EnvParams ep, RuleBots rb, const int32_t* __restrict__ seat_bot, uint64_t seed,
@@ -74,82 +43,36 @@ __global__ __launch_bounds__(256) void policy_rule_kernel(EnvParams ep, RuleBots
 }
 
 // ---- playout: bot -> step until the games end ------------------------------------------------------------------------------------------
-// env_playout_kernel with the bot of the seat on turn in place of the random pick: one wave per 64 games, the planes in LDS and the
-// generator context in registers for the whole launch, the same prologue, loop exit and epilogue.  The bot reads the planes where
-// they are (LdsPlanes); its per-slot sums are 15 registers of the lane.
+// playout_body (hsad_env_search.inc) with the bot of the seat on turn as its policy.  The bot reads the planes where they are
+// (LdsPlanes); its per-slot sums are 15 registers of the lane.
+struct RuleBotPolicy {
+  RbRules rr;             // the env's rules, with the kernel's compile-time players / hand size
+  LdsPlanes w;            // the lane's game in the staged planes
+  const uint32_t* s_rb;   // the staged RuleBots
+  template <int TH, class Ru>
+  __device__ __forceinline__ void act(const EnvParams& ep, const uint32_t* s_st, int lane, int g, int P, int H, const Ru& ru, uint64_t pkey,
+                                      uint32_t counter) const {
+    const int cur = board_cur(ST(PL_BOARD));
+    // (a live game has a seat on turn; the bound keeps the LDS read in range whatever the planes hold)
+    const int uid = (cur >= 0 && cur < P) ? rb_act(w, rr, cur, s_rb, (int)s_rb[RB_TABLE_WORDS + cur], ep.policy_seed, pkey, (uint64_t)counter, nullptr)
+                                          : ep.A - 1;
+    for (int p = 0; p < P; ++p) {
+      const int64_t v = p == cur ? uid : ep.A - 1;
+      ep.a_out[(size_t)g * P + p] = v;
+      if (ep.g_out) ep.g_out[(size_t)g * P + p] = v;
+    }
+  }
+};
+
 template <int TP, int TH, bool V>
 __global__ __launch_bounds__(kWave) void env_playout_rule_kernel(EnvParams ep, RuleBots rb, const int64_t* __restrict__ key) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // the planes playout_body stages
   __shared__ uint32_t s_rb[kRuleBotWords];
-  uint32_t* s_st = smem;
-  const int lane = threadIdx.x;
-  const int g = blockIdx.x * kWave + lane;   // < Gpad
-  const bool valid = g < ep.G;
-  const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
-  const auto ru = RulesOf<V>::make(ep);
-  stage_bots(rb, s_rb, lane, kWave);
-  for (int pl0 = 0; pl0 < ep.npl; pl0 += 8) {
-    uint32_t v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = ep.planes[(size_t)min(pl0 + j, ep.npl - 1) * ep.Gpad + g];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (pl0 + j < ep.npl) ST(pl0 + j) = v[j];
-  }
-  const uint32_t misc0 = ST(PL_MISC);
-  const bool live0 = valid && ((misc0 >> 15) & 1u) && !((misc0 >> 14) & 1u);
-  if (__ballot(live0) == 0ull) return;
-  const uint64_t pkey = valid ? (key ? (uint64_t)key[g] : (uint64_t)g) : 0ull;
+  stage_bots(rb, s_rb, threadIdx.x, kWave);
   RbRules rr = rb_rules_of(ep);
-  rr.P = P;
-  rr.H = H;
-  const LdsPlanes w = {s_st, lane};
-  Rng rng;
-  rng.mt = ep.mt + (size_t)g * kMtN;
-  rng.draws = ST(PL_DRAWS);
-  rng.la0 = ST(PL_LA0);
-  rng.la1 = ST(PL_LA1);
-  rng.la_n = (int)((misc0 >> 22) & 3u);
-  rng.spos = (rng.draws + (uint32_t)rng.la_n) % (uint32_t)kMtN;
-  rng.win = nullptr;
-  rng.w_c = rng.w_n = 0;
-#pragma clang loop unroll(disable)
-  for (int it = 0; it < ep.n_iter; ++it) {
-    const uint32_t misc = ST(PL_MISC);
-    const bool live = live0 && !((misc >> 14) & 1u);
-    if (__ballot(live) == 0ull) break;
-    if (live) {
-      const uint32_t counter = ep.act_count[g];
-      ep.act_count[g] = counter + 1u;
-      const int cur = board_cur(ST(PL_BOARD));
-      // (a live game has a seat on turn; the bound keeps the LDS read in range whatever the planes hold)
-      const int uid = (cur >= 0 && cur < P) ? rb_act(w, rr, cur, s_rb, (int)s_rb[RB_TABLE_WORDS + cur], ep.policy_seed, pkey, (uint64_t)counter, nullptr)
-                                            : ep.A - 1;
-      for (int p = 0; p < P; ++p) {
-        const int64_t v = p == cur ? uid : ep.A - 1;
-        ep.a_out[(size_t)g * P + p] = v;
-        if (ep.g_out) ep.g_out[(size_t)g * P + p] = v;
-      }
-    }
-    uint32_t greedy_rec = 0;
-    float reward = 0.f;
-    bool term = false;
-    env_logic<1, TP, TH, V>(ep, ep.a_out, ep.g_out, s_st, nullptr, nullptr, lane, g, live, false, rng, greedy_rec, reward, term);
-  }
-  if (live0) {
-    Refill rf;
-    refill_issue(rf, rng, true);
-    refill_finish(rf, rng);
-    ST(PL_DRAWS) = rng.draws;
-    ST(PL_LA0) = rng.la0;
-    ST(PL_LA1) = rng.la1;
-    ST(PL_MISC) = (ST(PL_MISC) & ~(3u << 22)) | ((uint32_t)rng.la_n << 22);
-    for (int p = 0; p < P; ++p)
-      ep.legal_bits[(size_t)g * P + p] =
-          legal_mask_of<TH>(P, H, ep.A, s_st, lane, p, ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru);
-    for (int pl = 0; pl < ep.npl; ++pl) ep.planes[(size_t)pl * ep.Gpad + g] = ST(pl);
-    ep.terminal[g] = (uint8_t)((ST(PL_MISC) >> 14) & 1u);
-  }
+  rr.P = TP ? TP : ep.P;
+  rr.H = TH ? TH : ep.H;
+  playout_body<TP, TH, V>(ep, key, RuleBotPolicy{rr, LdsPlanes{smem, (int)threadIdx.x}, s_rb});
 }
 
 typedef void (*EnvPlayoutRuleFn)(EnvParams, RuleBots, const int64_t*);
@@ -207,8 +130,7 @@ int hsad_internal_env_rulebot_view(const hsad_env* e, const uint32_t** planes, u
   *act_count = e->ep.act_count;
   *G = e->ep.G;
   *Gpad = e->ep.Gpad;
-  const EnvParams& ep = e->ep;
-  *ru = RbRules{ep.P, ep.H, ep.nC, ep.nR, ep.max_info, ep.A, ep.shuffle_color, ep.deck_full};   // rb_rules_of, on the host
+  *ru = rb_rules_of(e->ep);
   return HSAD_OK;
 }
 

@@ -63,21 +63,13 @@ __global__ __launch_bounds__(kEnvThreads) void env_observe_kernel(EnvParams ep, 
   const uint64_t todo = __ballot(chosen);
   if (todo == 0ull) return;   // the same 64 games in every wave: uniform over the workgroup
   if (wave == 0) {
-    for (int pl0 = 0; pl0 < ep.npl; pl0 += 8) {
-      uint32_t v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = ep.planes[(size_t)min(pl0 + j, ep.npl - 1) * ep.Gpad + g];
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (pl0 + j < ep.npl) ST(pl0 + j) = v[j];
-    }
+    stage_planes(ep, s_st, lane, g);
   } else {
     clear_rows(ep, s_obs, tid - kWave, nthreads - kWave);
   }
   __syncthreads();
   const uint32_t misc = ST(PL_MISC);
-  const bool started = (misc >> 15) & 1u;
-  if (chosen && started) {
+  if (chosen && misc_started(misc)) {
     build_rows<TP, TH, V>(ep, s_st, lane, g, s_obs, s_legal, s_own, 0u, wave, nwaves);
     if (ep.sad)
       for (int p = wave; p < P; p += nwaves)
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(kEnvThreads) void env_observe_kernel(EnvParams ep, 
   if (chosen && wave == 0) {
     for (int p = 0; p < P; ++p) ep.eps[(size_t)g * P + p] = __uint_as_float(ST(PLEPS(p)));
     ep.reward[g] = 0.f;
-    ep.terminal[g] = (uint8_t)((misc >> 14) & 1u);
+    ep.terminal[g] = (uint8_t)misc_term(misc);
   }
   if (ep.kmode == 1) v0_fixup<V>(ep, s_st, s_obs, mine, g0, lane);
 }
@@ -182,7 +174,7 @@ __global__ void env_determinize_kernel(EnvParams ep, const int32_t* __restrict__
   const uint32_t misc = GP(PL_MISC);
   int tries = 0;
   bool changed = false;
-  if (p >= 0 && p < P && ((misc >> 15) & 1u) && !((misc >> 14) & 1u)) {
+  if (p >= 0 && p < P && misc_live(misc)) {
     const uint32_t hw = GP(PLH(p)), kcp = GP(PLKCP(p)), krp = GP(PLKRP(p));
     const int L = (hw >> 25) & 7;
     const uint64_t k64 = (uint64_t)key[g];
@@ -246,7 +238,7 @@ __global__ void env_rewind_kernel(EnvParams ep, DealScript own, const uint8_t* _
   if (n <= 0) return;
   const int P = ep.P, H = ep.H;
   const uint32_t misc = GP(PL_MISC);
-  if (!((misc >> 15) & 1u)) return;   // never started: reset has drawn no eps and no permutation to keep
+  if (!misc_started(misc)) return;   // never started: reset has drawn no eps and no permutation to keep
   const uint8_t* sc = script + (size_t)g * 52;
   bool ok = n >= P * H && n <= ep.deck_max;
   uint64_t pool = ep.deck_full, deck = ep.deck_full;
@@ -293,15 +285,22 @@ __global__ void env_rewind_kernel(EnvParams ep, DealScript own, const uint8_t* _
   sel[g] = g;
 }
 
-// ---- playout: random-legal policy -> step until the games end, no restart, no observation rows ------------------------------------
+// ---- playout: policy -> step until the games end, no restart, no observation rows --------------------------------------------------
 // One wave per 64 games; the planes stay in LDS and the generator context in registers for the whole launch.  Per iteration and live
-// game: the policy of policy_kernel on the legal masks of the state itself (the masks build_rows would have stored), then the step
-// of MODE 1 on the actions just written.  key (or the game index) is the "game" field of the policy hash.  A lane whose game is
-// finished does nothing; the wave leaves the loop when none of its games is live, so a launch does at most n_iter iterations and
-// never looks at another workgroup.  Afterwards: look-ahead topped up as a step leaves it, planes written back, `terminal` and the
-// legal masks the next policy call reads made current.
-template <int TP, int TH, bool V>
-__global__ __launch_bounds__(kWave) void env_playout_kernel(EnvParams ep, const int64_t* __restrict__ key) {
+// game: the policy writes the actions of this iteration (a_out / g_out, all P seats of the lane's game), then the step of MODE 1 runs
+// on the actions just written.  key (or the game index) is the "game" field of the policy hash.  A lane whose game is finished does
+// nothing; the wave leaves the loop when none of its games is live, so a launch does at most n_iter iterations and never looks at
+// another workgroup.  Afterwards: look-ahead topped up as a step leaves it, planes written back, `terminal` and the legal masks the
+// next policy call reads made current.
+//
+// policy (by value, its call inlined): act<TH>(ep, s_st, lane, g, P, H, ru, pkey, counter) writes ep.a_out / ep.g_out [g, 0..P) for
+// the lane's live game from the planes in s_st; counter is the game's policy counter before this iteration.
+//
+// The two kernels' code is not what it was when each spelled this body out, and neither the helpers, the accessors nor the policy
+// object are why: the old kernel text moved verbatim into a force-inlined __device__ function gives the same new code (the kernel's
+// parameter struct then reaches the body through a reference, as it always did in env_body).  tools/isa_compare.py shows the sizes.
+template <int TP, int TH, bool V, class Policy>
+__device__ __forceinline__ void playout_body(const EnvParams& ep, const int64_t* __restrict__ key, const Policy policy) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* s_st = smem;
   const int lane = threadIdx.x;
@@ -309,40 +308,20 @@ __global__ __launch_bounds__(kWave) void env_playout_kernel(EnvParams ep, const 
   const bool valid = g < ep.G;
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
   const auto ru = RulesOf<V>::make(ep);
-  for (int pl0 = 0; pl0 < ep.npl; pl0 += 8) {
-    uint32_t v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = ep.planes[(size_t)min(pl0 + j, ep.npl - 1) * ep.Gpad + g];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (pl0 + j < ep.npl) ST(pl0 + j) = v[j];
-  }
+  stage_planes(ep, s_st, lane, g);
   const uint32_t misc0 = ST(PL_MISC);
-  const bool live0 = valid && ((misc0 >> 15) & 1u) && !((misc0 >> 14) & 1u);
+  const bool live0 = valid && misc_live(misc0);
   if (__ballot(live0) == 0ull) return;
   const uint64_t pkey = valid ? (key ? (uint64_t)key[g] : (uint64_t)g) : 0ull;
-  Rng rng;
-  rng.mt = ep.mt + (size_t)g * kMtN;
-  rng.draws = ST(PL_DRAWS);
-  rng.la0 = ST(PL_LA0);
-  rng.la1 = ST(PL_LA1);
-  rng.la_n = (int)((misc0 >> 22) & 3u);
-  rng.spos = (rng.draws + (uint32_t)rng.la_n) % (uint32_t)kMtN;
-  rng.win = nullptr;
-  rng.w_c = rng.w_n = 0;
+  Rng rng = rng_open(ep, s_st, lane, g, misc0);
 #pragma clang loop unroll(disable)
   for (int it = 0; it < ep.n_iter; ++it) {
-    const uint32_t misc = ST(PL_MISC);
-    const bool live = live0 && !((misc >> 14) & 1u);
+    const bool live = live0 && !misc_term(ST(PL_MISC));
     if (__ballot(live) == 0ull) break;
     if (live) {
       const uint32_t counter = ep.act_count[g];
       ep.act_count[g] = counter + 1u;
-      for (int p = 0; p < P; ++p) {
-        const uint64_t mask = legal_mask_of<TH>(P, H, ep.A, s_st, lane, p, ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru);
-        ep.a_out[(size_t)g * P + p] = policy_pick(ep.policy_seed, pkey, (uint64_t)counter, p, 0, mask);
-        if (ep.g_out) ep.g_out[(size_t)g * P + p] = policy_pick(ep.policy_seed, pkey, (uint64_t)counter, p, 1, mask);
-      }
+      policy.template act<TH>(ep, s_st, lane, g, P, H, ru, pkey, counter);
     }
     uint32_t greedy_rec = 0;
     float reward = 0.f;
@@ -353,16 +332,31 @@ __global__ __launch_bounds__(kWave) void env_playout_kernel(EnvParams ep, const 
     Refill rf;
     refill_issue(rf, rng, true);
     refill_finish(rf, rng);
-    ST(PL_DRAWS) = rng.draws;
-    ST(PL_LA0) = rng.la0;
-    ST(PL_LA1) = rng.la1;
-    ST(PL_MISC) = (ST(PL_MISC) & ~(3u << 22)) | ((uint32_t)rng.la_n << 22);
+    rng_close(rng, s_st, lane);
     for (int p = 0; p < P; ++p)
       ep.legal_bits[(size_t)g * P + p] =
           legal_mask_of<TH>(P, H, ep.A, s_st, lane, p, ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru);
     for (int pl = 0; pl < ep.npl; ++pl) ep.planes[(size_t)pl * ep.Gpad + g] = ST(pl);
-    ep.terminal[g] = (uint8_t)((ST(PL_MISC) >> 14) & 1u);
+    ep.terminal[g] = (uint8_t)misc_term(ST(PL_MISC));
   }
+}
+
+// the policy of policy_kernel on the legal masks of the state itself (the masks build_rows would have stored)
+struct RandomLegalPolicy {
+  template <int TH, class Ru>
+  __device__ __forceinline__ void act(const EnvParams& ep, const uint32_t* s_st, int lane, int g, int P, int H, const Ru& ru, uint64_t pkey,
+                                      uint32_t counter) const {
+    for (int p = 0; p < P; ++p) {
+      const uint64_t mask = legal_mask_of<TH>(P, H, ep.A, s_st, lane, p, ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm, ru);
+      ep.a_out[(size_t)g * P + p] = policy_pick(ep.policy_seed, pkey, (uint64_t)counter, p, 0, mask);
+      if (ep.g_out) ep.g_out[(size_t)g * P + p] = policy_pick(ep.policy_seed, pkey, (uint64_t)counter, p, 1, mask);
+    }
+  }
+};
+
+template <int TP, int TH, bool V>
+__global__ __launch_bounds__(kWave) void env_playout_kernel(EnvParams ep, const int64_t* __restrict__ key) {
+  playout_body<TP, TH, V>(ep, key, RandomLegalPolicy{});
 }
 
 typedef void (*EnvObserveFn)(EnvParams, ObserveArgs);

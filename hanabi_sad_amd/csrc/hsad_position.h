@@ -3,20 +3,14 @@
 // hsad_env_restore run before a word of a game is written.  Plain C++ (no HIP types, no allocation): hsad_env_position.inc includes
 // it under hipcc, tests/position/position_main.cc under g++.  Specification: include/hsad.h, HSAD_POS_* and hsad_env_import_state.
 //
-// Plane words of one game, index = plane number of csrc/hsad_env.hip (the .inc asserts that the two agree):
-//   0/1 deck counts, 2 bits per card type colour * 5 + rank;  2/3 discard counts;  4 board: fireworks 5x3b | info [15..18] | life
-//   [19..20] | turns_to_play [21..23] | cur_player + 1 [24..26] | next_non_chance_player [27..29];  5 misc: num_step [0..7] |
-//   deck size [8..13] | terminated [14] | started [15] | last_score + 1 [16..21] | look-ahead count [22..23];  6 last move: type
-//   [0..2] player [3..5] target offset [6..8] colour [9..11] rank [12..14] card index [15..17] reveal mask [18..22] card colour
-//   [23..25] card rank [26..28] scored [29] info token [30];  7 draws;  8/9 look-ahead;  then P words each of: hand (5x5b cards |
-//   length [25..27]), plausible colours 5x5b, plausible ranks 5x5b, hints 5x6b (colour + 1 | rank + 1), eps, colour permutation
-//   (5x3b | inverse [15..29]).
+// Plane words of one game: index = plane number, fields as hsad_planes.h describes them.
 #ifndef HSAD_POSITION_H
 #define HSAD_POSITION_H
 
 #include <stdint.h>
 
 #include "hsad.h"
+#include "hsad_planes.h"
 
 #if defined(__HIPCC__)
 #define HSAD_POS_FN __host__ __device__ inline
@@ -24,21 +18,13 @@
 #define HSAD_POS_FN inline
 #endif
 
-#define POS_PL_DECK 0
-#define POS_PL_DISC 2
-#define POS_PL_BOARD 4
-#define POS_PL_MISC 5
-#define POS_PL_LASTMV 6
-#define POS_PL_FIXED 10
 #define POS_MAX_PLAYERS 5
-#define POS_MAX_PLANES (POS_PL_FIXED + 6 * POS_MAX_PLAYERS)
+#define POS_MAX_PLANES (PL_FIXED + 6 * POS_MAX_PLAYERS)
 
 struct PosRules {
   int P, H, nC, nR, max_info, max_life, max_len, shuffle_color;
   uint64_t deck_full;   // the full deck's 2-bit counts
 };
-
-HSAD_POS_FN int pos_cnt(uint64_t q, int t) { return (int)((q >> (2 * t)) & 3u); }
 
 // v into a field of `bits` bits, biased by `bias` (the planes store cur_player + 1, hinted colour + 1, ...); sets *bad when it does not fit
 HSAD_POS_FN uint32_t pos_field(int32_t v, int bias, int bits, bool* bad) {
@@ -64,10 +50,10 @@ HSAD_POS_FN uint32_t pos_decode_record(const int32_t* o, const PosRules& r, uint
     deck |= (uint64_t)pos_field(o[t], 0, 2, &bad) << (2 * t);
     disc |= (uint64_t)pos_field(o[25 + t], 0, 2, &bad) << (2 * t);
   }
-  w[POS_PL_DECK] = (uint32_t)deck;
-  w[POS_PL_DECK + 1] = (uint32_t)(deck >> 32);
-  w[POS_PL_DISC] = (uint32_t)disc;
-  w[POS_PL_DISC + 1] = (uint32_t)(disc >> 32);
+  w[PL_DECK_LO] = (uint32_t)deck;
+  w[PL_DECK_HI] = (uint32_t)(deck >> 32);
+  w[PL_DISC_LO] = (uint32_t)disc;
+  w[PL_DISC_HI] = (uint32_t)(disc >> 32);
   uint32_t board = 0;
   for (int c = 0; c < 5; ++c) board |= pos_field(o[50 + c], 0, 3, &bad) << (3 * c);
   board |= pos_field(o[55], 0, 4, &bad) << 15;
@@ -75,7 +61,7 @@ HSAD_POS_FN uint32_t pos_decode_record(const int32_t* o, const PosRules& r, uint
   board |= pos_field(o[59], 0, 3, &bad) << 21;
   board |= pos_field(o[57], 1, 3, &bad) << 24;
   board |= pos_field(o[58], 0, 3, &bad) << 27;
-  w[POS_PL_BOARD] = board;
+  w[PL_BOARD] = board;
   uint32_t misc = 1u << 15;
   if (o[60] < 0 || o[60] > 255)
     flags |= HSAD_POS_STEP;
@@ -83,7 +69,7 @@ HSAD_POS_FN uint32_t pos_decode_record(const int32_t* o, const PosRules& r, uint
     misc |= (uint32_t)o[60];
   misc |= pos_field(o[61], 0, 6, &bad) << 8;
   misc |= pos_field(o[74], 1, 6, &bad) << 16;
-  w[POS_PL_MISC] = misc;
+  w[PL_MISC] = misc;
   uint32_t rec = pos_field(o[62], 0, 3, &bad);
   const int type = (int)rec;
   if (type) rec |= pos_field(o[63], 0, 3, &bad) << 3;
@@ -99,7 +85,7 @@ HSAD_POS_FN uint32_t pos_decode_record(const int32_t* o, const PosRules& r, uint
     rec |= pos_field(o[71], 0, 1, &bad) << 29;
     rec |= pos_field(o[72], 0, 1, &bad) << 30;
   }
-  w[POS_PL_LASTMV] = rec;
+  w[PL_LASTMV] = rec;
   for (int p = 0; p < P; ++p) {
     uint32_t hw = 0, kcp = 0, krp = 0, kh = 0;
     int len = 0;
@@ -121,17 +107,17 @@ HSAD_POS_FN uint32_t pos_decode_record(const int32_t* o, const PosRules& r, uint
       kh |= pos_field(s[4], 1, 3, &bad) << (6 * i + 3);
       len = i + 1;
     }
-    w[POS_PL_FIXED + p] = hw | ((uint32_t)len << 25);
-    w[POS_PL_FIXED + P + p] = kcp;
-    w[POS_PL_FIXED + 2 * P + p] = krp;
-    w[POS_PL_FIXED + 3 * P + p] = kh;
+    w[PLH(p)] = hw | ((uint32_t)len << 25);
+    w[PLKCP(p)] = kcp;
+    w[PLKRP(p)] = krp;
+    w[PLKH(p)] = kh;
     uint32_t pw = 0;
     const int base = 80 + P * H * 6;
     for (int c = 0; c < 5; ++c) {
       pw |= pos_field(o[base + p * 5 + c], 0, 3, &bad) << (3 * c);
       pw |= pos_field(o[base + P * 5 + p * 5 + c], 0, 3, &bad) << (15 + 3 * c);
     }
-    w[POS_PL_FIXED + 5 * P + p] = pw;
+    w[PLPERM(p)] = pw;
   }
   if (bad) return (uint32_t)HSAD_POS_FIELD;
   if (flags & HSAD_POS_HANDS) return (uint32_t)HSAD_POS_HANDS;
@@ -144,18 +130,18 @@ HSAD_POS_FN uint32_t pos_decode_record(const int32_t* o, const PosRules& r, uint
 HSAD_POS_FN uint32_t position_valid(const uint32_t* w, const PosRules& r) {
   const int P = r.P, H = r.H;
   uint32_t f = 0;
-  const uint64_t deck = (uint64_t)w[POS_PL_DECK] | ((uint64_t)w[POS_PL_DECK + 1] << 32);
-  const uint64_t disc = (uint64_t)w[POS_PL_DISC] | ((uint64_t)w[POS_PL_DISC + 1] << 32);
-  const uint32_t board = w[POS_PL_BOARD], misc = w[POS_PL_MISC], rec = w[POS_PL_LASTMV];
+  const uint64_t deck = (uint64_t)w[PL_DECK_LO] | ((uint64_t)w[PL_DECK_HI] << 32);
+  const uint64_t disc = (uint64_t)w[PL_DISC_LO] | ((uint64_t)w[PL_DISC_HI] << 32);
+  const uint32_t board = w[PL_BOARD], misc = w[PL_MISC], rec = w[PL_LASTMV];
   const uint32_t cmask = (1u << r.nC) - 1u, rmask = (1u << r.nR) - 1u;
-  const int info = (int)((board >> 15) & 15u), life = (int)((board >> 19) & 3u), turns = (int)((board >> 21) & 7u);
-  const int cur = (int)((board >> 24) & 7u) - 1, next = (int)((board >> 27) & 7u);
-  const int num_step = (int)(misc & 255u), deck_size = (int)((misc >> 8) & 63u);
+  const int info = board_info(board), life = board_life(board), turns = board_turns(board);
+  const int cur = board_cur(board), next = board_next(board);
+  const int num_step = misc_num_step(misc), deck_size = misc_deck_size(misc);
 
   // ---- hands: lengths, nothing above the length, and the cards held per type ----
   int n_short = 0, short_seat = -1;
   for (int p = 0; p < P; ++p) {
-    const uint32_t hw = w[POS_PL_FIXED + p];
+    const uint32_t hw = w[PLH(p)];
     int len = (int)((hw >> 25) & 7u);
     if (len > H || len < H - 1 || (hw >> 28) != 0u) f |= HSAD_POS_HANDS;
     if (len > H) len = H;
@@ -166,7 +152,7 @@ HSAD_POS_FN uint32_t position_valid(const uint32_t* w, const PosRules& r) {
     const uint32_t above5 = len >= 5 ? 0u : (0x1ffffffu >> (5 * len)) << (5 * len);
     const uint32_t above6 = len >= 5 ? 0xc0000000u : (0xffffffffu >> (6 * len)) << (6 * len);
     if (hw & above5) f |= HSAD_POS_HANDS;
-    const uint32_t kcp = w[POS_PL_FIXED + P + p], krp = w[POS_PL_FIXED + 2 * P + p], kh = w[POS_PL_FIXED + 3 * P + p];
+    const uint32_t kcp = w[PLKCP(p)], krp = w[PLKRP(p)], kh = w[PLKH(p)];
     if ((kcp & (above5 | 0xfe000000u)) || (krp & (above5 | 0xfe000000u)) || (kh & above6)) f |= HSAD_POS_KNOWLEDGE;
     for (int i = 0; i < len; ++i) {
       const int card = (int)((hw >> (5 * i)) & 31u);
@@ -186,7 +172,7 @@ HSAD_POS_FN uint32_t position_valid(const uint32_t* w, const PosRules& r) {
   // ---- conservation, per card type ----
   int deck_n = 0, fsum = 0;
   for (int c = 0; c < 5; ++c) {
-    const int fw = (int)((board >> (3 * c)) & 7u);
+    const int fw = board_fw(board, c);
     if (c >= r.nC) {
       if (fw) f |= HSAD_POS_CONSERVATION;
     } else {
@@ -197,14 +183,14 @@ HSAD_POS_FN uint32_t position_valid(const uint32_t* w, const PosRules& r) {
       const int t = c * 5 + k;
       int held = 0;
       for (int p = 0; p < P; ++p) {
-        const uint32_t hw = w[POS_PL_FIXED + p];
+        const uint32_t hw = w[PLH(p)];
         int len = (int)((hw >> 25) & 7u);
         if (len > H) len = H;
         for (int i = 0; i < len; ++i) held += ((int)((hw >> (5 * i)) & 31u) == t) ? 1 : 0;
       }
-      const int have = pos_cnt(deck, t) + pos_cnt(disc, t) + held + ((c < r.nC && fw > k) ? 1 : 0);
-      if (have != pos_cnt(r.deck_full, t)) f |= HSAD_POS_CONSERVATION;   // (deck_full is 0 outside the rules' colours and ranks)
-      deck_n += pos_cnt(deck, t);
+      const int have = (int)cnt2(deck, t) + (int)cnt2(disc, t) + held + ((c < r.nC && fw > k) ? 1 : 0);
+      if (have != (int)cnt2(r.deck_full, t)) f |= HSAD_POS_CONSERVATION;   // (deck_full is 0 outside the rules' colours and ranks)
+      deck_n += (int)cnt2(deck, t);
     }
   }
   if ((deck >> 50) || (disc >> 50)) f |= HSAD_POS_CONSERVATION;
@@ -252,7 +238,7 @@ HSAD_POS_FN uint32_t position_valid(const uint32_t* w, const PosRules& r) {
 
   // ---- colour permutations ----
   for (int p = 0; p < P; ++p) {
-    const uint32_t pw = w[POS_PL_FIXED + 5 * P + p];
+    const uint32_t pw = w[PLPERM(p)];
     bool ok = (pw >> 30) == 0u;
     uint32_t seen = 0;
     for (int c = 0; c < 5 && ok; ++c) {

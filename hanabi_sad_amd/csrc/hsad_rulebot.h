@@ -3,14 +3,15 @@
 // hsad_env_rulebot.inc includes it under hipcc, tests/rulebot/rulebot_main.cc under g++.  Specification: include/hsad.h,
 // HSAD_RULE_* and hsad_env_policy_rule (the header is the normative text; this file follows it).
 //
-// The state is read through an accessor `w(pl)` = plane word pl of the game (plane numbers of csrc/hsad_env.hip, restated in
-// hsad_position.h), so that a kernel can hand over its planes where they are (global memory or LDS) without a copy.
+// The state is read through an accessor `w(pl)` = plane word pl of the game (plane numbers and bit fields: hsad_planes.h), so that a
+// kernel can hand over its planes where they are (global memory or LDS) without a copy: GlobalPlanes and LdsPlanes below.
 #ifndef HSAD_RULEBOT_H
 #define HSAD_RULEBOT_H
 
 #include <stdint.h>
 
 #include "hsad.h"
+#include "hsad_planes.h"
 
 #if defined(__HIPCC__)
 #define HSAD_RB_FN __host__ __device__ inline
@@ -18,17 +19,17 @@
 #define HSAD_RB_FN inline
 #endif
 
-#define RB_PL_DECK 0
-#define RB_PL_DISC 2
-#define RB_PL_BOARD 4
-#define RB_PL_MISC 5
-#define RB_PL_FIXED 10
 #define RB_TABLE_WORDS (HSAD_RULE_MAX_BOTS * HSAD_RULE_MAX_RULES + HSAD_RULE_MAX_BOTS)
 
 struct RbRules {
   int P, H, nC, nR, max_info, A, shuffle_color;
   uint64_t deck_full;   // the full deck's 2-bit counts
 };
+// the rules of an env, from its parameter struct (csrc/hsad_env.hip: EnvParams)
+template <class EP>
+HSAD_RB_FN RbRules rb_rules_of(const EP& ep) {
+  return RbRules{ep.P, ep.H, ep.nC, ep.nR, ep.max_info, ep.A, ep.shuffle_color, ep.deck_full};
+}
 
 // a rule as one word: code [0..7] | k [8..15].  A bot table is HSAD_RULE_MAX_BOTS rows of HSAD_RULE_MAX_RULES such words followed
 // by the HSAD_RULE_MAX_BOTS list lengths (RB_TABLE_WORDS words in all).
@@ -44,18 +45,6 @@ HSAD_RB_FN int rb_rules_invalid(const hsad_rule* rules, int n_rules) {
     if (has_k ? (k < 0 || k > 100) : (k != 0)) return 3;
   }
   return 0;
-}
-
-// the policy's counter-based hash (csrc/hsad_env.hip: mix64 / policy_hash), restated so that the bot is one header
-HSAD_RB_FN uint64_t rb_mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-HSAD_RB_FN uint32_t rb_hash(uint64_t seed, uint64_t game, uint64_t counter, uint64_t stream) {
-  const uint64_t k = rb_mix64(seed ^ rb_mix64(game * 0xD1342543DE82EF95ull + stream));
-  return (uint32_t)(rb_mix64(k + counter) >> 32);
 }
 
 HSAD_RB_FN int rb_popc32(uint32_t x) {
@@ -105,27 +94,27 @@ HSAD_RB_FN int rb_act(const W& w, const RbRules& ru, int p, const uint32_t* tabl
                       int* fired) {
   const int P = ru.P, H = ru.H;
   if (fired) *fired = -1;
-  const uint32_t board = w(RB_PL_BOARD), misc = w(RB_PL_MISC);
-  if ((int)((board >> 24) & 7u) - 1 != p) return ru.A - 1;
-  const int info = (int)((board >> 15) & 15u), life = (int)((board >> 19) & 3u), deck_size = (int)((misc >> 8) & 63u);
-  const uint32_t pm = ru.shuffle_color ? (w(RB_PL_FIXED + 5 * P + p) & 0x7fffu) : ((1u << 3) | (2u << 6) | (3u << 9) | (4u << 12));
-  const uint64_t deck = (uint64_t)w(RB_PL_DECK) | ((uint64_t)w(RB_PL_DECK + 1) << 32);
-  const uint64_t disc = (uint64_t)w(RB_PL_DISC) | ((uint64_t)w(RB_PL_DISC + 1) << 32);
-  const uint32_t hw = w(RB_PL_FIXED + p), kcp = w(RB_PL_FIXED + P + p), krp = w(RB_PL_FIXED + 2 * P + p), kh = w(RB_PL_FIXED + 3 * P + p);
+  const uint32_t board = w(PL_BOARD), misc = w(PL_MISC);
+  if (board_cur(board) != p) return ru.A - 1;
+  const int info = board_info(board), life = board_life(board), deck_size = misc_deck_size(misc);
+  const uint32_t pm = ru.shuffle_color ? (w(PLPERM(p)) & 0x7fffu) : ((1u << 3) | (2u << 6) | (3u << 9) | (4u << 12));
+  const uint64_t deck = (uint64_t)w(PL_DECK_LO) | ((uint64_t)w(PL_DECK_HI) << 32);
+  const uint64_t disc = (uint64_t)w(PL_DISC_LO) | ((uint64_t)w(PL_DISC_HI) << 32);
+  const uint32_t hw = w(PLH(p)), kcp = w(PLKCP(p)), krp = w(PLKRP(p)), kh = w(PLKH(p));
   const int L = (int)((hw >> 25) & 7u);
 
   // type masks: playable, dead, and the types the full deck holds
   uint32_t playable = 0, dead = 0, exists = 0;
   for (int c = 0; c < 5; ++c) {
-    const int fw = (int)((board >> (3 * c)) & 7u);
+    const int fw = board_fw(board, c);
     bool blocked = false;
     for (int r = 0; r < 5; ++r) {
       const int t = c * 5 + r;
-      const uint32_t full = (uint32_t)(ru.deck_full >> (2 * t)) & 3u;
+      const uint32_t full = cnt2(ru.deck_full, t);
       if (full) exists |= 1u << t;
       if (r < fw || blocked) dead |= 1u << t;
       if (r == fw) playable |= 1u << t;
-      if (r >= fw && ((uint32_t)(disc >> (2 * t)) & 3u) == full) blocked = true;
+      if (r >= fw && cnt2(disc, t) == full) blocked = true;
     }
   }
 
@@ -139,7 +128,7 @@ HSAD_RB_FN int rb_act(const W& w, const RbRules& ru, int p, const uint32_t* tabl
   if (info > 0) {
     for (int o = 1; o < P; ++o) {
       const int q = (p + o) % P;
-      const uint32_t thw = w(RB_PL_FIXED + q);
+      const uint32_t thw = w(PLH(q));
       const int tl = (int)((thw >> 25) & 7u);
       uint32_t cm = 0, rm = 0;
       for (int i = 0; i < 5; ++i) {
@@ -206,7 +195,7 @@ HSAD_RB_FN int rb_act(const W& w, const RbRules& ru, int p, const uint32_t* tabl
         if (info <= 0) break;
         for (int o = 1; o < P && uid < 0; ++o) {
           const int q = (p + o) % P;
-          const uint32_t thw = w(RB_PL_FIXED + q), tcp = w(RB_PL_FIXED + P + q), trp = w(RB_PL_FIXED + 2 * P + q);
+          const uint32_t thw = w(PLH(q)), tcp = w(PLKCP(q)), trp = w(PLKRP(q));
           const int tl = (int)((thw >> 25) & 7u);
           for (int i = 0; i < 5 && uid < 0; ++i) {
             if (i >= tl) break;
@@ -227,7 +216,7 @@ HSAD_RB_FN int rb_act(const W& w, const RbRules& ru, int p, const uint32_t* tabl
         break;
       }
       case HSAD_RULE_HINT_RANDOM:
-        if (info > 0 && hint_bits) uid = rb_pick(rb_hash(seed, key, counter, (uint64_t)(128 + 16 * p + j)), hint_bits);
+        if (info > 0 && hint_bits) uid = rb_pick(policy_hash(seed, key, counter, (uint64_t)(128 + 16 * p + j)), hint_bits);
         break;
       case HSAD_RULE_DISCARD_UNHINTED_OLDEST:
         if (info >= ru.max_info) break;
@@ -238,10 +227,10 @@ HSAD_RB_FN int rb_act(const W& w, const RbRules& ru, int p, const uint32_t* tabl
         if (info < ru.max_info && L >= 1) uid = 0;
         break;
       case HSAD_RULE_DISCARD_RANDOM:
-        if (info < ru.max_info && discard_bits) uid = rb_pick(rb_hash(seed, key, counter, (uint64_t)(128 + 16 * p + j)), discard_bits);
+        if (info < ru.max_info && discard_bits) uid = rb_pick(policy_hash(seed, key, counter, (uint64_t)(128 + 16 * p + j)), discard_bits);
         break;
       case HSAD_RULE_LEGAL_RANDOM:
-        uid = rb_pick(rb_hash(seed, key, counter, (uint64_t)(128 + 16 * p + j)), legal);
+        uid = rb_pick(policy_hash(seed, key, counter, (uint64_t)(128 + 16 * p + j)), legal);
         break;
       default:
         break;
@@ -253,5 +242,36 @@ HSAD_RB_FN int rb_act(const W& w, const RbRules& ru, int p, const uint32_t* tabl
   }
   return rb_ctz64(legal);
 }
+
+#if defined(__HIPCC__)
+// ---- what a kernel that runs rb_act needs around it ----------------------------------------------------------------------------------
+// the bots of a launch, as a kernel argument (324 bytes): the packed rule table above, then the bot of each seat (only
+// hsad_env_playout_rule gives seats; elsewhere 0).  The kernels copy it to LDS once: which row a lane reads depends on its game.
+struct RuleBots {
+  uint32_t table[RB_TABLE_WORDS];
+  int32_t seat[8];
+  int n_bot;
+};
+constexpr int kRuleBotWords = RB_TABLE_WORDS + 8;
+
+__device__ __forceinline__ void stage_bots(const RuleBots& rb, uint32_t* s_rb, int tid, int nthreads) {
+  for (int k = tid; k < kRuleBotWords; k += nthreads) s_rb[k] = k < RB_TABLE_WORDS ? rb.table[k] : (uint32_t)rb.seat[k - RB_TABLE_WORDS];
+  __syncthreads();
+}
+
+// the accessor `w` of rb_act on planes [npl][Gpad] in global memory, and on a wave's staged planes [npl][64] in LDS
+struct GlobalPlanes {
+  const uint32_t* planes;
+  size_t Gpad;
+  int g;
+  __device__ __forceinline__ uint32_t operator()(int pl) const { return planes[(size_t)pl * Gpad + g]; }
+};
+constexpr int kRbPlaneStride = 64;   // one lane of a wave per game (hsad_env_rulebot.inc asserts that it is hsad_env.hip's kWave)
+struct LdsPlanes {
+  const uint32_t* s_st;
+  int lane;
+  __device__ __forceinline__ uint32_t operator()(int pl) const { return s_st[pl * kRbPlaneStride + lane]; }
+};
+#endif  // __HIPCC__
 
 #endif  // HSAD_RULEBOT_H

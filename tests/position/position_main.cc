@@ -21,7 +21,7 @@ int main() {
   r.deck_full = deck_bits(r.nC, r.nR);
   const int words = 80 + 6 * r.P * r.H + 10 * r.P;
   std::vector<int32_t> rec(words);            // exactly the record: a read past it is the sanitizer's to find
-  std::vector<uint32_t> w(POS_PL_FIXED + 6 * r.P);
+  std::vector<uint32_t> w(PL_FIXED + 6 * r.P);
   for (int k = 0; k < n; ++k) {
     for (int i = 0; i < words; ++i)
       if (scanf("%d", &rec[i]) != 1) return 2;

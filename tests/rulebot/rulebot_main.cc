@@ -43,7 +43,7 @@ int main() {
   const RbRules ru = {r.P, r.H, r.nC, r.nR, r.max_info, 2 * r.H + (r.P - 1) * (r.nC + r.nR) + 1, r.shuffle_color, r.deck_full};
   const int words = 80 + 6 * r.P * r.H + 10 * r.P;
   std::vector<int32_t> rec(words);
-  std::vector<uint32_t> w(POS_PL_FIXED + 6 * r.P);
+  std::vector<uint32_t> w(PL_FIXED + 6 * r.P);
   for (int k = 0; k < n; ++k) {
     for (int i = 0; i < words; ++i)
       if (scanf("%d", &rec[i]) != 1) return 2;

@@ -68,6 +68,11 @@ class ActorPartners(C.Structure):
                 ("seat_bot", C.c_void_p), ("bot_seed", C.c_uint64)]
 
 
+class ActorNetPartners(C.Structure):
+    """hsad_actor_net_partners (include/hsad.h): nets = a host array of n_net handles, seat_net = host int32 [G * P]"""
+    _fields_ = [("nets", C.c_void_p), ("n_net", C.c_int32), ("seat_net", C.c_void_p)]
+
+
 class LstmFusedBwdRec(C.Structure):
     """hsad_lstm_fused_bwd_rec (include/hsad.h)"""
     _fields_ = [("WhhT_blocked", C.c_void_p), ("WihT_above_blocked", C.c_void_p), ("gates", C.c_void_p), ("cseq", C.c_void_p),
@@ -260,6 +265,9 @@ SIGNATURES = {
     "hsad_actor_create": (C.c_int, [_P, _P, _P, _P, C.POINTER(ActorConfig), C.POINTER(ActorIO), C.POINTER(_P)]),
     "hsad_actor_create_partnered": (C.c_int, [_P, _P, _P, _P, C.POINTER(ActorConfig), C.POINTER(ActorIO), C.POINTER(ActorPartners),
                                               C.POINTER(_P)]),
+    "hsad_actor_create_partnered_nets": (C.c_int, [_P, _P, _P, _P, C.POINTER(ActorConfig), C.POINTER(ActorIO), C.POINTER(ActorPartners),
+                                                   C.POINTER(ActorNetPartners), C.POINTER(_P)]),
+    "hsad_actor_partner_state": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32)]),
     "hsad_actor_destroy": (None, [_P]),
     "hsad_actor_step": (C.c_int, [_P, _P]),
     "hsad_actor_set_run_ahead": (C.c_int, [_P, C.c_int]),

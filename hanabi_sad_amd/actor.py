@@ -35,41 +35,112 @@ class PartnerSeatsError(ValueError):
         self.verdict = verdict
 
 
+class NetPartner:
+    """A frozen network as a partner of a partnered actor (include/hsad.h, hsad_actor_net_partners): it acts greedily on the rows it
+    owns, carries its own LSTM state and never reaches the replay.  `source`: a weight dict (R2D2Net.state_dict() names), the path
+    of a weight file, or a composite.CNet, which is borrowed as it is -- the actor reads its weights on every step, so weights
+    written and refreshed between two steps act from the next step on (it must not be the learner's online or target net).
+    skip_connect is a constructor flag of the reference's net, not a weight, and therefore given here."""
+    MAX_NETS = 8
+
+    def __init__(self, source, name=None, skip_connect=False):
+        import os
+        self.source, self.skip_connect = source, bool(skip_connect)
+        self.path = os.fspath(source) if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__") else None
+        self.name = name if name is not None else (os.path.basename(self.path) if self.path is not None else "net")
+        self._weights = source if isinstance(source, dict) else None
+
+    @property
+    def is_cnet(self):
+        return self.path is None and not isinstance(self.source, dict)
+
+    def weights(self):
+        """the weight dict (a file is read once, on the host)"""
+        if self._weights is None and self.path is not None:
+            from .checkpoint import load_weights
+            self._weights = load_weights(self.path)
+        return self._weights
+
+    def dims(self):
+        """(in_dim, num_action), without a device"""
+        if self.is_cnet:
+            return int(self.source.F), int(self.source.A)
+        w = self.weights()
+        return int(w["net.0.weight"].shape[1]), int(w["fc_a.weight"].shape[0])
+
+    def make_net(self, device):
+        """the inference net on `device`: the borrowed CNet, or a new one from the weights"""
+        from .composite import CNet
+        if self.is_cnet:
+            return self.source
+        return CNet(self.weights(), device, skip_connect=self.skip_connect)
+
+    def seating_member(self, device):
+        """what eval.play_seatings seats for this partner"""
+        if self.path is not None and self.skip_connect:
+            from .checkpoint import agent_from_file
+            return agent_from_file(self.path, str(device), skip_connect=True)
+        if self.path is not None:
+            return self.path
+        if self.is_cnet or self.skip_connect:
+            from .composite import CompositeAgent
+            net = self.make_net(device)
+            return CompositeAgent(net, net, 1, 0.99)
+        return self.source
+
+
 class PartnerSeats:
-    """Who sits where when the learner trains next to fixed partners (include/hsad.h, hsad_actor_partners): `rows` int32 [M], the
-    learner's rows g * P + p, strictly ascending; `seat_bot` int32 [G * P], -1 on exactly those rows and an index into `bots`
-    (rulebot.RuleBot, at most 8) on every other row.  `verdict` / `check` restate the library's check (csrc/hsad_partner.h), refusal
+    """Who sits where when the learner trains next to fixed partners (include/hsad.h, hsad_actor_partners and hsad_actor_net_partners):
+    `rows` int32 [M], the learner's rows g * P + p, strictly ascending; `seat_bot` int32 [G * P], -1 on exactly those rows and an index
+    into `bots` (rulebot.RuleBot, at most 8) on every other row.  With frozen networks among the partners (NetPartner, at most 8) a
+    partner row is either a bot's (seat_bot[r] = its index in `bots`, seat_net[r] = -1) or a net's (seat_net[r] = its index in `nets`,
+    seat_bot[r] = -1); `seat_net` is None for a layout without nets.  The partner list may mix both kinds: `bots` and `nets` hold its
+    members of each kind in the order given.  `verdict` / `check` restate the library's check (csrc/hsad_partner.h), refusal
     for refusal and in its order, so that a layout can be judged without a device."""
     OK, VDN, PLAYERS, NUM_ROWS, ROW_RANGE, ROW_ORDER, N_BOT, N_RULES, RULE_CODE, RULE_K, LEARNER_BOT, PARTNER_BOT = range(12)
+    N_NET, NET_IN_DIM, NET_NUM_ACTION, LEARNER_NET, NET_RANGE, BOT_NET, NO_OWNER, NET_NO_ROW = range(12, 20)
 
-    def __init__(self, bots, rows, seat_bot, bot_seed=0):
+    def __init__(self, bots, rows, seat_bot, bot_seed=0, seat_net=None):
         import numpy as np
-        from . import rulebot
-        self.bots = [bots] if isinstance(bots, rulebot.RuleBot) else list(bots)
+        self.partners = self._as_list(bots)
+        self.bots = [x for x in self.partners if not isinstance(x, NetPartner)]
+        self.nets = [x for x in self.partners if isinstance(x, NetPartner)]
         self.rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1).astype(np.int32))
         self.seat_bot = np.ascontiguousarray(np.asarray(seat_bot, dtype=np.int64).reshape(-1).astype(np.int32))
+        if seat_net is None and self.nets:
+            seat_net = np.full(self.seat_bot.shape, -1)
+        self.seat_net = None if seat_net is None else np.ascontiguousarray(np.asarray(seat_net, dtype=np.int64).reshape(-1).astype(np.int32))
         self.bot_seed = int(bot_seed)
+
+    @staticmethod
+    def _as_list(partners):
+        from . import rulebot
+        return [partners] if isinstance(partners, (rulebot.RuleBot, NetPartner)) else list(partners)
 
     @property
     def M(self):
         return int(self.rows.shape[0])
 
+    @property
+    def net_rows(self):
+        """per net k: its rows, ascending (the order of its compact rows)"""
+        import numpy as np
+        return [np.nonzero(self.seat_net == k)[0].astype(np.int32) for k in range(len(self.nets))]
+
     @classmethod
     def alternate(cls, G, P, bots, bot_seed=0):
-        """the learner sits on seat g % P of game g and every other seat of that game gets bot (g // P) % len(bots): seats and
+        """the learner sits on seat g % P of game g and every other seat of that game gets partner (g // P) % len(bots): seats and
         partners are balanced over the batch"""
         import numpy as np
-        from . import rulebot
-        bots = [bots] if isinstance(bots, rulebot.RuleBot) else list(bots)
+        bots = cls._as_list(bots)
         g = np.arange(G)
         return cls._one_learner_seat(G, P, g % P, (g // P) % max(len(bots), 1), bots, bot_seed)
 
     @classmethod
     def fixed_seat(cls, G, P, seat, bots, bot_seed=0):
-        """the learner sits on `seat` in every game; the other seats of game g get bot g % len(bots)"""
+        """the learner sits on `seat` in every game; the other seats of game g get partner g % len(bots)"""
         import numpy as np
-        from . import rulebot
-        bots = [bots] if isinstance(bots, rulebot.RuleBot) else list(bots)
+        bots = cls._as_list(bots)
         if not 0 <= int(seat) < P:
             raise PartnerSeatsError("fixed_seat: seat = %d, must be 0..%d" % (seat, P - 1), (cls.ROW_RANGE, 0, int(seat)))
         g = np.arange(G)
@@ -77,16 +148,28 @@ class PartnerSeats:
 
     @classmethod
     def _one_learner_seat(cls, G, P, seat_of_game, bot_of_game, bots, bot_seed):
+        """partner j of the (mixed) list gets the games with bot_of_game == j, whatever its kind"""
         import numpy as np
-        seat_bot = np.repeat(bot_of_game.astype(np.int32), P).reshape(G, P)
+        is_net = np.array([isinstance(x, NetPartner) for x in bots] + [False], dtype=bool)      # (+ one entry: an empty list indexes too)
+        kind_index = np.array([sum(1 for y in bots[:j] if isinstance(y, NetPartner) == isinstance(x, NetPartner))
+                               for j, x in enumerate(bots)] + [0], dtype=np.int32)
+        own = np.repeat(bot_of_game.astype(np.int64), P).reshape(G, P)
+        seat_bot = np.where(is_net[own], -1, kind_index[own]).astype(np.int32)
         seat_bot[np.arange(G), seat_of_game] = -1
-        return cls(bots, np.arange(G) * P + seat_of_game, seat_bot, bot_seed)
+        seat_net = None
+        if is_net.any():
+            seat_net = np.where(is_net[own], kind_index[own], -1).astype(np.int32)
+            seat_net[np.arange(G), seat_of_game] = -1
+        return cls(bots, np.arange(G) * P + seat_of_game, seat_bot, bot_seed, seat_net)
 
-    def verdict(self, G, P, hand_size=5, vdn=False):
-        """(code, index, value) of partner_layout_verdict (csrc/hsad_partner.h): (0, 0, 0) for a layout the library runs"""
+    def verdict(self, G, P, hand_size=5, vdn=False, F=None, A=None):
+        """(code, index, value) of partner_layout_verdict_nets (csrc/hsad_partner.h; without nets: of partner_layout_verdict):
+        (0, 0, 0) for a layout the library runs.  F, A: the env's feature size and action count, which the nets are held to (None:
+        not known yet, that refusal is left to the call that knows them)"""
         from . import rulebot
         N, M, n_bot = G * P, self.M, len(self.bots)
         rows, sb = self.rows.tolist(), self.seat_bot.tolist()
+        with_nets = bool(self.nets) or self.seat_net is not None
         if vdn:
             return (self.VDN, 0, int(vdn))
         if P > 5 or hand_size > 5:
@@ -98,7 +181,7 @@ class PartnerSeats:
                 return (self.ROW_RANGE, i, r)
             if i > 0 and r <= rows[i - 1]:
                 return (self.ROW_ORDER, i, r)
-        if n_bot > rulebot.MAX_BOTS or (n_bot == 0 and M != N):
+        if n_bot > rulebot.MAX_BOTS or (n_bot == 0 and M != N and not with_nets):
             return (self.N_BOT, 0, n_bot)
         for b, bot in enumerate(self.bots):
             if not 1 <= len(bot.rules) <= rulebot.MAX_RULES:
@@ -111,6 +194,8 @@ class PartnerSeats:
         if len(sb) != N:
             raise PartnerSeatsError("seat_bot has %d entries, the env has %d rows" % (len(sb), N), (self.PARTNER_BOT, len(sb), 0))
         learner = set(rows)
+        if with_nets:
+            return self._verdict_nets(N, learner, sb, n_bot, F, A)
         for r in range(N):
             if r in learner:
                 if sb[r] != -1:
@@ -119,11 +204,62 @@ class PartnerSeats:
                 return (self.PARTNER_BOT, r, sb[r])
         return (self.OK, 0, 0)
 
-    def explain(self, verdict, G, P):
-        """the text of a refusal (partner_verdict_text); it names the offending entry"""
+    def _verdict_nets(self, N, learner, sb, n_bot, F, A):
+        """the part of partner_layout_verdict_nets behind the bots' rule lists: the nets, then one scan over the rows"""
+        n_net = len(self.nets)
+        if not 1 <= n_net <= NetPartner.MAX_NETS:
+            return (self.N_NET, 0, n_net)
+        for k, net in enumerate(self.nets):
+            in_dim, num_action = net.dims()
+            if F is not None and in_dim != F:
+                return (self.NET_IN_DIM, k, in_dim)
+            if A is not None and num_action != A:
+                return (self.NET_NUM_ACTION, k, num_action)
+        sn = self.seat_net.tolist()
+        if len(sn) != N:
+            raise PartnerSeatsError("seat_net has %d entries, the env has %d rows" % (len(sn), N), (self.NET_RANGE, len(sn), 0))
+        owns = [False] * n_net
+        for r in range(N):
+            b, k = sb[r], sn[r]
+            if r in learner:
+                if b != -1:
+                    return (self.LEARNER_BOT, r, b)
+                if k != -1:
+                    return (self.LEARNER_NET, r, k)
+                continue
+            if b < -1 or b >= n_bot:
+                return (self.PARTNER_BOT, r, b)
+            if k < -1 or k >= n_net:
+                return (self.NET_RANGE, r, k)
+            if b >= 0 and k >= 0:
+                return (self.BOT_NET, r, k)
+            if b < 0 and k < 0:
+                return (self.NO_OWNER, r, 0)
+            if k >= 0:
+                owns[k] = True
+        for k in range(n_net):
+            if not owns[k]:
+                return (self.NET_NO_ROW, k, 0)
+        return (self.OK, 0, 0)
+
+    def explain(self, verdict, G, P, F=None, A=None):
+        """the text of a refusal (partner_verdict_text / partner_verdict_text_nets); it names the offending entry"""
         from . import rulebot
         code, i, v = verdict
-        n_bot = len(self.bots)
+        n_bot, n_net = len(self.bots), len(self.nets)
+        if n_net or code >= self.N_NET:      # (the codes 0 .. 11 with n_net == 0: partner_verdict_text)
+            nets_text = {self.N_BOT: "n_bot = %d, must be 0..%d" % (v, rulebot.MAX_BOTS),
+                         self.PARTNER_BOT: "seat_bot[%d] = %d on a partner row, must be -1..%d" % (i, v, n_bot - 1),
+                         self.N_NET: "n_net = %d, must be 1..%d" % (v, NetPartner.MAX_NETS),
+                         self.NET_IN_DIM: "net %d has in_dim %d, the env's observation has %d features" % (i, v, -1 if F is None else F),
+                         self.NET_NUM_ACTION: "net %d has num_action %d, the env has %d actions" % (i, v, -1 if A is None else A),
+                         self.LEARNER_NET: "seat_net[%d] = %d on a learner row, must be -1" % (i, v),
+                         self.NET_RANGE: "seat_net[%d] = %d, must be -1..%d" % (i, v, n_net - 1),
+                         self.BOT_NET: "seat_net[%d] = %d on a row seat_bot gives to a bot: a row has one owner" % (i, v),
+                         self.NO_OWNER: "row %d is neither the learner's nor a bot's nor a net's (seat_bot[%d] = seat_net[%d] = -1)" % (i, i, i),
+                         self.NET_NO_ROW: "net %d owns no row: every net of the table must be seated" % i}
+            if code in nets_text:
+                return nets_text[code]
         return {self.OK: "ok",
                 self.VDN: "cfg->vdn = %d: a partnered actor is an IQL actor (one transition per learner row)" % v,
                 self.PLAYERS: "more than 5 players or 5 cards a hand (players = %d)" % v,
@@ -137,10 +273,10 @@ class PartnerSeats:
                 self.LEARNER_BOT: "seat_bot[%d] = %d on a learner row, must be -1" % (i, v),
                 self.PARTNER_BOT: "seat_bot[%d] = %d on a partner row, must be 0..%d" % (i, v, n_bot - 1)}[code]
 
-    def check(self, G, P, hand_size=5, vdn=False):
-        v = self.verdict(G, P, hand_size, vdn)
+    def check(self, G, P, hand_size=5, vdn=False, F=None, A=None):
+        v = self.verdict(G, P, hand_size, vdn, F, A)
         if v[0] != self.OK:
-            raise PartnerSeatsError("PartnerSeats: " + self.explain(v, G, P), v)
+            raise PartnerSeatsError("PartnerSeats: " + self.explain(v, G, P, F, A), v)
         return self
 
 
@@ -150,10 +286,11 @@ class DeviceActor:
         self.env, self.agent, self.replay = env, agent, replay
         self.G, self.P = env.G, env.P
         self.partners = partners
+        self.partner_nets = []
         if partners is not None:
             if native is not None and not native:
                 self._refuse_python_partners()
-            partners.check(self.G, self.P, env.H, vdn)
+            partners.check(self.G, self.P, env.H, vdn, env.F, env.A)
         # agent rows (hidden state [L, N, H]) in both layouts; with partners (PartnerSeats): the learner's rows only
         self.N = self.G * self.P if partners is None else partners.M
         self.vdn = bool(vdn)
@@ -231,8 +368,16 @@ class DeviceActor:
             rules, n_rules, n_bot = rulebot.pack(pt.bots)
             part = _lib.ActorPartners(pt.rows.ctypes.data, pt.M, C.addressof(rules), C.addressof(n_rules), n_bot, pt.seat_bot.ctypes.data,
                                       pt.bot_seed)
-            _lib.check(agent.lib.hsad_actor_create_partnered(env.h, agent.online.h, agent.target.h, self.replay.h, C.byref(cfg), C.byref(io),
-                                                             C.byref(part), C.byref(h)))
+            if pt.nets:
+                # one inference net per NetPartner on the env's device, built here or borrowed, alive as long as the actor
+                self.partner_nets = [n.make_net(env.device) for n in pt.nets]
+                handles = (C.c_void_p * len(self.partner_nets))(*[n.h for n in self.partner_nets])
+                net_part = _lib.ActorNetPartners(C.addressof(handles), len(self.partner_nets), pt.seat_net.ctypes.data)
+                _lib.check(agent.lib.hsad_actor_create_partnered_nets(env.h, agent.online.h, agent.target.h, self.replay.h, C.byref(cfg),
+                                                                      C.byref(io), C.byref(part), C.byref(net_part), C.byref(h)))
+            else:
+                _lib.check(agent.lib.hsad_actor_create_partnered(env.h, agent.online.h, agent.target.h, self.replay.h, C.byref(cfg), C.byref(io),
+                                                                 C.byref(part), C.byref(h)))
         else:
             _lib.check(agent.lib.hsad_actor_create(env.h, agent.online.h, agent.target.h, self.replay.h, C.byref(cfg), C.byref(io), C.byref(h)))
         self.c_actor, self._lib = h, agent.lib
@@ -271,6 +416,18 @@ class DeviceActor:
         _lib.check(self._lib.hsad_actor_state(self.c_actor, C.byref(h), C.byref(c)))
         n = self.agent.online.L * self.N * self.agent.online.H
         return _view(h.value, n, self.env.device, self), _view(c.value, n, self.env.device, self)
+
+    def partner_state(self, k):
+        """(h, c) fp32 [L_k, n_k, H_k] of network partner k: its carried state entering the next step (views of the library's buffers)"""
+        import ctypes as C
+        from . import _lib
+        from .composite import _view
+        h, c, n = C.c_void_p(), C.c_void_p(), C.c_int32()
+        _lib.check(self._lib.hsad_actor_partner_state(self.c_actor, int(k), C.byref(h), C.byref(c), C.byref(n)))
+        net = self.partner_nets[k]
+        shape = (net.L, n.value, net.H)
+        size = net.L * n.value * net.H
+        return _view(h.value, size, self.env.device, self).view(shape), _view(c.value, size, self.env.device, self).view(shape)
 
     @property
     def last_priority(self):

@@ -10,6 +10,9 @@
 //   partner_merge_kernel      one thread per game, between act and the env step: the full a / greedy_a [G, P] -- the learner's rows
 //                             from the compact act output, the partners' from their bots on the state planes (policy_rule_kernel's
 //                             sibling: the same rb_act, hash streams, default key and counter rule)
+// With frozen network partners (hsad_actor_create_partnered_nets) a partner row may belong to a net instead of a bot: the two gather
+// launches become partner_gather_nets_kernel<0> / <1> over the learner's and every net's rows, and one greedy hsad_r2d2_act per net
+// follows the learner's on the same stream.  An actor without nets launches what it launched before.
 #include "hsad_partner.h"
 
 // csrc/hsad_env_rulebot.inc
@@ -130,7 +133,74 @@ __global__ __launch_bounds__(256) void partner_merge_kernel(const uint32_t* __re
   }
 }
 
+// The gather of an actor with frozen network partners (hsad_actor_create_partnered_nets).  The compact rows of the learner and of
+// every net share one index space: e < g.M is the learner's row e, [off_k, off_k + n_k) are the rows of net k; g.rows, c_obs16,
+// c_legal and c_terminal hold n_all = M + sum n_k entries, every other compact buffer M.  A sibling of partner_gather_kernel, which an
+// actor without nets keeps launching as it is.
+//   PASS 0: one workgroup per compact row.  A learner row gets its 143 pieces; a net row only what hsad_r2d2_act reads, the bf16
+//           observation row and the legal row (no bit rows, eps or own hand: it never reaches the writer).
+//   PASS 1: one thread per compact row: the terminal flag of the row's game, and the reward for the learner's rows.
+struct PartnerGatherNets {
+  PartnerGather g;
+  int n_all;
+};
+
+template <int PASS>
+__global__ __launch_bounds__(kPartnerGatherThreads) void partner_gather_nets_kernel(PartnerGatherNets q) {
+  const PartnerGather& g = q.g;
+  if (PASS == 1) {
+    const int e = blockIdx.x * kPartnerGatherThreads + threadIdx.x;
+    if (e >= q.n_all) return;
+    const int game = g.rows[e] / g.P;
+    g.c_terminal[e] = g.terminal[game];
+    if (e < g.M) g.c_reward[e] = g.reward[game];
+    return;
+  }
+  const int e = blockIdx.x;   // < n_all: the grid is n_all workgroups
+  const size_t r = (size_t)g.rows[e];
+  const bool learner = e < g.M;   // (uniform over the workgroup)
+  const int n_pb = learner ? g.n_pb : 0;
+  const int total = g.n_obs + n_pb + g.n_lg + (learner ? 3 : 0);
+  for (int k = threadIdx.x; k < total; k += kPartnerGatherThreads) {
+    int j = k;
+    if (j < g.n_obs) {
+      g.c_obs16[(size_t)e * g.n_obs + j] = g.obs16[r * g.n_obs + j];
+      continue;
+    }
+    j -= g.n_obs;
+    if (j < n_pb) {
+      if (g.pb_vec)
+        reinterpret_cast<uint4*>(g.c_priv_bits)[(size_t)e * g.n_pb + j] = reinterpret_cast<const uint4*>(g.priv_bits)[r * g.n_pb + j];
+      else
+        g.c_priv_bits[(size_t)e * g.pw64 + j] = g.priv_bits[r * g.pw64 + j];
+      continue;
+    }
+    j -= n_pb;
+    if (j < g.n_lg) {
+      if (g.lg_vec)
+        reinterpret_cast<float4*>(g.c_legal)[(size_t)e * g.n_lg + j] = reinterpret_cast<const float4*>(g.legal)[r * g.n_lg + j];
+      else
+        g.c_legal[(size_t)e * g.A + j] = g.legal[r * g.A + j];
+      continue;
+    }
+    j -= g.n_lg;   // (learner rows only)
+    if (j == 0) g.c_eps[e] = g.eps[r];
+    else if (j == 1) g.c_legal_bits[e] = g.legal_bits[r];
+    else g.c_own_bits[e] = g.own_bits[r];
+  }
+}
+
 }  // namespace
+
+// a frozen network partner: its rows' slice of the compact index space and its carried state (two slots: act never writes the state
+// it reads; nothing of a partner is ever redone, so no ring)
+struct PartnerNet {
+  hsad_r2d2_net* net = nullptr;
+  int n = 0, off = 0, L = 0, H = 0;
+  bool fused = false;              // n >= 1024: the bf16 copy of the state is carried (the learner's fused_state rule per net)
+  float *h[2] = {nullptr, nullptr}, *c[2] = {nullptr, nullptr};
+  void* h16[2] = {nullptr, nullptr};
+};
 
 // what a partnered actor holds on top of hsad_actor
 struct PartnerSeats {
@@ -142,8 +212,13 @@ struct PartnerSeats {
   uint32_t* act_count = nullptr;
   int Gpad = 0;
   int32_t* seat = nullptr;         // [G * P], see partner_merge_kernel
-  int64_t *a_c = nullptr, *g_c = nullptr;   // compact act output [M]
+  int64_t *a_c = nullptr, *g_c = nullptr;   // compact act output [M] (with network partners [n_all]: every act call's slice)
   uint64_t bot_seed = 0;
+  // hsad_actor_create_partnered_nets
+  int n_net = 0, n_all = 0;        // n_all = M + sum n_k compact rows
+  int net_cur = 0;                 // the state slot that enters the nets' next act
+  uint64_t net_counter = 0;
+  PartnerNet nets[HSAD_PARTNER_MAX_NETS];
 };
 
 namespace {
@@ -163,13 +238,25 @@ int partner_step(hsad_actor* ac, void* stream) {
   const int cur = ac->cur, nxt = (cur + 1) % ac->nslot;
   if (ac->reset_pending) ac->reset_pending = false;
   else CK(hsad_env_reset(ac->env, stream));
-  hipLaunchKernelGGL(partner_gather_kernel<0>, dim3(M), dim3(kPartnerGatherThreads), 0, s, pt->g);
+  const PartnerGatherNets gn = {pt->g, pt->n_all};
+  if (pt->n_net) hipLaunchKernelGGL(partner_gather_nets_kernel<0>, dim3(pt->n_all), dim3(kPartnerGatherThreads), 0, s, gn);
+  else hipLaunchKernelGGL(partner_gather_kernel<0>, dim3(M), dim3(kPartnerGatherThreads), 0, s, pt->g);
   HIP_TRY(hipGetLastError());
   const uint64_t v_on = hsad_r2d2_net_version(ac->online);
   CK(hsad_r2d2_act(ac->online, ac->target, M, nullptr, pt->g.c_obs16, pt->g.c_legal, pt->g.c_eps, ac->h[cur], ac->c[cur],
                    ac->fused_state ? ac->h16[cur] : nullptr, ac->seed, ac->counter++, pt->a_c, pt->g_c, ac->h[nxt], ac->c[nxt],
                    ac->fused_state ? ac->h16[nxt] : nullptr, ac->qring[cur], ac->tq, stream));
   ac->qversion[cur] = v_on;
+  // the frozen networks, one after the other on the same stream (a net owns its workspace, and the recurrence launches exchange
+  // through inter-workgroup counters: two act calls never run side by side): greedy, no target pass, no cached Q-values
+  const int ncur = pt->net_cur, nnxt = ncur ^ 1;
+  for (int k = 0; k < pt->n_net; ++k) {
+    const PartnerNet& pn = pt->nets[k];
+    CK(hsad_r2d2_act(pn.net, nullptr, pn.n, nullptr, pt->g.c_obs16 + (size_t)pn.off * pt->g.n_obs, pt->g.c_legal + (size_t)pn.off * pt->g.A, nullptr,
+                     pn.h[ncur], pn.c[ncur], pn.fused ? pn.h16[ncur] : nullptr, ac->seed, pt->net_counter, pt->a_c + pn.off, pt->g_c + pn.off,
+                     pn.h[nnxt], pn.c[nnxt], pn.fused ? pn.h16[nnxt] : nullptr, nullptr, nullptr, stream));
+  }
+  pt->net_counter += 1;
   hipLaunchKernelGGL(partner_merge_kernel, dim3((ac->G + 255) / 256), dim3(256), 0, s, pt->planes, pt->act_count, ac->G, pt->Gpad, pt->ru, pt->bots,
                      pt->seat, pt->bot_seed, pt->a_c, pt->g_c, ac->a, ac->greedy);
   HIP_TRY(hipGetLastError());
@@ -181,8 +268,16 @@ int partner_step(hsad_actor* ac, void* stream) {
   CK(hsad_env_reset(ac->env, (void*)ac->side_reset));
   HIP_TRY(hipEventRecord(ac->ev_reset, ac->side_reset));
   ac->reset_pending = true;
-  hipLaunchKernelGGL(partner_gather_kernel<1>, dim3((M + kPartnerGatherThreads - 1) / kPartnerGatherThreads), dim3(kPartnerGatherThreads), 0, s, pt->g);
+  if (pt->n_net)
+    hipLaunchKernelGGL(partner_gather_nets_kernel<1>, dim3((pt->n_all + kPartnerGatherThreads - 1) / kPartnerGatherThreads), dim3(kPartnerGatherThreads), 0, s, gn);
+  else
+    hipLaunchKernelGGL(partner_gather_kernel<1>, dim3((M + kPartnerGatherThreads - 1) / kPartnerGatherThreads), dim3(kPartnerGatherThreads), 0, s, pt->g);
   HIP_TRY(hipGetLastError());
+  for (int k = 0; k < pt->n_net; ++k) {   // a net's state rows of the games that just ended
+    const PartnerNet& pn = pt->nets[k];
+    CK(hsad_zero_state_rows(pn.h[nnxt], pn.c[nnxt], pn.fused ? pn.h16[nnxt] : nullptr, pt->g.c_terminal + pn.off, pn.L, pn.n, pn.H, 1, stream));
+  }
+  pt->net_cur = nnxt;
   ac->num_act += M;
   ac->step_no += 1;
   return actor_tail(ac, stream, nxt, pt->g.c_reward, pt->g.c_terminal, 1);
@@ -190,19 +285,55 @@ int partner_step(hsad_actor* ac, void* stream) {
 
 }  // namespace
 
+// csrc/hsad_agent.hip
+extern "C" int hsad_internal_net_dims(const hsad_r2d2_net* n, int* in_dim, int* hid_dim, int* num_action, int* num_lstm_layer, int* device);
+
 extern "C" int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay,
                                            const hsad_actor_config* cfg, const hsad_actor_io* io, const hsad_actor_partners* partners,
                                            hsad_actor** out) {
+  return hsad_actor_create_partnered_nets(env, online, target, replay, cfg, io, partners, nullptr, out);
+}
+
+extern "C" int hsad_actor_create_partnered_nets(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay,
+                                                const hsad_actor_config* cfg, const hsad_actor_io* io, const hsad_actor_partners* partners,
+                                                const hsad_actor_net_partners* np, hsad_actor** out) {
   if (!env || !cfg || !partners || !out) return xfail(HSAD_ERR_INVALID, "actor_create_partnered: null argument");
   if (!partners->rows || !partners->seat_bot || (partners->n_bot > 0 && (!partners->rules || !partners->n_rules)))
     return xfail(HSAD_ERR_INVALID, "actor_create_partnered: null array in hsad_actor_partners");
+  if (np && (!np->nets || !np->seat_net)) return xfail(HSAD_ERR_INVALID, "actor_create_partnered: null array in hsad_actor_net_partners");
   const int G = hsad_env_num_games(env), P = hsad_env_num_players(env), M = partners->M;
-  const PartnerVerdict v = partner_layout_verdict(G, P, cfg->hand_size, cfg->vdn, partners->rows, M, partners->rules, partners->n_rules,
-                                                  partners->n_bot, partners->seat_bot);
+  const int F_env = hsad_env_feature_size(env), A_env = hsad_env_num_action(env);
+  const int n_net = np ? np->n_net : 0;
+  int32_t net_F[HSAD_PARTNER_MAX_NETS] = {}, net_A[HSAD_PARTNER_MAX_NETS] = {};
+  int net_H[HSAD_PARTNER_MAX_NETS] = {}, net_L[HSAD_PARTNER_MAX_NETS] = {}, net_dev[HSAD_PARTNER_MAX_NETS] = {};
+  if (n_net >= 1 && n_net <= HSAD_PARTNER_MAX_NETS) {   // (outside: the verdict refuses n_net before it reads a net's dimensions)
+    for (int k = 0; k < n_net; ++k) {
+      if (!np->nets[k]) return xfail(HSAD_ERR_INVALID, "actor_create_partnered: nets[%d] is NULL", k);
+      int f = 0, a = 0;
+      CK(hsad_internal_net_dims(np->nets[k], &f, &net_H[k], &a, &net_L[k], &net_dev[k]));
+      net_F[k] = f;
+      net_A[k] = a;
+    }
+  }
+  const PartnerVerdict v = partner_layout_verdict_nets(G, P, cfg->hand_size, cfg->vdn, partners->rows, M, partners->rules, partners->n_rules,
+                                                       partners->n_bot, partners->seat_bot, F_env, A_env, n_net, net_F, net_A,
+                                                       np ? np->seat_net : nullptr);
   if (v.code != PT_OK) {
     char why[256];
-    partner_verdict_text(v, G, P, partners->n_bot, why, sizeof(why));
+    partner_verdict_text_nets(v, G, P, partners->n_bot, n_net, F_env, A_env, why, sizeof(why));
     return xfail(HSAD_ERR_INVALID, "actor_create_partnered: %s", why);
+  }
+  int dev_now = 0;
+  (void)hipGetDevice(&dev_now);
+  for (int k = 0; k < n_net; ++k) {   // handle identity: two act calls never share a net's workspace
+    if (np->nets[k] == online || np->nets[k] == target)
+      return xfail(HSAD_ERR_INVALID, "actor_create_partnered: nets[%d] is the %s net of this actor: a partner is a handle of its own (make a copy)", k,
+                   np->nets[k] == online ? "online" : "target");
+    for (int j = 0; j < k; ++j)
+      if (np->nets[j] == np->nets[k])
+        return xfail(HSAD_ERR_INVALID, "actor_create_partnered: nets[%d] is the same handle as nets[%d]: a partner is a handle of its own (make a copy)", k, j);
+    if (net_dev[k] != dev_now)
+      return xfail(HSAD_ERR_INVALID, "actor_create_partnered: nets[%d] lives on device %d, the actor on device %d", k, net_dev[k], dev_now);
   }
   auto* pt = new PartnerSeats();
   int G_env = 0;
@@ -229,8 +360,27 @@ extern "C" int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online,
   pt->bots.n_bot = partners->n_bot;
   pt->bot_seed = partners->bot_seed;
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t total = up(M * 4) + up(N * 4) + up((size_t)M * Fp * 2) + up((size_t)M * A * 4) + up(M * 4) + up((size_t)M * pw64 * 8) +
-                       2 * up(M * 8) + up(M * 4) + up(M) + 2 * up(N * 8);
+  // the compact index space: the learner's M rows, then the rows of net 0, net 1, ... each in ascending order
+  std::vector<int32_t> rows_all(partners->rows, partners->rows + M);
+  size_t net_bytes = 0;
+  pt->n_net = n_net;
+  for (int k = 0; k < n_net; ++k) {
+    PartnerNet& pn = pt->nets[k];
+    pn.net = np->nets[k];
+    pn.off = (int)rows_all.size();
+    for (size_t r = 0; r < N; ++r)
+      if (np->seat_net[r] == k) rows_all.push_back((int32_t)r);
+    pn.n = (int)rows_all.size() - pn.off;
+    pn.L = net_L[k];
+    pn.H = net_H[k];
+    pn.fused = pn.n >= 1024;
+    const size_t nh = (size_t)pn.L * pn.n * pn.H;
+    net_bytes += 2 * (2 * up(nh * 4) + up(nh * 2));
+  }
+  const size_t n_all = rows_all.size();
+  pt->n_all = (int)n_all;
+  const size_t total = up(n_all * 4) + up(N * 4) + up(n_all * Fp * 2) + up(n_all * A * 4) + up(M * 4) + up((size_t)M * pw64 * 8) +
+                       2 * up(M * 8) + up(M * 4) + up(n_all) + 2 * up(N * 8) + (n_net ? 2 * up(n_all * 8) : 0) + net_bytes;
   if (hipMalloc((void**)&pt->arena, total) != hipSuccess) {
     hsad_actor_destroy(ac);
     return xfail(HSAD_ERR_NOMEM, "actor_create_partnered: hipMalloc of %zu bytes failed", total);
@@ -243,7 +393,7 @@ extern "C" int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online,
     return r;
   };
   PartnerGather& g = pt->g;
-  int32_t* d_rows = (int32_t*)take(M * 4);
+  int32_t* d_rows = (int32_t*)take(n_all * 4);
   pt->seat = (int32_t*)take(N * 4);
   g.rows = d_rows;
   g.M = M;
@@ -256,14 +406,14 @@ extern "C" int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online,
   g.own_bits = (const unsigned long long*)io->own_bits;
   g.reward = io->reward;
   g.terminal = io->terminal;
-  g.c_obs16 = (uint4*)take((size_t)M * Fp * 2);
-  g.c_legal = (float*)take((size_t)M * A * 4);
+  g.c_obs16 = (uint4*)take(n_all * Fp * 2);
+  g.c_legal = (float*)take(n_all * A * 4);
   g.c_eps = (float*)take(M * 4);
   g.c_priv_bits = (unsigned long long*)take((size_t)M * pw64 * 8);
   g.c_legal_bits = (unsigned long long*)take(M * 8);
   g.c_own_bits = (unsigned long long*)take(M * 8);
   g.c_reward = (float*)take(M * 4);
-  g.c_terminal = (uint8_t*)take(M);
+  g.c_terminal = (uint8_t*)take(n_all);
   g.n_obs = Fp / 8;
   g.pw64 = pw64;
   g.pb_vec = (pw64 % 2 == 0) && !((uintptr_t)io->priv_bits & 15u);
@@ -277,17 +427,39 @@ extern "C" int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online,
   pt->g_c = ac->greedy;
   ac->a = (int64_t*)take(N * 8);
   ac->greedy = (int64_t*)take(N * 8);
-  std::vector<int32_t> seat(N);
-  int next = 0;
-  for (size_t r = 0; r < N; ++r) {
-    if (next < M && (size_t)partners->rows[next] == r) seat[r] = -(next++ + 1);
-    else seat[r] = partners->seat_bot[r];
+  if (n_net) {   // every act call's output in one pair of arrays: the learner's slice in front, as the sequence writer reads it
+    pt->a_c = (int64_t*)take(n_all * 8);
+    pt->g_c = (int64_t*)take(n_all * 8);
   }
-  if (hipMemcpy(d_rows, partners->rows, (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess ||
+  for (int k = 0; k < n_net; ++k) {   // (zeroed with the arena: the initial state)
+    PartnerNet& pn = pt->nets[k];
+    const size_t nh = (size_t)pn.L * pn.n * pn.H;
+    for (int slot = 0; slot < 2; ++slot) {
+      pn.h[slot] = (float*)take(nh * 4);
+      pn.c[slot] = (float*)take(nh * 4);
+      pn.h16[slot] = (void*)take(nh * 2);
+    }
+  }
+  // seat[r] = -(e + 1) means "this row's action is entry e of the compact act output", for the learner's rows and the nets' alike
+  std::vector<int32_t> seat(N);
+  for (size_t r = 0; r < N; ++r) seat[r] = partners->seat_bot[r];
+  for (size_t e = 0; e < n_all; ++e) seat[rows_all[e]] = -((int32_t)e + 1);
+  if (hipMemcpy(d_rows, rows_all.data(), n_all * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(pt->seat, seat.data(), N * 4, hipMemcpyHostToDevice) != hipSuccess) {
     hsad_actor_destroy(ac);
     return xfail(HSAD_ERR_HIP, "actor_create_partnered: copying the seat layout to the device failed");
   }
   *out = ac;
+  return 0;
+}
+
+extern "C" int hsad_actor_partner_state(hsad_actor* ac, int k, float** h, float** c, int32_t* n_rows) {
+  if (!ac || !h || !c) return xfail(HSAD_ERR_INVALID, "actor_partner_state: null argument");
+  const PartnerSeats* pt = ac->partner;
+  if (!pt || k < 0 || k >= pt->n_net)
+    return xfail(HSAD_ERR_INVALID, "actor_partner_state: net %d, the actor has %d network partners", k, pt ? pt->n_net : 0);
+  *h = pt->nets[k].h[pt->net_cur];
+  *c = pt->nets[k].c[pt->net_cur];
+  if (n_rows) *n_rows = pt->nets[k].n;
   return 0;
 }

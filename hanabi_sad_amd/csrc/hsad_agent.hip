@@ -278,6 +278,17 @@ int hsad_r2d2_net_arch(const hsad_r2d2_net* n, int32_t* num_fc_layer, int32_t* n
   return 0;
 }
 
+// (hsad_actor_partner.inc: what a frozen network partner is held against, and the shape of its carried state)
+int hsad_internal_net_dims(const hsad_r2d2_net* n, int* in_dim, int* hid_dim, int* num_action, int* num_lstm_layer, int* device) {
+  if (!n) return afail(HSAD_ERR_INVALID, "null net");
+  *in_dim = n->F;
+  *hid_dim = n->H;
+  *num_action = n->A;
+  *num_lstm_layer = n->L;
+  *device = n->device;
+  return 0;
+}
+
 int hsad_r2d2_net_create_ex(int in_dim, int hid_dim, int num_action, int hand_size, int num_fc_layer, int num_lstm_layer, int skip_connect,
                             int with_backward, int device, hsad_r2d2_net** out) {
   if (!out || in_dim < 1 || num_action < 1 || hand_size < 1) return afail(HSAD_ERR_INVALID, "r2d2_net_create: bad dimensions");

@@ -57,10 +57,22 @@ def game_rules(args):
     return {k: int(getattr(args, k, d)) for k, d in (("colors", 5), ("ranks", 5), ("max_information_tokens", 8), ("max_life_tokens", 3))}
 
 
-def partner_bots(args):
-    """the rule bots of --partner (presets of rulebot.py), in the order given"""
+def parse_partner(entry):
+    """one --partner entry: a rule-bot preset of rulebot.py, or the path of a weight file (`PATH:skip`: a skip_connect net) ->
+    rulebot.RuleBot or actor.NetPartner; ValueError, naming both readings, for an entry that is neither"""
+    from .actor import NetPartner
     from .rulebot import PRESETS
-    return [PRESETS[name] for name in getattr(args, "partner", None) or []]
+    if entry in PRESETS:
+        return PRESETS[entry]
+    path, skip = (entry[:-len(":skip")], True) if entry.endswith(":skip") else (entry, False)
+    if os.path.isfile(path):
+        return NetPartner(path, skip_connect=skip)
+    raise ValueError("--partner %s: no rule-bot preset of that name (have: %s) and no weight file at %s" % (entry, ", ".join(sorted(PRESETS)), path))
+
+
+def partner_bots(args):
+    """the partners of --partner, in the order given: rule bots (presets of rulebot.py) and frozen networks (weight files)"""
+    return [parse_partner(entry) for entry in getattr(args, "partner", None) or []]
 
 
 def partner_seats(args, num_game):
@@ -74,12 +86,15 @@ def partner_seats(args, num_game):
 
 
 def print_partner_scores(args, weights, num_game, seed, device):
-    """one line per --partner bot: the score of `weights` seated with that bot through play_seatings, every bot on the same deals
-    (seating s puts the net on seat s and the bot on every other seat; the line is the mean over the P seatings)"""
+    """one line per --partner entry: the score of `weights` seated with that partner through play_seatings, every partner on the same
+    deals (seating s puts the net on seat s and the partner on every other seat; the line is the mean over the P seatings); a file
+    partner's line carries the file's basename"""
+    from .actor import NetPartner
     from .eval import play_seatings
     bots, P = partner_bots(args), args.num_player
     seatings = [[0 if p == seat else k for p in range(P)] for k in range(1, len(bots) + 1) for seat in range(P)]
-    xp = play_seatings([weights] + bots, seatings, num_game, seed, args.eval_bomb, args.sad, hand_size=args.hand_size, device=str(device),
+    pool = [b.seating_member(device) if isinstance(b, NetPartner) else b for b in bots]
+    xp = play_seatings([weights] + pool, seatings, num_game, seed, args.eval_bomb, args.sad, hand_size=args.hand_size, device=str(device),
                        shuffle_color=bool(args.shuffle_color), bot_seed=args.seed, **game_rules(args))
     scores = []
     for k, bot in enumerate(bots):
@@ -332,8 +347,9 @@ def parse_args(argv=None):
     p.add_argument("--eval_partner", type=str, nargs="+", default=[], help="weight files of fixed partners: after each epoch's self-play "
                    "evaluation the online net plays --num_eval_game deals with each of them, in both seat orders (one batched run)")
     p.add_argument("--partner", type=str, nargs="+", default=[], help="train next to fixed partners: rule-bot presets of rulebot.py (cautious, "
-                   "piers, flawed, random).  The net acts and learns on one seat per game, the bots play the others (actor.PartnerSeats); after "
-                   "each evaluation one line per partner gives the score of the current weights seated with that bot")
+                   "piers, flawed, random) and weight files of frozen networks (FILE:skip for a skip_connect net), at most 8 of each.  The net "
+                   "acts and learns on one seat per game, the partners play the others (actor.PartnerSeats); after each evaluation one line "
+                   "per partner gives the score of the current weights seated with that partner")
     p.add_argument("--partner_seats", type=str, default="alternate", help="with --partner: alternate = the learner's seat is g %% P and the "
                    "bots take turns over the games; 0, 1, ... = the learner keeps that seat in every game")
     p.add_argument("--early_draw", type=int, default=1, help="with --draw_ahead and the composite learner: priority write-back and the next draw are "
@@ -359,12 +375,14 @@ def parse_args(argv=None):
     if args.num_thread > 0 and args.num_game_per_thread > 0:
         args.num_game = args.num_thread * args.num_game_per_thread
     if args.partner:
-        from .rulebot import MAX_BOTS, PRESETS
-        unknown = [n for n in args.partner if n not in PRESETS]
-        if unknown:
-            raise SystemExit("--partner: no rule-bot preset named %s (have: %s)" % (", ".join(unknown), ", ".join(sorted(PRESETS))))
-        if len(args.partner) > MAX_BOTS:
-            raise SystemExit("--partner: at most %d bots" % MAX_BOTS)
+        from .actor import NetPartner
+        from .rulebot import MAX_BOTS
+        try:
+            kinds = [isinstance(parse_partner(entry), NetPartner) for entry in args.partner]
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if kinds.count(False) > MAX_BOTS or kinds.count(True) > NetPartner.MAX_NETS:
+            raise SystemExit("--partner: at most %d bots and %d nets" % (MAX_BOTS, NetPartner.MAX_NETS))
         if args.method == "vdn":
             raise SystemExit("--partner needs --method iql: a VDN transition holds every player's row, and the partners' rows are not the learner's")
         if args.partner_seats != "alternate" and not (args.partner_seats.isdigit() and int(args.partner_seats) < args.num_player):

@@ -1353,6 +1353,50 @@ int hsad_actor_create_partnered(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_
                                 const hsad_actor_config* cfg, const hsad_actor_io* io, const hsad_actor_partners* partners,
                                 hsad_actor** out);
 
+/* ---- Frozen networks as partners.  A partner row belongs either to a rule-list bot, as above, or to one of up to
+ * HSAD_PARTNER_MAX_NETS frozen networks.  A network partner acts greedily, carries its own LSTM state over the rows it owns and never
+ * reaches the replay; the learner's side is what hsad_actor_create_partnered describes.
+ *
+ * hsad_actor_net_partners:
+ *   nets      [n_net] handles, caller-owned and alive as long as the actor, on the actor's device; inference nets are enough.  Any
+ *             architecture hsad_r2d2_act runs (num_fc_layer 1..2, num_lstm_layer 1..3, skip_connect, its own hid_dim): a partner needs no
+ *             cached Q-values, so the skip_connect refusal of hsad_actor_create holds for the learner only.  in_dim and num_action
+ *             must be the env's (and so the padded row length the learner's).  No handle twice, none equal to online or target: two act
+ *             calls never share a workspace (the caller makes a copy).
+ *   n_net     1 .. HSAD_PARTNER_MAX_NETS.
+ *   seat_net  HOST int32 [G * P]: k on the rows of net k, -1 on every other row.
+ * Every row has exactly one owner: the learner (rows), a bot (seat_bot[r] >= 0, seat_net[r] == -1) or a net (seat_net[r] >= 0,
+ * seat_bot[r] == -1).  Net k owns n_k >= 1 rows; the compact index of a row of net k is its rank among them in ascending row order.
+ * n_bot == 0 is allowed whenever no row is a bot's.
+ *
+ * Per step, on the caller's stream and in this order: the learner's hsad_r2d2_act, then for k = 0 .. n_net - 1
+ *   hsad_r2d2_act(net_k, NULL, n_k, NULL, obs16_k, legal_k, eps = NULL, ..., q_online_a = NULL, q_target_greedy = NULL)
+ * (greedy: a == greedy_a; no target pass; seed = cfg->seed, counter = the step number).  Act calls are never put on different
+ * streams.  The state of net k ping-pongs between two slots and is zeroed on the terminal of the row's game (hsad_zero_state_rows,
+ * per-row flags); the bf16 state copy is carried iff n_k >= 1024.  A partner row of a game that is not live receives the noop, as
+ * hsad_seat_scatter writes it.  The weights are read through the handle on every step: weights written and refreshed on the same
+ * stream between two steps take effect at the next step.
+ * The compact rows of the learner and of all nets live in one index space (e < M: the learner; [off_k, off_k + n_k): net k): one
+ * gather launch of M + sum n_k workgroups in front of the acts (a net row gets its bf16 observation row and its legal row only) and
+ * one second pass behind the env step (terminal of every compact row, reward of the learner's) replace the two gather launches of
+ * hsad_actor_create_partnered; the merge is the same kernel.  With net_partners == NULL the call IS hsad_actor_create_partnered.
+ *
+ * Refused on top of hsad_actor_create_partnered's list, before anything is allocated or launched: n_net out of range; a net whose
+ * in_dim or num_action is not the env's; a seat_net entry on a learner row, on a bot's row, or outside -1 .. n_net - 1; a partner row
+ * owned by nobody; a net that owns no row (csrc/hsad_partner.h, partner_layout_verdict_nets); a NULL, repeated, online or target handle.
+ *
+ * hsad_actor_partner_state: the carried state of net k entering the next step, fp32 [L_k, n_k, H_k]; *n_rows = n_k. */
+enum { HSAD_PARTNER_MAX_NETS = 8 };
+typedef struct hsad_actor_net_partners {
+  hsad_r2d2_net* const* nets;
+  int32_t n_net;
+  const int32_t* seat_net;
+} hsad_actor_net_partners;
+int hsad_actor_create_partnered_nets(hsad_env* env, hsad_r2d2_net* online, hsad_r2d2_net* target, hsad_replay* replay,
+                                     const hsad_actor_config* cfg, const hsad_actor_io* io, const hsad_actor_partners* partners,
+                                     const hsad_actor_net_partners* net_partners, hsad_actor** out);
+int hsad_actor_partner_state(hsad_actor* actor, int k, float** h, float** c, int32_t* n_rows);
+
 /* ---- seat kernels of a tournament batch (eval.play_seatings): one env object holds every seating of a model pool over the same
  * deals (hsad_env_reseed with period = deals); a model acts once per step on the rows it owns, listed as flat row ids g * P + p.
  * All three are HBM-bound, one pass, launch-only. ---- */

@@ -310,6 +310,7 @@ SIGNATURES = {
     "hsad_seat_gather": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "hsad_seat_scatter": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "hsad_seating_stats": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "hsad_seating_behaviour": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "hsad_search_fork_state": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "hsad_search_actions": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "hsad_search_job_stats": (C.c_int, [_P, _P, C.c_int, _P, _P]),

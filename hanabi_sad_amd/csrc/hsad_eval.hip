@@ -1,4 +1,5 @@
-// hsad_eval.hip — the seat kernels of a tournament batch (include/hsad.h: hsad_seat_gather / hsad_seat_scatter / hsad_seating_stats).
+// hsad_eval.hip — the seat kernels of a tournament batch (include/hsad.h: hsad_seat_gather / hsad_seat_scatter / hsad_seating_stats /
+// hsad_seating_behaviour).
 //
 // What they serve: the cross-play measurement of the reference (pyhanabi/tools/eval_model.py, models/op_raw_data.txt) as ONE
 // batched run.  An env object holds S seatings x n deals (hsad_env_reseed with period n: every seating plays the same deals);
@@ -9,7 +10,8 @@
 //   scatter  its chosen actions back into a / greedy_a [G, P]; finished games receive the noop uid
 //   stats    per seating: sum score, sum score^2, perfect and finished games (integers), and the ONE word a host loop waits for,
 //            the number of games still running
-// All three stream each byte once and need no cross-workgroup communication beyond one integer atomic per workgroup (stats).
+//   behaviour (on request) per seating and seat: the HSAD_BH_* counters of the moves about to be stepped (csrc/hsad_behaviour.h)
+// The first three stream each byte once and need no cross-workgroup communication beyond one integer atomic per workgroup (stats).
 // The bf16 rows are whole 16-byte vectors (row length a multiple of 8, base 16-byte aligned); the float32 observation rows
 // (838 floats) and the legal-move rows (21 floats = 84 B) are not 16-byte aligned and move as dwords.
 #include <hip/hip_runtime.h>
@@ -19,9 +21,11 @@
 #include <cstdio>
 
 #include "hsad.h"
+#include "hsad_behaviour.h"
 
 extern "C" int hsad_internal_set_error(int code, const char* msg);
 extern "C" int hsad_internal_env_status(const hsad_env* e, const uint32_t** misc, int* G, int* P, int* A, int* perfect_score);
+extern "C" int hsad_internal_env_rulebot_view(const hsad_env* e, const uint32_t** planes, uint32_t** act_count, int* G, int* Gpad, RbRules* ru);
 
 namespace {
 
@@ -46,6 +50,8 @@ int efail(int code, const char* fmt, ...) {
 
 constexpr int kGatherThreads = 128;   // 896 bf16 = 112 vectors of 16 B per row: one pass of a 128-thread workgroup
 constexpr int kStatsThreads = 256;
+constexpr int kBhThreads = 256;
+constexpr int kBhMaxPlayers = 5;
 
 __device__ __forceinline__ uint32_t f2bf_bits(float f) {   // round to nearest even: the rounding of hsad_cast_pad_bf16
   uint32_t u = __float_as_uint(f);
@@ -134,6 +140,35 @@ __global__ __launch_bounds__(kStatsThreads) void seating_stats_kernel(const uint
   if (t == 0 && part[4][0]) atomicAdd(unfinished, (int)part[4][0]);
 }
 
+// grid (ceil(n_per / kBhThreads), S): one thread per game of seating blockIdx.y.  The P x 13 partial sums meet in LDS (32-bit: a
+// workgroup adds at most 256 x 15 to a counter), then one 64-bit atomic per non-zero counter per workgroup goes to HBM.
+__global__ __launch_bounds__(kBhThreads) void seating_behaviour_kernel(const uint32_t* __restrict__ planes, size_t Gpad, RbRules ru,
+                                                                       int n_per, const int64_t* __restrict__ a,
+                                                                       unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int part[kBhMaxPlayers * HSAD_BH_NSTAT];
+  const int t = threadIdx.x, s = blockIdx.y, k = blockIdx.x * kBhThreads + t;
+  const int cells = ru.P * HSAD_BH_NSTAT;
+  if (t < cells) part[t] = 0u;
+  __syncthreads();
+  if (k < n_per) {
+    const int g = s * n_per + k;
+    const GlobalPlanes w{planes, Gpad, g};
+    if (misc_live(w(PL_MISC))) {
+      const int p = board_cur(w(PL_BOARD));
+      if (p >= 0 && p < ru.P) {
+        const bh_inc inc = bh_classify(w, ru, p, a[(size_t)g * ru.P + p]);
+#pragma unroll
+        for (int q = 0; q < HSAD_BH_NSTAT; ++q) {
+          const int v = bh_get(inc, q);
+          if (v) atomicAdd(&part[p * HSAD_BH_NSTAT + q], (unsigned int)v);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (t < cells && part[t]) atomicAdd(&counts[(size_t)s * cells + t], (unsigned long long)part[t]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -181,6 +216,23 @@ int hsad_seating_stats(const hsad_env* env, int games_per_seating, int64_t* stat
   HIP_TRY(hipMemsetAsync(unfinished, 0, sizeof(int32_t), st));
   hipLaunchKernelGGL(seating_stats_kernel, dim3(G / games_per_seating), dim3(kStatsThreads), 0, st, misc, games_per_seating, perfect,
                      reinterpret_cast<long long*>(stats), reinterpret_cast<int*>(unfinished));
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_seating_behaviour(const hsad_env* env, int games_per_seating, const int64_t* a, int64_t* counts, void* stream) {
+  if (!env || !a || !counts) return efail(HSAD_ERR_INVALID, "hsad_seating_behaviour: null argument");
+  const uint32_t* planes;
+  uint32_t* act_count;
+  int G, Gpad;
+  RbRules ru;
+  CK(hsad_internal_env_rulebot_view(env, &planes, &act_count, &G, &Gpad, &ru));
+  if (games_per_seating < 1 || G % games_per_seating)
+    return efail(HSAD_ERR_INVALID, "hsad_seating_behaviour: %d games are no whole number of seatings of %d", G, games_per_seating);
+  if (ru.P > kBhMaxPlayers) return efail(HSAD_ERR_INVALID, "hsad_seating_behaviour: %d players, at most %d", ru.P, kBhMaxPlayers);
+  const dim3 grid((games_per_seating + kBhThreads - 1) / kBhThreads, G / games_per_seating);
+  hipLaunchKernelGGL(seating_behaviour_kernel, grid, dim3(kBhThreads), 0, (hipStream_t)stream, planes, (size_t)Gpad, ru, games_per_seating,
+                     a, reinterpret_cast<unsigned long long*>(counts));
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
 }

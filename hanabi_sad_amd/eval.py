@@ -150,14 +150,61 @@ def _acting_agent(x, precision, device):
     return R2D2Agent(net, net, 1, 0.99)
 
 
+BEHAVIOUR_NAMES = ("MOVES", "PLAY_OK", "PLAY_FAIL", "PLAY_CERTAIN", "DISCARD", "DISCARD_CERTAIN_DEAD", "HINT_COLOUR", "HINT_RANK",
+                   "HINT_CARDS", "HINT_PLAYABLE", "LAST_COPY_LOST", "INFO_SUM", "LAST_LIFE")     # include/hsad.h: HSAD_BH_*
+BEHAVIOUR_RATES = ("hint_share", "play_share", "discard_share", "colour_hint_share", "certain_play_share", "misplay_rate",
+                   "safe_discard_share", "playable_hint_share", "cards_per_hint", "mean_info")
+
+
+class BehaviourStats:
+    """the behaviour counters of a tournament: counts int64 [..., P, 13] as hsad_seating_behaviour summed them on the device (the
+    counters of include/hsad.h, HSAD_BH_*; names = their names in that order; play_seatings gives [S, P, 13], cross_play
+    [K, K, P, 13]) and the rates derived from them, float64 [..., P], nan where the denominator is 0:
+      hint_share, play_share, discard_share   of the seat's moves
+      colour_hint_share, playable_hint_share  of its hints;  cards_per_hint = cards touched per hint
+      certain_play_share, misplay_rate        of its plays (PLAY_CERTAIN, PLAY_FAIL)
+      safe_discard_share                      of its discards (DISCARD_CERTAIN_DEAD)
+      mean_info                               information tokens available per move
+    game_moves (play_seatings / cross_play only, else None): int64 [S, num_game], the moves each game took by the env's own step
+    counter; a seating's MOVES counters add up to its sum"""
+    names = BEHAVIOUR_NAMES
+
+    def __init__(self, counts, game_moves=None):
+        self.game_moves = game_moves
+        self.counts = c = np.ascontiguousarray(counts, dtype=np.int64)
+        assert c.ndim >= 2 and c.shape[-1] == len(self.names)
+        k = {n: c[..., i].astype(np.float64) for i, n in enumerate(self.names)}
+        moves, plays, hints, discards = k["MOVES"], k["PLAY_OK"] + k["PLAY_FAIL"], k["HINT_COLOUR"] + k["HINT_RANK"], k["DISCARD"]
+
+        def over(x, d):
+            return np.divide(x, d, out=np.full(d.shape, np.nan), where=d != 0)
+        self.hint_share, self.play_share, self.discard_share = over(hints, moves), over(plays, moves), over(discards, moves)
+        self.colour_hint_share, self.playable_hint_share = over(k["HINT_COLOUR"], hints), over(k["HINT_PLAYABLE"], hints)
+        self.cards_per_hint = over(k["HINT_CARDS"], hints)
+        self.certain_play_share, self.misplay_rate = over(k["PLAY_CERTAIN"], plays), over(k["PLAY_FAIL"], plays)
+        self.safe_discard_share = over(k["DISCARD_CERTAIN_DEAD"], discards)
+        self.mean_info = over(k["INFO_SUM"], moves)
+
+    def row(self, *index):
+        """row(s, p) (cross_play: row(i, j, p)) -> {counter name: int, ..., rate name: float, ...} of that seat"""
+        out = {n: int(v) for n, v in zip(self.names, self.counts[index])}
+        out.update({r: float(getattr(self, r)[index]) for r in BEHAVIOUR_RATES})
+        return out
+
+    def summed(self, cells):
+        """the counters of several (s, p) cells added up, as a BehaviourStats of shape [1, 13]"""
+        return BehaviourStats(sum(self.counts[c] for c in cells).reshape(1, -1))
+
+
 class SeatingScores:
     """what play_seatings returns: scores int64 [S, num_game]; totals int64 [S, 4] = (sum score, sum score^2, perfect, finished) as
     hsad_seating_stats reduced them on the device; mean / sem / perfect float64 [S] from those integers (sem = population std /
-    sqrt(n), tools/eval_model.py:41-42)"""
+    sqrt(n), tools/eval_model.py:41-42); behaviour = a BehaviourStats [S, P, 13] when play_seatings(behaviour=True) counted, else
+    None"""
 
-    def __init__(self, scores, totals, seatings):
+    def __init__(self, scores, totals, seatings, behaviour=None):
         import math
-        self.scores, self.totals, self.seatings = scores, totals, seatings
+        self.scores, self.totals, self.seatings, self.behaviour = scores, totals, seatings, behaviour
         n = scores.shape[1]
         self.num_game = n
         t = [[int(v) for v in row] for row in totals]
@@ -183,9 +230,10 @@ class _SeatedModel:
 class _TournamentBatch:
     """one env object of S x n games (seating-major) and the pool seated on it; play(seed) runs one chunk of n deals"""
 
-    def __init__(self, agents, seatings, n, env_kw, device, bot_seed=0):
+    def __init__(self, agents, seatings, n, env_kw, device, bot_seed=0, behaviour=False):
         S, P = seatings.shape
         self.n, self.S = n, S
+        self.behaviour = torch.zeros(S, P, len(BEHAVIOUR_NAMES), dtype=torch.int64, device=device) if behaviour else None
         self.env = env = BatchedHanabiEnv(S * n, players=P, seed=0, eps_list=[0.0], max_len=-1, device=device, track_deck_history=False,
                                           **env_kw)
         self.lib, self.device = env.lib, env.device
@@ -223,10 +271,13 @@ class _TournamentBatch:
                                     env.greedy_a.data_ptr(), st))
 
     def play(self, seed, max_steps):
-        """deals seed .. seed + n - 1 for every seating -> (scores int64 [S, n], totals int64 [S, 4])"""
+        """deals seed .. seed + n - 1 for every seating -> (scores int64 [S, n], totals int64 [S, 4]); with behaviour counting,
+        self.behaviour holds this chunk's counters afterwards"""
         env = self.env
         env.reseed(seed, self.n)
         env.reset()
+        if self.behaviour is not None:
+            self.behaviour.zero_()
         for m in self.models:
             m.hid = m.agent.get_h0(m.n)
         done = False
@@ -235,6 +286,8 @@ class _TournamentBatch:
                 self._act(m)
             if self.bots:     # the hash of a *_RANDOM rule is keyed by the deal's seed: a deal plays the same in every chunking
                 env.policy_rule(self.bots, self.seat_bot, seed=self.bot_seed, key=self.deal + int(seed))
+            if self.behaviour is not None:     # every seat's action is merged and the env not yet stepped: the moves about to be made
+                _lib.check(self.lib.hsad_seating_behaviour(env.h, self.n, env.a.data_ptr(), self.behaviour.data_ptr(), env._stream()))
             env.step(env.a, env.greedy_a)
             _lib.check(self.lib.hsad_seating_stats(env.h, self.n, self.stats.data_ptr(), self.unfinished.data_ptr(), env._stream()))
             # the host looks at ONE word, and one step late: it never waits for the step it has just enqueued (the extra step
@@ -250,13 +303,15 @@ class _TournamentBatch:
         totals = self.stats.cpu().numpy()
         if not done and int(self.unfinished.cpu()[0]) != 0:
             raise RuntimeError("%d game(s) still running after %d steps" % (int(self.unfinished.cpu()[0]), max_steps))
-        scores = env.query()[:, 5].cpu().numpy().astype(np.int64).reshape(self.S, self.n)
+        q = env.query().cpu().numpy().astype(np.int64)
+        scores = q[:, 5].reshape(self.S, self.n)
+        self.game_moves = q[:, 6].reshape(self.S, self.n)      # HSAD_Q_NUM_STEP: what the MOVES counters of a seating add up to
         return scores, totals
 
 
 def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_launch=1 << 18, precision="bf16", device="cuda:0",
                   hand_size=5, shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3, max_steps=200,
-                  bot_seed=0):
+                  bot_seed=0, behaviour=False):
     """Every seating of a model pool over the SAME deals, in one batched run -> SeatingScores.
 
     agents: the pool -- whatever `evaluate` accepts (weight dicts, kernel agents / nets, any object with act / get_h0 such as
@@ -268,7 +323,10 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
     on the rows it owns (seating_rows; fixed ascending order, so its hidden state never moves): hsad_seat_gather -> act ->
     hsad_seat_scatter, and hsad_seating_stats reduces the per-seating statistics on the device.  bf16 kernel nets read the env's
     packed bf16 rows; every other agent gets the float32 rows by the same index list.  games_per_launch caps S x n per env object;
-    larger jobs run in chunks of deals on the same object."""
+    larger jobs run in chunks of deals on the same object.
+
+    behaviour=True also counts what kind of moves every seat of every seating makes (SeatingScores.behaviour, a BehaviourStats):
+    one hsad_seating_behaviour launch per step, between the last action merge and the env step.  The games are the same either way."""
     try:
         shape = tuple(np.asarray(seatings).shape)
     except ValueError:                    # seatings of different widths
@@ -288,27 +346,35 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
     per = max(1, min(int(num_game), int(games_per_launch) // S))
     scores = np.zeros((S, num_game), dtype=np.int64)
     totals = np.zeros((S, 4), dtype=np.int64)
+    counts = np.zeros((S, P, len(BEHAVIOUR_NAMES)), dtype=np.int64) if behaviour else None
+    game_moves = np.zeros((S, num_game), dtype=np.int64) if behaviour else None
     batches = {}
     for start in range(0, num_game, per):
         n = min(per, num_game - start)
         if n not in batches:
-            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device, bot_seed)
+            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device, bot_seed, bool(behaviour))
             if (batches[n].env.F, batches[n].env.A) != (F, A):
                 raise _lib.HsadError("env_dims gives (%d, %d), the library (%d, %d)" % (F, A, batches[n].env.F, batches[n].env.A))
         sc, tt = batches[n].play(seed + start, max_steps)
         scores[:, start:start + n] = sc
         totals += tt
+        if behaviour:
+            counts += batches[n].behaviour.cpu().numpy()
+            game_moves[:, start:start + n] = batches[n].game_moves
     for b in batches.values():
         b.env.close()
-    return SeatingScores(scores, totals, seatings)
+    return SeatingScores(scores, totals, seatings, BehaviourStats(counts, game_moves) if behaviour else None)
 
 
 class CrossPlayScores:
     """cross_play's K x K view of SeatingScores: entry [i][j] = model i on seat 0 with model j on seat 1; row_mean[i] = the mean
-    of row i with the diagonal included (the last column of models/op_raw_data.txt)"""
+    of row i with the diagonal included (the last column of models/op_raw_data.txt); behaviour = the BehaviourStats of
+    cross_play(behaviour=True) with counts [K, K, P, 13], else None"""
 
     def __init__(self, res, K):
         self.seatings, self.num_game = res, res.num_game
+        self.behaviour = None if res.behaviour is None else BehaviourStats(res.behaviour.counts.reshape((K, K) + res.behaviour.counts.shape[1:]),
+                                                                         res.behaviour.game_moves.reshape(K, K, -1))
         self.scores = res.scores.reshape(K, K, -1)
         self.mean, self.sem, self.perfect = res.mean.reshape(K, K), res.sem.reshape(K, K), res.perfect.reshape(K, K)
         self.row_mean = self.mean.mean(axis=1)
@@ -339,6 +405,47 @@ def parse_cross_play_table(text):
     body = [l.split() for l in lines[4:4 + len(names)]]
     vals = np.array([[float(v) for v in r[1:]] for r in body], dtype=np.float64)
     return lines[0], names, vals[:, :-1], vals[:, -1]
+
+
+def format_behaviour_rates(stats, index):
+    """the derived rates of one seat as `name value` pairs on one line (nan where a denominator is 0)"""
+    return " ".join("%s %.4f" % (r, float(getattr(stats, r)[index])) for r in BEHAVIOUR_RATES)
+
+
+def format_behaviour_table(names, stats):
+    """the behaviour of a cross_play: a title, a rule, the header, then one line per (pairing, seat) -- `seat0-seat1 seat who`, the 13
+    counters, `|`, the derived rates.  stats: a BehaviourStats with counts [K, K, P, 13] (or [K * K, P, 13])"""
+    K = len(names)
+    counts = stats.counts.reshape((K, K) + stats.counts.shape[-2:])
+    assert counts.shape[2] == 2, "cross_play is the two-player tournament"
+    st = BehaviourStats(counts)
+    head = "%-15s %4s %-8s" % ("pairing", "seat", "who") + "".join(" %s" % n for n in BEHAVIOUR_NAMES) + " |" + "".join(" %s" % r for r in BEHAVIOUR_RATES)
+    lines = ["behaviour per pairing and seat", "-" * 30, head]
+    for i in range(K):
+        for j in range(K):
+            for p in range(counts.shape[2]):
+                lines.append("%-15s %4d %-8s" % ("%s-%s" % (names[i], names[j]), p, names[(i, j)[p]])
+                             + "".join(" %d" % v for v in counts[i, j, p]) + " |"
+                             + "".join(" %.4f" % float(getattr(st, r)[i, j, p]) for r in BEHAVIOUR_RATES))
+    return "\n".join(lines)
+
+
+def parse_behaviour_table(text):
+    """-> (names, counts int64 [K, K, P, 13]) of a table format_behaviour_table wrote (the counters are printed exactly)"""
+    lines = [l for l in text.splitlines() if l.strip()]
+    start = lines.index("behaviour per pairing and seat")
+    rows = []
+    for l in lines[start + 3:]:
+        left = l.split("|")[0].split()
+        if "|" not in l or len(left) != 3 + len(BEHAVIOUR_NAMES):
+            break
+        rows.append((left[0], int(left[1]), left[2], [int(v) for v in left[3:]]))
+    P = max(r[1] for r in rows) + 1
+    K = int(round((len(rows) // P) ** 0.5))
+    assert K * K * P == len(rows), "not a K x K x P table: %d lines" % len(rows)
+    names = [rows[i * K * P][2] for i in range(K)]          # seat 0 of the pairings (i, 0)
+    counts = np.array([r[3] for r in rows], dtype=np.int64).reshape(K, K, P, len(BEHAVIOUR_NAMES))
+    return names, counts
 
 
 def _drain_errors(env):

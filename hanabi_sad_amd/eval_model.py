@@ -9,6 +9,7 @@ layout.
   --paper op  --method sad --idx 0 3 6 9 --cross_play   the 4 x 4 matrix
   --paper sad --weight a.pthw b.pthw c.pthw --cross_play
   --paper op  --method sad --idx 0 3 --cross_play --bots cautious piers    the matrix with rule-bot partners (rulebot.PRESETS)
+  ... --cross_play --bots piers --behaviour             the matrix, then per pairing and seat the behaviour counters and rates
   --paper op  --method sad --idx 0 --search_worlds 8    M0 in self-play, blueprint only and blueprint + search over the same deals
   ... --search_worlds 32 --search_rounds 8,8,16         the same with the search in rounds (paired statistics, pruning)
 
@@ -18,7 +19,7 @@ game)."""
 import argparse
 import os
 
-from .eval import cross_play, env_dims, format_cross_play_table, play_seatings
+from .eval import cross_play, env_dims, format_behaviour_table, format_cross_play_table, play_seatings
 from .rulebot import PRESETS
 
 
@@ -38,6 +39,8 @@ def parse_args(argv=None):
     p.add_argument("--idx", default=None, type=int, nargs="+", help="--paper op --cross_play: the zoo models of the pool")
     p.add_argument("--bots", default=[], type=str, nargs="+", choices=sorted(PRESETS),
                    help="--cross_play: rule-bot presets appended to the pool (hand-coded partners; rulebot.PRESETS)")
+    p.add_argument("--behaviour", action="store_true", help="--cross_play: after the matrix, one line per (pairing, seat) with the "
+                   "behaviour counters of the moves made there and their rates (eval.BehaviourStats; include/hsad.h, HSAD_BH_*)")
     p.add_argument("--root", default=None, type=str, help="folder that holds models/op/<method>/M{idx}.pthw (default: the repository)")
     p.add_argument("--precision", default="bf16", type=str, choices=["bf16", "fp32"])
     p.add_argument("--search_worlds", default=0, type=int, help="> 0 with a single --idx: also play with blueprint-policy search "
@@ -109,6 +112,8 @@ def search_report(args):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.behaviour and not args.cross_play:
+        raise SystemExit("--behaviour needs --cross_play (the table has one line per pairing of the matrix and seat)")
     if args.search_worlds > 0:
         return search_report(args)
     agents, names, title, P = load_pool(args)
@@ -121,8 +126,13 @@ def main(argv=None):
         agents, names = agents + [PRESETS[b] for b in args.bots], names + list(args.bots)
         if P != 2:
             raise SystemExit("--cross_play is the two-player matrix")
+        if args.behaviour:
+            kw["behaviour"] = True
         res = cross_play(agents, n, 1, 0, sad, **kw)
         print(format_cross_play_table("self-play & cross-play of %s" % title, names, res.mean, res.row_mean))
+        if args.behaviour:
+            print()
+            print(format_behaviour_table(names, res.behaviour))
         return res
     seating = [0] * P if len(agents) == 1 else list(range(P))
     res = play_seatings(agents, [seating], n, 1, 0, sad, **kw)

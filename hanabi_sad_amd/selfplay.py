@@ -88,19 +88,25 @@ def partner_seats(args, num_game):
 def print_partner_scores(args, weights, num_game, seed, device):
     """one line per --partner entry: the score of `weights` seated with that partner through play_seatings, every partner on the same
     deals (seating s puts the net on seat s and the partner on every other seat; the line is the mean over the P seatings); a file
-    partner's line carries the file's basename"""
+    partner's line carries the file's basename.  With --partner_behaviour 1 two more lines follow each: the behaviour rates
+    (eval.BehaviourStats) of the learner's seats and of the partner's seats in those games"""
     from .actor import NetPartner
-    from .eval import play_seatings
+    from .eval import format_behaviour_rates, play_seatings
     bots, P = partner_bots(args), args.num_player
+    behaviour = bool(getattr(args, "partner_behaviour", 0))
     seatings = [[0 if p == seat else k for p in range(P)] for k in range(1, len(bots) + 1) for seat in range(P)]
     pool = [b.seating_member(device) if isinstance(b, NetPartner) else b for b in bots]
     xp = play_seatings([weights] + pool, seatings, num_game, seed, args.eval_bomb, args.sad, hand_size=args.hand_size, device=str(device),
-                       shuffle_color=bool(args.shuffle_color), bot_seed=args.seed, **game_rules(args))
+                       shuffle_color=bool(args.shuffle_color), bot_seed=args.seed, behaviour=behaviour, **game_rules(args))
     scores = []
     for k, bot in enumerate(bots):
         m = xp.mean[k * P:(k + 1) * P]
         scores.append(float(m.mean()))
         print("partner %s: score %.4f (%s)" % (bot.name, scores[-1], ", ".join("as seat %d: %.4f" % (q, float(m[q])) for q in range(P))))
+        if behaviour:        # seating k * P + seat has the learner on `seat` and the partner on every other seat
+            for who, cells in (("learner", [(k * P + q, q) for q in range(P)]),
+                               ("partner", [(k * P + q, r) for q in range(P) for r in range(P) if r != q])):
+                print("partner %s behaviour %s: %s" % (bot.name, who, format_behaviour_rates(xp.behaviour.summed(cells), 0)))
     return scores
 
 
@@ -352,6 +358,8 @@ def parse_args(argv=None):
                    "per partner gives the score of the current weights seated with that partner")
     p.add_argument("--partner_seats", type=str, default="alternate", help="with --partner: alternate = the learner's seat is g %% P and the "
                    "bots take turns over the games; 0, 1, ... = the learner keeps that seat in every game")
+    p.add_argument("--partner_behaviour", type=int, default=0, help="with --partner, 1: under each `partner NAME: score` line two more, the "
+                   "behaviour rates (who hints, who plays unsure, ...: eval.BehaviourStats) of the learner's and of the partner's seats")
     p.add_argument("--early_draw", type=int, default=1, help="with --draw_ahead and the composite learner: priority write-back and the next draw are "
                    "issued between the forward half and the BPTT of an update on a stream of their own (0: behind the optimizer step on the caller's stream)")
     p.add_argument("--draw_ahead", type=int, default=1, help="1: the batch of update u + 1 is drawn at the end of update u (behind its priority "

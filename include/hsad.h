@@ -1416,6 +1416,54 @@ int hsad_seat_scatter(const hsad_env* env, const int32_t* rows, int n, const int
  * the finished games: stats int64 [S, 4] = sum score, sum score^2, perfect games (score == colors * ranks), finished games; and
  * *unfinished int32 = games of the whole env not finished yet -- the one word a host loop reads.  Integer sums: exact, order-free. */
 int hsad_seating_stats(const hsad_env* env, int games_per_seating, int64_t* stats, int32_t* unfinished, void* stream);
+/* Behaviour counters: what KIND of moves each seat of each seating makes.  A move classifier (csrc/hsad_behaviour.h: bh_classify)
+ * looks at the position BEFORE the move and at the uid the seat on turn is about to play, and gives the increments of the
+ * HSAD_BH_NSTAT counters below; the position is never modified and nothing is remembered from move to move.  This text is the
+ * specification (csrc/hsad_behaviour.h follows it, tests/behaviour_ref.py restates it).  It uses the definitions of the rule-bot
+ * section above for the mover p: pool, compat_i, n_i, play_i, dead_i, playable(t), dead(t), full[t], discards[t].
+ *    #  name                  +1 (HINT_CARDS, INFO_SUM: +n) when the move is ...
+ *    0  MOVES                 any play, discard or hint
+ *    1  PLAY_OK               a play of slot i whose card is playable
+ *    2  PLAY_FAIL             a play whose card is not playable
+ *    3  PLAY_CERTAIN          a play of slot i with play_i == n_i (the mover's own knowledge: exactly the test of rule 1)
+ *    4  DISCARD               a discard
+ *    5  DISCARD_CERTAIN_DEAD  a discard of slot i with dead_i == n_i (the test of rule 8)
+ *    6  HINT_COLOUR           a colour hint
+ *    7  HINT_RANK             a rank hint
+ *    8  HINT_CARDS            +n, the number of cards of the target hand the hint touches
+ *    9  HINT_PLAYABLE         a hint that touches at least one card that is playable now
+ *   10  LAST_COPY_LOST        a discard or failed play of a card of type t with !dead(t) and discards[t] == full[t] - 1 before the move
+ *   11  INFO_SUM              +the information tokens available before the move (every counted move)
+ *   12  LAST_LIFE             a failed play with life == 1 before it
+ * The uid is decoded by the layout above: discard slot i = i, play slot i = H + i, colour hint = 2H + (o-1) C + colour, rank hint =
+ * 2H + (P-1) C + (o-1) R + rank, noop = A - 1.  With shuffle_color a colour hint names its colour through the ACTOR's permutation,
+ * as its legal_move row does; the classifier maps it back to the cards' colour.  The noop, a uid outside [0, A), a play or discard
+ * of an empty slot, and a hint that touches no card count NOTHING, not even MOVES (the env refuses and logs those; whether the
+ * tokens allow a hint or a discard is the env's business too and is not looked at here).
+ *
+ * hsad_seating_behaviour: a device int64 [G, P], the rows about to go into hsad_env_step; counts device int64 [S, P, HSAD_BH_NSTAT],
+ * S = G / games_per_seating.  For every live game g (started and not terminated) with seat p on turn:
+ *   counts[g / games_per_seating][p] += bh_classify(planes of g, p, a[g, p]);
+ * games that are not live add nothing.  It ACCUMULATES (as hsad_search_job_stats does): the caller zeroes counts.  Integer atomics
+ * only: exact, order-free.  Reads the state planes and `a`, writes nothing but counts.  HSAD_ERR_INVALID before any launch: a null
+ * argument, games_per_seating < 1 or not dividing G, more than 5 players.  Launch-only. */
+enum {
+  HSAD_BH_MOVES = 0,
+  HSAD_BH_PLAY_OK = 1,
+  HSAD_BH_PLAY_FAIL = 2,
+  HSAD_BH_PLAY_CERTAIN = 3,
+  HSAD_BH_DISCARD = 4,
+  HSAD_BH_DISCARD_CERTAIN_DEAD = 5,
+  HSAD_BH_HINT_COLOUR = 6,
+  HSAD_BH_HINT_RANK = 7,
+  HSAD_BH_HINT_CARDS = 8,
+  HSAD_BH_HINT_PLAYABLE = 9,
+  HSAD_BH_LAST_COPY_LOST = 10,
+  HSAD_BH_INFO_SUM = 11,
+  HSAD_BH_LAST_LIFE = 12,
+  HSAD_BH_NSTAT = 13
+};
+int hsad_seating_behaviour(const hsad_env* env, int games_per_seating, const int64_t* a, int64_t* counts, void* stream);
 
 /* ---- glue kernels of blueprint-policy search (search.PolicySearch): a search env of G slots plays (root game, candidate action,
  * sampled world) jobs with the R2D2 agent acting for every seat; hsad_env_fork + hsad_env_determinize place the worlds, these three

@@ -56,7 +56,8 @@ struct EnvParams {
   int n_iter;       // MODE 3: iterations this launch runs for its games (persistent rollout; 1 otherwise)
   int delta;        // env_rollout_pipe_kernel: two copies of the observation bit rows in LDS; every stream of the launch but the first
                     // stores only the lines of priv_s whose bits changed since the stream before (rollout_delta_active)
-  int compact;      // with delta: the stream wave lists the changed lines first and stores from the list (stream_bits_f32_compact)
+  int compact;      // with delta: the stream wave lists the changed units first and stores from the list (stream_bits_f32_compact):
+                    // 1 = 128-byte lines, 2 = 64-byte half lines (hsad_env_set_rollout_unit)
   int stagger_ticks;  // MODE 3, n_iter > 1: workgroup b starts (b % 8) * stagger_ticks (100 MHz) late, see env_kernel
   int stagger_mode;   // which workgroups start late (developer switch HSAD_ENV_STAGGER_MODE, see env_rollout_kernel)
   int64_t* a_out;                  // MODE 2: where the sampled actions are recorded ([G,P] each)
@@ -79,11 +80,17 @@ struct EnvParams {
   unsigned long long* own_bits;    // [G*P]
   unsigned short* priv16;          // [G*P][ld16] bf16, columns F..ld16-1 zero
   int pw64, ld16, obs_f32;
+  unsigned dbg_units_hi;           // (see dbg_units_lo)
   float* reward;
   uint8_t* terminal;
   unsigned long long* dbg;  // optional wall_clock64 stamps of thread 0 at phase boundaries: [grid][8] (hsad_env_debug_timing), or per
                             // iteration of a persistent launch [grid][dbg_iters][16] (hsad_env_debug_trace; slot map: env_stamp)
   int dbg_iters;
+  // optional, with the trace layout of dbg: the address of uint64 [grid][dbg_iters], the units of priv_s the stream wave stored for
+  // the rows of `it - 1`, counted in the unit that stream decided by (hsad_env_debug_units); 0: off.  Kept as two halves in what
+  // was padding behind dbg_iters and obs_f32, so that the struct keeps its size and every field its offset: a pointer appended to
+  // the struct moves the later kernel arguments and changes the code of kernels that never read it (tools/isa_compare.py).
+  unsigned dbg_units_lo;
   // phase lock of stream partitions (hsad_env_rollout_random with K > 1): partition p > 0 starts its launch `lock_ticks`
   // (10 ns units) after partition p-1 started the launch with the same tag, so that one partition's latency-bound logic
   // phase keeps overlapping the other's HBM stream.  Timing only: a bounded wait, results never depend on it.
@@ -436,7 +443,8 @@ __device__ __forceinline__ uint32_t hand_match_mask(uint32_t hw, bool by_color, 
 //                              8 stream wave (thread 64): rows of `it - 1` streamed and cleared, 5 last record only: epilogue stream done,
 //                              6 / 7 as above
 //                              12 pacing: ticks by which the stream of this iteration's rows is delayed (pace_delay)
-//                              13 delta stream (EnvParams::delta): 128-byte lines of priv_s the stream wave stored for the rows of `it - 1`;
+//                              13 delta stream (EnvParams::delta): 128-byte lines of priv_s the stream wave stored for the rows of `it - 1`
+//                                 (with half-line units: lines with any change); the units themselves go to EnvParams::dbg_units_lo / _hi
 //                              14 / 15 last record only: lines wave 0 / wave 1 stored in the epilogue stream
 //   both, trace layout:        9 HW_REG_HW_ID, 10 HW_REG_XCC_ID of the workgroup (written with slot 0)
 __device__ __forceinline__ void env_stamp(const EnvParams& ep, int it, int k, unsigned long long v) {
@@ -766,20 +774,28 @@ __device__ __forceinline__ unsigned stream_bits_f32_delta(const uint32_t* bits, 
 }
 
 // The compacted form of the same (EnvParams::compact), for one wave and a stream that is not an `all` stream: first a scan that
-// lists the changed words, then a store loop over the list only, eight whole lines per wave-store, without a predicate and with
-// several groups of LDS reads in flight.  Stores exactly the lines the direct form stores.  Returns the number of lines stored in
-// lane 0 and 0 in every other lane (the direct form's per-lane counts sum to the same).
+// lists the changed units, then a store loop over the list only, whole units per wave-store, without a predicate and with
+// several groups of LDS reads in flight.  UNIT is the floats of a unit: 32 (a word of bits, one 128-byte line: stores exactly the
+// lines the direct form stores) or 16 (a half word, one 64-byte half line, which is one native request of the L2 to the memory
+// fabric: a line whose change sits in one half costs half the bytes).  Returns the number of 128-byte lines with any change in
+// lane 0 and 0 in every other lane (the direct form's per-lane counts sum to the same); units: the units stored, likewise.
 //
-// The list costs no LDS: entry r (a word index, 32 bits) is written in place to list[r], where list is `old` itself.  Invariant:
-// scan step s reads positions [64s, 64s + 64) and lane l's entry goes to position base_s + rank <= 64s + l, base_s being the
-// number of changed words before step s and rank the number of changed lanes below l.  So a write of step s lands only on a
-// position that step s or an earlier one has read, and every later step reads only positions >= 64(s + 1): no read of `old` ever
-// sees a list entry.  Within a step the compare -> ballot -> rank dependence puts the step's reads before its writes.  The scan
-// below takes kScanSteps steps' reads together ahead of their writes, which keeps the invariant: those writes land below
-// 64(s + kScanSteps) at most, all read by then.  A partial last word (n / 4 not a multiple of 8) is not listed: its position is
-// beyond every entry, and the lanes of its chunks store it in the direct form.  The caller clears `old`, list included, afterwards.
+// The list costs no LDS: entry r is written in place to position r of list, which is `old` itself.
+//   UNIT 32: entries are word indices, 32 bits wide.  Invariant: scan step s reads positions [64s, 64s + 64) and lane l's entry
+//   goes to position base_s + rank <= 64s + l, base_s being the number of changed words before step s and rank the number of
+//   changed lanes below l.  So a write of step s lands only on a position that step s or an earlier one has read, and every later
+//   step reads only positions >= 64(s + 1): no read of `old` ever sees a list entry.
+//   UNIT 16: entries are half-line indices 2w and 2w + 1, 16 bits wide (the largest is 2 x 14,390 for five players with SAD in
+//   64-game workgroups), entry r at half-word r.  Scan step s reads words [64s, 64s + 64), that is half-words [128s, 128s + 128).
+//   At most 128s entries exist before step s and lane l's one or two entries (hi directly after lo, so that the halves of a line
+//   are neighbours in the list and their stores still form one 128-byte segment) go to half-words <= 128s + 2l + 1: inside the
+//   word that lane itself read in this step, or below.  Again no read of `old` ever sees an entry.
+// Within a step the compare -> ballot -> rank dependence puts the step's reads before its writes.  The scan below takes kScanSteps
+// steps' reads together ahead of their writes, which keeps the invariant: those writes land below word 64(s + kScanSteps) at most,
+// all read by then.  A partial last word (n / 4 not a multiple of 8) is not listed: its position is beyond every entry, and the
+// lanes of its chunks store it whole in the direct form, whichever the unit.  The caller clears `old`, list included, afterwards.
 constexpr int kScanSteps = 4;    // scan steps whose LDS reads are issued together
-constexpr int kStoreGroups = 4;  // store groups (eight lines each) whose LDS reads are issued together
+constexpr int kStoreGroups = 4;  // store groups (1 KiB each: eight lines or sixteen halves) whose LDS reads are issued together
 
 template <bool NT>
 __device__ __forceinline__ void store_chunk(float4* p, const float4 v) {
@@ -792,13 +808,18 @@ __device__ __forceinline__ void store_chunk(float4* p, const float4 v) {
   }
 }
 
-template <bool NT>
-__device__ __forceinline__ unsigned stream_bits_f32_compact(const uint32_t* bits, uint32_t* list, float* out, uint32_t n, int lane) {
+typedef uint16_t __attribute__((may_alias)) list16_t;   // the half-line list lives in the words of `old`
+
+template <bool NT, int UNIT>
+__device__ __forceinline__ unsigned stream_bits_f32_compact(const uint32_t* bits, uint32_t* list, float* out, uint32_t n, int lane,
+                                                            unsigned& units) {
+  static_assert(UNIT == 32 || UNIT == 16, "a unit is a line or a half line");
   float4* o4 = reinterpret_cast<float4*>(out);
+  list16_t* list16 = reinterpret_cast<list16_t*>(list);
   const uint32_t nch = n >> 2;
   const uint32_t nfull = nch >> 3;   // words that own eight chunks
-  // scan: count is wave-uniform
-  uint32_t count = 0;
+  // scan: count (entries) and lines are wave-uniform
+  uint32_t count = 0, lines = 0;
   for (uint32_t w0 = 0; w0 < nfull; w0 += 64u * kScanSteps) {
     uint32_t b[kScanSteps], o[kScanSteps];
 #pragma unroll
@@ -810,13 +831,26 @@ __device__ __forceinline__ unsigned stream_bits_f32_compact(const uint32_t* bits
 #pragma unroll
     for (int u = 0; u < kScanSteps; ++u) {
       const uint32_t w = w0 + 64u * u + (uint32_t)lane;
-      const bool changed = w < nfull && b[u] != o[u];
-      const unsigned long long m = __ballot(changed);
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      if (changed) list[count + rank] = w;
-      count += (uint32_t)__popcll(m);
+      if (UNIT == 32) {
+        const bool changed = w < nfull && b[u] != o[u];
+        const unsigned long long m = __ballot(changed);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (changed) list[count + rank] = w;
+        count += (uint32_t)__popcll(m);
+      } else {
+        const uint32_t x = w < nfull ? b[u] ^ o[u] : 0u;
+        const bool lo = (x & 0xffffu) != 0u, hi = (x >> 16) != 0u;
+        const unsigned long long m_lo = __ballot(lo), m_hi = __ballot(hi);
+        uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m_lo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_lo, 0u));
+        rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m_hi >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_hi, rank));
+        if (lo) list16[count + rank] = (list16_t)(2u * w);
+        if (hi) list16[count + rank + (lo ? 1u : 0u)] = (list16_t)(2u * w + 1u);
+        count += (uint32_t)__popcll(m_lo) + (uint32_t)__popcll(m_hi);
+        lines += (uint32_t)__popcll(m_lo | m_hi);
+      }
     }
   }
+  if (UNIT == 32) lines = count;
   // the partial last word, read before anything else is done (no entry reaches its position)
   const uint32_t kp = 8u * nfull + (uint32_t)lane;
   const bool part = kp < nch;   // lanes 0 .. (nch & 7) - 1
@@ -826,32 +860,62 @@ __device__ __forceinline__ unsigned stream_bits_f32_compact(const uint32_t* bits
     wp = bits[nfull];
     part_changed = wp != list[nfull];
   }
-  // store: lane l serves entry 8j + (l >> 3) of group j, chunk l & 7 of its line
-  const uint32_t sub = (uint32_t)lane >> 3, c = (uint32_t)lane & 7u;
-  uint32_t e0 = 0;
-  for (; e0 + 8u * kStoreGroups <= count; e0 += 8u * kStoreGroups) {
-    uint32_t idx[kStoreGroups], word[kStoreGroups];
+  if (UNIT == 32) {
+    // store: lane l serves entry 8j + (l >> 3) of group j, chunk l & 7 of its line
+    const uint32_t sub = (uint32_t)lane >> 3, c = (uint32_t)lane & 7u;
+    uint32_t e0 = 0;
+    for (; e0 + 8u * kStoreGroups <= count; e0 += 8u * kStoreGroups) {
+      uint32_t idx[kStoreGroups], word[kStoreGroups];
 #pragma unroll
-    for (int u = 0; u < kStoreGroups; ++u) idx[u] = list[e0 + 8u * u + sub];
+      for (int u = 0; u < kStoreGroups; ++u) idx[u] = list[e0 + 8u * u + sub];
 #pragma unroll
-    for (int u = 0; u < kStoreGroups; ++u) word[u] = bits[idx[u]];
+      for (int u = 0; u < kStoreGroups; ++u) word[u] = bits[idx[u]];
 #pragma unroll
-    for (int u = 0; u < kStoreGroups; ++u) store_chunk<NT>(o4 + 8u * idx[u] + c, nib_to_f4((word[u] >> (4u * c)) & 15u));
+      for (int u = 0; u < kStoreGroups; ++u) store_chunk<NT>(o4 + 8u * idx[u] + c, nib_to_f4((word[u] >> (4u * c)) & 15u));
+    }
+    if (e0 < count) {   // the last, partial block of groups: the lanes of entries >= count are off
+      uint32_t idx[kStoreGroups], word[kStoreGroups];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u) idx[u] = list[min(e0 + 8u * u + sub, count - 1u)];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u) word[u] = bits[idx[u]];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u)
+        if (e0 + 8u * u + sub < count) store_chunk<NT>(o4 + 8u * idx[u] + c, nib_to_f4((word[u] >> (4u * c)) & 15u));
+    }
+  } else {
+    // store: lane l serves entry 16j + (l >> 2) of group j, chunk l & 3 of its half line
+    const uint32_t sub = (uint32_t)lane >> 2, c = (uint32_t)lane & 3u;
+    uint32_t e0 = 0;
+    for (; e0 + 16u * kStoreGroups <= count; e0 += 16u * kStoreGroups) {
+      uint32_t idx[kStoreGroups], word[kStoreGroups];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u) idx[u] = list16[e0 + 16u * u + sub];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u) word[u] = bits[idx[u] >> 1];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u)
+        store_chunk<NT>(o4 + 4u * idx[u] + c, nib_to_f4((word[u] >> (16u * (idx[u] & 1u) + 4u * c)) & 15u));
+    }
+    if (e0 < count) {   // the last, partial block of groups: the lanes of entries >= count are off
+      uint32_t idx[kStoreGroups], word[kStoreGroups];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u) idx[u] = list16[min(e0 + 16u * u + sub, count - 1u)];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u) word[u] = bits[idx[u] >> 1];
+#pragma unroll
+      for (int u = 0; u < kStoreGroups; ++u)
+        if (e0 + 16u * u + sub < count)
+          store_chunk<NT>(o4 + 4u * idx[u] + c, nib_to_f4((word[u] >> (16u * (idx[u] & 1u) + 4u * c)) & 15u));
+    }
   }
-  if (e0 < count) {   // the last, partial block of groups: the lanes of entries >= count are off
-    uint32_t idx[kStoreGroups], word[kStoreGroups];
-#pragma unroll
-    for (int u = 0; u < kStoreGroups; ++u) idx[u] = list[min(e0 + 8u * u + sub, count - 1u)];
-#pragma unroll
-    for (int u = 0; u < kStoreGroups; ++u) word[u] = bits[idx[u]];
-#pragma unroll
-    for (int u = 0; u < kStoreGroups; ++u)
-      if (e0 + 8u * u + sub < count) store_chunk<NT>(o4 + 8u * idx[u] + c, nib_to_f4((word[u] >> (4u * c)) & 15u));
-  }
-  if (part_changed) store_chunk<NT>(o4 + kp, nib_to_f4((wp >> (4u * c)) & 15u));
+  if (part_changed) store_chunk<NT>(o4 + kp, nib_to_f4((wp >> (4u * ((uint32_t)lane & 7u))) & 15u));
   const uint32_t done = nch << 2;
   if ((uint32_t)lane < n - done) out[done + lane] = get1(bits, done + lane) ? 1.f : 0.f;
-  return lane == 0 ? count + (part_changed ? 1u : 0u) : 0u;
+  // the partial word went out whole: one line, and as many units as its chunks reach into
+  const uint32_t part_units = UNIT == 32 || (nch & 7u) <= 4u ? 1u : 2u;
+  units = lane == 0 ? count + (part_changed ? part_units : 0u) : 0u;
+  return lane == 0 ? lines + (part_changed ? 1u : 0u) : 0u;
 }
 
 __device__ __forceinline__ uint32_t perm_c(uint32_t pm, int c) { return (pm >> (3 * c)) & 7u; }
@@ -1144,27 +1208,39 @@ __device__ __forceinline__ void stream_rows(const EnvParams& ep, const uint32_t*
 // The same for the pipelined rollout, whose later streams of a launch reduce the float32 observation to the lines that changed
 // (EnvParams::delta).  s_old: the bit rows priv_s was last written from; all: every line (the first stream of a launch, and every
 // stream without delta).  The packed forms, legal moves and own hand go out in full from the current rows.  Returns this lane's
-// count of observation lines stored (count on: the trace).  compact: one wave streams (t its lane, n == kWave) and takes the
-// compacted form where the stream is not an `all` stream; that form writes its list of changed lines into s_old, which the caller
-// clears afterwards anyway.  The choice is wave-uniform and made once per stream.
+// count of observation lines stored (count on: the trace) and, in units, of the units stored (lines, or half lines where the
+// stream decided by those).  compact: one wave streams (t its lane, n == kWave) and takes the compacted form where the stream is not
+// an `all` stream, by lines (1) or by half lines (2); that form writes its list of changed units into s_old, which the caller
+// clears afterwards anyway.  The choice is wave-uniform and made once per stream.  Mixing units within a launch is safe: after any
+// stream priv_s equals the rows streamed, whichever unit decided what to skip.
 __device__ __forceinline__ unsigned stream_rows_delta(const EnvParams& ep, const uint32_t* s_obs, uint32_t* s_old, bool all,
                                                       const uint32_t* s_legal, const uint32_t* s_own, int g0, int ng, int P, int H,
-                                                      int t, int n, bool count, bool compact) {
+                                                      int t, int n, bool count, int compact, unsigned& units) {
   const size_t PF = (size_t)P * ep.F, PA = (size_t)P * ep.A, PO = (size_t)P * 3 * H;
   unsigned stored = 0;
+  bool by_lines = true;
   if (!ep.obs_f32) {
     // device consumers only: no float32 observation leaves the chip
   } else if (compact && !all) {
-    if (ep.nt_stores) {
-      stored = stream_bits_f32_compact<true>(s_obs, s_old, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t);
+    by_lines = false;
+    float* out = ep.priv_s + (size_t)g0 * PF;
+    if (compact == 2) {
+      if (ep.nt_stores) {
+        stored = stream_bits_f32_compact<true, 16>(s_obs, s_old, out, (uint32_t)(ng * PF), t, units);
+      } else {
+        stored = stream_bits_f32_compact<false, 16>(s_obs, s_old, out, (uint32_t)(ng * PF), t, units);
+      }
+    } else if (ep.nt_stores) {
+      stored = stream_bits_f32_compact<true, 32>(s_obs, s_old, out, (uint32_t)(ng * PF), t, units);
     } else {
-      stored = stream_bits_f32_compact<false>(s_obs, s_old, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t);
+      stored = stream_bits_f32_compact<false, 32>(s_obs, s_old, out, (uint32_t)(ng * PF), t, units);
     }
   } else if (ep.nt_stores) {
     stored = stream_bits_f32_delta<true>(s_obs, s_old, all, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t, n, count);
   } else {
     stored = stream_bits_f32_delta<false>(s_obs, s_old, all, ep.priv_s + (size_t)g0 * PF, (uint32_t)(ng * PF), t, n, count);
   }
+  if (by_lines) units = stored;
   stream_rows_packed(ep, s_obs, 0, ng * P, (size_t)g0 * P, t, n);
   stream_bits_f32_aligned<false>(s_legal, ep.legal + (size_t)g0 * PA, (uint32_t)(ng * PA), t, n);
   stream_bits_f32_aligned<false>(s_own, ep.own + (size_t)g0 * PO, (uint32_t)(ng * PO), t, n);
@@ -1973,16 +2049,26 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       const bool dbg_lines = ep.dbg && ep.dbg_iters > 0;
       int sl = lane;
       asm volatile("" : "+v"(sl));   // opaque: the stream's per-lane addresses are worked out here, not kept in registers for the launch
+      unsigned units = 0;
       unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || iter == 1, s_legal, s_own, g0, ng, P, H, sl, kWave, dbg_lines,
-                                          ep.compact != 0);
+                                          ep.compact, units);
       clear_words(prev, ep.obs_words, sl, kWave);
       clear_words(s_legal, ep.legal_words + ep.own_words, sl, kWave);
       if (dbg_lines) {
         stored = wave_sum(stored);
         if (lane == 0) env_stamp(ep, dbg_it, 13, stored);
+        unsigned long long* dbg_units = reinterpret_cast<unsigned long long*>(((uint64_t)ep.dbg_units_hi << 32) | ep.dbg_units_lo);
+        if (dbg_units) {
+          units = wave_sum(units);
+          if (lane == 0)
+            dbg_units[((size_t)(ep.g_begin / ep.gpw) + blockIdx.x) * ep.dbg_iters + (size_t)min(dbg_it, ep.dbg_iters - 1)] = units;
+        }
       }
       STAMP_T(8, kWave);
     }
+    // the barrier's own wait, spelled out: LDS only.  (With the second form of the stream the compiler otherwise leaves an empty
+    // s_waitcnt here; this one it keeps as it is.  It is the wait a barrier after LDS writes needs in any case.)
+    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
     __syncthreads();
     STAMP(2);
     // ---- phase B: both waves build the rows of `iter`; wave 0 finishes the look-ahead refill and writes the scalars ----
@@ -2020,8 +2106,9 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     const uint32_t* rows = (ep.n_iter & 1) ? s_obs : s_obs1;
     uint32_t* prev = (ep.n_iter & 1) ? s_obs1 : s_obs;
     const bool dbg_lines = ep.dbg && ep.dbg_iters > 0;
+    unsigned units = 0;
     unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || ep.n_iter == 1, s_legal, s_own, g0, ng, P, H, tid, ep.nthreads, dbg_lines,
-                                        false);
+                                        0, units);
     if (dbg_lines) {
       stored = wave_sum(stored);
       if (lane == 0) env_stamp(ep, dbg_it, 14 + wave, stored);
@@ -2236,6 +2323,8 @@ struct hsad_env {
   // launches, so reset / step / fork or a caller writing into priv_s cannot make anything stale.
   int rollout_delta;              // hsad_env_set_rollout_delta; HSAD_ENV_DELTA=0 at creation: every stream in full, for A/B
   int rollout_compact;            // hsad_env_set_rollout_compact; HSAD_ENV_COMPACT=0 at creation: the direct form of the delta stream
+  int rollout_unit;               // hsad_env_set_rollout_unit; HSAD_ENV_UNIT=128|64 at creation: bytes of priv_s the compacted form
+                                  // decides "changed" by (a line or a half line)
   bool delta_fits;                // the second copy of the rows costs the pipelined kernel no resident workgroup per CU
   size_t lds_bytes_delta;         // lds_bytes_reset + the second copy
   unsigned long long* d_pace;     // the progress word (allocated with the env, zero)
@@ -2364,7 +2453,7 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
   size_t lds = (mode == 1 || mode == 2) ? e->lds_bytes : e->lds_bytes_reset;
   EnvParams ep = e->ep;
   ep.delta = mode == 3 && n_iter > 1 && rollout_delta_active(e) ? 1 : 0;
-  ep.compact = ep.delta && e->rollout_compact ? 1 : 0;
+  ep.compact = ep.delta && e->rollout_compact ? (e->rollout_unit == 64 ? 2 : 1) : 0;
   if (ep.delta) lds = e->lds_bytes_delta;
   ep.phase = part >= 0 ? e->d_phase : nullptr;
   ep.part = part < 0 ? 0 : part;
@@ -2532,6 +2621,7 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->rollout_pace = getenv("HSAD_ENV_PACE") ? atoi(getenv("HSAD_ENV_PACE")) != 0 : 1;
   e->rollout_delta = getenv("HSAD_ENV_DELTA") ? atoi(getenv("HSAD_ENV_DELTA")) != 0 : 1;
   e->rollout_compact = getenv("HSAD_ENV_COMPACT") ? atoi(getenv("HSAD_ENV_COMPACT")) != 0 : 1;
+  e->rollout_unit = getenv("HSAD_ENV_UNIT") && atoi(getenv("HSAD_ENV_UNIT")) == 128 ? 128 : 64;
   e->delta_fits = false;
   e->d_pace = nullptr;
   e->pace_base = 0;
@@ -2842,6 +2932,14 @@ int hsad_env_set_rollout_compact(hsad_env* e, int on) {
 
 int hsad_env_rollout_compact_active(const hsad_env* e) { return e && e->rollout_compact && rollout_delta_active(e) ? 1 : 0; }
 
+int hsad_env_set_rollout_unit(hsad_env* e, int bytes) {
+  if (!e || (bytes != 128 && bytes != 64)) return set_error(HSAD_ERR_INVALID, "the rollout unit is 128 or 64 bytes");
+  e->rollout_unit = bytes;
+  return HSAD_OK;
+}
+
+int hsad_env_rollout_unit(const hsad_env* e) { return e ? (hsad_env_rollout_compact_active(e) ? e->rollout_unit : 128) : 0; }
+
 int hsad_env_debug_pace_bias(hsad_env* e, int64_t bias) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");
   e->pace_bias = (long long)bias;
@@ -2906,6 +3004,13 @@ int hsad_env_debug_trace(hsad_env* e, uint64_t* buf, int n_iters) {
   if (!e || (buf && n_iters < 1)) return set_error(HSAD_ERR_INVALID, "bad argument");
   e->ep.dbg = reinterpret_cast<unsigned long long*>(buf);
   e->ep.dbg_iters = buf ? n_iters : 0;
+  return HSAD_OK;
+}
+
+int hsad_env_debug_units(hsad_env* e, uint64_t* buf) {
+  if (!e) return set_error(HSAD_ERR_INVALID, "null env");
+  e->ep.dbg_units_lo = (unsigned)(reinterpret_cast<uint64_t>(buf) & 0xffffffffull);
+  e->ep.dbg_units_hi = (unsigned)(reinterpret_cast<uint64_t>(buf) >> 32);
   return HSAD_OK;
 }
 

@@ -204,6 +204,16 @@ class BatchedHanabiEnv:
         """whether persistent launches use the compacted form of the delta stream as the env stands"""
         return bool(self.lib.hsad_env_rollout_compact_active(self.h))
 
+    def set_rollout_unit(self, nbytes):
+        """compacted delta stream: decide "changed" by whole lines (128) or by half lines (64, the default); results are
+        identical, see include/hsad.h"""
+        _lib.check(self.lib.hsad_env_set_rollout_unit(self.h, int(nbytes)))
+
+    def rollout_unit(self):
+        """the unit (bytes) persistent launches decide "changed" by as the env stands: 128 wherever the compacted form is not
+        active"""
+        return int(self.lib.hsad_env_rollout_unit(self.h))
+
     def debug_pace_bias(self, bias):
         """test seam: offset of the counter base the paced kernels are told"""
         _lib.check(self.lib.hsad_env_debug_pace_bias(self.h, int(bias)))

@@ -182,6 +182,14 @@ int hsad_env_rollout_delta_active(const hsad_env* env);
  * are bit-identical.  hsad_env_rollout_compact_active: true only where hsad_env_rollout_delta_active is. */
 int hsad_env_set_rollout_compact(hsad_env* env, int on);
 int hsad_env_rollout_compact_active(const hsad_env* env);
+/* Unit of the compacted form: the bytes of priv_s it decides "changed" by.  128 is a whole line (one 32-bit word of the bit rows),
+ * 64 a half line (16 bits), which is one native write request of the L2: a line whose change sits in one half then costs half the
+ * bytes (-20 % of the bytes written at configs[1]).  Results are bit-identical either way, and units may change between launches.
+ * HSAD_ENV_UNIT=128|64 when the env is created, or bytes here; the default is 64 (2-3 % faster at the median with the pacing on,
+ * 4 % without; DESIGN.md 3a has the runs).  hsad_env_rollout_unit: the unit persistent launches use as the env stands, 128
+ * wherever hsad_env_rollout_compact_active is false (the direct form and the epilogue stream always go by lines). */
+int hsad_env_set_rollout_unit(hsad_env* env, int bytes);
+int hsad_env_rollout_unit(const hsad_env* env);
 /* Test seams of the pacing.  bias is added to the counter base every later persistent launch is told (not to the host's own
  * record), so that every workgroup's lead reads bias / workgroups iterations too high: all far ahead (bias > 0) or far behind (bias < 0); 0
  * restores the truth.  A lead no launch could produce (beyond its iteration count) switches the delay off.
@@ -227,6 +235,12 @@ int hsad_env_debug_timing(hsad_env* env, uint64_t* buf);
  * wall_clock64 stamps (100 MHz) of every iteration plus each workgroup's HW_ID / XCC_ID; slot map in csrc/hsad_env.hip (env_stamp).
  * buf == NULL switches the trace (and hsad_env_debug_timing) off. */
 int hsad_env_debug_trace(hsad_env* env, uint64_t* buf, int n_iters);
+/* Developer aid, with hsad_env_debug_trace: buf (device uint64 [Gpad / games_per_workgroup, n_iters], the trace's n_iters) receives
+ * the number of units of priv_s the stream wave stored for the rows of each iteration's predecessor, counted in the unit that stream
+ * decided by: half lines where hsad_env_rollout_unit is 64 (the first stream of a launch, which stores everything, and the direct
+ * form count lines).  Slot 13 of the trace keeps counting 128-byte lines with any change.  Written only while the trace is on;
+ * buf == NULL switches it off. */
+int hsad_env_debug_units(hsad_env* env, uint64_t* buf);
 /* Dynamic LDS bytes per workgroup of the reset / rollout kernels (what a persistent rollout launch requests: with the second copy
  * of the observation rows while hsad_env_rollout_delta_active). */
 int64_t hsad_env_rollout_lds_bytes(const hsad_env* env);

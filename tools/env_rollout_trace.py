@@ -1,7 +1,7 @@
 """Per-iteration trace of one persistent rollout launch at configs[1] (65,536 two-player games): where each workgroup's time goes,
 and how many workgroups stream observations on each CU and on the chip over time.
 
-  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--delta on|off] [--compact on|off] [--json OUT]
+  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--delta on|off] [--compact on|off] [--unit 128|64] [--json OUT]
 
 The driver's shape is --warmup 5 --iters 20 (one 5-iteration launch, then the traced 20-iteration launch).  --schedule single runs
 env_rollout_kernel (HSAD_ENV_PIPE=0), pipe the default env_rollout_pipe_kernel.  Stamps are wall_clock64 (100 MHz, 10 ns) of
@@ -14,7 +14,9 @@ position of its rows in the output buffers); per grouping the spread between the
 groups (`share_of_variance_between_groups` is the usual eta squared).  --pace off traces the unpaced launch (HSAD_ENV_PACE=0); with
 pacing on, `pace` says how many iterations delayed their stream and by how much (--l0-q8 / --cap-us: the developer switches
 HSAD_ENV_PACE_L0_Q8 / HSAD_ENV_PACE_CAP_US).  --delta off traces the full observation stream (HSAD_ENV_DELTA=0),
---compact off the direct form of the delta stream (HSAD_ENV_COMPACT=0).
+--compact off the direct form of the delta stream (HSAD_ENV_COMPACT=0), --unit the bytes the compacted form decides "changed" by
+(HSAD_ENV_UNIT; default: the library's).  `stored` gives what the stream wave stored per workgroup-iteration: 128-byte lines with any
+change (slot 13) and, where the library has hsad_env_debug_units, the units themselves and their bytes.
 
 `reset_iterations` splits the logic wave's time in the workgroup-iterations whose lane 0 restarted its game (the only ones that carry
 the reset stamps 6 / 7): the wait for the mt19937 window, the deal, and the rest (eps, colour shuffle, policy and step)."""
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--pace", choices=("on", "off"), default="on")
     ap.add_argument("--delta", choices=("on", "off"), default="on")
     ap.add_argument("--compact", choices=("on", "off"), default="on")
+    ap.add_argument("--unit", type=int, choices=(128, 64), default=None)
     ap.add_argument("--l0-q8", type=int, default=None)
     ap.add_argument("--cap-us", type=int, default=None)
     ap.add_argument("--json", default=None)
@@ -47,6 +50,8 @@ def main():
     os.environ["HSAD_ENV_PACE"] = "1" if args.pace == "on" else "0"
     os.environ["HSAD_ENV_DELTA"] = "1" if args.delta == "on" else "0"
     os.environ["HSAD_ENV_COMPACT"] = "1" if args.compact == "on" else "0"
+    if args.unit is not None:
+        os.environ["HSAD_ENV_UNIT"] = str(args.unit)
     if args.l0_q8 is not None:
         os.environ["HSAD_ENV_PACE_L0_Q8"] = str(args.l0_q8)
     if args.cap_us is not None:
@@ -61,14 +66,29 @@ def main():
     nwg = (G + env.games_per_workgroup - 1) // env.games_per_workgroup
     env.rollout_random(args.warmup, 12345)
     buf = torch.zeros(nwg * args.iters * 16, dtype=torch.int64, device="cuda:0")
+    has_units = hasattr(env.lib, "hsad_env_debug_units")
+    ubuf = torch.zeros(nwg * args.iters, dtype=torch.int64, device="cuda:0") if has_units else None
     torch.cuda.synchronize()
     _lib.check(env.lib.hsad_env_debug_trace(env.h, buf.data_ptr(), args.iters))
+    if has_units:
+        _lib.check(env.lib.hsad_env_debug_units(env.h, ubuf.data_ptr()))
     env.rollout_random(args.iters, 12345)
     torch.cuda.synchronize()
+    if has_units:
+        _lib.check(env.lib.hsad_env_debug_units(env.h, None))
     _lib.check(env.lib.hsad_env_debug_trace(env.h, None, 0))
     env.check_errors()
     s = buf.view(nwg, args.iters, 16).cpu().numpy().astype(np.int64)
     rec = analyse(s, args.schedule == "pipe", args)
+    if args.schedule == "pipe" and args.iters > 2:
+        lines = s[:, 2:, 13]                                         # records 2..: the delta streams (record 1 stores everything)
+        rec["stored"] = {"lines_with_any_change_mean": round(float(lines.mean()), 1)}
+        if has_units:
+            unit = env.rollout_unit()
+            u = ubuf.view(nwg, args.iters).cpu().numpy()[:, 2:]
+            rec["stored"].update(unit_bytes=unit, units_mean=round(float(u.mean()), 1),
+                                 priv_s_bytes_per_iteration=int(round(float(u.sum(axis=0).mean()) * unit)))
+            rec["rollout_unit"] = unit
     rec["delta_stream_active"] = bool(env.rollout_delta_active())
     rec["compact_stream_active"] = bool(env.rollout_compact_active())
     rec["pace"] = dict(rec.get("pace", {}), on=args.pace == "on", cap_us=env.rollout_pace_cap_us(),

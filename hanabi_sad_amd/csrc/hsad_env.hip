@@ -31,6 +31,7 @@
 
 #include "hsad.h"
 #include "hsad_deal_fast.h"
+#include "hsad_obs_row.h"
 #include "hsad_planes.h"
 
 namespace {
@@ -991,7 +992,9 @@ __device__ __forceinline__ uint64_t legal_mask_of(int P, int H, int A, const uin
 
 // Build the observation / legal-move / own-hand bit rows of this lane's game for every observer
 // (HanabiEnv::computeFeatureAndLegalMove, cpp/hanabi_env.cc:115-205, on top of the canonical encoder).
-template <int TP, int TH, bool V = false>
+// FIXED (env_rollout_pipe_kernel, TP > 0, full rules): the observation row is assembled in registers at its compile-time bit positions
+// and placed with one shifted write (hsad_obs_row.h) instead of field by field; the same bits.
+template <int TP, int TH, bool V = false, bool FIXED = false>
 __device__ __forceinline__ void build_rows(const EnvParams& ep, const uint32_t* s_st, int lane, int g, uint32_t* s_obs,
                                            uint32_t* s_legal, uint32_t* s_own, uint32_t greedy_rec, int p_begin,
                                            int p_step, uint32_t* s_lmask = nullptr) {
@@ -1009,62 +1012,79 @@ __device__ __forceinline__ void build_rows(const EnvParams& ep, const uint32_t* 
   for (int p = p_begin; p < P; p += p_step) {
     const uint32_t base = (uint32_t)(lane * P + p) * F;
     const uint32_t pm = ep.shuffle_color ? (ST(PLPERM(p)) & 0x7fffu) : kIdentityPerm;
-    uint32_t miss = 0;
+    if constexpr (FIXED) {
+      static_assert(TP > 0 && TH > 0 && !V, "fixed bit positions need a fixed game shape and the full rules");
+      uint32_t hand[TP], kcp[TP], krp[TP], kh[TP];
 #pragma unroll
-    for (int o = 0; o < (TP ? TP : 5); ++o) {
-      if (o >= P) break;
-      int q = p + o;
-      if (q >= P) q -= P;
-      const uint32_t hw = ST(PLH(q));
-      const int len = (hw >> 25) & 7;
-      if (len < H) miss |= 1u << o;
-      const uint32_t kcp = ST(PLKCP(q)), krp = ST(PLKRP(q)), kh = ST(PLKH(q));
+      for (int o = 0; o < TP; ++o) {
+        int q = p + o;
+        if (q >= P) q -= P;
+        hand[o] = ST(PLH(q));
+        kcp[o] = ST(PLKCP(q));
+        krp[o] = ST(PLKRP(q));
+        kh[o] = ST(PLKH(q));
+      }
+      uint32_t row[ObsRowGeom<TP, TH>::NW];
+      obs_row_assemble<TP, TH>(row, board, misc, disc, lastmv, greedy_rec, hand, kcp, krp, kh, p, pm, ep.sad != 0);
+      obs_row_place<TP, TH>(row, base, ep.sad != 0, [s_obs](uint32_t w, uint32_t v) { atomicOr(&s_obs[w], v); });
+    } else {
+      uint32_t miss = 0;
 #pragma unroll
-      for (int i = 0; i < (TH ? TH : 5); ++i) {
-        if (i < len) {
-          if (o > 0) {
-            const int card = (hw >> (5 * i)) & 31;
-            const int c = (card * 13) >> 6, r = card - 5 * c;
-            or_bit(s_obs, base + (uint32_t)((o * H + i) * ru.CR) + perm_c(pm, c) * RR + (uint32_t)r);
+      for (int o = 0; o < (TP ? TP : 5); ++o) {
+        if (o >= P) break;
+        int q = p + o;
+        if (q >= P) q -= P;
+        const uint32_t hw = ST(PLH(q));
+        const int len = (hw >> 25) & 7;
+        if (len < H) miss |= 1u << o;
+        const uint32_t kcp = ST(PLKCP(q)), krp = ST(PLKRP(q)), kh = ST(PLKH(q));
+#pragma unroll
+        for (int i = 0; i < (TH ? TH : 5); ++i) {
+          if (i < len) {
+            if (o > 0) {
+              const int card = (hw >> (5 * i)) & 31;
+              const int c = (card * 13) >> 6, r = card - 5 * c;
+              or_bit(s_obs, base + (uint32_t)((o * H + i) * ru.CR) + perm_c(pm, c) * RR + (uint32_t)r);
+            }
+            const uint32_t cp = (kcp >> (5 * i)) & 31u, rp = (krp >> (5 * i)) & 31u;
+            const uint32_t h6 = (kh >> (6 * i)) & 63u;
+            uint64_t m = 0;
+#pragma unroll
+            for (int c = 0; c < 5; ++c) m |= ((cp >> c) & 1u) ? ((uint64_t)rp << (perm_c(pm, c) * RR)) : 0ull;
+            if (h6 & 7u) m |= 1ull << (CR + perm_c(pm, (int)(h6 & 7u) - 1));
+            if (h6 >> 3) m |= 1ull << (CR + (uint32_t)ru.C + (h6 >> 3) - 1u);
+            or_bits64(s_obs, base + (uint32_t)ep.OK + (uint32_t)((o * H + i) * ru.KS), m);
           }
-          const uint32_t cp = (kcp >> (5 * i)) & 31u, rp = (krp >> (5 * i)) & 31u;
-          const uint32_t h6 = (kh >> (6 * i)) & 63u;
-          uint64_t m = 0;
-#pragma unroll
-          for (int c = 0; c < 5; ++c) m |= ((cp >> c) & 1u) ? ((uint64_t)rp << (perm_c(pm, c) * RR)) : 0ull;
-          if (h6 & 7u) m |= 1ull << (CR + perm_c(pm, (int)(h6 & 7u) - 1));
-          if (h6 >> 3) m |= 1ull << (CR + (uint32_t)ru.C + (h6 >> 3) - 1u);
-          or_bits64(s_obs, base + (uint32_t)ep.OK + (uint32_t)((o * H + i) * ru.KS), m);
         }
       }
-    }
-    or_bits32(s_obs, base + (uint32_t)(P * H * ru.CR), miss);
-    // board: deck thermometer | fireworks one-hot | info thermometer | life thermometer
-    or_bits64(s_obs, base + (uint32_t)ep.OB, (1ull << deck_size) - 1ull);
-    uint64_t bm = 0;
+      or_bits32(s_obs, base + (uint32_t)(P * H * ru.CR), miss);
+      // board: deck thermometer | fireworks one-hot | info thermometer | life thermometer
+      or_bits64(s_obs, base + (uint32_t)ep.OB, (1ull << deck_size) - 1ull);
+      uint64_t bm = 0;
 #pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      const int f = board_fw(board, c);
-      bm |= (f > 0) ? (1ull << (perm_c(pm, c) * RR + (uint32_t)f - 1u)) : 0ull;
-    }
-    bm |= (uint64_t)((1u << info) - 1u) << CR;
-    bm |= (uint64_t)((1u << life) - 1u) << (CR + (uint32_t)ru.MI);
-    or_bits64(s_obs, base + (uint32_t)(ep.OB + ep.DECKW), bm);
-    // discards: thermometers of width 3,2,2,2,1 per colour (a variant's R ranks: 3, 2 ... 2, 1; R = 1: 3)
-    uint64_t dm = 0;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      const uint32_t pc = perm_c(pm, c);
-#pragma unroll
-      for (int r = 0; r < 5; ++r) {
-        const uint32_t n = cnt2(disc, c * 5 + r);
-        const uint32_t roff = (r == 0) ? 0u : (1u + 2u * (uint32_t)r);
-        dm |= (uint64_t)((1u << n) - 1u) << (pc * (uint32_t)ru.DW + roff);
+      for (int c = 0; c < 5; ++c) {
+        const int f = board_fw(board, c);
+        bm |= (f > 0) ? (1ull << (perm_c(pm, c) * RR + (uint32_t)f - 1u)) : 0ull;
       }
+      bm |= (uint64_t)((1u << info) - 1u) << CR;
+      bm |= (uint64_t)((1u << life) - 1u) << (CR + (uint32_t)ru.MI);
+      or_bits64(s_obs, base + (uint32_t)(ep.OB + ep.DECKW), bm);
+      // discards: thermometers of width 3,2,2,2,1 per colour (a variant's R ranks: 3, 2 ... 2, 1; R = 1: 3)
+      uint64_t dm = 0;
+#pragma unroll
+      for (int c = 0; c < 5; ++c) {
+        const uint32_t pc = perm_c(pm, c);
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+          const uint32_t n = cnt2(disc, c * 5 + r);
+          const uint32_t roff = (r == 0) ? 0u : (1u + 2u * (uint32_t)r);
+          dm |= (uint64_t)((1u << n) - 1u) << (pc * (uint32_t)ru.DW + roff);
+        }
+      }
+      or_bits64(s_obs, base + (uint32_t)ep.OD, dm);
+      or_bits64(s_obs, base + (uint32_t)ep.OL, encode_last_action(P, H, lastmv, p, pm, ru));
+      if (ep.sad) or_bits64(s_obs, base + (uint32_t)ep.F0, encode_last_action(P, H, greedy_rec, p, pm, ru));
     }
-    or_bits64(s_obs, base + (uint32_t)ep.OD, dm);
-    or_bits64(s_obs, base + (uint32_t)ep.OL, encode_last_action(P, H, lastmv, p, pm, ru));
-    if (ep.sad) or_bits64(s_obs, base + (uint32_t)ep.F0, encode_last_action(P, H, greedy_rec, p, pm, ru));
 
     const uint64_t lm = legal_mask_of<TH>(P, H, ep.A, s_st, lane, p, pm, ru);
     or_bits64(s_legal, (uint32_t)(lane * P + p) * (uint32_t)ep.A, lm);
@@ -1935,6 +1955,17 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
 // CU happen to be out of phase.  The state planes stay in LDS for the whole launch (loaded once, written back after the last
 // iteration: nothing else reads them while the launch runs).  Same arithmetic, draw order and values as env_rollout_kernel: only
 // which wave writes the rows, and when, differs.
+// Which instances of env_rollout_pipe_kernel build their observation rows in registers (build_rows<.., FIXED>, hsad_obs_row.h):
+// the fixed game shapes.  The generic instance has no compile-time offsets.  -DHSAD_ENV_ROWBUILD_SCATTER: none, for an A/B of the
+// two builds within one tree.
+#ifdef HSAD_ENV_ROWBUILD_SCATTER
+template <int TP, int TH>
+constexpr bool kRowBuildFixed = false;
+#else
+template <int TP, int TH>
+constexpr bool kRowBuildFixed = TP > 0 && TH > 0;
+#endif
+
 __device__ __forceinline__ unsigned wave_sum(unsigned v) {
   for (int o = kWave / 2; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, kWave);
   return v;
@@ -1942,6 +1973,12 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v) {
 
 template <int TP, int TH>
 __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void env_rollout_pipe_kernel(EnvParams ep) {
+  // The kernel is scheduled for two waves per SIMD (waves_per_eu(2, 2): four 128-thread workgroups per CU, which the LDS sizes,
+  // delta_fits and the pacing assume), but the runtime places workgroups by the registers a kernel uses, not by that attribute.
+  // With the rows built in registers the fixed instances use fewer than 171 VGPRs, the number from which a SIMD holds two waves
+  // and not three; naming v175 keeps the allocation, and with it the residency and what configure_env_kernels decides from it,
+  // where they were.  No instruction.
+  if constexpr (kRowBuildFixed<TP, TH>) asm volatile("" ::: "v175");
   rollout_stagger(ep);
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* s_st = smem;
@@ -2074,7 +2111,9 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     // ---- phase B: both waves build the rows of `iter`; wave 0 finishes the look-ahead refill and writes the scalars ----
     Refill rf;
     refill_issue(rf, rng, valid && wave == 0);
-    if (valid) build_rows<TP, TH>(ep, s_st, lane, g, (iter & 1) ? S_OBS1(zero) : s_obs, s_legal, s_own, s_grec[lane], wave, 2, s_win);
+    if (valid)
+      build_rows<TP, TH, false, kRowBuildFixed<TP, TH>>(ep, s_st, lane, g, (iter & 1) ? S_OBS1(zero) : s_obs, s_legal, s_own, s_grec[lane],
+                                                        wave, 2, s_win);
     STAMP(3);
     if (valid && wave == 0) {
       refill_finish(rf, rng);
@@ -2318,7 +2357,7 @@ struct hsad_env {
                       // single-phase schedule of env_rollout_kernel everywhere, for A/B)
   // pacing of persistent launches (pace_delay).  Only paced launches touch the word, and each adds exactly pace_blocks x n_iter
   // to it, so the host knows its value at the start of the next one without a memset: *d_pace == pace_base between launches
-  int rollout_pace;               // hsad_env_set_rollout_pace; HSAD_ENV_PACE=0 at creation
+  int rollout_pace;               // hsad_env_set_rollout_pace, HSAD_ENV_PACE at creation: 1 / 0; -1 neither (rollout_paced decides)
   // delta stream of the pipelined launches (EnvParams::delta).  Scope: one launch.  Nothing about priv_s is remembered between
   // launches, so reset / step / fork or a caller writing into priv_s cannot make anything stale.
   int rollout_delta;              // hsad_env_set_rollout_delta; HSAD_ENV_DELTA=0 at creation: every stream in full, for A/B
@@ -2409,6 +2448,15 @@ bool rollout_delta_active(const hsad_env* e) {
   return e->rollout_delta && e->delta_fits && rollout_pipelined(e) && e->ep.obs_f32;
 }
 
+// Pacing is on unless switched off, except where the pipelined kernel runs the compacted delta stream: pacing was made for a
+// write-bound iteration, in which a workgroup ahead of the mean only adds to the queue in front of HBM.  With the compacted
+// stream the iteration is the chain stream -> build -> stream of a workgroup's own waves, and the sleep sits inside it
+// (measured unpaced: -2.4 % at unit 128, -3.9 % at unit 64, profiles/r15_env_subline_ab.json; profiles/r16_env_rowbuild_ab.json).
+bool rollout_paced(const hsad_env* e) {
+  if (e->rollout_pace >= 0) return e->rollout_pace != 0;
+  return !(e->rollout_compact && rollout_delta_active(e));
+}
+
 EnvRolloutFn pick_rollout_kernel(int P, int H, bool pipe, bool variant) {
   if (variant) return env_rollout_kernel<0, 0, true>;
 #define HSAD_ROLLOUT_SPECIALISE(PP, HH) \
@@ -2471,7 +2519,7 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
   ep.a_out = a_out;
   ep.g_out = g_out;
   ep.pace = nullptr;
-  if (mode == 3 && n_iter > 1 && e->rollout_pace) {
+  if (mode == 3 && n_iter > 1 && rollout_paced(e)) {
     // workgroups with games: the padded game count may add an empty one (32-game workgroups), which returns at once
     const int g_end = std::min(ep.G, g_begin + g_count);
     const long long blocks = g_end > g_begin ? (g_end - g_begin + ep.gpw - 1) / ep.gpw : 0;
@@ -2618,7 +2666,7 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->n_part_active = 1;
   e->rollout_chunk = 0;
   e->rollout_pipe = getenv("HSAD_ENV_PIPE") ? atoi(getenv("HSAD_ENV_PIPE")) != 0 : 1;
-  e->rollout_pace = getenv("HSAD_ENV_PACE") ? atoi(getenv("HSAD_ENV_PACE")) != 0 : 1;
+  e->rollout_pace = getenv("HSAD_ENV_PACE") ? atoi(getenv("HSAD_ENV_PACE")) != 0 : -1;
   e->rollout_delta = getenv("HSAD_ENV_DELTA") ? atoi(getenv("HSAD_ENV_DELTA")) != 0 : 1;
   e->rollout_compact = getenv("HSAD_ENV_COMPACT") ? atoi(getenv("HSAD_ENV_COMPACT")) != 0 : 1;
   e->rollout_unit = getenv("HSAD_ENV_UNIT") && atoi(getenv("HSAD_ENV_UNIT")) == 128 ? 128 : 64;

@@ -179,8 +179,8 @@ class BatchedHanabiEnv:
         _lib.check(self.lib.hsad_env_set_rollout_chunk(self.h, int(iterations_per_launch)))
 
     def set_rollout_pace(self, on):
-        """persistent rollout: workgroups ahead of the launch's mean progress delay their observation stream (default on;
-        timing only, see include/hsad.h)"""
+        """persistent rollout: workgroups ahead of the launch's mean progress delay their observation stream (default: on,
+        except where the compacted delta stream runs; timing only, see include/hsad.h)"""
         _lib.check(self.lib.hsad_env_set_rollout_pace(self.h, int(bool(on))))
 
     def rollout_pace_cap_us(self):

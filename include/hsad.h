@@ -159,7 +159,9 @@ int hsad_env_set_partitions(hsad_env* env, int n_part);
  * that the workgroups of a CU stream their observations at different times.  Takes precedence over partitions; 0 (the
  * default) = one launch per iteration and partition.  Results are bit-identical either way. */
 int hsad_env_set_rollout_chunk(hsad_env* env, int iterations_per_launch);
-/* Pacing of persistent launches (on by default; HSAD_ENV_PACE=0 when the env is created, or on = 0 here, turns it off).  The
+/* Pacing of persistent launches.  Default: on, except where the pipelined launches run the compacted delta stream
+ * (hsad_env_rollout_compact_active), whose iteration is no longer write-bound and only loses the delay.  HSAD_ENV_PACE=0 / 1 when
+ * the env is created, or a call here, decides for every kind of launch.  The
  * workgroups of a launch run at persistently different rates and the launch ends on the slowest.  Every workgroup counts its
  * iteration starts on one device word of the env; one that is ahead of the mean by more than a dead band delays its next
  * observation stream by (lead - dead band) x its own iteration time, at most hsad_env_rollout_pace_cap_us(), and so leaves HBM

@@ -32,6 +32,12 @@ class EnvRules(C.Structure):
                 ("max_life_tokens", C.c_int32)]
 
 
+class GameFilter(C.Structure):
+    """hsad_game_filter (include/hsad.h): which finished games hsad_game_log_select keeps"""
+    _fields_ = [(k, C.c_int32) for k in ("score_min", "score_max", "max_lives", "moves_min", "moves_max", "end_mask", "seat_mask",
+                                          "flag_mask")]
+
+
 class Field(C.Structure):
     _fields_ = [("width", C.c_int32), ("dtype", C.c_int32)]
 
@@ -314,6 +320,16 @@ SIGNATURES = {
     "hsad_seat_scatter": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "hsad_seating_stats": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "hsad_seating_behaviour": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "hsad_game_log_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "hsad_game_log_destroy": (None, [_P]),
+    "hsad_game_log_clear": (C.c_int, [_P, _P]),
+    "hsad_game_log_capacity": (C.c_int, [_P]),
+    "hsad_game_record_bytes": (C.c_int64, [_P]),
+    "hsad_game_log_overflow_count": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "hsad_game_log_append": (C.c_int, [_P, _P, _P, _P, _P]),
+    "hsad_game_log_select": (C.c_int, [_P, _P, C.POINTER(GameFilter), _P, _P, _P, _P]),
+    "hsad_game_log_gather": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+    "hsad_env_playout_logged": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P]),
     "hsad_search_fork_state": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "hsad_search_actions": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "hsad_search_job_stats": (C.c_int, [_P, _P, C.c_int, _P, _P]),

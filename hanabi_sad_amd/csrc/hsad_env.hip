@@ -2381,6 +2381,13 @@ struct hsad_env {
   bool scripted;
   DealScript script;
   unsigned long long* d_sad;   // [Gpad * P] the SAD sections hsad_env_restore hands to the observe pass (hsad_env_position.inc); allocated on first use
+  // replay of game records (hsad_env_record.inc), allocated on first use: the records of the last call, the script rows and counts
+  // taken from them, and the action rows [2][Gpad * P] the replay steps on
+  uint8_t* d_records;
+  size_t d_records_cap;
+  uint8_t* d_log_script;
+  int32_t* d_log_count;
+  int64_t* d_log_a;
 };
 
 namespace {
@@ -2681,6 +2688,11 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->scripted = false;
   e->script = DealScript{nullptr, nullptr};
   e->d_sad = nullptr;
+  e->d_records = nullptr;
+  e->d_records_cap = 0;
+  e->d_log_script = nullptr;
+  e->d_log_count = nullptr;
+  e->d_log_a = nullptr;
   if (e->lds_bytes_reset > 160 * 1024) {
     const size_t need = e->lds_bytes_reset;
     delete e;
@@ -2735,6 +2747,10 @@ void hsad_env_destroy(hsad_env* e) {
   if (e->script.cards) (void)hipFree(e->script.cards);
   if (e->script.count) (void)hipFree(e->script.count);
   if (e->d_sad) (void)hipFree(e->d_sad);
+  if (e->d_records) (void)hipFree(e->d_records);
+  if (e->d_log_script) (void)hipFree(e->d_log_script);
+  if (e->d_log_count) (void)hipFree(e->d_log_count);
+  if (e->d_log_a) (void)hipFree(e->d_log_a);
   if (e->ep.planes) (void)hipFree(e->ep.planes);
   if (e->ep.mt) (void)hipFree(e->ep.mt);
   if (e->ep.deck_hist) (void)hipFree(e->ep.deck_hist);
@@ -3099,3 +3115,6 @@ int hsad_env_error_count(hsad_env* e, int32_t* count, int32_t* first_game, int32
 
 // rule-list bots as a policy: one call on the planes, and whole playouts in one launch
 #include "hsad_env_rulebot.inc"
+
+// game records: replay a logged game to any move in one launch
+#include "hsad_env_record.inc"

@@ -238,3 +238,6 @@ int hsad_seating_behaviour(const hsad_env* env, int games_per_seating, const int
 }
 
 }  // extern "C"
+
+// the device log of a tournament's games: append, select, gather (hsad_game_log_*)
+#include "hsad_game_log.inc"

@@ -358,6 +358,25 @@ class BatchedHanabiEnv:
         c = self._i32(count, self.G)
         _lib.check(self.lib.hsad_env_rewind_scripted(self.h, s.data_ptr(), c.data_ptr(), self._stream()))
 
+    def playout_logged(self, records, src_index, stop=None):
+        """game j becomes game record src_index[j] (int32 [G]; -1 = leave game j alone) played from its first deal up to move
+        min(stop[j], n_moves) (int32 [G]; None: to the end) in one launch, and its rows are rewritten (SAD section all-zero, reward
+        0).  records: uint8 [n, record_bytes] on the host (numpy or a CPU tensor; game_record.GameRecord.to_bytes rows).  The game
+        is rewound as rewind_scripted rewinds it, the record's deck its script.  Returns status int32 [G]: the moves played, or
+        HSAD_GR_STATUS_* (-1 left alone, -2 refused: bad deck or a game never started, -3 index out of range); a logged move that
+        is illegal stops its game there (check_errors() reports code 8).  See hsad_env_playout_logged."""
+        import numpy as np
+        rec = np.ascontiguousarray(records.numpy() if isinstance(records, torch.Tensor) else records, dtype=np.uint8)
+        rb = int(self.lib.hsad_game_record_bytes(self.h))
+        assert rec.ndim == 2 and rec.shape[1] == rb, "expected uint8 [n, %d] records, got %s" % (rb, tuple(rec.shape))
+        idx = self._i32(src_index, self.G)
+        st = self._i32(stop, self.G) if stop is not None else None
+        status = torch.zeros(self.G, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.hsad_env_playout_logged(self.h, rec.ctypes.data, int(rec.shape[0]), idx.data_ptr(),
+                                                    st.data_ptr() if st is not None else None, status.data_ptr(), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()   # `rec` is host memory the copy reads: keep it alive until it is done
+        return status
+
     def sad_section(self, out=None):
         """int64 [G, P]: the SAD greedy-action section of the current rows, one word per row (zeros with sad = 0); what a GameLog
         keeps of an observation.  See hsad_env_sad_section."""
@@ -507,5 +526,6 @@ class BatchedHanabiEnv:
             what = {1: "illegal move", 2: "illegal greedy move", 3: "step on a finished game",
                     4: "fork source index out of range", 5: "deal script names a card the deck does not hold",
                     6: "position refused (import_state / restore; see the call's status)",
-                    7: "policy_rule: a seat_bot entry names no bot"}.get(c.value, "?")
+                    7: "policy_rule: a seat_bot entry names no bot",
+                    8: "replay of a game record met an illegal logged move"}.get(c.value, "?")
             raise _lib.HsadError("%d game(s) violated the env contract; first: game %d, %s" % (n.value, g.value, what))

@@ -200,11 +200,12 @@ class SeatingScores:
     """what play_seatings returns: scores int64 [S, num_game]; totals int64 [S, 4] = (sum score, sum score^2, perfect, finished) as
     hsad_seating_stats reduced them on the device; mean / sem / perfect float64 [S] from those integers (sem = population std /
     sqrt(n), tools/eval_model.py:41-42); behaviour = a BehaviourStats [S, P, 13] when play_seatings(behaviour=True) counted, else
-    None"""
+    None; records = the game_record.GameRecord list of play_seatings(records=...), each tagged meta = {seating, deal_seed, seats (the
+    seat names), game (its deal's index in `scores`)}, else None"""
 
-    def __init__(self, scores, totals, seatings, behaviour=None):
+    def __init__(self, scores, totals, seatings, behaviour=None, records=None):
         import math
-        self.scores, self.totals, self.seatings, self.behaviour = scores, totals, seatings, behaviour
+        self.scores, self.totals, self.seatings, self.behaviour, self.records = scores, totals, seatings, behaviour, records
         n = scores.shape[1]
         self.num_game = n
         t = [[int(v) for v in row] for row in totals]
@@ -230,12 +231,17 @@ class _SeatedModel:
 class _TournamentBatch:
     """one env object of S x n games (seating-major) and the pool seated on it; play(seed) runs one chunk of n deals"""
 
-    def __init__(self, agents, seatings, n, env_kw, device, bot_seed=0, behaviour=False):
+    def __init__(self, agents, seatings, n, env_kw, device, bot_seed=0, behaviour=False, records=None):
         S, P = seatings.shape
         self.n, self.S = n, S
         self.behaviour = torch.zeros(S, P, len(BEHAVIOUR_NAMES), dtype=torch.int64, device=device) if behaviour else None
-        self.env = env = BatchedHanabiEnv(S * n, players=P, seed=0, eps_list=[0.0], max_len=-1, device=device, track_deck_history=False,
-                                          **env_kw)
+        # a record needs the deal: only a recording tournament's env tracks its deck history
+        self.env = env = BatchedHanabiEnv(S * n, players=P, seed=0, eps_list=[0.0], max_len=-1, device=device,
+                                          track_deck_history=records is not None, **env_kw)
+        self.recorder = self.where = self.records = None
+        if records is not None:
+            from .game_record import GameRecorder
+            self.recorder, self.where = GameRecorder(env), (None if records is True else records)
         self.lib, self.device = env.lib, env.device
         owned = seating_rows(seatings, n, len(agents))
         self.models = [_SeatedModel(ag, rows, env, self.device)
@@ -278,6 +284,8 @@ class _TournamentBatch:
         env.reset()
         if self.behaviour is not None:
             self.behaviour.zero_()
+        if self.recorder is not None:
+            self.recorder.clear()
         for m in self.models:
             m.hid = m.agent.get_h0(m.n)
         done = False
@@ -288,6 +296,8 @@ class _TournamentBatch:
                 env.policy_rule(self.bots, self.seat_bot, seed=self.bot_seed, key=self.deal + int(seed))
             if self.behaviour is not None:     # every seat's action is merged and the env not yet stepped: the moves about to be made
                 _lib.check(self.lib.hsad_seating_behaviour(env.h, self.n, env.a.data_ptr(), self.behaviour.data_ptr(), env._stream()))
+            if self.recorder is not None:      # the same moment: the log classifies the move on the position before it
+                self.recorder.append(env.a, env.greedy_a)
             env.step(env.a, env.greedy_a)
             _lib.check(self.lib.hsad_seating_stats(env.h, self.n, self.stats.data_ptr(), self.unfinished.data_ptr(), env._stream()))
             # the host looks at ONE word, and one step late: it never waits for the step it has just enqueued (the extra step
@@ -306,12 +316,17 @@ class _TournamentBatch:
         q = env.query().cpu().numpy().astype(np.int64)
         scores = q[:, 5].reshape(self.S, self.n)
         self.game_moves = q[:, 6].reshape(self.S, self.n)      # HSAD_Q_NUM_STEP: what the MOVES counters of a seating add up to
+        if self.recorder is not None:     # filtered on the device; only the kept games' bytes cross to the host
+            lost = self.recorder.overflow_count()
+            if lost:
+                raise _lib.HsadError("the game log overflowed %d time(s): a game ran past the capacity the rules allow" % lost)
+            self.records = self.recorder.collect(self.where)
         return scores, totals
 
 
 def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_launch=1 << 18, precision="bf16", device="cuda:0",
                   hand_size=5, shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3, max_steps=200,
-                  bot_seed=0, behaviour=False):
+                  bot_seed=0, behaviour=False, records=None, names=None):
     """Every seating of a model pool over the SAME deals, in one batched run -> SeatingScores.
 
     agents: the pool -- whatever `evaluate` accepts (weight dicts, kernel agents / nets, any object with act / get_h0 such as
@@ -326,7 +341,12 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
     larger jobs run in chunks of deals on the same object.
 
     behaviour=True also counts what kind of moves every seat of every seating makes (SeatingScores.behaviour, a BehaviourStats):
-    one hsad_seating_behaviour launch per step, between the last action merge and the env step.  The games are the same either way."""
+    one hsad_seating_behaviour launch per step, between the last action merge and the env step.  The games are the same either way.
+
+    records=True, or a game_record.GameFilter, also writes every game down on the device (one hsad_game_log_append launch per step
+    at that same point; the env then tracks its deck history) and returns the finished games the filter keeps as
+    SeatingScores.records, tagged with seating, deal seed and seat names (names: one per pool member; default a RuleBot's own name,
+    "model<k>" otherwise).  The games are the same either way."""
     try:
         shape = tuple(np.asarray(seatings).shape)
     except ValueError:                    # seatings of different widths
@@ -348,11 +368,17 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
     totals = np.zeros((S, 4), dtype=np.int64)
     counts = np.zeros((S, P, len(BEHAVIOUR_NAMES)), dtype=np.int64) if behaviour else None
     game_moves = np.zeros((S, num_game), dtype=np.int64) if behaviour else None
+    if records is False:
+        records = None
+    if names is None:
+        names = [getattr(x, "name", None) if isinstance(x, RuleBot) else None for x in models]
+        names = [n if n is not None else "model%d" % k for k, n in enumerate(names)]
+    kept = [] if records is not None else None
     batches = {}
     for start in range(0, num_game, per):
         n = min(per, num_game - start)
         if n not in batches:
-            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device, bot_seed, bool(behaviour))
+            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device, bot_seed, bool(behaviour), records)
             if (batches[n].env.F, batches[n].env.A) != (F, A):
                 raise _lib.HsadError("env_dims gives (%d, %d), the library (%d, %d)" % (F, A, batches[n].env.F, batches[n].env.A))
         sc, tt = batches[n].play(seed + start, max_steps)
@@ -361,18 +387,27 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
         if behaviour:
             counts += batches[n].behaviour.cpu().numpy()
             game_moves[:, start:start + n] = batches[n].game_moves
+        if kept is not None:
+            for rec in batches[n].records:
+                s, d = divmod(rec.meta.pop("game"), n)
+                rec.meta.update(seating=int(s), deal_seed=int(seed + start + d), game=int(start + d),
+                                seats=[str(names[k]) for k in seatings[s]])
+                kept.append(rec)
     for b in batches.values():
+        if b.recorder is not None:
+            b.recorder.close()
         b.env.close()
-    return SeatingScores(scores, totals, seatings, BehaviourStats(counts, game_moves) if behaviour else None)
+    return SeatingScores(scores, totals, seatings, BehaviourStats(counts, game_moves) if behaviour else None, kept)
 
 
 class CrossPlayScores:
     """cross_play's K x K view of SeatingScores: entry [i][j] = model i on seat 0 with model j on seat 1; row_mean[i] = the mean
     of row i with the diagonal included (the last column of models/op_raw_data.txt); behaviour = the BehaviourStats of
-    cross_play(behaviour=True) with counts [K, K, P, 13], else None"""
+    cross_play(behaviour=True) with counts [K, K, P, 13], else None; records = the GameRecord list of cross_play(records=...)
+    (meta["seating"] = i * K + j), else None"""
 
     def __init__(self, res, K):
-        self.seatings, self.num_game = res, res.num_game
+        self.seatings, self.num_game, self.records = res, res.num_game, res.records
         self.behaviour = None if res.behaviour is None else BehaviourStats(res.behaviour.counts.reshape((K, K) + res.behaviour.counts.shape[1:]),
                                                                          res.behaviour.game_moves.reshape(K, K, -1))
         self.scores = res.scores.reshape(K, K, -1)

@@ -10,6 +10,8 @@ layout.
   --paper sad --weight a.pthw b.pthw c.pthw --cross_play
   --paper op  --method sad --idx 0 3 --cross_play --bots cautious piers    the matrix with rule-bot partners (rulebot.PRESETS)
   ... --cross_play --bots piers --behaviour             the matrix, then per pairing and seat the behaviour counters and rates
+  ... --save_games g.jsonl --save_games_where "score<=10,flag=last_life,seat=1"    also write the games the filter keeps to a file
+                                                        (game_record; read it with python -m hanabi_sad_amd.game_record g.jsonl)
   --paper op  --method sad --idx 0 --search_worlds 8    M0 in self-play, blueprint only and blueprint + search over the same deals
   ... --search_worlds 32 --search_rounds 8,8,16         the same with the search in rounds (paired statistics, pruning)
 
@@ -41,6 +43,11 @@ def parse_args(argv=None):
                    help="--cross_play: rule-bot presets appended to the pool (hand-coded partners; rulebot.PRESETS)")
     p.add_argument("--behaviour", action="store_true", help="--cross_play: after the matrix, one line per (pairing, seat) with the "
                    "behaviour counters of the moves made there and their rates (eval.BehaviourStats; include/hsad.h, HSAD_BH_*)")
+    p.add_argument("--save_games", default=None, type=str, metavar="FILE", help="record the games on the device and write them to FILE "
+                   "as JSON lines (game_record.save): every finished game, or those --save_games_where keeps")
+    p.add_argument("--save_games_where", default=None, type=str, metavar="FILTER", help="with --save_games: comma-separated terms "
+                   "score / moves (<=, >=, =), lives<=K, end=lives|deck|perfect, flag=NAME, seat=P (game_record.GameFilter.parse), "
+                   "e.g. \"score<=10,flag=last_life,seat=1\"")
     p.add_argument("--root", default=None, type=str, help="folder that holds models/op/<method>/M{idx}.pthw (default: the repository)")
     p.add_argument("--precision", default="bf16", type=str, choices=["bf16", "fp32"])
     p.add_argument("--search_worlds", default=0, type=int, help="> 0 with a single --idx: also play with blueprint-policy search "
@@ -114,7 +121,18 @@ def main(argv=None):
     args = parse_args(argv)
     if args.behaviour and not args.cross_play:
         raise SystemExit("--behaviour needs --cross_play (the table has one line per pairing of the matrix and seat)")
+    if args.save_games_where and not args.save_games:
+        raise SystemExit("--save_games_where needs --save_games FILE")
+    where = None
+    if args.save_games:
+        from .game_record import GameFilter, save
+        try:
+            where = GameFilter.parse(args.save_games_where) if args.save_games_where else True
+        except ValueError as e:
+            raise SystemExit("--save_games_where: %s" % e)
     if args.search_worlds > 0:
+        if args.save_games:
+            raise SystemExit("--save_games records tournament games (no --search_worlds)")
         return search_report(args)
     agents, names, title, P = load_pool(args)
     net = agents[0].online
@@ -128,15 +146,25 @@ def main(argv=None):
             raise SystemExit("--cross_play is the two-player matrix")
         if args.behaviour:
             kw["behaviour"] = True
+        if where is not None:
+            kw.update(records=where, names=names)
         res = cross_play(agents, n, 1, 0, sad, **kw)
+        if where is not None:
+            save(args.save_games, res.records)
+            print("%d game(s) written to %s" % (len(res.records), args.save_games))
         print(format_cross_play_table("self-play & cross-play of %s" % title, names, res.mean, res.row_mean))
         if args.behaviour:
             print()
             print(format_behaviour_table(names, res.behaviour))
         return res
     seating = [0] * P if len(agents) == 1 else list(range(P))
+    if where is not None:
+        kw.update(records=where, names=names)
     res = play_seatings(agents, [seating], n, 1, 0, sad, **kw)
     print("score: %f +/- %f" % (res.mean[0], res.sem[0]), "; perfect: ", res.perfect[0])
+    if where is not None:
+        save(args.save_games, res.records)
+        print("%d game(s) written to %s" % (len(res.records), args.save_games))
     return res
 
 

@@ -255,7 +255,7 @@ int hsad_env_rollout_resident_workgroups(const hsad_env* env);
  * Codes: 1 illegal move, 2 illegal greedy move, 3 step on a finished game, 4 hsad_env_fork / hsad_env_restore source index out of
  * range, 5 a deal script names a card the deck does not hold (hsad_env_rewind_scripted), 6 hsad_env_import_state / hsad_env_restore
  * refused a position (the call's status word holds the HSAD_POS_* flags that say why), 7 a hsad_env_policy_rule seat_bot entry names
- * no bot. */
+ * no bot, 8 hsad_env_playout_logged met a logged move that is illegal where the record makes it. */
 int hsad_env_error_count(hsad_env* env, int32_t* count, int32_t* first_game, int32_t* first_code);
 
 /* ---- The env as a simulator for test-time search (determinised Monte Carlo, SPARTA-style single-agent search): branch a game,
@@ -1573,6 +1573,97 @@ int hsad_search_world_script(const hsad_env* world_env, const int32_t* src_index
 int hsad_search_replay_actions(const hsad_env* env, const int32_t* src_index, const int32_t* viewer, const int64_t* log_a_t,
                                const int64_t* log_greedy_t, int G_root, const int64_t* greedy_src, int64_t* a, int64_t* greedy_a,
                                int32_t* mismatch, void* stream);
+
+/* ---- Game records: which game, and show it to me.  A tournament's counters say how often; a record is one game written down --
+ * its rules, its deal, every move with its greedy alternative and a flag byte from the move classifier, and how it ended -- so that
+ * it can be filtered on the device, read on the host and replayed to any move in one launch.  The reference has no such call;
+ * nothing below changes what reset / step / rollout or the existing playouts compute.  csrc/hsad_game_record.h holds the layout.
+ *
+ * Capacity.  With D = max deck size - P * H: exactly D plays + discards are made while the deck holds a card (each deals one), at
+ * most max_information_tokens + D + colors hints (a hint spends a token; tokens come from the initial stock, from discards and
+ * from completed stacks), and the last round adds P turns: a game has at most
+ *     L = 2 * D + max_information_tokens + colors + P      (95 for the standard 2-player game)
+ * moves.  A log whose game is at move index >= L counts an overflow instead of writing.  L > 255 is refused (HSAD_ERR_INVALID: the
+ * env counts steps in 8 bits).
+ *
+ * The record, hsad_game_record_bytes(env) = 68 + 3 L bytes, every field one byte:
+ *    0 version (HSAD_GR_VERSION)   1 P   2 H   3 colors   4 ranks   5 max_information_tokens   6 max_life_tokens   7 bomb
+ *    8 n_moves   9 n_dealt   10 score (the latched last score of a finished game, the fireworks' sum of a running one, 0 after a
+ *    bomb)   11 lives   12 information tokens   13 how it ended (HSAD_GR_END_*)   14 L   15 0
+ *    16..67 the deck: card types (colour * 5 + rank) in deal order, 0 past n_dealt -- the deck-history row, the layout of a script
+ *    68.. move[L], greedy[L], flags[L], 0 past n_moves
+ * move / greedy: the uid (layout: hsad_seating_behaviour above) the mover played / would have played greedily, with a colour
+ * hint's colour as the cards' TRUE colour: with shuffle_color the actor's permutation is undone, as bh_classify undoes it.
+ * flags: HSAD_GR_* bits, read off the increments bh_classify gives for the move on the position before it:
+ *    COUNTED            MOVES != 0 (every other bit is 0 without it)
+ *    PLAY_FAIL          PLAY_FAIL
+ *    PLAY_UNCERTAIN     a play (PLAY_OK or PLAY_FAIL) without PLAY_CERTAIN
+ *    LAST_COPY_LOST     LAST_COPY_LOST
+ *    LAST_LIFE          LAST_LIFE
+ *    HINT_NOT_PLAYABLE  a hint (HINT_COLOUR or HINT_RANK) without HINT_PLAYABLE
+ *    DISCARD_UNCERTAIN  a DISCARD without DISCARD_CERTAIN_DEAD
+ *    NO_INFO            INFO_SUM == 0: made with no information token available
+ * Move k is made by seat k % P (seat 0 opens, every move passes the turn on). */
+#define HSAD_GR_VERSION 1
+enum {
+  HSAD_GR_COUNTED = 1, HSAD_GR_PLAY_FAIL = 2, HSAD_GR_PLAY_UNCERTAIN = 4, HSAD_GR_LAST_COPY_LOST = 8, HSAD_GR_LAST_LIFE = 16,
+  HSAD_GR_HINT_NOT_PLAYABLE = 32, HSAD_GR_DISCARD_UNCERTAIN = 64, HSAD_GR_NO_INFO = 128
+};
+/* how a game ended: no life left, the turns after the last card used up, every firework complete, max_len reached */
+enum { HSAD_GR_END_UNFINISHED = 0, HSAD_GR_END_LIVES = 1, HSAD_GR_END_DECK = 2, HSAD_GR_END_PERFECT = 3, HSAD_GR_END_MAX_LEN = 4 };
+/* negative status words of hsad_env_playout_logged */
+enum { HSAD_GR_STATUS_SKIPPED = -1, HSAD_GR_STATUS_REFUSED = -2, HSAD_GR_STATUS_BAD_INDEX = -3 };
+
+/* which finished games hsad_game_log_select keeps: score in [score_min, score_max], lives left <= max_lives, n_moves in
+ * [moves_min, moves_max], end_mask == 0 or bit (1 << HSAD_GR_END_*) of it set, and flag_mask == 0 or some move k whose seat k % P
+ * is in seat_mask (seat_mask == 0: every seat) carries a flag of flag_mask. */
+typedef struct hsad_game_filter {
+  int32_t score_min, score_max, max_lives, moves_min, moves_max, end_mask, seat_mask, flag_mask;
+} hsad_game_filter;
+
+typedef struct hsad_game_log hsad_game_log;
+
+/* A log for `env`'s games: three time-major byte planes [L, Gpad] (an append and the gather touch consecutive bytes across a
+ * wave), a move count per game and an overflow counter, all zero.  HSAD_ERR_STATE when the env does not track its deck history
+ * (the record needs the deal) or is not bound; HSAD_ERR_INVALID when L > 255.  The log keeps `env`'s sizes, not the env. */
+int hsad_game_log_create(const hsad_env* env, hsad_game_log** out);
+void hsad_game_log_destroy(hsad_game_log* log);
+int hsad_game_log_clear(hsad_game_log* log, void* stream);
+int hsad_game_log_capacity(const hsad_game_log* log);                 /* L */
+int64_t hsad_game_record_bytes(const hsad_env* env);                   /* 68 + 3 L; 0 for a null env */
+/* overflows counted since creation / the last clear; synchronises the device */
+int hsad_game_log_overflow_count(hsad_game_log* log, int32_t* count);
+/* Called where hsad_seating_behaviour is called: a / greedy_a device int64 [G, P] hold every seat's action, the env is not yet
+ * stepped.  One lane per game: for a live game (started, not terminated) with seat p on turn and 0 <= a[g, p] < A - 1 it writes
+ * move, greedy and flags at index HSAD_Q_NUM_STEP of game g and sets the game's move count to that index + 1.  Finished and
+ * never-started games, the noop and a uid outside [0, A) write nothing; a greedy uid outside [0, A - 1) is logged as the move.
+ * greedy_a may be NULL (greedy = move).  Launch-only. */
+int hsad_game_log_append(hsad_game_log* log, const hsad_env* env, const int64_t* a, const int64_t* greedy_a, void* stream);
+/* Stable stream compaction: index_out (device int32 [G]) receives, ascending, the games that are finished and pass `filter`
+ * (NULL: every finished game) and have take[g] != 0 (take device uint8 [G], or NULL); *n_out (device int32) their number.  Three
+ * launches (count, scan, write), no atomics: the same bits run to run.  Entries of index_out past n_out are not written. */
+int hsad_game_log_select(hsad_game_log* log, const hsad_env* env, const hsad_game_filter* filter, const uint8_t* take,
+                         int32_t* index_out, int32_t* n_out, void* stream);
+/* The records of games index[0 .. n) (device int32, each in [0, G); others give an all-zero record), contiguous in `out` (device
+ * uint8 [n, hsad_game_record_bytes]).  The result fields come from the env's planes, the deck from its deck history, the moves
+ * from the log: gather before the env is reset.  Only these bytes need to cross to the host. */
+int hsad_game_log_gather(hsad_game_log* log, const hsad_env* env, const int32_t* index, int n, uint8_t* out, void* stream);
+/* Replay: game j of a started env becomes record src_index[j] (device int32 [G]) played from its first deal up to move
+ * min(stop[j], n_moves) (stop device int32 [G], or NULL: to the end), in one launch.  -1 leaves game j alone (status
+ * HSAD_GR_STATUS_SKIPPED), any other index outside [0, n_rec) is logged as code 4 (HSAD_GR_STATUS_BAD_INDEX).  records: HOST
+ * memory, n_rec records of hsad_game_record_bytes(env) each; a record of another version, other rules (P, H, colors, ranks, token
+ * limits, bomb), another capacity, n_moves > L or n_dealt > 52 is refused with HSAD_ERR_INVALID before anything is launched.
+ * The game is first rewound as hsad_env_rewind_scripted rewinds it, with the record's deck as its script, and that call's rules
+ * hold: eps, colour permutations, generator and policy counter are kept, the env holds a deal script afterwards; a deck the rules
+ * cannot deal is code 5 and a game that was never started is left alone (both HSAD_GR_STATUS_REFUSED).  Then one wave per 64
+ * games plays the moves with the planes and the records' move planes staged in LDS, dealing from the script; no observation row
+ * is written during the replay.  A logged colour hint is mapped forward through the mover's colour permutation.  Before each move
+ * the mover's legal mask is consulted: an illegal logged move (or, with sad = 1, greedy move) stops that game at the position
+ * before it and is logged as code 8.  status[j] (device int32 [G]) = the number of moves played, which for a stopped game is the
+ * index of the refused move.  Afterwards the look-ahead, planes, `terminal` and legal masks are current as after a playout, and
+ * the observe pass runs as after hsad_env_import_state: rows current, SAD section all-zero, reward 0.  Launch-only. */
+int hsad_env_playout_logged(hsad_env* env, const uint8_t* records, int n_rec, const int32_t* src_index, const int32_t* stop,
+                            int32_t* status, void* stream);
 
 /* ---- one-sided intra-node transport (dist.py ReplayLink(transport = "ipc")): landing buffers exported by IPC handle and written by the
  * SENDER with a device-to-device copy -- SDMA over xGMI, no kernel resident on either GPU while a peer has not answered (a posted RCCL

@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "hsad.h"
+#include "hsad_gemm_plan.h"
 
 extern "C" int hsad_internal_set_error(int code, const char* msg);
 
@@ -224,7 +225,8 @@ static int g8_launch(int epi, G8Args& P, int n_cu, hipStream_t s) {
 static int gemm_launch(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const float* bias, float* C32,
                        int ldc, void* C16, int ldc16, int relu, int accumulate, int split_k, const void* relu_mask16,
                        int ldmask, const int32_t* row_map, size_t slab_stride, int* n_split_out, void* stream,
-                       const GemmPair* pair = nullptr) {
+                       const GemmPair* pair = nullptr, int range_ktiles = 0) {
+  // range_ktiles > 0 (with split_k > 1): the caller's own plan -- K ranges of that many k tiles instead of ceil(k tiles / split_k)
   if (!A || !B || (!C32 && !C16)) return nfail(HSAD_ERR_INVALID, "gemm: null operand");
   if (K % kBK || (lda % 8) || (ldb % 8)) return nfail(HSAD_ERR_INVALID, "gemm: K must be a multiple of 64 and lda/ldb of 8");
   if (((uintptr_t)A | (uintptr_t)B) & 15) return nfail(HSAD_ERR_INVALID, "gemm: operands must be 16-byte aligned");
@@ -245,9 +247,9 @@ static int gemm_launch(const void* A, int lda, const void* B, int ldb, int M, in
   const int np = g.npair;
   int gz = 1;
   if (split_k > 1) {
-    int chunk = ((K / kBK + split_k - 1) / split_k) * kBK;
-    g.k_chunk = chunk;
-    gz = (K + chunk - 1) / chunk;
+    const hsad_gemm_plan::KPlan kp = range_ktiles > 0 ? hsad_gemm_plan::plan_with_chunk(K, range_ktiles) : hsad_gemm_plan::plain_plan(K, split_k);
+    g.k_chunk = kp.chunk * kBK;
+    gz = kp.count;
     if (gz == 1) g.k_chunk = 0;      // one k range after all (K <= 64 x split): a plain GEMM, not a one-slab atomic accumulation
   }
   g.gz = gz;
@@ -384,21 +386,15 @@ static int gemm_splitk_impl(const void* A, int lda, const void* B, int ldb, int 
   return HSAD_OK;
 }
 
-// k tiles per range of a grouped split: an even number, as the 256 x 256 core needs
-static inline int group_kchunk(int K, int split_k) {
-  const int nk = K / kBK;
-  int c = (nk + split_k - 1) / split_k;
-  c += c & 1;
-  return std::max(c, 2);
-}
+static_assert(hsad_gemm_plan::kTileK == kBK, "csrc/hsad_gemm_plan.h plans in the kernels' k tiles");
 int64_t hsad_gemm_group_workspace_floats(int n, const hsad_gemm_group_item* items) {
   if (!items || n < 1) return 0;
   int64_t w = 0;
   for (int k = 0; k < n; ++k) {
     const hsad_gemm_group_item& it = items[k];
-    if (it.K < 128 || it.split_k < 1) return 0;
-    const int kc = group_kchunk(it.K, it.split_k);
-    w += (int64_t)((it.K / kBK + kc - 1) / kc) * it.M * it.N;
+    const int64_t f = hsad_gemm_plan::group_item_floats(it.M, it.N, it.K, it.split_k);
+    if (f == 0) return 0;
+    w += f;
   }
   return w;
 }
@@ -419,7 +415,8 @@ int hsad_gemm_nt_bf16_group_splitk(int n, const hsad_gemm_group_item* items, flo
     if (!it.A || !it.B || !it.C || it.M < 1 || it.N < 4 || (it.N & 3) || it.K < 128 || (it.K % 128) || (it.lda & 7) || (it.ldb & 7) || it.n_out < 1 || it.n_out > it.N ||
         it.split_k < 1 || (((uintptr_t)it.A | (uintptr_t)it.B) & 15))
       return nfail(HSAD_ERR_INVALID, "gemm_group: item %d: N a multiple of 4, K of 128, lda / ldb of 8, 16-byte aligned operands, 1 <= n_out <= N", k);
-    const int kc = group_kchunk(it.K, it.split_k), nsplit = (it.K / kBK + kc - 1) / kc;
+    const hsad_gemm_plan::KPlan plan = hsad_gemm_plan::core_plan(it.K, it.split_k);
+    const int kc = plan.chunk, nsplit = plan.count;
     if ((it.M % 256) || (size_t)257 * (size_t)std::max(it.lda, it.ldb) * 2 + (size_t)it.K * 2 >= ((size_t)1 << 31)) core = false;
     G8Prob& q = P.p[k];
     q.A = (const bf16_t*)it.A; q.A2 = nullptr; q.B = (const bf16_t*)it.B; q.bias = nullptr; q.C32 = ws; q.C16 = nullptr;
@@ -438,12 +435,12 @@ int hsad_gemm_nt_bf16_group_splitk(int n, const hsad_gemm_group_item* items, flo
     const int rc = g8_launch(G8_F32, P, n_cu, s);
     if (rc) return rc;
   } else {
-    for (int k = 0; k < n; ++k) {       // the 128 x 128 kernel, one launch per item, same k ranges, same slabs
+    for (int k = 0; k < n; ++k) {       // the 128 x 128 kernel, one launch per item: the core plan's range length is handed over, so same k ranges, same slabs
       const hsad_gemm_group_item& it = items[k];
       const G8Prob& q = P.p[k];
       int n_split = 1;
       const int rc = gemm_launch(it.A, it.lda, it.B, it.ldb, it.M, it.N, it.K, nullptr, q.C32, it.N, nullptr, 0, 0, 0, q.ksplit, nullptr, 0, nullptr,
-                                 (size_t)it.M * it.N, &n_split, stream);
+                                 (size_t)it.M * it.N, &n_split, stream, nullptr, q.kchunk);
       if (rc) return rc;
       if (n_split != q.ksplit) return nfail(HSAD_ERR_STATE, "gemm_group: item %d was cut into %d ranges, %d planned", k, n_split, q.ksplit);
     }

@@ -797,8 +797,10 @@ int hsad_gemm_nt_bf16_splitk_acc(const void* A, int lda, const void* B, int ldb,
  * input layer, K = T x B = 10,240) are a handful of problems that are each too small to fill the chip.  Every item's K is cut into
  * split_k ranges (an even number of 64-deep k tiles each), every (problem, range, tile) is a work item of the same launch, partial
  * results go to `workspace` (sum over items of ranges x M x N floats: hsad_gemm_group_workspace_floats) and are added up in range order
- * (deterministic).  M a multiple of 256, N of 4, K of 128, lda / ldb of 8; B is read up to its row N - 1 only.  Items the core does not
- * take (shape) run on the 128 x 128 kernel, one launch each, into the same slabs. */
+ * (deterministic).  M a multiple of 256, N of 4, K of 128, lda / ldb of 8; B is read up to its row N - 1 only.  When the core does not
+ * take one of the items (an M that is no multiple of 256; hsad_gemm_set_pp(0)), every item runs on the 128 x 128 kernel, one launch each,
+ * over the SAME k ranges (the planned range length is handed to it: csrc/hsad_gemm_plan.h) into the same slabs: identical bits on
+ * either path (tests/test_gemm_group_gpu.py). */
 typedef struct hsad_gemm_group_item {
   const void* A;            /* bf16 [M, K], row stride lda */
   const void* B;            /* bf16 [N, K], row stride ldb */

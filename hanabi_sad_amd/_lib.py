@@ -236,6 +236,7 @@ SIGNATURES = {
     "hsad_aux_xent": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "hsad_loss_tail": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                  C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "hsad_clone_tail": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P]),
     "hsad_colsum": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "hsad_colsum_acc": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "hsad_colsum_acc_ordered": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
@@ -359,6 +360,7 @@ SIGNATURES = {
     "hsad_r2d2_learner_set_optim": (C.c_int, [_P, C.c_float, C.c_float, C.c_float]),
     "hsad_r2d2_loss_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_float, _P, _P, C.c_int, _P]),
     "hsad_r2d2_loss_bwd": (C.c_int, [_P, _P]),
+    "hsad_r2d2_clone_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "hsad_r2d2_optimizer_step": (C.c_int, [_P, C.c_float, C.c_float, C.POINTER(_P), _P]),
     "hsad_r2d2_learner_grad_norm_dev": (_P, [_P]),
     "hsad_r2d2_sync_target_with_online": (C.c_int, [_P, _P]),

@@ -1,0 +1,322 @@
+"""Behaviour cloning: fit the R2D2 net to recorded games (game_record.GameRecord) on the device.
+
+  records_from_teacher     play the games to clone: eval.play_seatings(records=True) with rule bots, networks or both in the seats
+  sequences_from_records   records -> the observation sequences of every seat: game_record.replay(stop=0), then one env.step per move
+                           with the recorded move and its recorded greedy alternative (the deals come from the record's deck script)
+  CloneDataset             those sequences; split(holdout, seed) by game, batches(rows, seed) of a fixed row count
+  CompositeLearner.clone_loss (composite.py) is the update: cross-entropy of the recorded move under softmax over the legal
+  advantages (hsad_r2d2_clone_fwd), BPTT and Adam as in the TD learner.  The greedy policy of the fitted net is what every consumer of
+  an R2D2 weight file plays: eval.evaluate, eval_model --cross_play, actor.NetPartner, search's blueprint, selfplay --load_model.
+  The value head gets no gradient from cloning.
+
+    python -m hanabi_sad_amd.clone (--games FILE.jsonl | --teacher piers [--num_game N]) [--seat NAME] --sad 1 \\
+           --num_epoch E --batchsize 128 --holdout 0.1 --save_dir D
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import game_record as gr
+
+
+# ---- host-side logic (no device) --------------------------------------------------------------------------------------------------
+def check_rules(records):
+    """the rules all records share; ValueError for none or for records of different rules"""
+    records = list(records)
+    if not records:
+        raise ValueError("no records")
+    r = records[0].rules
+    if any(rec.rules != r for rec in records):
+        raise ValueError("the records were played under different rules")
+    return dict(r)
+
+
+def select_seats(records, seats):
+    """-> bool [len(records), P]: the seats whose sequences are kept.  seats: None = all; a list of seat indices; or a name held
+    against each record's meta["seats"] (what play_seatings writes: the pool member on every seat), e.g. only the seats `piers` played"""
+    P = check_rules(records)["players"]
+    keep = np.zeros((len(records), P), dtype=bool)
+    if seats is None:
+        keep[:] = True
+    elif isinstance(seats, str):
+        for j, rec in enumerate(records):
+            names = rec.meta.get("seats")
+            if not names or len(names) != P:
+                raise ValueError("record %d carries no seat names (meta[\"seats\"]); select seats by index" % j)
+            keep[j] = [n == seats for n in names]
+        if not keep.any():
+            raise ValueError("no seat of these records is named %r" % seats)
+    else:
+        idx = [int(s) for s in seats]
+        if not idx or any(not 0 <= s < P for s in idx):
+            raise ValueError("seats %s: a %d-player game has seats 0..%d" % (idx, P, P - 1))
+        keep[:, idx] = True
+    return keep
+
+
+def sequence_lengths(n_moves, max_len, capacity=None):
+    """-> (int64 [n]: moves kept per game, how many games were cut).  max_len None: the rules' capacity (nothing is cut)"""
+    n = np.asarray(list(n_moves), dtype=np.int64)
+    T = int(capacity if max_len is None else max_len)
+    return np.minimum(n, T), int((n > T).sum())
+
+
+def padding_rows(n_rows, rows):
+    """rows of weight 0 that fill the last batch"""
+    return (-int(n_rows)) % int(rows)
+
+
+class CloneDataset:
+    """priv_s float32 [T, N, F] or priv_s_bf16 [T, N, in_dim_padded] (the other None); legal_move float32 [T, N, A]; a int64 [T, N]
+    (the recorded move on the mover's row, the no-op on the others); seq_len float32 [N]; game, seat int64 [N] (game = the record's
+    index); truncated = games cut at max_len.  Rows at and past seq_len are padding: zeros, no-op."""
+
+    def __init__(self, priv_s, priv_s_bf16, legal_move, a, seq_len, game, seat, truncated=0):
+        self.priv_s, self.priv_s_bf16, self.legal_move, self.a = priv_s, priv_s_bf16, legal_move, a
+        self.seq_len, self.game, self.seat, self.truncated = seq_len, game, seat, int(truncated)
+
+    @property
+    def n_rows(self):
+        return int(self.seq_len.shape[0])
+
+    @property
+    def T(self):
+        return int(self.legal_move.shape[0])
+
+    def _obs(self):
+        return ("priv_s_bf16", self.priv_s_bf16) if self.priv_s_bf16 is not None else ("priv_s", self.priv_s)
+
+    def take(self, rows):
+        """the dataset of these rows (an index tensor), in that order"""
+        rows = torch.as_tensor(rows, dtype=torch.int64, device=self.seq_len.device)
+        sel = lambda x: None if x is None else x.index_select(1, rows)      # noqa: E731
+        return CloneDataset(sel(self.priv_s), sel(self.priv_s_bf16), sel(self.legal_move), sel(self.a), self.seq_len[rows], self.game[rows],
+                            self.seat[rows], self.truncated)
+
+    def split(self, holdout, seed):
+        """-> (train, held_out), split by GAME: every kept seat of a game goes to the same side.  holdout: the fraction of games held
+        out (at least one, never all)"""
+        games = torch.unique(self.game.cpu()).tolist()
+        n_held = max(1, int(round(float(holdout) * len(games))))
+        if not 0.0 < float(holdout) < 1.0 or n_held >= len(games):
+            raise ValueError("holdout %s of %d games leaves nothing on one side" % (holdout, len(games)))
+        order = torch.randperm(len(games), generator=torch.Generator().manual_seed(int(seed))).tolist()
+        held = torch.tensor(sorted(games[k] for k in order[:n_held]), dtype=torch.int64)
+        is_held = torch.isin(self.game.cpu(), held)
+        rows = torch.arange(self.n_rows)
+        return self.take(rows[~is_held]), self.take(rows[is_held])
+
+    def batches(self, rows, seed):
+        """shuffled batches of exactly `rows` sequences -> (batch, weight, index) each: batch = the dict CompositeLearner.clone_loss
+        takes, weight float32 [rows], index int64 [rows] = the dataset row in each column.  The last batch is filled with padding
+        columns (index -1): weight 0, seq_len 0, zero observations -- a CompositeLearner is created for one (T, rows)."""
+        rows, dev = int(rows), self.seq_len.device
+        order = torch.randperm(self.n_rows, generator=torch.Generator().manual_seed(int(seed)))
+        key, obs = self._obs()
+        for start in range(0, self.n_rows, rows):
+            index = torch.full((rows,), -1, dtype=torch.int64)
+            part = order[start:start + rows]
+            index[:len(part)] = part
+            index = index.to(dev)
+            real = index >= 0
+            src = index.clamp(min=0)
+            full = bool(len(part) == rows)
+            pick = lambda x: x.index_select(1, src) if full else x.index_select(1, src) * real.view(1, -1, *([1] * (x.dim() - 2))).to(x.dtype)   # noqa: E731
+            noop = self.legal_move.shape[2] - 1
+            a = self.a.index_select(1, src)
+            if not full:
+                a = torch.where(real.view(1, -1), a, torch.full_like(a, noop))
+            batch = {key: pick(obs), "legal_move": pick(self.legal_move), "a": a, "seq_len": self.seq_len[src] * real.float()}
+            yield batch, real.float(), index
+
+
+# ---- device side --------------------------------------------------------------------------------------------------------------------
+def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:0", bf16=True):
+    """the observation sequences of the recorded games -> CloneDataset with T = max_len (None: game_record.capacity(rules)).
+    Game j is records[j] reopened at its first deal (game_record.replay(records, stop=0) on an env of the records' rules, sad as
+    given) and stepped with its recorded moves and greedy alternatives; step t's rows are the observations BEFORE move t.  One
+    sequence per kept seat (select_seats), row order game-major.  Games longer than max_len are cut and counted in .truncated."""
+    from .env import BatchedHanabiEnv
+    from .eval import _drain_errors
+    records = list(records)
+    r = check_rules(records)
+    for j, rec in enumerate(records):
+        if not len(rec.moves) == len(rec.greedy):
+            raise ValueError("record %d has %d moves and %d greedy moves" % (j, len(rec.moves), len(rec.greedy)))
+    keep = select_seats(records, seats)
+    G, P = len(records), r["players"]
+    lens, truncated = sequence_lengths([rec.n_moves for rec in records], max_len, gr.capacity(r))
+    T = int(gr.capacity(r) if max_len is None else max_len)
+    steps = int(lens.max()) if G else 0
+    env = BatchedHanabiEnv(G, players=P, hand_size=r["hand_size"], bomb=r["bomb"], eps_list=[0.0], max_len=-1, sad=bool(sad), device=device,
+                           colors=r["colors"], ranks=r["ranks"], max_information_tokens=r["max_information_tokens"],
+                           max_life_tokens=r["max_life_tokens"])
+    try:
+        env.reset()
+        gr.replay(records, stop=[0] * G, env=env)
+        status = env.replay_status.cpu().numpy()[:G]
+        if (status < 0).any():
+            j = int(np.nonzero(status < 0)[0][0])
+            raise ValueError("record %d cannot be dealt under its rules (replay status %d)" % (j, int(status[j])))
+        dev, F, A = env.device, env.F, env.A
+        noop = A - 1
+        mv, gv = np.full((max(steps, 1), G), noop, dtype=np.int64), np.full((max(steps, 1), G), noop, dtype=np.int64)
+        for j, rec in enumerate(records):
+            n = int(lens[j])
+            mv[:n, j], gv[:n, j] = rec.moves[:n], rec.greedy[:n]
+        mv, gv = torch.from_numpy(mv).to(dev), torch.from_numpy(gv).to(dev)
+        flat = np.nonzero(keep.reshape(-1))[0]
+        rows = torch.from_numpy(flat).to(dev)
+        row_game = torch.from_numpy(flat // P).to(dev)
+        N = int(len(flat))
+        Fp = (F + 63) // 64 * 64
+        priv = torch.zeros(T, N, Fp, dtype=torch.bfloat16, device=dev) if bf16 else torch.zeros(T, N, F, dtype=torch.float32, device=dev)
+        legal = torch.zeros(T, N, A, dtype=torch.float32, device=dev)
+        act = torch.full((T, N), noop, dtype=torch.int64, device=dev)
+        lens_d = torch.from_numpy(lens).to(dev)
+        a_step, g_step = torch.empty(G, P, dtype=torch.int64, device=dev), torch.empty(G, P, dtype=torch.int64, device=dev)
+        for t in range(steps):
+            live = t < lens_d                                   # [G]
+            live_rows = live[row_game]
+            p_rows = env.priv_s.view(G * P, F)[rows] * live_rows.view(-1, 1)
+            if bf16:
+                priv[t, :, :F] = p_rows.to(torch.bfloat16)      # (0 / 1 features: exact)
+            else:
+                priv[t] = p_rows
+            legal[t] = env.legal_move.view(G * P, A)[rows] * live_rows.view(-1, 1)
+            a_step.fill_(noop)
+            g_step.fill_(noop)
+            a_step[:, t % P] = torch.where(live, mv[t], torch.full_like(mv[t], noop))
+            g_step[:, t % P] = torch.where(live, gv[t], torch.full_like(gv[t], noop))
+            act[t] = a_step.view(-1)[rows]
+            env.step(a_step, g_step)                            # (a game past its kept moves is handed the no-op and left alone)
+        _drain_errors(env)
+        torch.cuda.synchronize(dev)
+    finally:
+        env.close()
+    seq_len = torch.from_numpy(lens[flat // P]).to(dev).float()
+    return CloneDataset(None if bf16 else priv, priv if bf16 else None, legal, act, seq_len, row_game.clone(), torch.from_numpy(flat % P).to(dev),
+                        truncated)
+
+
+def records_from_teacher(pool, num_game, seed, sad, *, seating=None, num_player=2, bomb=0, device="cuda:0", names=None, **env_kw):
+    """play the games to clone -> [GameRecord], tagged with seat names: eval.play_seatings(pool, [seating], ..., records=True).  pool:
+    rulebot.RuleBot members, weight dicts / files / agents, or both; seating: the pool index on every seat (default: member
+    p % len(pool) on seat p -- one teacher plays itself).  env_kw: hand_size and the rule keywords of play_seatings."""
+    from .eval import play_seatings
+    pool = list(pool)
+    if seating is None:
+        seating = [p % len(pool) for p in range(int(num_player))]
+    res = play_seatings(pool, [list(seating)], int(num_game), int(seed), bomb, sad, device=device, records=True, names=names, bot_seed=int(seed),
+                        **env_kw)
+    return res.records
+
+
+# ---- the driver ---------------------------------------------------------------------------------------------------------------------
+def run_epoch(learner, data, rows, seed, train):
+    """one pass over `data` in batches of `rows` -> (loss per decision, hits, decisions); train: backward + optimizer step per batch"""
+    dev = data.seq_len.device
+    total = torch.zeros(3, dtype=torch.float64, device=dev)
+    bad = torch.zeros((), dtype=torch.int64, device=dev)
+    for batch, weight, _ in data.batches(rows, seed):
+        loss, stats = learner.clone_loss(batch, weight, compute_grad=train)
+        if train:
+            learner.optimizer_step()
+        total += torch.stack([(loss * weight).sum().double(), stats["hits"].sum().double(), stats["decisions"].sum().double()])
+        bad += stats["bad"].sum()
+    if int(bad):
+        from ._lib import HsadError
+        raise HsadError("%d recorded moves are illegal in their position or out of range" % int(bad))
+    s, h, n = total.tolist()
+    return s / max(n, 1.0), int(h), int(n)
+
+
+def parse_args(argv=None):
+    import argparse
+    p = argparse.ArgumentParser(description="fit the R2D2 net to recorded games")
+    p.add_argument("--games", type=str, default="", help="a file of game records (JSON lines, game_record.save)")
+    p.add_argument("--teacher", type=str, nargs="+", default=[], help="instead of --games: rule-bot presets of rulebot.py or weight files; "
+                                                                      "member p %% len plays seat p, the games are recorded and cloned")
+    p.add_argument("--num_game", type=int, default=1000, help="with --teacher: games to play")
+    p.add_argument("--seat", type=str, default="", help="clone only the seats of this name (the records' meta[\"seats\"]), or a seat index")
+    p.add_argument("--save_dir", type=str, default="")
+    p.add_argument("--load_model", type=str, default="")
+    p.add_argument("--seed", type=int, default=10001)
+    p.add_argument("--sad", type=int, default=1)
+    p.add_argument("--num_player", type=int, default=2)
+    p.add_argument("--hand_size", type=int, default=5)
+    p.add_argument("--colors", type=int, default=5)
+    p.add_argument("--ranks", type=int, default=5)
+    p.add_argument("--max_information_tokens", type=int, default=8)
+    p.add_argument("--max_life_tokens", type=int, default=3)
+    p.add_argument("--eval_bomb", type=int, default=0)
+    p.add_argument("--lr", type=float, default=6.25e-5)
+    p.add_argument("--eps", type=float, default=1.5e-5)
+    p.add_argument("--grad_clip", type=float, default=5.0)
+    p.add_argument("--num_lstm_layer", type=int, default=2)
+    p.add_argument("--rnn_hid_dim", type=int, default=512)
+    p.add_argument("--train_device", type=str, default="cuda:0")
+    p.add_argument("--batchsize", type=int, default=128)
+    p.add_argument("--num_epoch", type=int, default=10)
+    p.add_argument("--max_len", type=int, default=80)
+    p.add_argument("--holdout", type=float, default=0.1)
+    p.add_argument("--num_eval_game", type=int, default=1000)
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    from .checkpoint import load_weights, save_weights
+    from .composite import CompositeLearner
+    from .eval import env_dims, evaluate
+    from .rulebot import PRESETS
+    from .selfplay import game_rules, init_weights
+    args = parse_args(argv)
+    dev = args.train_device
+    if bool(args.games) == bool(args.teacher):
+        raise SystemExit("give either --games FILE or --teacher NAME")
+    if args.games:
+        records = gr.load(args.games)
+    else:
+        pool = []
+        for entry in args.teacher:
+            if entry not in PRESETS and not os.path.isfile(entry):
+                raise SystemExit("--teacher %s: no rule-bot preset of that name (have: %s) and no weight file" % (entry, ", ".join(sorted(PRESETS))))
+            pool.append(PRESETS.get(entry, entry))
+        names = [e if e in PRESETS else os.path.basename(e) for e in args.teacher]
+        records = records_from_teacher(pool, args.num_game, args.seed, args.sad, num_player=args.num_player, bomb=args.eval_bomb, device=dev,
+                                       names=names, hand_size=args.hand_size, **game_rules(args))
+    if args.save_dir:
+        os.makedirs(args.save_dir, exist_ok=True)
+        if args.teacher:     # the games that were cloned, for --games of a later run
+            gr.save(os.path.join(args.save_dir, "games.jsonl"), records)
+    r = check_rules(records)
+    seats = None if not args.seat else ([int(args.seat)] if args.seat.isdigit() else args.seat)
+    data = sequences_from_records(records, args.sad, seats=seats, max_len=args.max_len, device=dev)
+    train, held = data.split(args.holdout, args.seed)
+    print("%d games (%d cut at %d moves, mean score %.2f), %d sequences: %d to fit, %d held out"
+          % (len(records), data.truncated, args.max_len, float(np.mean([rec.score for rec in records])), data.n_rows, train.n_rows, held.n_rows))
+    rules = {k: r[k] for k in ("colors", "ranks", "max_information_tokens", "max_life_tokens")}
+    F, A = env_dims(r["players"], r["hand_size"], args.sad, **rules)
+    if args.load_model:
+        W = load_weights(args.load_model)
+    else:
+        W = init_weights(F, args.rnn_hid_dim, A, r["hand_size"], args.seed, num_lstm_layer=args.num_lstm_layer)
+    learner = CompositeLearner(W, W, 1, 0.999, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip, device=dev)
+    for epoch in range(args.num_epoch):
+        loss, hits, n = run_epoch(learner, train, args.batchsize, args.seed + epoch, True)
+        _, hh, hn = run_epoch(learner, held, args.batchsize, 0, False)
+        weights = {k: v.detach().clone() for k, v in learner.online.w.items()}
+        score = evaluate(weights, args.num_eval_game, args.seed, args.eval_bomb, args.sad, num_player=r["players"], hand_size=r["hand_size"],
+                         device=dev, **rules)[0]
+        print("epoch %d: loss per decision %.4f, agreement %.4f (%d / %d), held-out agreement %.4f (%d / %d), self-play score %.3f"
+              % (epoch, loss, hits / max(n, 1), hits, n, hh / max(hn, 1), hh, hn, score), flush=True)
+        if args.save_dir:
+            save_weights(weights, os.path.join(args.save_dir, "clone_epoch%d.pthw" % epoch))
+            save_weights(weights, os.path.join(args.save_dir, "clone.pthw"))
+    learner.close()
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -191,6 +191,17 @@ class CompositeAgent:
         return out
 
 
+class CloneStats(dict):
+    """what CompositeLearner.clone_loss counts per sequence, as device tensors: hits, decisions, bad (int32 [B])"""
+
+    def read(self):
+        """-> (hits, decisions) summed over the batch, as ints (synchronises); raises if any recorded move was illegal or out of range"""
+        h, n, bad = (int(v) for v in torch.stack([self["hits"].sum(), self["decisions"].sum(), self["bad"].sum()]).tolist())
+        if bad:
+            raise _lib.HsadError("clone_loss: %d recorded moves are illegal in their position or out of range (they were left out of the loss)" % bad)
+        return h, n
+
+
 class CompositeLearner:
     """the learner step of selfplay.py:208-244 as library calls: loss() = hsad_r2d2_loss_fwd (+ hsad_r2d2_loss_bwd),
     optimizer_step(), sync_target_with_online().  Same surface as r2d2.R2D2Learner (flat / gflat / grad / online.w)."""
@@ -287,6 +298,33 @@ class CompositeLearner:
         w = weight.contiguous().float()
         self._alive.append(w)
         _lib.check(self.lib.hsad_r2d2_loss_bwd_weighted(self.h, w.data_ptr(), self._seq_len.data_ptr(), _s(self.device)))
+
+    def clone_loss(self, batch, weight, compute_grad=True):
+        """behaviour cloning (hsad_r2d2_clone_fwd + hsad_r2d2_loss_bwd): cross-entropy of the recorded moves batch["a"] [T, B] under softmax
+        over the legal advantages of the ONLINE net (the target net does not run), summed over the steps inside batch["seq_len"].  IQL layout
+        only: priv_s [T, B, F] (or priv_s_bf16 [T, B, in_dim_padded]), legal_move [T, B, A].  -> loss [B], CloneStats with the device tensors
+        hits / decisions / bad [B] int32; the gradient of (loss * weight).mean() is left where optimizer_step() finds it.  The value head
+        gets no gradient.  CloneStats.read() -> (hits, decisions) as ints and raises if a recorded move was illegal or out of range."""
+        legal, a = batch["legal_move"], batch["a"]
+        p16 = batch.get("priv_s_bf16")
+        priv = p16 if p16 is not None else batch["priv_s"]
+        if legal.dim() != 3 or priv.dim() != 3 or a.dim() != 2:
+            raise _lib.HsadError("clone_loss takes the IQL layout: priv_s [T, B, F], legal_move [T, B, A], a [T, B]")
+        T, rows, _ = legal.shape
+        if p16 is not None and (priv.dtype != torch.bfloat16 or tuple(priv.shape) != (T, rows, self.online.Fp)):
+            raise _lib.HsadError("priv_s_bf16 must be bf16 [T, rows, %d]; got %s %s" % (self.online.Fp, priv.dtype, tuple(priv.shape)))
+        self._ensure(T, rows)
+        d = self.device
+        loss = torch.empty(rows, dtype=torch.float32, device=d)
+        cnt = torch.empty(3, rows, dtype=torch.int32, device=d)
+        keep = [priv.contiguous(), legal.contiguous().float(), a.contiguous().long(), batch["seq_len"].contiguous().float(), weight.contiguous().float()]
+        self._alive = keep       # loss_bwd reads these
+        _lib.check(self.lib.hsad_r2d2_clone_fwd(self.h, None if p16 is not None else keep[0].data_ptr(), keep[0].data_ptr() if p16 is not None else None,
+                                                keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), keep[4].data_ptr(), loss.data_ptr(),
+                                                cnt[0].data_ptr(), cnt[1].data_ptr(), cnt[2].data_ptr(), 1 if compute_grad else 0, _s(d)))
+        if compute_grad:
+            _lib.check(self.lib.hsad_r2d2_loss_bwd(self.h, _s(d)))
+        return loss, CloneStats(hits=cnt[0], decisions=cnt[1], bad=cnt[2])
 
     def set_optim(self, lr, eps, max_grad_norm):
         self.cfg = self.cfg[:2] + (float(lr), float(eps), float(max_grad_norm) if max_grad_norm else 0.0)

@@ -99,6 +99,7 @@ struct FwdHandoff {
   bool dheads_ready = false;      // the loss tail already produced d loss / d heads
   bool dO_ready = false;          // ... and d loss / d o of the top layer
   bool dc01_zero = false;         // ... and cleared dc[0], dc[1] (contiguous)
+  bool clone = false;             // the forward was hsad_r2d2_clone_fwd: no TD errors to re-weight
   LossArgs batch{};               // the caller's batch (must still be alive)
 };
 
@@ -168,7 +169,8 @@ Shape shape_of(const hsad_r2d2_learner* L) {
 // {256, 512}, at most 512 rows, rows a multiple of 8 and T * rows a multiple of the GEMM K tile; the layer pipeline is written for two LSTM
 // layers; everything else takes the unchunked (plain) schedule.  Fused forward (persistent launches over the whole sequence): a (net, row
 // block)'s layers x H/32 workgroups must share an XCD (one workgroup per CU).
-void plan_forward(const hsad_r2d2_learner* L, LearnerPlan& P) {
+// nets: how many nets the forward runs (2: online + target, the TD loss; 1: the online net alone, cloning).
+void plan_forward(const hsad_r2d2_learner* L, LearnerPlan& P, int nets) {
   const Shape d = shape_of(L);
   const int T = d.T, B = d.B, H = d.H, nrb = nrb_of(B);
   P.pipe = d.NL == 2 && (H == 256 || H == 512) && B <= 512 && B % 8 == 0 && d.M % 64 == 0;
@@ -178,7 +180,7 @@ void plan_forward(const hsad_r2d2_learner* L, LearnerPlan& P) {
   // (T < 2: a one-step "sequence" has no recurrence to fuse -- the fused forward launch faulted on it, found in round 6; the chunked schedule runs it)
   if (L->fused_fwd && T >= 2 && (H == 256 || H == 512) && B % 32 == 0 && (size_t)T * B * H * 16 < (1ull << 32))
     for (int g = std::min(d.NL, 2); g >= 1 && !P.fwd_nets; --g)
-      for (int nn = 2; nn >= 1 && !P.fwd_nets; --nn)
+      for (int nn = nets; nn >= 1 && !P.fwd_nets; --nn)
         if (g * (H / 32) * ((nn * nrb + 7) / 8) <= L->n_cu / 8) P.fwd_nets = nn, P.fwd_layers = g;
   P.fwd_kind = P.fwd_nets ? kFused : P.pipe ? kPipelined : kPlain;
 }
@@ -217,9 +219,9 @@ void plan_bptt(const hsad_r2d2_learner* L, LearnerPlan& P) {
 }
 
 // pure: no HIP call, no write to L
-LearnerPlan plan_update(const hsad_r2d2_learner* L) {
+LearnerPlan plan_update(const hsad_r2d2_learner* L, int nets = 2) {
   LearnerPlan P{};
-  plan_forward(L, P);
+  plan_forward(L, P, nets);
   plan_bptt(L, P);
   return P;
 }
@@ -534,7 +536,7 @@ int hsad_r2d2_learner_inject_timeout(hsad_r2d2_learner* L, int set) {
 namespace {
 
 // the input MLP (R2D2Net.net); the online / target pair of each forward GEMM is ONE launch (hsad_gemm_nt_bf16_pair)
-int fwd_input_mlp(hsad_r2d2_learner* L, const Shape& d, const float* priv_s, const void* priv_s_bf16, void* stream) {
+int fwd_input_mlp(hsad_r2d2_learner* L, const Shape& d, const float* priv_s, const void* priv_s_bf16, int n_nets, void* stream) {
   hsad_r2d2_net* nets[2] = {L->on, L->tg};
   const int M = d.M, H = d.H, Fp = d.Fp;
   // priv_s_bf16: [M, Fp] zero-padded, e.g. straight out of hsad_replay_sample (HSAD_BITS_AS_BF16); it must stay valid until
@@ -543,6 +545,11 @@ int fwd_input_mlp(hsad_r2d2_learner* L, const Shape& d, const float* priv_s, con
   else {
     CK(hsad_cast_pad_bf16(priv_s, M, d.F, d.F, L->a16, Fp, stream));
     L->a16_in = L->a16;
+  }
+  if (n_nets == 1) {      // the online net alone: the same GEMMs as single problems
+    CK(hsad_gemm_nt_bf16(L->a16_in, Fp, nets[0]->W1, Fp, M, H, Fp, nets[0]->w(nets[0]->iB1), nullptr, 0, L->x1[0], H, 1, 0, stream));
+    if (d.nfc == 2) CK(hsad_gemm_nt_bf16(L->x1[0], H, nets[0]->W2, H, M, H, H, nets[0]->w(nets[0]->iB2), nullptr, 0, L->x2[0], H, 1, 0, stream));
+    return 0;
   }
   CK(hsad_gemm_nt_bf16_pair(L->a16_in, L->a16_in, Fp, nets[0]->W1, nets[1]->W1, Fp, M, H, Fp, nets[0]->w(nets[0]->iB1), nets[1]->w(nets[1]->iB1),
                             nullptr, nullptr, 0, L->x1[0], L->x1[1], H, 1, stream));
@@ -554,11 +561,11 @@ int fwd_input_mlp(hsad_r2d2_learner* L, const Shape& d, const float* priv_s, con
 
 // the LSTM over the whole sequence as persistent launches with the projections computed inside the recurrences
 // (hsad_lstm_forward_fused): up to two stacked layers and both nets per launch; the target net keeps neither gates nor c
-int fwd_recurrence_fused(hsad_r2d2_learner* L, const Shape& d, const LearnerPlan& P, bool want_grad, void* stream) {
+int fwd_recurrence_fused(hsad_r2d2_learner* L, const Shape& d, const LearnerPlan& P, bool want_grad, int n_nets, void* stream) {
   hsad_r2d2_net* nets[2] = {L->on, L->tg};
   for (int l0 = 0; l0 < d.NL; l0 += P.fwd_layers) {
     const int g = std::min(P.fwd_layers, d.NL - l0);
-    for (int q0 = 0; q0 < 2; q0 += P.fwd_nets) {
+    for (int q0 = 0; q0 < n_nets; q0 += P.fwd_nets) {
       hsad_lstm_fused_rec recs[4];
       for (int qi = 0; qi < P.fwd_nets; ++qi)
         for (int li = 0; li < g; ++li) {
@@ -584,17 +591,20 @@ int fwd_recurrence_fused(hsad_r2d2_learner* L, const Shape& d, const LearnerPlan
 
 // the layer-0 projection; then the layers software-pipelined over time chunks: stage st runs layer 0 on chunk st and layer 1
 // on chunk st - 1, for both nets, as ONE multi-recurrence persistent launch
-int fwd_recurrence_pipelined(hsad_r2d2_learner* L, const Shape& d, const LearnerPlan& P, void* stream) {
+int fwd_recurrence_pipelined(hsad_r2d2_learner* L, const Shape& d, const LearnerPlan& P, int n_nets, void* stream) {
   hsad_r2d2_net* nets[2] = {L->on, L->tg};
   const int B = d.B, H = d.H, H4 = d.H4, nch = P.fwd_chunks;
-  CK(hsad_gemm_nt_bf16_pair(L->xin[0], L->xin[1], H, nets[0]->Wih[0], nets[1]->Wih[0], H, d.M, H4, H, nets[0]->bg[0], nets[1]->bg[0],
-                            L->gates[0][0], L->gates[1][0], H4, nullptr, nullptr, 0, 0, stream));
+  if (n_nets == 1)
+    CK(hsad_gemm_nt_bf16(L->xin[0], H, nets[0]->Wih[0], H, d.M, H4, H, nets[0]->bg[0], L->gates[0][0], H4, nullptr, 0, 0, 0, stream));
+  else
+    CK(hsad_gemm_nt_bf16_pair(L->xin[0], L->xin[1], H, nets[0]->Wih[0], nets[1]->Wih[0], H, d.M, H4, H, nets[0]->bg[0], nets[1]->bg[0],
+                              L->gates[0][0], L->gates[1][0], H4, nullptr, nullptr, 0, 0, stream));
   const int Tc = d.T / nch, nrb = nrb_of(B);
   const int per_launch = std::max(1, std::min(4, L->n_cu / ((H / 32) * nrb)));
   for (int st = 0; st <= nch; ++st) {
     hsad_lstm_fwd_rec recs[4];
     int nr = 0;
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < n_nets; ++q) {
       auto rec = [&](int l, int c) {
         const size_t t0 = (size_t)c * Tc;
         hsad_lstm_fwd_rec r;
@@ -613,9 +623,13 @@ int fwd_recurrence_pipelined(hsad_r2d2_learner* L, const Shape& d, const Learner
     }
     if (st >= 1) {      // layer-1 projection of chunk st - 1, both nets in one launch
       const size_t t0 = (size_t)(st - 1) * Tc;
-      CK(hsad_gemm_nt_bf16_pair(L->hseq[0][0] + t0 * B * H, L->hseq[1][0] + t0 * B * H, H, nets[0]->Wih[1], nets[1]->Wih[1], H, Tc * B, H4,
-                                H, nets[0]->bg[1], nets[1]->bg[1], L->gates[0][1] + t0 * B * H4, L->gates[1][1] + t0 * B * H4, H4, nullptr,
-                                nullptr, 0, 0, stream));
+      if (n_nets == 1)
+        CK(hsad_gemm_nt_bf16(L->hseq[0][0] + t0 * B * H, H, nets[0]->Wih[1], H, Tc * B, H4, H, nets[0]->bg[1], L->gates[0][1] + t0 * B * H4, H4, nullptr,
+                             0, 0, 0, stream));
+      else
+        CK(hsad_gemm_nt_bf16_pair(L->hseq[0][0] + t0 * B * H, L->hseq[1][0] + t0 * B * H, H, nets[0]->Wih[1], nets[1]->Wih[1], H, Tc * B, H4,
+                                  H, nets[0]->bg[1], nets[1]->bg[1], L->gates[0][1] + t0 * B * H4, L->gates[1][1] + t0 * B * H4, H4, nullptr,
+                                  nullptr, 0, 0, stream));
     }
     for (int i = 0; i < nr; i += per_launch) {
       const int n = std::min(per_launch, nr - i);
@@ -628,9 +642,9 @@ int fwd_recurrence_pipelined(hsad_r2d2_learner* L, const Shape& d, const Learner
 }
 
 // any T, B: per net and layer one projection GEMM + one unchunked recurrence
-int fwd_recurrence_plain(hsad_r2d2_learner* L, const Shape& d, void* stream) {
+int fwd_recurrence_plain(hsad_r2d2_learner* L, const Shape& d, int n_nets, void* stream) {
   hsad_r2d2_net* nets[2] = {L->on, L->tg};
-  for (int q = 0; q < 2; ++q)
+  for (int q = 0; q < n_nets; ++q)
     for (int l = 0; l < d.NL; ++l) {
       CK(hsad_gemm_nt_bf16(l == 0 ? L->xin[q] : L->hseq[q][l - 1], d.H, nets[q]->Wih[l], d.H, d.M, d.H4, d.H, nets[q]->bg[l], L->gates[q][l], d.H4,
                            nullptr, 0, 0, 0, stream));
@@ -724,13 +738,13 @@ int loss_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_
   hd.batch = b;
   hd.have_fwd = b.want_grad;
 
-  CK(fwd_input_mlp(L, d, priv_s, priv_s_bf16, stream));
+  CK(fwd_input_mlp(L, d, priv_s, priv_s_bf16, 2, stream));
   // (the LSTM operands may still be in the side-stream half of the last optimizer step's refresh: the input layer above did not need them)
   CK(net_wait(L->on, s));
   CK(net_wait(L->tg, s));
-  if (P.fwd_kind == kFused) CK(fwd_recurrence_fused(L, d, P, b.want_grad, stream));
-  else if (P.fwd_kind == kPipelined) CK(fwd_recurrence_pipelined(L, d, P, stream));
-  else CK(fwd_recurrence_plain(L, d, stream));
+  if (P.fwd_kind == kFused) CK(fwd_recurrence_fused(L, d, P, b.want_grad, 2, stream));
+  else if (P.fwd_kind == kPipelined) CK(fwd_recurrence_pipelined(L, d, P, 2, stream));
+  else CK(fwd_recurrence_plain(L, d, 2, stream));
   if (hd.pre_T) CK(fwd_early_transposes(L, d, s));
   if (iql) CK(heads_loss_iql(L, d, hd, b, stream));
   else CK(heads_loss_vdn(L, d, b, s));
@@ -738,7 +752,49 @@ int loss_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_
   return 0;
 }
 
+// Behaviour cloning: the online net alone through the same stages, then the clone tail on its head outputs.  The hand-off is the one loss_bwd
+// already continues from: d loss / d heads is ready, the dO GEMM and the clearing of d loss / d c_T are left to it.
+int clone_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_bf16, const LossArgs& b, int32_t* hits, int32_t* decisions, int32_t* bad,
+                   void* stream) {
+  if (!L || (!priv_s && !priv_s_bf16) || !b.legal || !b.a || !b.seq_len || !b.loss || !hits || !decisions || !bad)
+    return afail(HSAD_ERR_INVALID, "r2d2_clone_fwd: bad arguments");
+  CK(timeout_check(L, "r2d2_clone_fwd"));
+  if (b.want_grad && !b.weight) return afail(HSAD_ERR_INVALID, "r2d2_clone_fwd: the gradient needs the weights");
+  hipStream_t s = (hipStream_t)stream;
+  const Shape d = shape_of(L);
+  const LearnerPlan P = plan_update(L, 1);
+  FwdHandoff hd;
+  hd.plan = P;
+  hd.pre_T = b.want_grad && P.pipe && L->side && d.Mp == d.M;
+  hd.dheads_ready = b.want_grad;
+  hd.clone = true;
+  hd.batch = b;
+  hd.have_fwd = b.want_grad;
+
+  CK(fwd_input_mlp(L, d, priv_s, priv_s_bf16, 1, stream));
+  CK(net_wait(L->on, s));
+  if (P.fwd_kind == kFused) CK(fwd_recurrence_fused(L, d, P, b.want_grad, 1, stream));
+  else if (P.fwd_kind == kPipelined) CK(fwd_recurrence_pipelined(L, d, P, 1, stream));
+  else CK(fwd_recurrence_plain(L, d, 1, stream));
+  if (hd.pre_T) CK(fwd_early_transposes(L, d, s));
+  const int top = d.NL - 1;
+  CK(hsad_gemm_nt_bf16(L->hseq[0][top], d.H, L->on->Wheads, d.H, d.M, d.NH, d.H, L->on->bheads, L->heads, d.NH, nullptr, 0, 0, 0, stream));
+  CK(hsad_clone_tail(L->heads, d.NH, b.legal, b.a, b.seq_len, b.weight, d.T, d.B, d.A, b.loss, hits, decisions, bad, b.want_grad ? L->dheads : nullptr, d.NHp,
+                     stream));
+  L->hand = hd;
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int hsad_r2d2_clone_fwd(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a,
+                                   const float* seq_len, const float* weight, float* loss, int32_t* hits, int32_t* decisions, int32_t* bad, int want_grad,
+                                   void* stream) {
+  const LossArgs b{legal_move, nullptr, nullptr, seq_len, nullptr, weight, a, 1, 0.f, loss, nullptr, want_grad != 0};
+  const int rc = clone_fwd_impl(L, priv_s, priv_s_bf16, b, hits, decisions, bad, stream);
+  if (rc || want_grad) return rc;       // (with a backward pass to follow, hsad_r2d2_loss_bwd gathers for both)
+  return timeout_gather(L, (hipStream_t)stream);
+}
 
 extern "C" int hsad_r2d2_loss_fwd(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a, const float* reward,
                                   const float* bootstrap, const float* seq_len, const float* own_hand, const float* weight, int num_player,
@@ -1163,6 +1219,9 @@ extern "C" {
 int hsad_r2d2_loss_bwd_weighted(hsad_r2d2_learner* L, const float* weight, const float* seq_len, void* stream) {
   if (!L || !weight || !seq_len) return afail(HSAD_ERR_INVALID, "r2d2_loss_bwd_weighted: null argument");
   if (!L->hand.have_fwd) return afail(HSAD_ERR_STATE, "r2d2_loss_bwd: call loss_fwd(want_grad = 1) first");
+  if (L->hand.clone)
+    return afail(HSAD_ERR_STATE, "r2d2_loss_bwd_weighted: the last forward was hsad_r2d2_clone_fwd -- it keeps no TD errors to re-weight; give the weights "
+                                 "to clone_fwd and call hsad_r2d2_loss_bwd");
   const int Bg = L->B / L->hand.batch.num_player, n = L->T * Bg;
   hipLaunchKernelGGL(dqa_reweight_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, L->err, seq_len, weight, L->T, Bg, L->dqa);
   HIP_TRY(hipGetLastError());

@@ -47,6 +47,7 @@ namespace {
 #include "r2d2/lstm_fused_bwd.inc"
 #include "r2d2/lstm_bptt_wide.inc"
 #include "r2d2/heads_loss_optim.inc"
+#include "r2d2/clone_loss.inc"
 #include "r2d2/act.inc"
 }  // namespace
 
@@ -1062,6 +1063,20 @@ int hsad_loss_tail(const float* heads, const float* heads_t, int ldh, const floa
   return hsad_internal_loss_tail(heads, heads_t, ldh, legal, q_online, online_qa, block_min, n_block_min, reward, bootstrap, seq_len, weight, own_hand,
                                  action, T, B, A, NP, multi_step, gamma, pred_weight, greedy, target_qa, err, priority, loss, xent_sum, dqa, dheads16,
                                  ldo, nullptr, 0, nullptr, nullptr, 0, stream);
+}
+
+int hsad_clone_tail(const float* heads, int ldh, const float* legal, const int64_t* action, const float* seq_len, const float* weight, int T, int B,
+                    int A, float* loss, int32_t* hits, int32_t* decisions, int32_t* bad, void* dheads16, int ldo, void* stream) {
+  if (!heads || !legal || !action || !seq_len || !loss || !hits || !decisions || !bad || T < 1 || B < 1 || A < 1 || ldh < A)
+    return nfail(HSAD_ERR_INVALID, "clone_tail: null argument or bad shape");
+  if (dheads16 && (!weight || ldo < A + 1)) return nfail(HSAD_ERR_INVALID, "clone_tail: the head gradient needs the weights and ldo >= A + 1");
+  const int threads = 128;
+  const size_t lds = ((size_t)T + 3 * threads) * 4;
+  if (lds > 64 * 1024) return nfail(HSAD_ERR_INVALID, "clone_tail: T too long for one workgroup's step buffer");
+  CloneTailArgs p{heads, legal, seq_len, weight, action, ldh, T, B, A, loss, hits, decisions, bad, (bf16_t*)dheads16, ldo};
+  hipLaunchKernelGGL(clone_tail_kernel, dim3(B), dim3(threads), lds, (hipStream_t)stream, p);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
 }
 
 // library-internal (the learner's loss_fwd): the head layers of the online and the target net + the online dueling head as ONE launch

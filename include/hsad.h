@@ -858,6 +858,15 @@ int hsad_loss_tail(const float* heads, const float* heads_t, int ldh, const floa
                    const float* weight, const float* own_hand, const int64_t* action, int T, int B, int A, int NP, int multi_step, double gamma,
                    float pred_weight, int64_t* greedy, float* target_qa, float* err, float* priority, float* loss, float* xent_sum, float* dqa,
                    void* dheads16, int ldo, void* stream);
+/* Behaviour cloning on the head outputs, one launch (IQL layout, any T): row m = t B + b, z_j = heads[m ldh + j] (j < A), legal 0 / 1 [M, A],
+ * action [M], valid = t < seq_len[b].  Policy = softmax over the LEGAL advantages (= softmax over legal Q under the dueling head; its argmax is
+ * the greedy action of hsad_r2d2_act).  loss[b] = sum_t xent_t in ascending t, xent = log sum_legal exp(z_j - max) - (z_act - max);
+ * decisions[b] = valid steps with >= 2 legal actions, hits[b] = those whose legal argmax (ties: lowest index) is the action; bad[b] = valid
+ * steps whose action is out of range or illegal (they contribute nothing).  dheads16 (NULL = no gradient): bf16 [M, ldo],
+ * (weight[b] / B) (softmax_j - delta_{j, act}) in the A advantage columns, 0 in the value column (cloning gives the value no gradient) and up to
+ * ldo; all-zero rows for invalid, bad and single-legal steps (a single legal action is exactly xent = 0).  No float atomics. */
+int hsad_clone_tail(const float* heads, int ldh, const float* legal, const int64_t* action, const float* seq_len, const float* weight, int T, int B,
+                    int A, float* loss, int32_t* hits, int32_t* decisions, int32_t* bad, void* dheads16, int ldo, void* stream);
 /* column sums (bias gradients) of a bf16 / fp32 [M, ld] matrix -> fp32 [N] */
 int hsad_colsum(const void* src, int is_bf16, int M, int N, int ld, float* out, void* stream);
 /* accumulating variant (no zeroing): out[col_map ? col_map[c] : c] += column sum c, and the same into out2 when given
@@ -1168,6 +1177,13 @@ int hsad_r2d2_loss_fwd(hsad_r2d2_learner* learner, const float* priv_s, const vo
                        float pred_weight, float* loss, float* priority, int want_grad, void* stream);
 /* (loss * weight).mean().backward(): BPTT into hsad_r2d2_learner_grad; the batch given to loss_fwd must still be alive */
 int hsad_r2d2_loss_bwd(hsad_r2d2_learner* learner, void* stream);
+/* Behaviour cloning: the forward half of a supervised update on recorded moves.  IQL layout (rows = sequences, no num_player); runs the ONLINE
+ * net only, on the schedule the planner resolves for one net (hsad_learner_plan.fwd_nets == 1 where fused), then hsad_clone_tail: loss [rows],
+ * hits / decisions / bad int32 [rows].  want_grad (weight required) leaves d mean_b(weight_b loss_b) / d heads for the unchanged
+ * hsad_r2d2_loss_bwd and hsad_r2d2_optimizer_step; hsad_r2d2_loss_bwd_weighted behind it is refused (HSAD_ERR_STATE).  No auxiliary task. */
+int hsad_r2d2_clone_fwd(hsad_r2d2_learner* learner, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a,
+                        const float* seq_len, const float* weight, float* loss, int32_t* hits, int32_t* decisions, int32_t* bad, int want_grad,
+                        void* stream);
 /* clip_grad_norm_ + Adam.step + operand refresh; grad_norm_sq_dev (may be NULL) receives a device pointer to the squared
  * pre-clip gradient norm */
 int hsad_r2d2_optimizer_step(hsad_r2d2_learner* learner, float beta1, float beta2, float** grad_norm_sq_dev, void* stream);

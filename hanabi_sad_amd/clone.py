@@ -7,10 +7,12 @@
   CompositeLearner.clone_loss (composite.py) is the update: cross-entropy of the recorded move under softmax over the legal
   advantages (hsad_r2d2_clone_fwd), BPTT and Adam as in the TD learner.  The greedy policy of the fitted net is what every consumer of
   an R2D2 weight file plays: eval.evaluate, eval_model --cross_play, actor.NetPartner, search's blueprint, selfplay --load_model.
-  The value head gets no gradient from cloning.
+  The value head gets no gradient from cloning -- unless the value term is asked for (--value_weight W > 0): then the dataset carries
+  the discounted return-to-go of every recorded game (returns_to_go, sequences_from_records(gamma=...)) and the update also regresses
+  Q(o_t, a_t) on it (hsad_r2d2_clone_value_fwd), so that the cloned net's Q-values are on the scale TD training continues from.
 
     python -m hanabi_sad_amd.clone (--games FILE.jsonl | --teacher piers [--num_game N]) [--seat NAME] --sad 1 \\
-           --num_epoch E --batchsize 128 --holdout 0.1 --save_dir D
+           --num_epoch E --batchsize 128 --holdout 0.1 --save_dir D [--value_weight 1 --gamma 0.999]
 """
 import os
 
@@ -62,6 +64,20 @@ def sequence_lengths(n_moves, max_len, capacity=None):
     return np.minimum(n, T), int((n > T).sum())
 
 
+def returns_to_go(rewards, n_moves, gamma):
+    """rewards [steps, G] (the reward of move t of game j), n_moves [G] -> float32 [steps, G]: G_t = r_t + gamma G_{t+1} for t < n_moves[j],
+    0 at and past it (whatever rewards holds there).  Accumulated in float64, rounded to float32 once."""
+    r = np.asarray(rewards, dtype=np.float64)
+    n = np.asarray(n_moves, dtype=np.int64)
+    steps, G = r.shape
+    out = np.zeros((steps, G), dtype=np.float64)
+    run = np.zeros(G, dtype=np.float64)
+    for t in range(steps - 1, -1, -1):
+        run = np.where(t < n, r[t] + float(gamma) * run, 0.0)
+        out[t] = run
+    return out.astype(np.float32)
+
+
 def padding_rows(n_rows, rows):
     """rows of weight 0 that fill the last batch"""
     return (-int(n_rows)) % int(rows)
@@ -70,11 +86,13 @@ def padding_rows(n_rows, rows):
 class CloneDataset:
     """priv_s float32 [T, N, F] or priv_s_bf16 [T, N, in_dim_padded] (the other None); legal_move float32 [T, N, A]; a int64 [T, N]
     (the recorded move on the mover's row, the no-op on the others); seq_len float32 [N]; game, seat int64 [N] (game = the record's
-    index); truncated = games cut at max_len.  Rows at and past seq_len are padding: zeros, no-op."""
+    index); truncated = games cut at max_len.  Rows at and past seq_len are padding: zeros, no-op.  ret (None unless the sequences were
+    made with a gamma): float32 [T, N], the discounted return-to-go of the WHOLE recorded game from step t on, the same on every seat's
+    row of a game, 0 at and past seq_len."""
 
-    def __init__(self, priv_s, priv_s_bf16, legal_move, a, seq_len, game, seat, truncated=0):
+    def __init__(self, priv_s, priv_s_bf16, legal_move, a, seq_len, game, seat, truncated=0, ret=None):
         self.priv_s, self.priv_s_bf16, self.legal_move, self.a = priv_s, priv_s_bf16, legal_move, a
-        self.seq_len, self.game, self.seat, self.truncated = seq_len, game, seat, int(truncated)
+        self.seq_len, self.game, self.seat, self.truncated, self.ret = seq_len, game, seat, int(truncated), ret
 
     @property
     def n_rows(self):
@@ -92,7 +110,7 @@ class CloneDataset:
         rows = torch.as_tensor(rows, dtype=torch.int64, device=self.seq_len.device)
         sel = lambda x: None if x is None else x.index_select(1, rows)      # noqa: E731
         return CloneDataset(sel(self.priv_s), sel(self.priv_s_bf16), sel(self.legal_move), sel(self.a), self.seq_len[rows], self.game[rows],
-                            self.seat[rows], self.truncated)
+                            self.seat[rows], self.truncated, sel(self.ret))
 
     def split(self, holdout, seed):
         """-> (train, held_out), split by GAME: every kept seat of a game goes to the same side.  holdout: the fraction of games held
@@ -128,15 +146,20 @@ class CloneDataset:
             if not full:
                 a = torch.where(real.view(1, -1), a, torch.full_like(a, noop))
             batch = {key: pick(obs), "legal_move": pick(self.legal_move), "a": a, "seq_len": self.seq_len[src] * real.float()}
+            if self.ret is not None:
+                batch["ret"] = pick(self.ret)
             yield batch, real.float(), index
 
 
 # ---- device side --------------------------------------------------------------------------------------------------------------------
-def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:0", bf16=True):
+def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:0", bf16=True, gamma=None):
     """the observation sequences of the recorded games -> CloneDataset with T = max_len (None: game_record.capacity(rules)).
     Game j is records[j] reopened at its first deal (game_record.replay(records, stop=0) on an env of the records' rules, sad as
     given) and stepped with its recorded moves and greedy alternatives; step t's rows are the observations BEFORE move t.  One
-    sequence per kept seat (select_seats), row order game-major.  Games longer than max_len are cut and counted in .truncated."""
+    sequence per kept seat (select_seats), row order game-major.  Games longer than max_len are cut and counted in .truncated.
+    gamma (None: no returns, and nothing below happens): env.reward is collected after every step and CloneDataset.ret is
+    returns_to_go of it.  A game cut at max_len is then stepped on with its recorded moves to its recorded end, no observations
+    stored, so that its return is that of the whole recorded game and not of the kept part."""
     from .env import BatchedHanabiEnv
     from .eval import _drain_errors
     records = list(records)
@@ -148,7 +171,10 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
     G, P = len(records), r["players"]
     lens, truncated = sequence_lengths([rec.n_moves for rec in records], max_len, gr.capacity(r))
     T = int(gr.capacity(r) if max_len is None else max_len)
-    steps = int(lens.max()) if G else 0
+    n_all = np.asarray([rec.n_moves for rec in records], dtype=np.int64)
+    kept_steps = int(lens.max()) if G else 0
+    steps = kept_steps if gamma is None else int(n_all.max()) if G else 0
+    step_lens = lens if gamma is None else n_all      # how far each game is stepped
     env = BatchedHanabiEnv(G, players=P, hand_size=r["hand_size"], bomb=r["bomb"], eps_list=[0.0], max_len=-1, sad=bool(sad), device=device,
                            colors=r["colors"], ranks=r["ranks"], max_information_tokens=r["max_information_tokens"],
                            max_life_tokens=r["max_life_tokens"])
@@ -163,7 +189,7 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
         noop = A - 1
         mv, gv = np.full((max(steps, 1), G), noop, dtype=np.int64), np.full((max(steps, 1), G), noop, dtype=np.int64)
         for j, rec in enumerate(records):
-            n = int(lens[j])
+            n = int(step_lens[j])
             mv[:n, j], gv[:n, j] = rec.moves[:n], rec.greedy[:n]
         mv, gv = torch.from_numpy(mv).to(dev), torch.from_numpy(gv).to(dev)
         flat = np.nonzero(keep.reshape(-1))[0]
@@ -174,30 +200,41 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
         priv = torch.zeros(T, N, Fp, dtype=torch.bfloat16, device=dev) if bf16 else torch.zeros(T, N, F, dtype=torch.float32, device=dev)
         legal = torch.zeros(T, N, A, dtype=torch.float32, device=dev)
         act = torch.full((T, N), noop, dtype=torch.int64, device=dev)
-        lens_d = torch.from_numpy(lens).to(dev)
+        lens_d, step_lens_d = torch.from_numpy(lens).to(dev), torch.from_numpy(step_lens).to(dev)
+        rewards = torch.zeros(max(steps, 1), G, dtype=torch.float32, device=dev) if gamma is not None else None
         a_step, g_step = torch.empty(G, P, dtype=torch.int64, device=dev), torch.empty(G, P, dtype=torch.int64, device=dev)
         for t in range(steps):
-            live = t < lens_d                                   # [G]
-            live_rows = live[row_game]
-            p_rows = env.priv_s.view(G * P, F)[rows] * live_rows.view(-1, 1)
-            if bf16:
-                priv[t, :, :F] = p_rows.to(torch.bfloat16)      # (0 / 1 features: exact)
-            else:
-                priv[t] = p_rows
-            legal[t] = env.legal_move.view(G * P, A)[rows] * live_rows.view(-1, 1)
+            live = t < lens_d                                   # [G]: the step is kept
+            moving = t < step_lens_d                            # [G]: the game is stepped (past `live` only for the returns of cut games)
+            if t < kept_steps:
+                live_rows = live[row_game]
+                p_rows = env.priv_s.view(G * P, F)[rows] * live_rows.view(-1, 1)
+                if bf16:
+                    priv[t, :, :F] = p_rows.to(torch.bfloat16)  # (0 / 1 features: exact)
+                else:
+                    priv[t] = p_rows
+                legal[t] = env.legal_move.view(G * P, A)[rows] * live_rows.view(-1, 1)
             a_step.fill_(noop)
             g_step.fill_(noop)
-            a_step[:, t % P] = torch.where(live, mv[t], torch.full_like(mv[t], noop))
-            g_step[:, t % P] = torch.where(live, gv[t], torch.full_like(gv[t], noop))
-            act[t] = a_step.view(-1)[rows]
-            env.step(a_step, g_step)                            # (a game past its kept moves is handed the no-op and left alone)
+            a_step[:, t % P] = torch.where(moving, mv[t], torch.full_like(mv[t], noop))
+            g_step[:, t % P] = torch.where(moving, gv[t], torch.full_like(gv[t], noop))
+            if t < kept_steps:
+                act[t] = a_step.view(-1)[rows]                  # (t < kept_steps <= T: a game that still moves here is live here)
+            env.step(a_step, g_step)                            # (a game past its moves is handed the no-op and left alone)
+            if rewards is not None:
+                rewards[t] = env.reward[:G] * moving            # (the reward of move t; past a game's end: whatever, never read)
         _drain_errors(env)
         torch.cuda.synchronize(dev)
     finally:
         env.close()
     seq_len = torch.from_numpy(lens[flat // P]).to(dev).float()
+    ret = None
+    if gamma is not None:
+        whole = torch.from_numpy(returns_to_go(rewards.cpu().numpy()[:steps], n_all, gamma)).to(dev)      # [steps, G]
+        ret = torch.zeros(T, N, dtype=torch.float32, device=dev)
+        ret[:kept_steps] = whole[:kept_steps][:, row_game] * (torch.arange(kept_steps, device=dev).view(-1, 1) < seq_len.view(1, -1))
     return CloneDataset(None if bf16 else priv, priv if bf16 else None, legal, act, seq_len, row_game.clone(), torch.from_numpy(flat % P).to(dev),
-                        truncated)
+                        truncated, ret)
 
 
 def records_from_teacher(pool, num_game, seed, sad, *, seating=None, num_player=2, bomb=0, device="cuda:0", names=None, **env_kw):
@@ -214,21 +251,28 @@ def records_from_teacher(pool, num_game, seed, sad, *, seating=None, num_player=
 
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------------------
-def run_epoch(learner, data, rows, seed, train):
-    """one pass over `data` in batches of `rows` -> (loss per decision, hits, decisions); train: backward + optimizer step per batch"""
+def run_epoch(learner, data, rows, seed, train, value_weight=0.0):
+    """one pass over `data` in batches of `rows` -> (loss per decision, hits, decisions); train: backward + optimizer step per batch.
+    value_weight > 0 (data.ret needed): the updates carry the value term, and a fourth result is the value loss per step"""
     dev = data.seq_len.device
-    total = torch.zeros(3, dtype=torch.float64, device=dev)
+    total = torch.zeros(5 if value_weight else 3, dtype=torch.float64, device=dev)
     bad = torch.zeros((), dtype=torch.int64, device=dev)
     for batch, weight, _ in data.batches(rows, seed):
-        loss, stats = learner.clone_loss(batch, weight, compute_grad=train)
+        loss, stats = learner.clone_loss(batch, weight, compute_grad=train, value_weight=value_weight)
         if train:
             learner.optimizer_step()
-        total += torch.stack([(loss * weight).sum().double(), stats["hits"].sum().double(), stats["decisions"].sum().double()])
+        sums = [(loss * weight).sum().double(), stats["hits"].sum().double(), stats["decisions"].sum().double()]
+        if value_weight:      # (a padding column has seq_len 0: no steps, no value loss)
+            sums += [stats["value_loss"].sum().double(), stats["steps"].sum().double()]
+        total += torch.stack(sums)
         bad += stats["bad"].sum()
     if int(bad):
         from ._lib import HsadError
         raise HsadError("%d recorded moves are illegal in their position or out of range" % int(bad))
-    s, h, n = total.tolist()
+    s, h, n = total.tolist()[:3]
+    if value_weight:
+        v, k = total.tolist()[3:]
+        return s / max(n, 1.0), int(h), int(n), v / max(k, 1.0)
     return s / max(n, 1.0), int(h), int(n)
 
 
@@ -262,6 +306,9 @@ def parse_args(argv=None):
     p.add_argument("--max_len", type=int, default=80)
     p.add_argument("--holdout", type=float, default=0.1)
     p.add_argument("--num_eval_game", type=int, default=1000)
+    p.add_argument("--value_weight", type=float, default=0.0, help="> 0: also fit Q(o, a_recorded) to the discounted return of the recorded game "
+                                                                   "(Huber), with this weight next to the cross-entropy")
+    p.add_argument("--gamma", type=float, default=0.999, help="with --value_weight: the discount of the returns (the one TD training will use)")
     return p.parse_args(argv)
 
 
@@ -292,7 +339,10 @@ def main(argv=None):
             gr.save(os.path.join(args.save_dir, "games.jsonl"), records)
     r = check_rules(records)
     seats = None if not args.seat else ([int(args.seat)] if args.seat.isdigit() else args.seat)
-    data = sequences_from_records(records, args.sad, seats=seats, max_len=args.max_len, device=dev)
+    vw = float(args.value_weight)
+    if vw < 0:
+        raise SystemExit("--value_weight must not be negative")
+    data = sequences_from_records(records, args.sad, seats=seats, max_len=args.max_len, device=dev, gamma=args.gamma if vw > 0 else None)
     train, held = data.split(args.holdout, args.seed)
     print("%d games (%d cut at %d moves, mean score %.2f), %d sequences: %d to fit, %d held out"
           % (len(records), data.truncated, args.max_len, float(np.mean([rec.score for rec in records])), data.n_rows, train.n_rows, held.n_rows))
@@ -304,13 +354,14 @@ def main(argv=None):
         W = init_weights(F, args.rnn_hid_dim, A, r["hand_size"], args.seed, num_lstm_layer=args.num_lstm_layer)
     learner = CompositeLearner(W, W, 1, 0.999, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip, device=dev)
     for epoch in range(args.num_epoch):
-        loss, hits, n = run_epoch(learner, train, args.batchsize, args.seed + epoch, True)
-        _, hh, hn = run_epoch(learner, held, args.batchsize, 0, False)
+        loss, hits, n, *vtrain = run_epoch(learner, train, args.batchsize, args.seed + epoch, True, vw)
+        _, hh, hn, *vheld = run_epoch(learner, held, args.batchsize, 0, False, vw)
         weights = {k: v.detach().clone() for k, v in learner.online.w.items()}
         score = evaluate(weights, args.num_eval_game, args.seed, args.eval_bomb, args.sad, num_player=r["players"], hand_size=r["hand_size"],
                          device=dev, **rules)[0]
-        print("epoch %d: loss per decision %.4f, agreement %.4f (%d / %d), held-out agreement %.4f (%d / %d), self-play score %.3f"
-              % (epoch, loss, hits / max(n, 1), hits, n, hh / max(hn, 1), hh, hn, score), flush=True)
+        value = ", value loss per step %.4f, held-out value loss per step %.4f" % (vtrain[0], vheld[0]) if vw > 0 else ""
+        print("epoch %d: loss per decision %.4f, agreement %.4f (%d / %d), held-out agreement %.4f (%d / %d), self-play score %.3f%s"
+              % (epoch, loss, hits / max(n, 1), hits, n, hh / max(hn, 1), hh, hn, score, value), flush=True)
         if args.save_dir:
             save_weights(weights, os.path.join(args.save_dir, "clone_epoch%d.pthw" % epoch))
             save_weights(weights, os.path.join(args.save_dir, "clone.pthw"))

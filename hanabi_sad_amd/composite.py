@@ -192,7 +192,20 @@ class CompositeAgent:
 
 
 class CloneStats(dict):
-    """what CompositeLearner.clone_loss counts per sequence, as device tensors: hits, decisions, bad (int32 [B])"""
+    """what CompositeLearner.clone_loss counts per sequence, as device tensors: hits, decisions, bad, steps (int32 [B]; steps = the valid rows
+    that are not bad, the rows the value term runs over) and value_loss (float32 [B]: the Huber sums of Q(o, a_recorded) against the
+    returns; zeros without a value term).  A call without a value term launches nothing for the last two: they are made when first asked for."""
+    seq_len, T = None, 0      # set by a clone_loss that did not run the value tail
+
+    def __missing__(self, key):
+        if self.seq_len is None or key not in ("steps", "value_loss"):
+            raise KeyError(key)
+        if key == "steps":      # the valid rows less the bad ones
+            valid = torch.arange(self.T, device=self.seq_len.device).view(-1, 1) < self.seq_len.view(1, -1)
+            self[key] = (valid.sum(0) - self["bad"]).to(torch.int32)
+        else:
+            self[key] = torch.zeros_like(self.seq_len)
+        return self[key]
 
     def read(self):
         """-> (hits, decisions) summed over the batch, as ints (synchronises); raises if any recorded move was illegal or out of range"""
@@ -299,12 +312,19 @@ class CompositeLearner:
         self._alive.append(w)
         _lib.check(self.lib.hsad_r2d2_loss_bwd_weighted(self.h, w.data_ptr(), self._seq_len.data_ptr(), _s(self.device)))
 
-    def clone_loss(self, batch, weight, compute_grad=True):
+    def clone_loss(self, batch, weight, compute_grad=True, value_weight=0.0, policy_weight=1.0):
         """behaviour cloning (hsad_r2d2_clone_fwd + hsad_r2d2_loss_bwd): cross-entropy of the recorded moves batch["a"] [T, B] under softmax
         over the legal advantages of the ONLINE net (the target net does not run), summed over the steps inside batch["seq_len"].  IQL layout
         only: priv_s [T, B, F] (or priv_s_bf16 [T, B, in_dim_padded]), legal_move [T, B, A].  -> loss [B], CloneStats with the device tensors
         hits / decisions / bad [B] int32; the gradient of (loss * weight).mean() is left where optimizer_step() finds it.  The value head
-        gets no gradient.  CloneStats.read() -> (hits, decisions) as ints and raises if a recorded move was illegal or out of range."""
+        gets no gradient.  CloneStats.read() -> (hits, decisions) as ints and raises if a recorded move was illegal or out of range.
+        value_weight > 0 (hsad_r2d2_clone_value_fwd) also fits Q(o_t, a_t) to batch["ret"] float32 [T, B], the return-to-go of the recorded
+        game (Huber, the TD loss's): the objective becomes (weight * (policy_weight * loss + value_weight * stats["value_loss"])).mean(), and
+        the value head learns.  With the defaults the calls are those of a learner without the value term."""
+        value_weight, policy_weight = float(value_weight), float(policy_weight)
+        with_value = value_weight != 0.0 or policy_weight != 1.0
+        if value_weight != 0.0 and batch.get("ret") is None:
+            raise _lib.HsadError("clone_loss(value_weight=%g) needs batch[\"ret\"], the returns-to-go [T, B] (sequences_from_records(gamma=...))" % value_weight)
         legal, a = batch["legal_move"], batch["a"]
         p16 = batch.get("priv_s_bf16")
         priv = p16 if p16 is not None else batch["priv_s"]
@@ -316,15 +336,33 @@ class CompositeLearner:
         self._ensure(T, rows)
         d = self.device
         loss = torch.empty(rows, dtype=torch.float32, device=d)
-        cnt = torch.empty(3, rows, dtype=torch.int32, device=d)
         keep = [priv.contiguous(), legal.contiguous().float(), a.contiguous().long(), batch["seq_len"].contiguous().float(), weight.contiguous().float()]
-        self._alive = keep       # loss_bwd reads these
-        _lib.check(self.lib.hsad_r2d2_clone_fwd(self.h, None if p16 is not None else keep[0].data_ptr(), keep[0].data_ptr() if p16 is not None else None,
-                                                keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), keep[4].data_ptr(), loss.data_ptr(),
-                                                cnt[0].data_ptr(), cnt[1].data_ptr(), cnt[2].data_ptr(), 1 if compute_grad else 0, _s(d)))
+        f32, f16 = (None, keep[0].data_ptr()) if p16 is not None else (keep[0].data_ptr(), None)
+        if with_value:
+            cnt = torch.empty(4, rows, dtype=torch.int32, device=d)
+            vloss = torch.zeros(rows, dtype=torch.float32, device=d)
+            ret = None
+            if value_weight != 0.0:
+                ret = batch["ret"].contiguous().float()
+                if tuple(ret.shape) != (T, rows):
+                    raise _lib.HsadError("ret must be [T, rows] = [%d, %d]; got %s" % (T, rows, tuple(ret.shape)))
+                keep.append(ret)
+            self._alive = keep       # loss_bwd reads these
+            _lib.check(self.lib.hsad_r2d2_clone_value_fwd(self.h, f32, f16, keep[1].data_ptr(), keep[2].data_ptr(), None if ret is None else ret.data_ptr(),
+                                                          keep[3].data_ptr(), keep[4].data_ptr(), policy_weight, value_weight, loss.data_ptr(),
+                                                          vloss.data_ptr(), cnt[0].data_ptr(), cnt[1].data_ptr(), cnt[2].data_ptr(), cnt[3].data_ptr(),
+                                                          1 if compute_grad else 0, _s(d)))
+            stats = CloneStats(hits=cnt[0], decisions=cnt[1], bad=cnt[2], steps=cnt[3], value_loss=vloss)
+        else:
+            cnt = torch.empty(3, rows, dtype=torch.int32, device=d)
+            self._alive = keep       # loss_bwd reads these
+            _lib.check(self.lib.hsad_r2d2_clone_fwd(self.h, f32, f16, keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), keep[4].data_ptr(),
+                                                    loss.data_ptr(), cnt[0].data_ptr(), cnt[1].data_ptr(), cnt[2].data_ptr(), 1 if compute_grad else 0, _s(d)))
+            stats = CloneStats(hits=cnt[0], decisions=cnt[1], bad=cnt[2])
+            stats.seq_len, stats.T = keep[3], T
         if compute_grad:
             _lib.check(self.lib.hsad_r2d2_loss_bwd(self.h, _s(d)))
-        return loss, CloneStats(hits=cnt[0], decisions=cnt[1], bad=cnt[2])
+        return loss, stats
 
     def set_optim(self, lr, eps, max_grad_norm):
         self.cfg = self.cfg[:2] + (float(lr), float(eps), float(max_grad_norm) if max_grad_norm else 0.0)

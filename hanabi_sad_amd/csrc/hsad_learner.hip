@@ -4,6 +4,7 @@
 // and backward kind, chunk boundaries, the stages of the fused BPTT launch, grouped weight gradients), loss_fwd / loss_bwd are lists of stage
 // functions that read that plan, and FwdHandoff is everything the backward half continues from.  The kernels are the ones in hsad_r2d2.hip.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <vector>
 
@@ -754,10 +755,23 @@ int loss_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_
 
 // Behaviour cloning: the online net alone through the same stages, then the clone tail on its head outputs.  The hand-off is the one loss_bwd
 // already continues from: d loss / d heads is ready, the dO GEMM and the clearing of d loss / d c_T are left to it.
+// The value term of hsad_r2d2_clone_value_fwd (NULL: hsad_r2d2_clone_fwd, the policy term alone through hsad_clone_tail)
+struct CloneValueTerm {
+  const float* ret;
+  float policy_weight, value_weight, *vloss;
+  int32_t* steps;
+};
+
 int clone_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_bf16, const LossArgs& b, int32_t* hits, int32_t* decisions, int32_t* bad,
-                   void* stream) {
+                   const CloneValueTerm* vt, void* stream) {
   if (!L || (!priv_s && !priv_s_bf16) || !b.legal || !b.a || !b.seq_len || !b.loss || !hits || !decisions || !bad)
     return afail(HSAD_ERR_INVALID, "r2d2_clone_fwd: bad arguments");
+  if (vt) {      // (what hsad_clone_value_tail would refuse, before anything is launched)
+    if (!vt->steps) return afail(HSAD_ERR_INVALID, "r2d2_clone_value_fwd: bad arguments");
+    if (!(vt->policy_weight >= 0.f) || !(vt->value_weight >= 0.f) || std::isinf(vt->policy_weight) || std::isinf(vt->value_weight))
+      return afail(HSAD_ERR_INVALID, "r2d2_clone_value_fwd: the weights of the two terms must be finite and not negative");
+    if (vt->value_weight != 0.f && (!vt->ret || !vt->vloss)) return afail(HSAD_ERR_INVALID, "r2d2_clone_value_fwd: the value term needs the returns and vloss");
+  }
   CK(timeout_check(L, "r2d2_clone_fwd"));
   if (b.want_grad && !b.weight) return afail(HSAD_ERR_INVALID, "r2d2_clone_fwd: the gradient needs the weights");
   hipStream_t s = (hipStream_t)stream;
@@ -779,8 +793,12 @@ int clone_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s
   if (hd.pre_T) CK(fwd_early_transposes(L, d, s));
   const int top = d.NL - 1;
   CK(hsad_gemm_nt_bf16(L->hseq[0][top], d.H, L->on->Wheads, d.H, d.M, d.NH, d.H, L->on->bheads, L->heads, d.NH, nullptr, 0, 0, 0, stream));
-  CK(hsad_clone_tail(L->heads, d.NH, b.legal, b.a, b.seq_len, b.weight, d.T, d.B, d.A, b.loss, hits, decisions, bad, b.want_grad ? L->dheads : nullptr, d.NHp,
-                     stream));
+  if (vt)
+    CK(hsad_clone_value_tail(L->heads, d.NH, b.legal, b.a, vt->ret, b.seq_len, b.weight, d.T, d.B, d.A, vt->policy_weight, vt->value_weight, b.loss, vt->vloss,
+                             hits, decisions, bad, vt->steps, b.want_grad ? L->dheads : nullptr, d.NHp, stream));
+  else
+    CK(hsad_clone_tail(L->heads, d.NH, b.legal, b.a, b.seq_len, b.weight, d.T, d.B, d.A, b.loss, hits, decisions, bad, b.want_grad ? L->dheads : nullptr,
+                       d.NHp, stream));
   L->hand = hd;
   return 0;
 }
@@ -791,8 +809,18 @@ extern "C" int hsad_r2d2_clone_fwd(hsad_r2d2_learner* L, const float* priv_s, co
                                    const float* seq_len, const float* weight, float* loss, int32_t* hits, int32_t* decisions, int32_t* bad, int want_grad,
                                    void* stream) {
   const LossArgs b{legal_move, nullptr, nullptr, seq_len, nullptr, weight, a, 1, 0.f, loss, nullptr, want_grad != 0};
-  const int rc = clone_fwd_impl(L, priv_s, priv_s_bf16, b, hits, decisions, bad, stream);
+  const int rc = clone_fwd_impl(L, priv_s, priv_s_bf16, b, hits, decisions, bad, nullptr, stream);
   if (rc || want_grad) return rc;       // (with a backward pass to follow, hsad_r2d2_loss_bwd gathers for both)
+  return timeout_gather(L, (hipStream_t)stream);
+}
+
+extern "C" int hsad_r2d2_clone_value_fwd(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a,
+                                         const float* ret, const float* seq_len, const float* weight, float policy_weight, float value_weight, float* loss,
+                                         float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps, int want_grad, void* stream) {
+  const LossArgs b{legal_move, nullptr, nullptr, seq_len, nullptr, weight, a, 1, 0.f, loss, nullptr, want_grad != 0};
+  const CloneValueTerm vt{ret, policy_weight, value_weight, vloss, steps};
+  const int rc = clone_fwd_impl(L, priv_s, priv_s_bf16, b, hits, decisions, bad, &vt, stream);
+  if (rc || want_grad) return rc;
   return timeout_gather(L, (hipStream_t)stream);
 }
 

@@ -867,6 +867,19 @@ int hsad_loss_tail(const float* heads, const float* heads_t, int ldh, const floa
  * ldo; all-zero rows for invalid, bad and single-legal steps (a single legal action is exactly xent = 0).  No float atomics. */
 int hsad_clone_tail(const float* heads, int ldh, const float* legal, const int64_t* action, const float* seq_len, const float* weight, int T, int B,
                     int A, float* loss, int32_t* hits, int32_t* decisions, int32_t* bad, void* dheads16, int ldo, void* stream);
+/* hsad_clone_tail with a value term, one launch: next to the cross-entropy (loss, hits, decisions, bad as there) every valid row that is not bad
+ * regresses the dueling Q of the recorded action on ret [M], the return-to-go of the step: v = heads[m ldh + A], al_j = z_j l_j,
+ * q = v + al_act - (sum_j al_j) / A, e = ret[m] - q, Huber term |e| < 1 ? e e / 2 : |e| - 1/2 (the TD loss's), g = -clamp(e, -1, 1).
+ * vloss[b] = sum_t Huber_t in ascending t; steps[b] = valid rows that are not bad (single-legal rows included: the off-turn no-op has a Q too).
+ * dheads16 (NULL = no gradient): bf16 [M, ldo], with s = weight[b] / B
+ *   column j < A: s (policy_weight (softmax_j - delta_{j, act}) [>= 2 legal] + value_weight g l_j (delta_{j, act} - 1/A)), summed in fp32, rounded once
+ *   column A: s value_weight g; columns A + 1 .. ldo - 1: 0; invalid and bad rows: all-zero bits (they read neither ret nor the logits).
+ * value_weight == 0 reads no ret and writes no vloss (both may be NULL); with policy_weight == 1 loss, hits, decisions, bad and dheads16 then
+ * have the bits of hsad_clone_tail.  Refused: what hsad_clone_tail refuses, value_weight != 0 without ret, vloss or a value column (ldh >= A + 1),
+ * negative or non-finite weights.  No float atomics. */
+int hsad_clone_value_tail(const float* heads, int ldh, const float* legal, const int64_t* action, const float* ret, const float* seq_len,
+                          const float* weight, int T, int B, int A, float policy_weight, float value_weight, float* loss, float* vloss, int32_t* hits,
+                          int32_t* decisions, int32_t* bad, int32_t* steps, void* dheads16, int ldo, void* stream);
 /* column sums (bias gradients) of a bf16 / fp32 [M, ld] matrix -> fp32 [N] */
 int hsad_colsum(const void* src, int is_bf16, int M, int N, int ld, float* out, void* stream);
 /* accumulating variant (no zeroing): out[col_map ? col_map[c] : c] += column sum c, and the same into out2 when given
@@ -1184,6 +1197,14 @@ int hsad_r2d2_loss_bwd(hsad_r2d2_learner* learner, void* stream);
 int hsad_r2d2_clone_fwd(hsad_r2d2_learner* learner, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a,
                         const float* seq_len, const float* weight, float* loss, int32_t* hits, int32_t* decisions, int32_t* bad, int want_grad,
                         void* stream);
+/* hsad_r2d2_clone_fwd with hsad_clone_value_tail at its end: the same path (online net only, the one-net schedule, the same hand-off to
+ * hsad_r2d2_loss_bwd + hsad_r2d2_optimizer_step; hsad_r2d2_loss_bwd_weighted behind it is refused), and additionally Q(o_t, a_t) of the online net
+ * is fitted to ret [T, rows], the return-to-go of the recorded game: vloss [rows] = the Huber sums, steps int32 [rows] = the rows they run over.
+ * The objective is mean_b(weight_b (policy_weight loss_b + value_weight vloss_b)); the value head now gets a gradient.  value_weight == 0:
+ * ret and vloss may be NULL.  Negative or non-finite weights are refused before anything is launched. */
+int hsad_r2d2_clone_value_fwd(hsad_r2d2_learner* learner, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a,
+                              const float* ret, const float* seq_len, const float* weight, float policy_weight, float value_weight, float* loss,
+                              float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps, int want_grad, void* stream);
 /* clip_grad_norm_ + Adam.step + operand refresh; grad_norm_sq_dev (may be NULL) receives a device pointer to the squared
  * pre-clip gradient norm */
 int hsad_r2d2_optimizer_step(hsad_r2d2_learner* learner, float beta1, float beta2, float** grad_norm_sq_dev, void* stream);

@@ -2,7 +2,8 @@
 optimizer_step: online and target net) of the SAME learner in the same process, at B = 128, T = 80, H = 512 (F = 838, A = 21):
 ms per update from a host clock around windows that end in a device synchronise, the two kinds alternating window by window so that
 whatever else the host does hits both alike; the spread over the windows is reported with the medians.  Also the forward halves alone
-(compute_grad=False).  Writes profiles/clone_probe.json (or --out).  Needs the GPU: there is no CPU path to time."""
+(compute_grad=False), and the clone update with the value term (clone_loss(value_weight=1): hsad_r2d2_clone_value_fwd, the same schedule
+with clone_value_tail_kernel at its end).  Writes profiles/clone_probe.json (or --out).  Needs the GPU: there is no CPU path to time."""
 import argparse
 import json
 import os
@@ -34,6 +35,7 @@ def main(argv=None):
     a = torch.multinomial(legal.view(-1, A), 1, generator=g).view(T, B)
     batch = {"priv_s": (torch.rand(T, B, F, generator=g) < 0.15).float() * mask.unsqueeze(2), "legal_move": legal * mask.unsqueeze(2),
              "a": a * mask.long(), "reward": (torch.rand(T, B, generator=g) < 0.05).float() * mask, "bootstrap": mask.clone(), "seq_len": seq_len}
+    batch["ret"] = torch.flip(torch.cumsum(torch.flip(batch["reward"], [0]), 0), [0])      # the undiscounted return-to-go of those rewards
     batch = {k: v.to(dev) for k, v in batch.items()}
     weight = torch.ones(B, device=dev)
     lr = CompositeLearner(W, W, 3, 0.999, lr=0.0, device=dev)      # lr 0: the weights, and with them the work, stay what they are
@@ -46,8 +48,14 @@ def main(argv=None):
         lr.clone_loss(batch, weight)
         lr.optimizer_step()
 
-    kinds = {"td_update": td, "clone_update": clone, "td_forward": lambda: lr.loss(batch, weight, 0.0, compute_grad=False),
-             "clone_forward": lambda: lr.clone_loss(batch, weight, compute_grad=False)}
+    def clone_value():
+        lr.clone_loss(batch, weight, value_weight=1.0)
+        lr.optimizer_step()
+
+    kinds = {"td_update": td, "clone_update": clone, "clone_value_update": clone_value,
+             "td_forward": lambda: lr.loss(batch, weight, 0.0, compute_grad=False),
+             "clone_forward": lambda: lr.clone_loss(batch, weight, compute_grad=False),
+             "clone_value_forward": lambda: lr.clone_loss(batch, weight, compute_grad=False, value_weight=1.0)}
     plans = {}
     for name, fn in kinds.items():          # warm up every kind: code objects, counter blocks, the schedule
         for _ in range(10):
@@ -72,7 +80,9 @@ def main(argv=None):
         print("%-14s %.3f ms (min %.3f, max %.3f over %d windows of %d)" % (name, out[name]["ms_median"], min(v), max(v), args.windows, args.updates), flush=True)
     out["clone_over_td_update"] = out["clone_update"]["ms_median"] / out["td_update"]["ms_median"]
     out["clone_over_td_forward"] = out["clone_forward"]["ms_median"] / out["td_forward"]["ms_median"]
-    print("clone / TD: update %.3f, forward %.3f" % (out["clone_over_td_update"], out["clone_over_td_forward"]))
+    out["clone_value_over_clone_update"] = out["clone_value_update"]["ms_median"] / out["clone_update"]["ms_median"]
+    print("clone / TD: update %.3f, forward %.3f; clone with the value term / clone: update %.3f"
+          % (out["clone_over_td_update"], out["clone_over_td_forward"], out["clone_value_over_clone_update"]))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)

@@ -131,6 +131,8 @@ SIGNATURES = {
     "hsad_env_rollout_pace_cap_us": (C.c_int, [_P]),
     "hsad_env_set_rollout_delta": (C.c_int, [_P, C.c_int]),
     "hsad_env_rollout_delta_active": (C.c_int, [_P]),
+    "hsad_env_set_rollout_chain": (C.c_int, [_P, C.c_int]),
+    "hsad_env_rollout_chain_active": (C.c_int, [_P]),
     "hsad_env_set_rollout_compact": (C.c_int, [_P, C.c_int]),
     "hsad_env_rollout_compact_active": (C.c_int, [_P]),
     "hsad_env_set_rollout_unit": (C.c_int, [_P, C.c_int]),

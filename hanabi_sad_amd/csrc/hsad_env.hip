@@ -56,7 +56,8 @@ struct EnvParams {
   unsigned long long policy_seed;  // MODE 2 (step with built-in random-legal policy)
   int n_iter;       // MODE 3: iterations this launch runs for its games (persistent rollout; 1 otherwise)
   int delta;        // env_rollout_pipe_kernel: two copies of the observation bit rows in LDS; every stream of the launch but the first
-                    // stores only the lines of priv_s whose bits changed since the stream before (rollout_delta_active)
+                    // stores only the lines of priv_s whose bits changed since the stream before (rollout_delta_active).  Bit 0;
+                    // bits 1 and 2 link the launches of one call (see phase below)
   int compact;      // with delta: the stream wave lists the changed units first and stores from the list (stream_bits_f32_compact):
                     // 1 = 128-byte lines, 2 = 64-byte half lines (hsad_env_set_rollout_unit)
   int stagger_ticks;  // MODE 3, n_iter > 1: workgroup b starts (b % 8) * stagger_ticks (100 MHz) late, see env_kernel
@@ -98,6 +99,12 @@ struct EnvParams {
   unsigned long long* phase;  // [16][2]: {tag, wall_clock64 at launch start} per partition, or NULL
   int part, n_part, lock_ticks;
   unsigned long long launch_tag, first_tag;   // first_tag: tag of the first iteration of this rollout call
+  // The carry buffer of the chain of one call's persistent launches (hsad_env_set_rollout_chain) travels in `phase`, which only
+  // partitioned launches (part >= 0, always one iteration) otherwise use, so that the struct keeps its size and every field its
+  // offset (see dbg_units_lo).  In a launch of env_rollout_pipe_kernel with delta: phase = the env's carry buffer, uint32
+  // [workgroups][obs_words], or NULL; delta bit 1 (kChainIn) = the buffer holds the rows the launch before streamed last,
+  // bit 2 (kChainOut) = leave this launch's last rows there for the next one.  (The flags ride in delta because the loop of the
+  // kernel reads that field anyway: a flag in a field of its own is one more value the kernel holds for the whole launch.)
   // pacing of a persistent launch (rollout_pace): every workgroup adds 1 to *pace at the top of each iteration, so the word says how
   // far the launch as a whole has come; a workgroup ahead of that mean delays its observation stream.  Timing only.
   unsigned long long* pace;        // the env's progress word, or NULL: no pacing (and no atomics) in this launch
@@ -1971,6 +1978,16 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v) {
   return v;
 }
 
+// The chain of a call's launches (EnvParams::delta bits 1 and 2, EnvParams::phase; hsad_env_rollout_random).
+// Launches 2, 3, ... of one call follow their predecessor on the same stream with nothing in between, so priv_s holds exactly the rows the predecessor's epilogue streamed.
+// The predecessor leaves those bit rows in the workgroup's slice of the env's carry buffer and the follower takes them as the
+// `prev` of its first stream, which then is a delta stream like every later one instead of 448 MB of lines HBM already holds.
+// Blocks, g_begin and gpw are the same in every launch of a call: the slice index is the block index.
+constexpr int kChainIn = 2, kChainOut = 4;   // in EnvParams::delta, next to bit 0 = the delta stream is on
+__device__ __forceinline__ uint4* chain_slice(const EnvParams& ep) {
+  return reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(ep.phase) + (size_t)blockIdx.x * ep.obs_words);
+}
+
 template <int TP, int TH>
 __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void env_rollout_pipe_kernel(EnvParams ep) {
   // The kernel is scheduled for two waves per SIMD (waves_per_eu(2, 2): four 128-thread workgroups per CU, which the LDS sizes,
@@ -1991,7 +2008,8 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
   uint32_t* s_pace = s_grec + kWave + 128;   // one word: the delay (ticks) of the next stream, logic wave -> stream wave
   // ep.delta: a second copy of the observation bit rows behind everything else.  The rows of iteration i are built in copy i & 1;
   // while they are streamed the other copy still holds the rows of i - 1, which is what priv_s holds, so only the lines whose
-  // word differs are stored.  The first stream of a launch stores every line: nothing is assumed about priv_s before the launch.
+  // word differs are stored.  The first stream of a launch stores every line: nothing is assumed about priv_s before the launch,
+  // unless it is chained in (chain_slice above).
   // (the copy's address is worked out where it is used: as one more launch-long value it costs the generic instance a register it
   // does not have)
 #define S_OBS1(z) (ep.delta ? s_pace + 4 + (z) : s_obs)
@@ -2031,6 +2049,11 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     }
   } else {
     clear_rows(ep, s_obs, lane, kWave);
+    if (ep.delta & kChainIn) {   // the rows priv_s holds, into the copy the stream of iteration 1 compares against
+      const uint4* src = chain_slice(ep);
+      uint4* dst = reinterpret_cast<uint4*>(S_OBS1(0));
+      for (int k = lane; k < (ep.obs_words >> 2); k += kWave) dst[k] = src[k];
+    }
     for (int k = lane; k < min(ep.n_eps, 128); k += kWave) s_eps[k] = ep.eps_list[k];
     if (lane == 0) s_pace[0] = 0u;
   }
@@ -2079,7 +2102,8 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
         if (d) pace_sleep(d);
       }
       // rows of iter - 1; with delta, against the copy this iteration builds in, which holds the rows of iter - 2: the last ones
-      // written (iter 1: nothing written yet, every line goes out)
+      // written (iter 1: nothing written yet, every line goes out, unless the launch is chained in: then that copy holds the rows
+      // the launch before wrote last)
       uint32_t* s_obs1 = S_OBS1(zero);
       uint32_t* rows = (iter & 1) ? s_obs : s_obs1;
       uint32_t* prev = (iter & 1) ? s_obs1 : s_obs;
@@ -2087,8 +2111,8 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       int sl = lane;
       asm volatile("" : "+v"(sl));   // opaque: the stream's per-lane addresses are worked out here, not kept in registers for the launch
       unsigned units = 0;
-      unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || iter == 1, s_legal, s_own, g0, ng, P, H, sl, kWave, dbg_lines,
-                                          ep.compact, units);
+      const bool all = !ep.delta || (iter == 1 && !(ep.delta & kChainIn));
+      unsigned stored = stream_rows_delta(ep, rows, prev, all, s_legal, s_own, g0, ng, P, H, sl, kWave, dbg_lines, ep.compact, units);
       clear_words(prev, ep.obs_words, sl, kWave);
       clear_words(s_legal, ep.legal_words + ep.own_words, sl, kWave);
       if (dbg_lines) {
@@ -2151,6 +2175,11 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     if (dbg_lines) {
       stored = wave_sum(stored);
       if (lane == 0) env_stamp(ep, dbg_it, 14 + wave, stored);
+    }
+    if (ep.delta & kChainOut) {   // the rows just streamed, for the next launch of the call (the stream left them as they were)
+      const uint4* src = reinterpret_cast<const uint4*>(rows);
+      uint4* dst = chain_slice(ep);
+      for (int k = tid; k < (ep.obs_words >> 2); k += ep.nthreads) dst[k] = src[k];
     }
   }
   STAMP(5);
@@ -2366,6 +2395,12 @@ struct hsad_env {
                                   // decides "changed" by (a line or a half line)
   bool delta_fits;                // the second copy of the rows costs the pipelined kernel no resident workgroup per CU
   size_t lds_bytes_delta;         // lds_bytes_reset + the second copy
+  // chain of the delta launches of one hsad_env_rollout_random call (EnvParams::delta bits 1 and 2).  Scope: one call.  The first
+  // launch of every call streams in full and never reads the buffer, so the rule above holds between calls as it did between
+  // launches.
+  int rollout_chain;              // hsad_env_set_rollout_chain; HSAD_ENV_CHAIN=0 at creation: every launch on its own, for A/B
+  uint32_t* d_chain;              // [workgroups][obs_words], allocated on first use
+  bool chain_unavailable;         // that allocation failed: the env runs unchained
   unsigned long long* d_pace;     // the progress word (allocated with the env, zero)
   unsigned long long pace_base;   // its value once everything launched so far has run
   long long pace_bias;            // hsad_env_debug_pace_bias: added to the base the kernels are told, never to pace_base
@@ -2464,6 +2499,11 @@ bool rollout_paced(const hsad_env* e) {
   return !(e->rollout_compact && rollout_delta_active(e));
 }
 
+// the chain links launches that run the delta stream
+int rollout_chain_mode(const hsad_env* e) {
+  return rollout_delta_active(e) && !e->chain_unavailable ? e->rollout_chain : 0;
+}
+
 EnvRolloutFn pick_rollout_kernel(int P, int H, bool pipe, bool variant) {
   if (variant) return env_rollout_kernel<0, 0, true>;
 #define HSAD_ROLLOUT_SPECIALISE(PP, HH) \
@@ -2504,7 +2544,8 @@ int configure_env_kernels(hsad_env* e) {
 // launch one env kernel over games [g_begin, g_begin + g_count) (g_begin multiple of 64)
 void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipStream_t stream, int g_begin,
                 int g_count, uint64_t policy_seed = 0, int64_t* a_out = nullptr, int64_t* g_out = nullptr, int part = -1,
-                unsigned long long tag = 0, unsigned long long first_tag = 0, int n_part = 1, int n_iter = 1) {
+                unsigned long long tag = 0, unsigned long long first_tag = 0, int n_part = 1, int n_iter = 1,
+                int chain = 0) {
   size_t lds = (mode == 1 || mode == 2) ? e->lds_bytes : e->lds_bytes_reset;
   EnvParams ep = e->ep;
   ep.delta = mode == 3 && n_iter > 1 && rollout_delta_active(e) ? 1 : 0;
@@ -2515,6 +2556,10 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
   ep.lock_ticks = (int)(e->stagger_ns / 10);
   ep.launch_tag = tag;
   ep.first_tag = first_tag;
+  if (part < 0 && ep.delta && chain && e->d_chain) {   // (EnvParams::delta: the chain of a call's persistent launches)
+    ep.phase = reinterpret_cast<unsigned long long*>(e->d_chain);
+    ep.delta |= chain;
+  }
   ep.n_part = n_part;
   ep.g_begin = g_begin;
   ep.g_count = g_count;
@@ -2678,6 +2723,9 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->rollout_compact = getenv("HSAD_ENV_COMPACT") ? atoi(getenv("HSAD_ENV_COMPACT")) != 0 : 1;
   e->rollout_unit = getenv("HSAD_ENV_UNIT") && atoi(getenv("HSAD_ENV_UNIT")) == 128 ? 128 : 64;
   e->delta_fits = false;
+  e->rollout_chain = getenv("HSAD_ENV_CHAIN") ? (atoi(getenv("HSAD_ENV_CHAIN")) != 0 ? 1 : 0) : 1;
+  e->d_chain = nullptr;
+  e->chain_unavailable = false;
   e->d_pace = nullptr;
   e->pace_base = 0;
   e->pace_bias = 0;
@@ -2743,6 +2791,7 @@ void hsad_env_destroy(hsad_env* e) {
   (void)hipSetDevice(e->device);
   if (e->d_phase) (void)hipFree(e->d_phase);
   if (e->d_pace) (void)hipFree(e->d_pace);
+  if (e->d_chain) (void)hipFree(e->d_chain);
   if (e->d_sel) (void)hipFree(e->d_sel);
   if (e->script.cards) (void)hipFree(e->script.cards);
   if (e->script.count) (void)hipFree(e->script.count);
@@ -2907,9 +2956,24 @@ int hsad_env_rollout_random(hsad_env* e, int n_iter, uint64_t policy_seed, int64
   const int K = e->n_part_active;
   const int blocks = e->ep.Gpad / e->ep.gpw;
   if (e->rollout_chunk > 0) {   // persistent: one launch = rollout_chunk iterations of every game (the last one may be shorter)
-    for (int i = 0; i < n_iter; i += e->rollout_chunk)
-      launch_env(e, 3, nullptr, nullptr, (hipStream_t)stream, 0, e->ep.Gpad, policy_seed, a, greedy_a, -1, 0, 0, 1,
-                 std::min(e->rollout_chunk, n_iter - i));
+    // The chain: a launch hands its last rows to the next one of this call where both run the delta stream (more than one
+    // iteration each).  The launches follow each other on one stream, so nothing can touch priv_s in between; the first launch
+    // of the call is never chained in, whatever an earlier call left in the buffer.
+    bool chained = rollout_chain_mode(e) != 0 && n_iter > e->rollout_chunk;
+    if (chained && !e->d_chain) {
+      if (hipMalloc((void**)&e->d_chain, sizeof(uint32_t) * (size_t)blocks * e->ep.obs_words) != hipSuccess) {
+        (void)hipGetLastError();   // no room: not an error, the env runs unchained from now on
+        e->d_chain = nullptr;
+        e->chain_unavailable = true;
+        chained = false;
+      }
+    }
+    int chain = 0;
+    for (int i = 0; i < n_iter; i += e->rollout_chunk) {
+      const int n = std::min(e->rollout_chunk, n_iter - i), n_next = std::min(e->rollout_chunk, n_iter - i - n);
+      chain = (chain & kChainOut ? kChainIn : 0) | (chained && n > 1 && n_next > 1 ? kChainOut : 0);
+      launch_env(e, 3, nullptr, nullptr, (hipStream_t)stream, 0, e->ep.Gpad, policy_seed, a, greedy_a, -1, 0, 0, 1, n, chain);
+    }
     HIP_TRY(hipGetLastError());
     return HSAD_OK;
   }
@@ -2987,6 +3051,14 @@ int hsad_env_set_rollout_delta(hsad_env* e, int on) {
 }
 
 int hsad_env_rollout_delta_active(const hsad_env* e) { return e && rollout_delta_active(e) ? 1 : 0; }
+
+int hsad_env_set_rollout_chain(hsad_env* e, int mode) {
+  if (!e || (mode != 0 && mode != 1)) return set_error(HSAD_ERR_INVALID, "the rollout chain mode is 0 or 1");
+  e->rollout_chain = mode;
+  return HSAD_OK;
+}
+
+int hsad_env_rollout_chain_active(const hsad_env* e) { return e ? rollout_chain_mode(e) : 0; }
 
 int hsad_env_set_rollout_compact(hsad_env* e, int on) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");

@@ -195,6 +195,16 @@ class BatchedHanabiEnv:
         """whether persistent launches use the delta stream as the env stands"""
         return bool(self.lib.hsad_env_rollout_delta_active(self.h))
 
+    def set_rollout_chain(self, mode):
+        """persistent rollout: launches 2, 3, ... of one rollout_random call take the rows their predecessor streamed last from a
+        buffer of the env, so their first stream stores only what changed (1, the default; 0: every launch on its own; results are
+        identical, see include/hsad.h)"""
+        _lib.check(self.lib.hsad_env_set_rollout_chain(self.h, int(mode)))
+
+    def rollout_chain_active(self):
+        """the chain mode persistent launches use as the env stands: 0 wherever the delta stream is not active"""
+        return int(self.lib.hsad_env_rollout_chain_active(self.h))
+
     def set_rollout_compact(self, on):
         """delta stream: list the changed lines first and store from the list (default on; results are identical, see
         include/hsad.h)"""

@@ -172,12 +172,24 @@ int hsad_env_rollout_pace_cap_us(const hsad_env* env);
 /* Delta stream of the pipelined persistent launches (on by default; HSAD_ENV_DELTA=0 when the env is created, or on = 0 here, gives
  * the full stream, for A/B).  One move changes little of an observation, so within one launch every observation stream after the
  * first stores only the 128-byte lines of priv_s whose bits differ from what the stream before wrote; the workgroup keeps those bits
- * in a second copy of its LDS rows.  The first stream of every launch stores everything and nothing is carried between launches, so
- * whatever happens to priv_s or the games between launches cannot matter.  Results are bit-identical.  The packed outputs, legal
+ * in a second copy of its LDS rows.  The first stream of every launch stores everything and nothing is carried between launches
+ * (except between the launches of one call, which nothing can come between: hsad_env_set_rollout_chain below), so whatever happens
+ * to priv_s or the games between calls cannot matter.  Results are bit-identical.  The packed outputs, legal
  * moves and own hand are streamed in full.  hsad_env_rollout_delta_active: whether persistent launches use it now -- not without the
  * pipelined schedule or the float32 observation, and not where the second copy would cost a resident workgroup per CU. */
 int hsad_env_set_rollout_delta(hsad_env* env, int on);
 int hsad_env_rollout_delta_active(const hsad_env* env);
+/* Chain of the launches of one hsad_env_rollout_random call (mode 1, the default; HSAD_ENV_CHAIN=0 when the env is created, or mode 0
+ * here, runs every launch on its own, for A/B).  A persistent call of more than one launch issues its launches back to back on one
+ * stream, so launch 2, 3, ... finds in priv_s exactly the rows its predecessor streamed last.  The predecessor leaves those bit rows
+ * in a buffer of the env ([workgroups][row words], allocated by the first call that needs it; if that fails the env runs unchained
+ * and reports no error) and the follower's first stream stores only what changed against them, like every later stream of the
+ * launch, instead of every line.  Only launches that run the delta stream are linked (a last launch of one iteration is not).
+ * The first launch of every call stores everything and never reads the buffer: nothing is carried from one call to the next, so
+ * reset, step, fork or a caller writing into priv_s between calls still cannot matter.  Results are bit-identical.
+ * hsad_env_rollout_chain_active: the mode in use, 0 wherever hsad_env_rollout_delta_active is false. */
+int hsad_env_set_rollout_chain(hsad_env* env, int mode);
+int hsad_env_rollout_chain_active(const hsad_env* env);
 /* Compacted form of the delta stream (on by default wherever the delta stream is active; HSAD_ENV_COMPACT=0 when the env is created,
  * or on = 0 here, gives the direct form, for A/B).  The stream wave first lists the lines that changed, in place in the LDS copy it
  * has just compared, and then stores from the list, eight whole lines per wave-store.  The same lines are stored either way: results

@@ -1,7 +1,7 @@
 """Per-iteration trace of one persistent rollout launch at configs[1] (65,536 two-player games): where each workgroup's time goes,
 and how many workgroups stream observations on each CU and on the chip over time.
 
-  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--delta on|off] [--compact on|off] [--unit 128|64] [--json OUT]
+  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--delta on|off] [--compact on|off] [--unit 128|64] [--chain 0|1] [--launches N] [--json OUT]
 
 The driver's shape is --warmup 5 --iters 20 (one 5-iteration launch, then the traced 20-iteration launch).  --schedule single runs
 env_rollout_kernel (HSAD_ENV_PIPE=0), pipe the default env_rollout_pipe_kernel.  Stamps are wall_clock64 (100 MHz, 10 ns) of
@@ -17,6 +17,12 @@ HSAD_ENV_PACE_L0_Q8 / HSAD_ENV_PACE_CAP_US).  --delta off traces the full observ
 --compact off the direct form of the delta stream (HSAD_ENV_COMPACT=0), --unit the bytes the compacted form decides "changed" by
 (HSAD_ENV_UNIT; default: the library's).  `stored` gives what the stream wave stored per workgroup-iteration: 128-byte lines with any
 change (slot 13) and, where the library has hsad_env_debug_units, the units themselves and their bytes.
+
+--launches N makes the traced call N launches of --iters iterations each (the trace holds the last one, which with --chain 1,
+HSAD_ENV_CHAIN, takes its predecessor's last rows from the env's carry buffer; the launches before it also hand over, which
+costs them the copy after their epilogue and does not show in the last one's trace).  `edges` says what of the traced launch is
+not its steady iteration: launch start to first iteration start, iterations 0 and 1, the epilogue, and the spread of the
+workgroups' end times with its share between XCCs.
 
 `reset_iterations` splits the logic wave's time in the workgroup-iterations whose lane 0 restarted its game (the only ones that carry
 the reset stamps 6 / 7): the wait for the mt19937 window, the deal, and the rest (eps, colour shuffle, policy and step)."""
@@ -44,8 +50,12 @@ def main():
     ap.add_argument("--unit", type=int, choices=(128, 64), default=None)
     ap.add_argument("--l0-q8", type=int, default=None)
     ap.add_argument("--cap-us", type=int, default=None)
+    ap.add_argument("--chain", type=int, choices=(0, 1), default=None)
+    ap.add_argument("--launches", type=int, default=1)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.chain is not None:
+        os.environ["HSAD_ENV_CHAIN"] = str(args.chain)
     os.environ["HSAD_ENV_PIPE"] = "1" if args.schedule == "pipe" else "0"
     os.environ["HSAD_ENV_PACE"] = "1" if args.pace == "on" else "0"
     os.environ["HSAD_ENV_DELTA"] = "1" if args.delta == "on" else "0"
@@ -61,7 +71,7 @@ def main():
     G = 65536
     eps = [0.1 ** (1 + 7 * i / 79) for i in range(80)]
     env = BatchedHanabiEnv(G, seed=1, eps_list=eps, device="cuda:0", track_deck_history=False)
-    env.set_rollout_chunk(max(50, args.iters))
+    env.set_rollout_chunk(max(50, args.iters) if args.launches == 1 else args.iters)
     assert env.threads_per_workgroup == 128
     nwg = (G + env.games_per_workgroup - 1) // env.games_per_workgroup
     env.rollout_random(args.warmup, 12345)
@@ -72,7 +82,7 @@ def main():
     _lib.check(env.lib.hsad_env_debug_trace(env.h, buf.data_ptr(), args.iters))
     if has_units:
         _lib.check(env.lib.hsad_env_debug_units(env.h, ubuf.data_ptr()))
-    env.rollout_random(args.iters, 12345)
+    env.rollout_random(args.iters * args.launches, 12345)          # the trace holds the last launch of the call
     torch.cuda.synchronize()
     if has_units:
         _lib.check(env.lib.hsad_env_debug_units(env.h, None))
@@ -89,6 +99,11 @@ def main():
             rec["stored"].update(unit_bytes=unit, units_mean=round(float(u.mean()), 1),
                                  priv_s_bytes_per_iteration=int(round(float(u.sum(axis=0).mean()) * unit)))
             rec["rollout_unit"] = unit
+            # record 1: the launch's first stream (everything, counted in lines; a chained launch: what changed, in units)
+            rec["stored"]["first_stream_units_mean"] = round(float(ubuf.view(nwg, args.iters).cpu().numpy()[:, 1].mean()), 1)
+    rec["launches_in_the_traced_call"] = args.launches
+    if hasattr(env.lib, "hsad_env_rollout_chain_active"):
+        rec["chain_mode_active"] = env.rollout_chain_active()
     rec["delta_stream_active"] = bool(env.rollout_delta_active())
     rec["compact_stream_active"] = bool(env.rollout_compact_active())
     rec["pace"] = dict(rec.get("pace", {}), on=args.pace == "on", cap_us=env.rollout_pace_cap_us(),
@@ -139,6 +154,8 @@ def analyse(s, pipe, args):
     rec["end_spread_us"] = round(float(end.max() - end.min()), 2)
     if n > 2:
         rec["who_lags"] = who_lags(t, hw, xcc, cu)
+    if pipe and n > 3:
+        rec["edges"] = edges(t, xcc)
     if pipe:
         d = s[:, :n - 1, 12].astype(np.float64) * TICK_US          # delay decided in iteration k = of the stream in k + 1
         rec["pace"] = {"share_of_iterations_that_slept": round(float((d > 0).mean()), 4),
@@ -169,6 +186,37 @@ def analyse(s, pipe, args):
     step = max(1, nb // 40)
     rec["chip_streaming_workgroups_series"] = {"bin_us": 0.5 * step, "values": [int(chip[i:i + step].mean()) for i in range(0, nb, step)]}
     return rec
+
+
+def edges(t, xcc):
+    """what of a pipelined launch is not its steady iteration: medians over workgroups, µs.  t: [workgroup, iteration, column] as in
+    analyse (columns = slots 0-8, column 9 = slot 11), relative to the first workgroup's first stamp, which stands for the launch's
+    start (the kernel has no stamp before its prologue)."""
+    nwg, n = t.shape[0], t.shape[1]
+    med = lambda a: round(float(np.median(a)), 2)
+    start, end = t[:, 0, 0], t[:, n - 1, 5]
+    steady = np.median(np.diff(t[:, 2:, 0], axis=1), axis=1) if n > 3 else np.diff(t[:, 1:3, 0], axis=1)[:, 0]   # iterations 2 .. n - 2
+    out = {"launch_start_to_first_iteration_start_us": med(start),
+           "iteration_0_us": med(t[:, 1, 0] - t[:, 0, 0]),
+           "iteration_0_phase_a_us": med(t[:, 0, 2] - t[:, 0, 0]), "iteration_0_phase_b_us": med(t[:, 0, 4] - t[:, 0, 2]),
+           "iteration_1_us": med(t[:, 2, 0] - t[:, 1, 0]),
+           "iteration_1_stream_and_clear_us": med(t[:, 1, 8] - t[:, 1, 0]),
+           "iteration_1_phase_a_us": med(t[:, 1, 2] - t[:, 1, 0]), "iteration_1_phase_b_us": med(t[:, 1, 4] - t[:, 1, 2]),
+           "steady_iteration_us": med(steady),
+           "epilogue_us": med(end - t[:, n - 1, 4]),
+           "end_us_first_median_last": [round(float(end.min()), 1), med(end), round(float(end.max()), 1)],
+           "workgroup_time_not_n_times_its_steady_iteration_us": med((end - start) - n * steady),
+           "launch_us": round(float(end.max()), 1)}
+    out["launch_not_n_times_the_steady_iteration_us"] = round(out["launch_us"] - n * out["steady_iteration_us"], 1)
+    out["tail_last_end_minus_median_end_us"] = round(float(end.max() - np.median(end)), 1)
+    x = xcc & 0xF
+    ids = np.unique(x)
+    within = float(sum(((end[x == i] - end[x == i].mean()) ** 2).sum() for i in ids))
+    total = float(((end - end.mean()) ** 2).sum())
+    out["end_us_median_by_xcc"] = {str(int(i)): round(float(np.median(end[x == i])), 1) for i in ids}
+    out["end_us_last_by_xcc"] = {str(int(i)): round(float(end[x == i].max()), 1) for i in ids}
+    out["end_share_of_variance_between_xccs"] = round(1.0 - within / total, 4) if total > 0 else None
+    return out
 
 
 def who_lags(t, hw, xcc, cu):

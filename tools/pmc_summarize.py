@@ -121,6 +121,9 @@ for spec in sys.argv[2:]:
         r = {"dispatches": len(wv), "WRITE_SIZE_KiB": mean(wv), "FETCH_SIZE_KiB_raw": mean(fv), "hbm_bytes_per_launch": hbm,
              "hbm_write_bytes_per_launch": mean(wv) * cal["write_factor"] * 1024.0,
              "hbm_read_bytes_per_launch": (mean(fv) or 0.0) * cal["fetch_factor"] * 1024.0}
+        if len(wv) <= 8:   # few dispatches: each one, in the order of the file (the launches of one rollout call differ: the chain)
+            r["hbm_write_bytes_by_dispatch"] = [v * cal["write_factor"] * 1024.0 for v in wv]
+            r["hbm_read_bytes_by_dispatch"] = [v * cal["fetch_factor"] * 1024.0 for v in fv]
         if algo:
             r["algorithmic_bytes_per_launch"] = algo
             r["traffic_over_algorithmic"] = hbm / algo

@@ -262,6 +262,7 @@ SIGNATURES = {
     "hsad_refresh_add_bias": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "hsad_refresh_launch": (C.c_int, [_P]),
     "hsad_act_select_q": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
+    "hsad_act_sample_q": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
     "hsad_act_select_q2": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, _P]),
     "hsad_q_at": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P]),
     "hsad_zero_state_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -307,6 +308,9 @@ SIGNATURES = {
     "hsad_r2d2_net_refresh": (C.c_int, [_P, _P]),
     "hsad_r2d2_net_version": (C.c_uint64, [_P]),
     "hsad_r2d2_net_in_dim_padded": (C.c_int, [_P]),
+    "hsad_r2d2_act_soft": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P,
+                                     _P, _P]),
+    "hsad_actor_set_partner_temperature": (C.c_int, [_P, C.c_int, C.c_float]),
     "hsad_r2d2_target_q": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hsad_comm_unique_id": (C.c_int, [_P, C.c_int]),
     "hsad_comm_init": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),

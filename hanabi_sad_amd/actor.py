@@ -40,12 +40,19 @@ class NetPartner:
     owns, carries its own LSTM state and never reaches the replay.  `source`: a weight dict (R2D2Net.state_dict() names), the path
     of a weight file, or a composite.CNet, which is borrowed as it is -- the actor reads its weights on every step, so weights
     written and refreshed between two steps act from the next step on (it must not be the learner's online or target net).
-    skip_connect is a constructor flag of the reference's net, not a weight, and therefore given here."""
+    skip_connect is a constructor flag of the reference's net, not a weight, and therefore given here.
+    temperature > 0: the partner plays its softmax policy instead -- every move sampled from the softmax over its legal advantages at that
+    temperature (hsad_actor_set_partner_temperature; at 1 the distribution behaviour cloning fits), the common way to a population of
+    partners out of one frozen net.  0 (the default) is the greedy partner, with the launches it always had."""
     MAX_NETS = 8
 
-    def __init__(self, source, name=None, skip_connect=False):
+    def __init__(self, source, name=None, skip_connect=False, temperature=0.0):
+        import math
         import os
         self.source, self.skip_connect = source, bool(skip_connect)
+        self.temperature = float(temperature)
+        if not math.isfinite(self.temperature) or self.temperature < 0:
+            raise ValueError("NetPartner: temperature must be finite and >= 0; got %r" % (temperature,))
         self.path = os.fspath(source) if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__") else None
         self.name = name if name is not None else (os.path.basename(self.path) if self.path is not None else "net")
         self._weights = source if isinstance(source, dict) else None
@@ -76,7 +83,8 @@ class NetPartner:
         return CNet(self.weights(), device, skip_connect=self.skip_connect)
 
     def seating_member(self, device):
-        """what eval.play_seatings seats for this partner"""
+        """what eval.play_seatings seats for this partner; its entry of play_seatings' `temperature` list is self.temperature (every
+        member this returns is, or becomes at precision "bf16", a kernel agent with the sampling tail)"""
         if self.path is not None and self.skip_connect:
             from .checkpoint import agent_from_file
             return agent_from_file(self.path, str(device), skip_connect=True)
@@ -380,6 +388,9 @@ class DeviceActor:
                                                                  C.byref(part), C.byref(h)))
         else:
             _lib.check(agent.lib.hsad_actor_create(env.h, agent.online.h, agent.target.h, self.replay.h, C.byref(cfg), C.byref(io), C.byref(h)))
+        for k, n in enumerate(self.partners.nets if self.partners is not None else []):
+            if n.temperature > 0:       # a greedy partner makes no call: the actor is the one built without the keyword
+                _lib.check(agent.lib.hsad_actor_set_partner_temperature(h, k, n.temperature))
         self.c_actor, self._lib = h, agent.lib
         nf = agent.lib.hsad_actor_n_finished_dev(h)
         from .composite import _view

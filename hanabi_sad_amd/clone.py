@@ -237,16 +237,19 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
                         truncated, ret)
 
 
-def records_from_teacher(pool, num_game, seed, sad, *, seating=None, num_player=2, bomb=0, device="cuda:0", names=None, **env_kw):
+def records_from_teacher(pool, num_game, seed, sad, *, seating=None, num_player=2, bomb=0, device="cuda:0", names=None, temperature=None,
+                         sample_seed=0, **env_kw):
     """play the games to clone -> [GameRecord], tagged with seat names: eval.play_seatings(pool, [seating], ..., records=True).  pool:
     rulebot.RuleBot members, weight dicts / files / agents, or both; seating: the pool index on every seat (default: member
-    p % len(pool) on seat p -- one teacher plays itself).  env_kw: hand_size and the rule keywords of play_seatings."""
+    p % len(pool) on seat p -- one teacher plays itself).  env_kw: hand_size and the rule keywords of play_seatings.
+    temperature / sample_seed: play_seatings' -- a network teacher at a temperature > 0 plays its softmax policy, so the set holds more
+    than one line of play per deal-and-position; the records keep the move made and the greedy move apart."""
     from .eval import play_seatings
     pool = list(pool)
     if seating is None:
         seating = [p % len(pool) for p in range(int(num_player))]
     res = play_seatings(pool, [list(seating)], int(num_game), int(seed), bomb, sad, device=device, records=True, names=names, bot_seed=int(seed),
-                        **env_kw)
+                        temperature=temperature, sample_seed=sample_seed, **env_kw)
     return res.records
 
 
@@ -308,6 +311,10 @@ def parse_args(argv=None):
     p.add_argument("--num_eval_game", type=int, default=1000)
     p.add_argument("--value_weight", type=float, default=0.0, help="> 0: also fit Q(o, a_recorded) to the discounted return of the recorded game "
                                                                    "(Huber), with this weight next to the cross-entropy")
+    p.add_argument("--eval_temperature", type=float, default=0.0, help="> 0: each epoch line also gives the self-play score of the net "
+                                                                       "playing its softmax policy at this temperature (1 = the fitted distribution)")
+    p.add_argument("--teacher_temperature", type=float, default=0.0, help="with --teacher: network teachers play their softmax policy at this "
+                                                                          "temperature (rule bots ignore it)")
     p.add_argument("--gamma", type=float, default=0.999, help="with --value_weight: the discount of the returns (the one TD training will use)")
     return p.parse_args(argv)
 
@@ -322,6 +329,9 @@ def main(argv=None):
     dev = args.train_device
     if bool(args.games) == bool(args.teacher):
         raise SystemExit("give either --games FILE or --teacher NAME")
+    for flag in ("eval_temperature", "teacher_temperature"):
+        if not np.isfinite(getattr(args, flag)) or getattr(args, flag) < 0:
+            raise SystemExit("--%s must be finite and not negative" % flag)
     if args.games:
         records = gr.load(args.games)
     else:
@@ -332,7 +342,8 @@ def main(argv=None):
             pool.append(PRESETS.get(entry, entry))
         names = [e if e in PRESETS else os.path.basename(e) for e in args.teacher]
         records = records_from_teacher(pool, args.num_game, args.seed, args.sad, num_player=args.num_player, bomb=args.eval_bomb, device=dev,
-                                       names=names, hand_size=args.hand_size, **game_rules(args))
+                                       names=names, hand_size=args.hand_size, temperature=args.teacher_temperature or None,
+                                       sample_seed=args.seed, **game_rules(args))
     if args.save_dir:
         os.makedirs(args.save_dir, exist_ok=True)
         if args.teacher:     # the games that were cloned, for --games of a later run
@@ -359,9 +370,15 @@ def main(argv=None):
         weights = {k: v.detach().clone() for k, v in learner.online.w.items()}
         score = evaluate(weights, args.num_eval_game, args.seed, args.eval_bomb, args.sad, num_player=r["players"], hand_size=r["hand_size"],
                          device=dev, **rules)[0]
+        if args.eval_temperature > 0:      # the policy the loss fits, next to its mode
+            soft = evaluate(weights, args.num_eval_game, args.seed, args.eval_bomb, args.sad, num_player=r["players"], hand_size=r["hand_size"],
+                            device=dev, temperature=args.eval_temperature, sample_seed=args.seed, **rules)[0]
+            score_text = "%.3f (sampled at temperature %g: %.3f)" % (score, args.eval_temperature, soft)
+        else:
+            score_text = "%.3f" % score
         value = ", value loss per step %.4f, held-out value loss per step %.4f" % (vtrain[0], vheld[0]) if vw > 0 else ""
-        print("epoch %d: loss per decision %.4f, agreement %.4f (%d / %d), held-out agreement %.4f (%d / %d), self-play score %.3f%s"
-              % (epoch, loss, hits / max(n, 1), hits, n, hh / max(hn, 1), hh, hn, score, value), flush=True)
+        print("epoch %d: loss per decision %.4f, agreement %.4f (%d / %d), held-out agreement %.4f (%d / %d), self-play score %s%s"
+              % (epoch, loss, hits / max(n, 1), hits, n, hh / max(hn, 1), hh, hn, score_text, value), flush=True)
         if args.save_dir:
             save_weights(weights, os.path.join(args.save_dir, "clone_epoch%d.pthw" % epoch))
             save_weights(weights, os.path.join(args.save_dir, "clone.pthw"))

@@ -117,10 +117,14 @@ class CompositeAgent:
         z = torch.zeros(self.online.L, n, self.online.H, dtype=torch.float32, device=self.device)
         return {"h0": z, "c0": z.clone()}
 
-    def act(self, obs, hid, with_q=False, defer_target=False):
+    def act(self, obs, hid, with_q=False, defer_target=False, sample_seed=None):
         """obs["priv_s"] float32 [N,F], or obs["priv_s_bf16"] [N, in_dim_padded] as the env's packed outputs provide it.
         with_q: also Q_online(s, a) and Q_target(s, greedy_a); defer_target: leave the target half to target_q() -- the caller
-        issues the env step (which only needs the actions) first and runs the two side by side"""
+        issues the env step (which only needs the actions) first and runs the two side by side.
+        obs["temp"] float32 [N] (hsad_r2d2_act_soft): the rows with temp > 0 sample their action from the softmax over the legal
+        advantages at that temperature, the others stay eps-greedy; obs["sample_key"] int64 [N] keys the sample draw by
+        (sample_seed, key) instead of (seed, row, counter) -- sample_seed defaults to the agent's seed.  The online net alone runs
+        (no Q_target: with_q needs defer_target).  Without obs["temp"] the call is hsad_r2d2_act, as ever."""
         n, on, d = obs["legal_move"].shape[0], self.online, self.device
         a = torch.empty(n, dtype=torch.int64, device=d)
         g = torch.empty(n, dtype=torch.int64, device=d)
@@ -136,10 +140,22 @@ class CompositeAgent:
         p16 = obs.get("priv_s_bf16")
         if p16 is not None and (p16.dtype != torch.bfloat16 or p16.shape[-1] != on.Fp or p16.numel() != n * on.Fp):
             raise _lib.HsadError("priv_s_bf16 must be bf16 [%d, %d]; got %s %s" % (n, on.Fp, p16.dtype, tuple(p16.shape)))
-        _lib.check(self.lib.hsad_r2d2_act(on.h, self.target.h if tq is not None else None, n, None if p16 is not None else p(obs["priv_s"]),
-                                          p(p16), p(obs["legal_move"]), p(eps),
-                                          p(hid["h0"]), p(hid["c0"]), p(h16_in), self.seed, self.counter, a.data_ptr(), g.data_ptr(),
-                                          h.data_ptr(), c.data_ptr(), p(h16), p(qa), p(tq), _s(d)))
+        temp = obs.get("temp")
+        if temp is not None:
+            if tq is not None:
+                raise _lib.HsadError("act with obs[\"temp\"] runs the online net alone: with_q needs defer_target=True")
+            key = obs.get("sample_key")
+            if temp.dtype != torch.float32 or temp.numel() != n or (key is not None and (key.dtype != torch.int64 or key.numel() != n)):
+                raise _lib.HsadError("temp must be float32 [%d] and sample_key int64 [%d]" % (n, n))
+            _lib.check(self.lib.hsad_r2d2_act_soft(on.h, n, None if p16 is not None else p(obs["priv_s"]), p(p16), p(obs["legal_move"]), p(eps),
+                                                   p(temp), p(key), (self.seed if sample_seed is None else int(sample_seed)) & ((1 << 64) - 1),
+                                                   p(hid["h0"]), p(hid["c0"]), p(h16_in), self.seed, self.counter, a.data_ptr(),
+                                                   g.data_ptr(), h.data_ptr(), c.data_ptr(), p(h16), p(qa), _s(d)))
+        else:
+            _lib.check(self.lib.hsad_r2d2_act(on.h, self.target.h if tq is not None else None, n, None if p16 is not None else p(obs["priv_s"]),
+                                              p(p16), p(obs["legal_move"]), p(eps),
+                                              p(hid["h0"]), p(hid["c0"]), p(h16_in), self.seed, self.counter, a.data_ptr(), g.data_ptr(),
+                                              h.data_ptr(), c.data_ptr(), p(h16), p(qa), p(tq), _s(d)))
         self.counter += 1
         reply, new_hid = {"a": a, "greedy_a": g}, {"h0": h, "c0": c}
         if fused:

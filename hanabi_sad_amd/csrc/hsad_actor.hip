@@ -14,6 +14,7 @@
 // nets and replay belong to the caller, as do the env's output buffers (hsad_actor_io = what the caller bound to the env).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>

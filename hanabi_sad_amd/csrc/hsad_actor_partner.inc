@@ -200,6 +200,8 @@ struct PartnerNet {
   bool fused = false;              // n >= 1024: the bf16 copy of the state is carried (the learner's fused_state rule per net)
   float *h[2] = {nullptr, nullptr}, *c[2] = {nullptr, nullptr};
   void* h16[2] = {nullptr, nullptr};
+  float* temp = nullptr;           // [n], every entry tau (hsad_actor_set_partner_temperature); read by the act call only while tau > 0
+  float tau = 0.f;
 };
 
 // what a partnered actor holds on top of hsad_actor
@@ -252,6 +254,12 @@ int partner_step(hsad_actor* ac, void* stream) {
   const int ncur = pt->net_cur, nnxt = ncur ^ 1;
   for (int k = 0; k < pt->n_net; ++k) {
     const PartnerNet& pn = pt->nets[k];
+    if (pn.tau > 0.f) {   // the partner plays its softmax policy: the same net pass, the sampling tail
+      CK(hsad_r2d2_act_soft(pn.net, pn.n, nullptr, pt->g.c_obs16 + (size_t)pn.off * pt->g.n_obs, pt->g.c_legal + (size_t)pn.off * pt->g.A, nullptr,
+                            pn.temp, nullptr, 0, pn.h[ncur], pn.c[ncur], pn.fused ? pn.h16[ncur] : nullptr, ac->seed, pt->net_counter,
+                            pt->a_c + pn.off, pt->g_c + pn.off, pn.h[nnxt], pn.c[nnxt], pn.fused ? pn.h16[nnxt] : nullptr, nullptr, stream));
+      continue;
+    }
     CK(hsad_r2d2_act(pn.net, nullptr, pn.n, nullptr, pt->g.c_obs16 + (size_t)pn.off * pt->g.n_obs, pt->g.c_legal + (size_t)pn.off * pt->g.A, nullptr,
                      pn.h[ncur], pn.c[ncur], pn.fused ? pn.h16[ncur] : nullptr, ac->seed, pt->net_counter, pt->a_c + pn.off, pt->g_c + pn.off,
                      pn.h[nnxt], pn.c[nnxt], pn.fused ? pn.h16[nnxt] : nullptr, nullptr, nullptr, stream));
@@ -375,7 +383,7 @@ extern "C" int hsad_actor_create_partnered_nets(hsad_env* env, hsad_r2d2_net* on
     pn.H = net_H[k];
     pn.fused = pn.n >= 1024;
     const size_t nh = (size_t)pn.L * pn.n * pn.H;
-    net_bytes += 2 * (2 * up(nh * 4) + up(nh * 2));
+    net_bytes += 2 * (2 * up(nh * 4) + up(nh * 2)) + up((size_t)pn.n * 4);
   }
   const size_t n_all = rows_all.size();
   pt->n_all = (int)n_all;
@@ -439,6 +447,7 @@ extern "C" int hsad_actor_create_partnered_nets(hsad_env* env, hsad_r2d2_net* on
       pn.c[slot] = (float*)take(nh * 4);
       pn.h16[slot] = (void*)take(nh * 2);
     }
+    pn.temp = (float*)take((size_t)pn.n * 4);
   }
   // seat[r] = -(e + 1) means "this row's action is entry e of the compact act output", for the learner's rows and the nets' alike
   std::vector<int32_t> seat(N);
@@ -461,5 +470,21 @@ extern "C" int hsad_actor_partner_state(hsad_actor* ac, int k, float** h, float*
   *h = pt->nets[k].h[pt->net_cur];
   *c = pt->nets[k].c[pt->net_cur];
   if (n_rows) *n_rows = pt->nets[k].n;
+  return 0;
+}
+
+extern "C" int hsad_actor_set_partner_temperature(hsad_actor* ac, int k, float tau) {
+  if (!ac) return xfail(HSAD_ERR_INVALID, "actor_set_partner_temperature: null actor");
+  PartnerSeats* pt = ac->partner;
+  if (!pt || k < 0 || k >= pt->n_net)
+    return xfail(HSAD_ERR_INVALID, "actor_set_partner_temperature: net %d, the actor has %d network partners", k, pt ? pt->n_net : 0);
+  if (!(tau >= 0.f) || !std::isfinite(tau))
+    return xfail(HSAD_ERR_INVALID, "actor_set_partner_temperature: the temperature must be finite and >= 0; got %g", (double)tau);
+  PartnerNet& pn = pt->nets[k];
+  // rare and host-side: wait for the steps that may still read the vector, then write it with a blocking copy
+  const std::vector<float> v((size_t)pn.n, tau);
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(pn.temp, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return xfail(HSAD_ERR_HIP, "actor_set_partner_temperature: writing the temperature vector failed");
+  pn.tau = tau;
   return 0;
 }

@@ -479,6 +479,41 @@ int hsad_r2d2_act(hsad_r2d2_net* online, hsad_r2d2_net* target, int N, const flo
   return 0;
 }
 
+// hsad_r2d2_act's single-net path with the sampling tail (hsad_act_sample_q): the same workspace layout, cast, net_step and heads GEMM
+// as hsad_r2d2_act(online = net, target = NULL), so the new state and -- with temp == NULL -- every output are that call's bits
+int hsad_r2d2_act_soft(hsad_r2d2_net* net, int N, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const float* eps,
+                       const float* temp, const int64_t* row_key, uint64_t sample_seed, const float* h0, const float* c0,
+                       const void* h0_bf16, uint64_t seed, uint64_t counter, int64_t* a, int64_t* greedy_a, float* h_out, float* c_out,
+                       void* h_out_bf16, float* q_online_a, void* stream) {
+  if (net) CK(net_wait(net, (hipStream_t)stream));
+  if (!net || (!priv_s && !priv_s_bf16) || !legal_move || !h0 || !c0 || !a || !greedy_a || !h_out || !c_out || N < 1)
+    return afail(HSAD_ERR_INVALID, "r2d2_act_soft: null argument");
+  if (q_online_a && net->skip)
+    return afail(HSAD_ERR_INVALID, "r2d2_act_soft: cached Q-values are undefined for a skip_connect net (see hsad_r2d2_act)");
+  hsad_r2d2_net* n = net;
+  hipStream_t s = (hipStream_t)stream;
+  const int H = n->H, A = n->A, NH = n->NH;
+  const size_t a16_b = (size_t)N * n->Fp * 2, hd_b = (size_t)N * NH * 4, sc_b = (4 + (N + 255) / 256) * 4;
+  const size_t step_b = step_ws_bytes(n, N);
+  CK(n->ws.need(a16_b + 2 * step_b + 2 * hd_b + sc_b + 1024));
+  char* p = n->ws.as<char>();
+  bf16_t* a16 = (bf16_t*)p;
+  p += a16_b;
+  char* ws_on = p;
+  p += 2 * step_b;
+  float* hd = (float*)p;
+  p += 2 * hd_b;
+  float* scratch = (float*)p;
+  if (priv_s_bf16) a16 = (bf16_t*)priv_s_bf16;
+  else CK(hsad_cast_pad_bf16(priv_s, N, n->F, n->F, a16, n->Fp, stream));
+  if (h_out_bf16 && h_out_bf16 == h0_bf16) return afail(HSAD_ERR_INVALID, "r2d2_act_soft: h_out_bf16 must not alias h0_bf16");
+  StepOut so{};
+  CK(net_step(n, N, a16, h0, c0, (const bf16_t*)h0_bf16, h_out, c_out, ws_on, &so, s, (bf16_t*)h_out_bf16, false, true));
+  CK(hsad_gemm_nt_bf16(so.o16, H, n->Wheads, H, N, NH, H, n->bheads, hd, NH, nullptr, 0, 0, 0, stream));
+  CK(hsad_act_sample_q(hd, NH, legal_move, eps, temp, row_key, sample_seed, N, A, seed, counter, a, greedy_a, q_online_a, scratch, stream));
+  return 0;
+}
+
 // Q_target(s, greedy_a) alone: the target-net half of an acting step as its own call, so that a caller can issue the env step
 // (which only needs the online half's actions) before it and run the two side by side (actor.DeviceActor does)
 int hsad_r2d2_target_q(hsad_r2d2_net* target, int N, const float* priv_s, const void* priv_s_bf16, const float* legal_move,

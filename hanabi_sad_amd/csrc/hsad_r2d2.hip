@@ -32,6 +32,7 @@
 
 #include "hsad.h"
 #include "hsad_gemm_plan.h"
+#include "hsad_act_sample.h"
 
 extern "C" int hsad_internal_set_error(int code, const char* msg);
 
@@ -50,6 +51,7 @@ namespace {
 #include "r2d2/clone_loss.inc"
 #include "r2d2/clone_value.inc"
 #include "r2d2/act.inc"
+#include "r2d2/act_sample.inc"
 }  // namespace
 
 // ---- launch helpers for the persistent recurrences (nrec independent recurrences per launch) ----
@@ -1252,6 +1254,25 @@ int hsad_act_select_q2(const float* heads, const float* heads_target, int ldh, c
   hipLaunchKernelGGL(act_select_q_kernel, dim3((N + R - 1) / R), dim3(256), (size_t)R * (2 * ldh + A) * 4, s, heads, ldh, legal, eps,
                      scratch + 1, nb, N, A, (unsigned long long)seed, (unsigned long long)counter, a_out, greedy_out, qa_out, R, heads_target,
                      q_target_greedy);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+// hsad_act_select_q for seats that play their softmax policy: rows with temp[m] > 0 sample from the softmax over the legal advantages at
+// that temperature (csrc/hsad_act_sample.h); rows with temp[m] <= 0, and every row when temp is NULL, are hsad_act_select_q's rows
+int hsad_act_sample_q(const float* heads, int ldh, const float* legal, const float* eps, const float* temp, const int64_t* row_key,
+                      uint64_t sample_seed, int N, int A, uint64_t seed, uint64_t counter, int64_t* a_out, int64_t* greedy_out,
+                      float* qa_out, float* scratch, void* stream) {
+  if (!heads || !legal || !a_out || !greedy_out || !scratch) return nfail(HSAD_ERR_INVALID, "act_sample_q: null");
+  if (N < 1 || A < 1 || ldh <= A) return nfail(HSAD_ERR_INVALID, "act_sample_q: needs N >= 1 and rows of A advantages and the value (ldh > A)");
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = (N + 255) / 256;
+  const int R = staged_rows(ldh, A);
+  if (R < 1) return nfail(HSAD_ERR_INVALID, "act_sample_q: heads / legal rows too wide for the staged kernel");
+  hipLaunchKernelGGL(adv_min_kernel, dim3(nb), dim3(256), 0, s, heads, ldh, N, A, scratch + 1);
+  hipLaunchKernelGGL(act_sample_q_kernel, dim3((N + R - 1) / R), dim3(256), (size_t)R * (ldh + A) * 4, s, heads, ldh, legal, eps, temp, row_key,
+                     (unsigned long long)sample_seed, scratch + 1, nb, N, A, (unsigned long long)seed, (unsigned long long)counter, a_out,
+                     greedy_out, qa_out, R);
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
 }

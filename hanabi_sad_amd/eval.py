@@ -14,14 +14,88 @@ from .r2d2 import R2D2Agent, R2D2NetKernels
 from .rulebot import RuleBot
 
 
+SAMPLE_KEY_STEPS = 4096      # move numbers per (deal, seat) in a sample key: max_steps may not exceed it when a seat samples
+
+
+def sample_key_base(deal_seed, seat):
+    """the sample key of (deal seed, seat, move t) is sample_key_base + t: injective over the deals of one call (seat < 8,
+    t < SAMPLE_KEY_STEPS; int64 arithmetic, wrapping).  deal_seed, seat: int64 tensors"""
+    return (deal_seed * 8 + seat) * SAMPLE_KEY_STEPS
+
+
+def pool_temperatures(temperature, K):
+    """the `temperature` argument of play_seatings / cross_play -> None (nobody samples: the greedy code path) or float32 [K].
+    None, a number for every member, or one number per member; negative and non-finite values are refused"""
+    if temperature is None:
+        return None
+    t = np.asarray(temperature, dtype=np.float64)
+    if t.ndim == 0:
+        t = np.full(K, float(t))
+    if t.ndim != 1 or len(t) != K:
+        raise ValueError("temperature must be None, one number, or one per pool member (%d); got shape %s" % (K, tuple(t.shape)))
+    if not np.all(np.isfinite(t)) or np.any(t < 0):
+        raise ValueError("temperatures must be finite and >= 0; got %s" % t.tolist())
+    return t.astype(np.float32) if np.any(t > 0) else None
+
+
+def _is_bf16_kernel_agent(x):
+    """the Python-orchestrated bf16 agent: r2d2.R2D2Agent over an R2D2NetKernels (what checkpoint.agent_from_file builds for the
+    default architecture at bf16).  It has no sampling tail itself, but its fp32 master weights make the composite agent that has"""
+    return isinstance(x, R2D2Agent) and type(x.online) is R2D2NetKernels
+
+
+def _samples_on_device(x, precision):
+    """can this pool member (as _check_pool returns it) play at a temperature?  The sampling tail belongs to the library's bf16 agent
+    (composite.CompositeAgent): weight dicts become one at precision "bf16", and a bf16 R2D2Agent is re-seated as one over its own
+    weights (_soft_agent).  The fp32 agents (R2D2Agent over R2D2NetF32, weights at precision "fp32"), obl.OBLAgent and
+    rela.ContractAgent are not"""
+    from .composite import CompositeAgent
+    if isinstance(x, dict):
+        return precision == "bf16"
+    return isinstance(x, CompositeAgent) or _is_bf16_kernel_agent(x)
+
+
+def _soft_agent(x, precision, device):
+    """the acting agent of a member that plays at a temperature > 0 (check_pool_temperatures has passed it): a CompositeAgent.  A bf16
+    R2D2Agent is re-seated as CNet + CompositeAgent over its online net's fp32 master weights -- the same kernels behind one library
+    call, as NetPartner.seating_member does for a borrowed net; a member at temperature 0 keeps the agent it always had"""
+    if _is_bf16_kernel_agent(x):
+        from .composite import CNet, CompositeAgent
+        net = CNet(x.online.w, device)
+        return CompositeAgent(net, net, 1, 0.99)
+    return _acting_agent(x, precision, device)
+
+
+def check_pool_temperatures(models, temps, names, precision):
+    """refuses, before any device work, a temperature > 0 on a member without the sampling tail (rule bots ignore theirs)"""
+    if temps is None:
+        return
+    for k, (x, t) in enumerate(zip(models, temps)):
+        if t > 0 and not isinstance(x, RuleBot) and not _samples_on_device(x, precision):
+            raise ValueError("pool member %d (%s) cannot play at temperature %g: only bf16 kernel agents (weights at precision \"bf16\", "
+                             "composite.CompositeAgent, a bf16 r2d2.R2D2Agent) sample their softmax policy; fp32 nets, obl.OBLAgent, "
+                             "rela.ContractAgent and bare nets act greedily" % (k, names[k], t))
+
+
 def evaluate(weights, num_game, seed, bomb, sad, *, num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16",
-             shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3):
+             shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3, temperature=0.0, sample_seed=0):
     """-> (mean score, fraction of perfect games, scores list, num perfect) like eval.evaluate.  `weights`: a weight dict, or
-    an R2D2Agent / net already on the device (its online net acts for every player)"""
+    an R2D2Agent / net already on the device (its online net acts for every player).  temperature > 0 (bf16 kernel agents only): every
+    player samples its move from the softmax over the legal advantages at that temperature, keyed by (sample_seed; deal seed, seat,
+    move number) like play_seatings, whose one-member tournament over the same deals plays the same games"""
+    temperature = float(temperature)
+    if not np.isfinite(temperature) or temperature < 0:
+        raise ValueError("temperature must be finite and >= 0; got %r" % temperature)
+    if temperature > 0:
+        check_pool_temperatures([weights], [temperature], ["weights"], precision)
+        if max_steps > SAMPLE_KEY_STEPS:
+            raise ValueError("max_steps %d exceeds the %d moves a sample key numbers" % (max_steps, SAMPLE_KEY_STEPS))
     env = BatchedHanabiEnv(num_game, players=num_player, hand_size=hand_size, seed=seed, bomb=bomb, eps_list=[0.0],
                            max_len=-1, sad=bool(sad), shuffle_color=bool(shuffle_color), device=device, track_deck_history=False,
                            colors=colors, ranks=ranks, max_information_tokens=max_information_tokens, max_life_tokens=max_life_tokens)
-    if isinstance(weights, R2D2Agent):
+    if temperature > 0:
+        agent = _soft_agent(weights, precision, device)
+    elif isinstance(weights, R2D2Agent):
         agent = R2D2Agent(weights.online, weights.online, 1, 0.99)
     elif hasattr(weights, "act") and hasattr(weights, "get_h0"):
         agent = weights                      # any acting agent (obl.OBLAgent, rela.ContractAgent): used as it is
@@ -39,9 +113,17 @@ def evaluate(weights, num_game, seed, bomb, sad, *, num_player=2, hand_size=5, d
     env.reset()
     done = torch.zeros(num_game, dtype=torch.bool, device=device)
     noop = env.A - 1
-    for _ in range(max_steps):
+    if temperature > 0:
+        row = torch.arange(N, dtype=torch.int64, device=device)
+        key0 = sample_key_base(row // num_player + int(seed), row % num_player)
+        temp = torch.full((N,), temperature, dtype=torch.float32, device=device)
+    for t in range(max_steps):
         obs = {"priv_s": env.priv_s.view(N, env.F), "legal_move": env.legal_move.view(N, env.A), "eps": env.eps.view(N)}
-        reply, hid = agent.act(obs, hid)
+        if temperature > 0:
+            obs["temp"], obs["sample_key"] = temp, key0 + t
+            reply, hid = agent.act(obs, hid, sample_seed=sample_seed)
+        else:
+            reply, hid = agent.act(obs, hid)
         a = reply["a"].view(num_game, num_player)
         # finished games may not be stepped again (HanabiEnv::step asserts !terminated()): park them on a copy that
         # the kernel ignores by keeping their state untouched -> step only the live ones through a masked action
@@ -217,8 +299,15 @@ class SeatingScores:
 class _SeatedModel:
     """one pool member inside a tournament batch: its rows, its act operands and its carried state"""
 
-    def __init__(self, agent, rows, env, device):
+    def __init__(self, agent, rows, env, device, temperature=0.0, deals=None):
         self.agent, self.n = agent, int(len(rows))
+        # a member that samples: its temperature on every row, and what the sample key of a row is made of (game s * deals + d
+        # plays deal d; the seat is the row's player) -- key0 is set per chunk by _TournamentBatch.play
+        self.temp = self.key0 = None
+        if temperature > 0:
+            self.temp = torch.full((self.n,), float(temperature), dtype=torch.float32, device=device)
+            self.deal = torch.from_numpy((rows.astype(np.int64) // env.P) % int(deals)).to(device)
+            self.seat = torch.from_numpy(rows.astype(np.int64) % env.P).to(device)
         self.rows = torch.from_numpy(rows).to(device)
         self.bf16 = bool(getattr(agent, "accepts_bf16_obs", False))
         self.Kp = agent.online.Fp if self.bf16 else env.F
@@ -231,9 +320,10 @@ class _SeatedModel:
 class _TournamentBatch:
     """one env object of S x n games (seating-major) and the pool seated on it; play(seed) runs one chunk of n deals"""
 
-    def __init__(self, agents, seatings, n, env_kw, device, bot_seed=0, behaviour=False, records=None):
+    def __init__(self, agents, seatings, n, env_kw, device, bot_seed=0, behaviour=False, records=None, temps=None, sample_seed=0):
         S, P = seatings.shape
         self.n, self.S = n, S
+        self.sample_seed = int(sample_seed)
         self.behaviour = torch.zeros(S, P, len(BEHAVIOUR_NAMES), dtype=torch.int64, device=device) if behaviour else None
         # a record needs the deal: only a recording tournament's env tracks its deck history
         self.env = env = BatchedHanabiEnv(S * n, players=P, seed=0, eps_list=[0.0], max_len=-1, device=device,
@@ -244,8 +334,8 @@ class _TournamentBatch:
             self.recorder, self.where = GameRecorder(env), (None if records is True else records)
         self.lib, self.device = env.lib, env.device
         owned = seating_rows(seatings, n, len(agents))
-        self.models = [_SeatedModel(ag, rows, env, self.device)
-                       for ag, rows in zip(agents, owned) if len(rows) and not isinstance(ag, RuleBot)]
+        self.models = [_SeatedModel(ag, rows, env, self.device, 0.0 if temps is None else float(temps[k]), n)
+                       for k, (ag, rows) in enumerate(zip(agents, owned)) if len(rows) and not isinstance(ag, RuleBot)]
         # the rule bots of the pool own no _SeatedModel: one policy_rule call per step serves all their rows
         seated_bots = [k for k, ag in enumerate(agents) if isinstance(ag, RuleBot) and len(owned[k])]
         self.bots, self.bot_seed = [agents[k] for k in seated_bots], int(bot_seed)
@@ -265,13 +355,17 @@ class _TournamentBatch:
         self.host = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)]
         self.copied = [torch.cuda.Event() for _ in range(2)]
 
-    def _act(self, m):
+    def _act(self, m, t=0):
         env, lib, st = self.env, self.lib, self.env._stream()
         src = env.priv_s_bf16 if m.bf16 else env.priv_s
         _lib.check(lib.hsad_seat_gather(m.rows.data_ptr(), m.n, env.G * env.P, 0 if m.bf16 else 2, src.data_ptr(), env.F, m.Kp,
                                    env.legal_move.data_ptr(), env.A, m.obs.data_ptr(), m.legal.data_ptr(), st))
         obs = {"priv_s_bf16" if m.bf16 else "priv_s": m.obs, "legal_move": m.legal, "eps": m.eps}
-        reply, m.hid = m.agent.act(obs, m.hid)
+        if m.temp is not None:      # the key names (deal, seat, move): a deal plays the same in every chunking
+            obs["temp"], obs["sample_key"] = m.temp, m.key0 + t
+            reply, m.hid = m.agent.act(obs, m.hid, sample_seed=self.sample_seed)
+        else:
+            reply, m.hid = m.agent.act(obs, m.hid)
         a, g = reply["a"].contiguous(), reply["greedy_a"].contiguous()
         _lib.check(lib.hsad_seat_scatter(env.h, m.rows.data_ptr(), m.n, a.data_ptr(), g.data_ptr(), env.a.data_ptr(),
                                     env.greedy_a.data_ptr(), st))
@@ -288,10 +382,12 @@ class _TournamentBatch:
             self.recorder.clear()
         for m in self.models:
             m.hid = m.agent.get_h0(m.n)
+            if m.temp is not None:
+                m.key0 = sample_key_base(m.deal + int(seed), m.seat)
         done = False
         for t in range(max_steps):
             for m in self.models:
-                self._act(m)
+                self._act(m, t)
             if self.bots:     # the hash of a *_RANDOM rule is keyed by the deal's seed: a deal plays the same in every chunking
                 env.policy_rule(self.bots, self.seat_bot, seed=self.bot_seed, key=self.deal + int(seed))
             if self.behaviour is not None:     # every seat's action is merged and the env not yet stepped: the moves about to be made
@@ -326,7 +422,7 @@ class _TournamentBatch:
 
 def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_launch=1 << 18, precision="bf16", device="cuda:0",
                   hand_size=5, shuffle_color=False, colors=5, ranks=5, max_information_tokens=8, max_life_tokens=3, max_steps=200,
-                  bot_seed=0, behaviour=False, records=None, names=None):
+                  bot_seed=0, behaviour=False, records=None, names=None, temperature=None, sample_seed=0):
     """Every seating of a model pool over the SAME deals, in one batched run -> SeatingScores.
 
     agents: the pool -- whatever `evaluate` accepts (weight dicts, kernel agents / nets, any object with act / get_h0 such as
@@ -346,7 +442,14 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
     records=True, or a game_record.GameFilter, also writes every game down on the device (one hsad_game_log_append launch per step
     at that same point; the env then tracks its deck history) and returns the finished games the filter keeps as
     SeatingScores.records, tagged with seating, deal seed and seat names (names: one per pool member; default a RuleBot's own name,
-    "model<k>" otherwise).  The games are the same either way."""
+    "model<k>" otherwise).  The games are the same either way.
+
+    temperature: None, one number, or one per pool member.  A member with temperature > 0 plays its softmax policy: each of its moves is
+    sampled from the softmax over the legal advantages at that temperature (hsad_r2d2_act_soft; at 1 the distribution behaviour cloning
+    fits) instead of their argmax.  The draw is keyed by sample_seed and (deal seed, seat, move number), so a deal plays the same in
+    every games_per_launch chunking and the same call gives the same games.  Rule bots ignore their entry; a member with a
+    temperature > 0 that is not a bf16 kernel agent is refused.  Records keep `a` and `greedy_a` apart, as for eps-greedy play.
+    None or all zeros runs the greedy calls: the same launches and the same bits as without the argument."""
     try:
         shape = tuple(np.asarray(seatings).shape)
     except ValueError:                    # seatings of different widths
@@ -361,7 +464,15 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
         raise ValueError("num_game must be >= 1")
     models, seatings = _check_pool(agents, seatings, P, F, A)
     S = seatings.shape[0]
-    acting = [x if isinstance(x, RuleBot) else _acting_agent(x, precision, device) for x in models]
+    if names is None:
+        names = [getattr(x, "name", None) if isinstance(x, RuleBot) else None for x in models]
+        names = [n if n is not None else "model%d" % k for k, n in enumerate(names)]
+    temps = pool_temperatures(temperature, len(models))
+    check_pool_temperatures(models, temps, names, precision)
+    if temps is not None and max_steps > SAMPLE_KEY_STEPS:
+        raise ValueError("max_steps %d exceeds the %d moves a sample key numbers" % (max_steps, SAMPLE_KEY_STEPS))
+    acting = [x if isinstance(x, RuleBot) else
+              (_soft_agent if temps is not None and temps[k] > 0 else _acting_agent)(x, precision, device) for k, x in enumerate(models)]
     env_kw = dict(hand_size=hand_size, bomb=bomb, sad=bool(sad), shuffle_color=bool(shuffle_color), **rules)
     per = max(1, min(int(num_game), int(games_per_launch) // S))
     scores = np.zeros((S, num_game), dtype=np.int64)
@@ -370,15 +481,12 @@ def play_seatings(agents, seatings, num_game, seed, bomb, sad, *, games_per_laun
     game_moves = np.zeros((S, num_game), dtype=np.int64) if behaviour else None
     if records is False:
         records = None
-    if names is None:
-        names = [getattr(x, "name", None) if isinstance(x, RuleBot) else None for x in models]
-        names = [n if n is not None else "model%d" % k for k, n in enumerate(names)]
     kept = [] if records is not None else None
     batches = {}
     for start in range(0, num_game, per):
         n = min(per, num_game - start)
         if n not in batches:
-            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device, bot_seed, bool(behaviour), records)
+            batches[n] = _TournamentBatch(acting, seatings, n, env_kw, device, bot_seed, bool(behaviour), records, temps, sample_seed)
             if (batches[n].env.F, batches[n].env.A) != (F, A):
                 raise _lib.HsadError("env_dims gives (%d, %d), the library (%d, %d)" % (F, A, batches[n].env.F, batches[n].env.A))
         sc, tt = batches[n].play(seed + start, max_steps)

@@ -48,6 +48,10 @@ def parse_args(argv=None):
     p.add_argument("--save_games_where", default=None, type=str, metavar="FILTER", help="with --save_games: comma-separated terms "
                    "score / moves (<=, >=, =), lives<=K, end=lives|deck|perfect, flag=NAME, seat=P (game_record.GameFilter.parse), "
                    "e.g. \"score<=10,flag=last_life,seat=1\"")
+    p.add_argument("--temperature", default=None, type=float, nargs="+", metavar="T", help="the models play their softmax policy: moves "
+                   "sampled from the softmax over the legal advantages at this temperature (one value, or one per model; 0 = greedy; "
+                   "bf16 models only; --bots ignore it)")
+    p.add_argument("--sample_seed", default=0, type=int, help="with --temperature: seeds the sample draws")
     p.add_argument("--root", default=None, type=str, help="folder that holds models/op/<method>/M{idx}.pthw (default: the repository)")
     p.add_argument("--precision", default="bf16", type=str, choices=["bf16", "fp32"])
     p.add_argument("--search_worlds", default=0, type=int, help="> 0 with a single --idx: also play with blueprint-policy search "
@@ -130,7 +134,11 @@ def main(argv=None):
             where = GameFilter.parse(args.save_games_where) if args.save_games_where else True
         except ValueError as e:
             raise SystemExit("--save_games_where: %s" % e)
+    if args.temperature is not None and any(not t >= 0 or t == float("inf") for t in args.temperature):
+        raise SystemExit("--temperature must be finite and not negative")
     if args.search_worlds > 0:
+        if args.temperature is not None:
+            raise SystemExit("--temperature samples tournament seats (no --search_worlds: the search plays the blueprint's greedy moves)")
         if args.save_games:
             raise SystemExit("--save_games records tournament games (no --search_worlds)")
         return search_report(args)
@@ -140,6 +148,11 @@ def main(argv=None):
     sad = args.paper == "obl" or getattr(net, "F", None) == env_dims(P, kw["hand_size"], sad=True)[0]
     if args.bots and not args.cross_play:
         raise SystemExit("--bots needs --cross_play (the bots join the pool of the matrix)")
+    if args.temperature is not None:
+        if len(args.temperature) not in (1, len(agents)):
+            raise SystemExit("--temperature takes one value or one per model (%d); got %d" % (len(agents), len(args.temperature)))
+        temps = list(args.temperature) * (len(agents) if len(args.temperature) == 1 else 1)
+        kw.update(temperature=temps + [0.0] * (len(args.bots) if args.cross_play else 0), sample_seed=args.sample_seed)
     if args.cross_play:
         agents, names = agents + [PRESETS[b] for b in args.bots], names + list(args.bots)
         if P != 2:

@@ -57,22 +57,23 @@ def game_rules(args):
     return {k: int(getattr(args, k, d)) for k, d in (("colors", 5), ("ranks", 5), ("max_information_tokens", 8), ("max_life_tokens", 3))}
 
 
-def parse_partner(entry):
+def parse_partner(entry, temperature=0.0):
     """one --partner entry: a rule-bot preset of rulebot.py, or the path of a weight file (`PATH:skip`: a skip_connect net) ->
-    rulebot.RuleBot or actor.NetPartner; ValueError, naming both readings, for an entry that is neither"""
+    rulebot.RuleBot or actor.NetPartner (at `temperature`, --partner_temperature); ValueError, naming both readings, for an entry that
+    is neither"""
     from .actor import NetPartner
     from .rulebot import PRESETS
     if entry in PRESETS:
         return PRESETS[entry]
     path, skip = (entry[:-len(":skip")], True) if entry.endswith(":skip") else (entry, False)
     if os.path.isfile(path):
-        return NetPartner(path, skip_connect=skip)
+        return NetPartner(path, skip_connect=skip, temperature=temperature)
     raise ValueError("--partner %s: no rule-bot preset of that name (have: %s) and no weight file at %s" % (entry, ", ".join(sorted(PRESETS)), path))
 
 
 def partner_bots(args):
     """the partners of --partner, in the order given: rule bots (presets of rulebot.py) and frozen networks (weight files)"""
-    return [parse_partner(entry) for entry in getattr(args, "partner", None) or []]
+    return [parse_partner(entry, float(getattr(args, "partner_temperature", 0.0))) for entry in getattr(args, "partner", None) or []]
 
 
 def partner_seats(args, num_game):
@@ -97,7 +98,9 @@ def print_partner_scores(args, weights, num_game, seed, device):
     seatings = [[0 if p == seat else k for p in range(P)] for k in range(1, len(bots) + 1) for seat in range(P)]
     pool = [b.seating_member(device) if isinstance(b, NetPartner) else b for b in bots]
     xp = play_seatings([weights] + pool, seatings, num_game, seed, args.eval_bomb, args.sad, hand_size=args.hand_size, device=str(device),
-                       shuffle_color=bool(args.shuffle_color), bot_seed=args.seed, behaviour=behaviour, **game_rules(args))
+                       shuffle_color=bool(args.shuffle_color), bot_seed=args.seed, behaviour=behaviour,
+                       temperature=[0.0] + [b.temperature if isinstance(b, NetPartner) else 0.0 for b in bots], sample_seed=args.seed,
+                       **game_rules(args))
     scores = []
     for k, bot in enumerate(bots):
         m = xp.mean[k * P:(k + 1) * P]
@@ -358,6 +361,9 @@ def parse_args(argv=None):
                    "per partner gives the score of the current weights seated with that partner")
     p.add_argument("--partner_seats", type=str, default="alternate", help="with --partner: alternate = the learner's seat is g %% P and the "
                    "bots take turns over the games; 0, 1, ... = the learner keeps that seat in every game")
+    p.add_argument("--partner_temperature", type=float, default=0.0, help="with --partner: every frozen-network partner plays its softmax "
+                   "policy at this temperature (moves sampled from the softmax over its legal advantages; 1 = the distribution behaviour "
+                   "cloning fits), in training and in the partner evaluation games; 0 = greedy partners")
     p.add_argument("--partner_behaviour", type=int, default=0, help="with --partner, 1: under each `partner NAME: score` line two more, the "
                    "behaviour rates (who hints, who plays unsure, ...: eval.BehaviourStats) of the learner's and of the partner's seats")
     p.add_argument("--early_draw", type=int, default=1, help="with --draw_ahead and the composite learner: priority write-back and the next draw are "

@@ -926,6 +926,16 @@ int hsad_zero_rows(float* x, const uint8_t* flag, int L, int N, int H, int rows_
  * (hsad_q_head's value at a_out; qa_out may be NULL), and Q(s, action) alone for the target pass */
 int hsad_act_select_q(const float* heads, int ldh, const float* legal, const float* eps, int N, int A, uint64_t seed,
                       uint64_t counter, int64_t* a_out, int64_t* greedy_out, float* qa_out, float* scratch, void* stream);
+/* hsad_act_select_q for seats that play their softmax policy.  temp [N] (NULL = all 0): a row with temp[m] <= 0 is hsad_act_select_q's row
+ * bit for bit (a, greedy, qa).  On a row with temp[m] > 0 the exploration draw comes first (same hash, same uniform legal action when it
+ * fires); otherwise a = an action sampled from softmax(adv_j / temp[m]) over the legal j -- at temp 1 the distribution whose
+ * cross-entropy hsad_r2d2_clone_fwd minimises.  greedy_out is always hsad_act_select_q's; qa_out (optional) = hsad_q_at(heads, ..., a_out).
+ * The sample uniform comes from the exploration hash of (seed, row, counter) by one more mixing round, or, with row_key int64 [N],
+ * from (sample_seed, row_key[m]) alone: no row index and no counter, the caller owns uniqueness (and a row then plays the same wherever
+ * it lies in the batch).  Draws, Pick and its fp32 range: csrc/hsad_act_sample.h.  scratch as hsad_act_select_q. */
+int hsad_act_sample_q(const float* heads, int ldh, const float* legal, const float* eps, const float* temp, const int64_t* row_key,
+                      uint64_t sample_seed, int N, int A, uint64_t seed, uint64_t counter, int64_t* a_out, int64_t* greedy_out,
+                      float* qa_out, float* scratch, void* stream);
 /* the same plus hsad_q_at(heads_target, greedy action) in ONE launch: the tail of hsad_r2d2_act when the two nets' heads come out of one
  * paired GEMM (Q_online(s, a) and Q_target(s, greedy) of r2d2.py:341-368 for the priorities); identical bits to the two calls */
 int hsad_act_select_q2(const float* heads, const float* heads_target, int ldh, const float* legal, const float* eps, int N, int A,
@@ -1118,6 +1128,13 @@ int hsad_r2d2_act(hsad_r2d2_net* online, hsad_r2d2_net* target, int N, const flo
                   const float* legal_move, const float* eps, const float* h0, const float* c0, const void* h0_bf16, uint64_t seed, uint64_t counter,
                   int64_t* a, int64_t* greedy_a, float* h_out, float* c_out, void* h_out_bf16, float* q_online_a,
                   float* q_target_greedy, void* stream);
+/* hsad_r2d2_act's single-net path (target = NULL) with hsad_act_sample_q as its tail: temp [N], row_key int64 [N] and sample_seed as
+ * there.  With temp == NULL every output equals hsad_r2d2_act(net, NULL, ...) bit for bit; h_out / c_out never depend on temp.
+ * q_online_a (optional) = Q_net(s, a) at the action taken; refused on a skip_connect net like hsad_r2d2_act's. */
+int hsad_r2d2_act_soft(hsad_r2d2_net* net, int N, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const float* eps,
+                       const float* temp, const int64_t* row_key, uint64_t sample_seed, const float* h0, const float* c0,
+                       const void* h0_bf16, uint64_t seed, uint64_t counter, int64_t* a, int64_t* greedy_a, float* h_out, float* c_out,
+                       void* h_out_bf16, float* q_online_a, void* stream);
 /* the two halves of that call separately: hsad_r2d2_act with target = NULL, q_target_greedy = NULL and q_online_a set gives the action,
  * the greedy action, the new state and Q_online(s, a); hsad_r2d2_target_q gives Q_target(s, greedy_a) from the same inputs.  A caller
  * that issues the env step between them (it only needs the actions) can run it next to the target pass. */
@@ -1463,6 +1480,13 @@ int hsad_actor_create_partnered_nets(hsad_env* env, hsad_r2d2_net* online, hsad_
                                      const hsad_actor_config* cfg, const hsad_actor_io* io, const hsad_actor_partners* partners,
                                      const hsad_actor_net_partners* net_partners, hsad_actor** out);
 int hsad_actor_partner_state(hsad_actor* actor, int k, float** h, float** c, int32_t* n_rows);
+/* Net partner k plays its softmax policy at temperature tau from the next step on: its per-step call becomes
+ *   hsad_r2d2_act_soft(net_k, n_k, NULL, obs16_k, legal_k, eps = NULL, temp_k, row_key = NULL, 0, ..., seed = cfg->seed, counter = the
+ *   step number, ..., q_online_a = NULL)
+ * with temp_k [n_k] = tau on every row (a vector in the partner arena; the setter waits for the device and fills it with a blocking copy).  tau = 0 restores the hsad_r2d2_act
+ * call above: a partner whose temperature was never set keeps today's launches.  tau < 0 or not finite is refused.  The learner's
+ * rows are not touched, and nothing of a partner reaches the replay, as before. */
+int hsad_actor_set_partner_temperature(hsad_actor* actor, int k, float tau);
 
 /* ---- seat kernels of a tournament batch (eval.play_seatings): one env object holds every seating of a model pool over the same
  * deals (hsad_env_reseed with period = deals); a model acts once per step on the rows it owns, listed as flat row ids g * P + p.

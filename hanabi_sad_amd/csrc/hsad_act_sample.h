@@ -1,11 +1,20 @@
-// hsad_act_sample.h — the sampler core of softmax-policy acting: the counter-based draws of the acting tail and the choice of an action
-// from the softmax over the legal advantages at a temperature.  Plain C++ (no HIP types, no allocation): act_sample_q_kernel of
-// csrc/r2d2/act_sample.inc includes it under hipcc, tests/act_sample/act_sample_main.cc under g++.  Specification: include/hsad.h,
-// hsad_act_sample_q; DESIGN.md section 3c.
+// hsad_act_sample.h — the row of the acting tail: what turns one row of network heads (A advantages, then the value) and its legal
+// mask into the greedy action, the action played and Q(s, a).  Plain C++ (no HIP types, no allocation): the kernels of csrc/r2d2/act.inc
+// call it under hipcc, tests/act_sample/act_sample_main.cc under g++ -- the acting-tail entry points are this one function on their
+// rows (act_sample_q_kernel, the rows at a temperature, writes the same row out from these pieces: DESIGN.md section 3c says why).
+// Specification: include/hsad.h, hsad_act_select .. hsad_act_sample_q; DESIGN.md section 3c.
 //
-// Draws (as_mix64 = act_mix64 of csrc/r2d2/act.inc, the same constants):
-//   eps draw           hh = mix64(mix64(seed ^ K m) + counter), K = 0xD1342543DE82EF95, m the row: act_select_q_kernel's hash; its top 24
-//                      bits are the exploration uniform, its low 32 bits choose the uniform legal action
+// The row (as_tail_row), fp32, in this order of operations:
+//   greedy             argmax_j (1 + h[j] - mn) * legal[j], mn the minimum advantage of the whole batch (R2D2Agent.act, pyhanabi/r2d2.py:
+//                      235-277); strict >, so ties go to the lowest index and a row without a legal action gives 0
+//   the draw           only when (eps > 0 or tau > 0) and an action is legal.  Exploration first: when u(hh) < eps the action is the k-th
+//                      legal one, k = as_eps_index(hh, nlegal).  Otherwise, when tau > 0, Pick at u(hs).  Otherwise greedy.
+//   Q(s, act)          as_q_at: h[A] + h[act] legal[act] - (sum_j h[j] legal[j]) / A, the sum in ascending j (R2D2Net's dueling head,
+//                      q_head_kernel's value at one action)
+//
+// Draws (counter-based: the reference draws from torch's global generator, which no implementation can reproduce bit for bit):
+//   eps draw           hh = mix64(mix64(seed ^ K m) + counter), K = 0xD1342543DE82EF95, m the row; its top 24 bits are the exploration
+//                      uniform, its low 32 bits choose the uniform legal action
 //   sample draw        hs = mix64(hh ^ 0xA0761D6478BD642F)                                              without a row key
 //                      hs = mix64(mix64(sample_seed ^ K (uint64) row_key[m]) ^ 0xA0761D6478BD642F)      with one: no row index and no
 //                      counter in it, the caller owns uniqueness (a tournament keys by (deal, seat, move), so a deal plays the same
@@ -43,7 +52,7 @@ HSAD_AS_FN uint64_t as_mix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 
-// hh of row m: the exploration hash of act_select_q_kernel
+// hh of row m: the exploration hash
 HSAD_AS_FN uint64_t as_eps_hash(uint64_t seed, uint64_t m, uint64_t counter) {
   return as_mix64(as_mix64(seed ^ (HSAD_AS_ROW_MUL * m)) + counter);
 }
@@ -83,6 +92,56 @@ HSAD_AS_FN int as_pick(const float* z, const float* legal, int A, float tau, flo
     if (c > thr) return j;
   }
   return last;
+}
+
+// Q(s, act) of a row from the sum of its legal advantages (sum_j h[j] legal[j] in ascending j)
+HSAD_AS_FN float as_q_from_sum(const float* h, const float* legal, int A, int act, float sum) {
+  return h[A] + h[act] * legal[act] - sum / (float)A;
+}
+
+HSAD_AS_FN float as_q_at(const float* h, const float* legal, int A, int act) {
+  float sum = 0.f;
+  for (int j = 0; j < A; ++j) sum += h[j] * legal[j];
+  return as_q_from_sum(h, legal, A, act, sum);
+}
+
+struct as_tail {
+  int greedy, act;
+  float qa;   // Q(s, act) when asked for, else 0
+};
+
+// One row of the acting tail (head comment).  h: A advantages (and the value h[A], read only with want_qa); mn: the batch minimum;
+// m, seed, counter: the exploration draw's key; row_key: this row's sample key or NULL (then the sample draw follows the exploration
+// draw's hash and sample_seed is not read).
+HSAD_AS_FN as_tail as_tail_row(const float* h, const float* legal, int A, float mn, float eps, float tau, uint64_t m, uint64_t seed,
+                               uint64_t counter, const int64_t* row_key, uint64_t sample_seed, bool want_qa) {
+  float best = -3.4e38f, sum = 0.f;
+  int bi = 0, nlegal = 0;
+  for (int j = 0; j < A; ++j) {
+    const float l = legal[j];
+    const float sc = (1.f + h[j] - mn) * l;
+    if (sc > best) {
+      best = sc;
+      bi = j;
+    }
+    nlegal += l != 0.f;
+    sum += h[j] * l;
+  }
+  int act = bi;
+  if ((eps > 0.f || tau > 0.f) && nlegal > 0) {
+    const uint64_t hh = as_eps_hash(seed, m, counter);
+    if (eps > 0.f && as_uniform(hh) < eps) {
+      int k = as_eps_index(hh, nlegal);
+      for (int j = 0; j < A; ++j)
+        if (legal[j] != 0.f && k-- == 0) {
+          act = j;
+          break;
+        }
+    } else if (tau > 0.f) {
+      act = as_pick(h, legal, A, tau, as_uniform(row_key ? as_sample_hash_keyed(sample_seed, *row_key) : as_sample_hash(hh)));
+    }
+  }
+  return as_tail{bi, act, want_qa ? as_q_from_sum(h, legal, A, act, sum) : 0.f};
 }
 
 #endif  // HSAD_ACT_SAMPLE_H

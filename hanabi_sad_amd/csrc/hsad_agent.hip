@@ -229,6 +229,44 @@ size_t step_ws_bytes(const hsad_r2d2_net* n, int N) {
   return 2 * NH_ * 2 + std::max<size_t>(2 * L * NH_ * 2, (size_t)N * 4 * n->H * 4 + (L + 1) * NH_ * 2 + 2 * L * NH_ * 4) + 256;
 }
 
+// the workspace of a network pass on N rows, carved from n->ws: a16 | `nets` step areas | `nets` heads | scratch | extra
+struct PassWs {
+  bf16_t* a16;     // [N, Fp] the observation in bf16 (obs_bf16 points it at the caller's copy when there is one)
+  char* step[2];   // net_step's / net_step_pair's workspaces
+  float* hd[2];    // [N, NH] heads
+  float* scratch;  // the acting tail's block minima
+  char* extra;     // extra_b bytes, 16-byte aligned
+};
+
+int pass_ws(hsad_r2d2_net* n, int N, int nets, size_t extra_b, PassWs* w) {
+  const size_t a16_b = (size_t)N * n->Fp * 2, hd_b = (size_t)N * n->NH * 4, sc_b = (4 + (N + 255) / 256) * 4, step_b = step_ws_bytes(n, N);
+  CK(n->ws.need(a16_b + nets * (step_b + hd_b) + sc_b + 1024 + extra_b));
+  char* p = n->ws.as<char>();
+  w->a16 = (bf16_t*)p;
+  p += a16_b;
+  for (int k = 0; k < nets; ++k, p += step_b) w->step[k] = p;
+  for (int k = 0; k < nets; ++k, p += hd_b) w->hd[k] = (float*)p;
+  w->scratch = (float*)p;
+  w->extra = (char*)(((uintptr_t)p + sc_b + 15) & ~(uintptr_t)15);
+  return 0;
+}
+
+// the observation as the GEMMs read it: priv_s_bf16 ([N, Fp] as hsad_env_bind_packed writes it) adopted, else priv_s cast into w->a16
+int obs_bf16(hsad_r2d2_net* n, int N, const float* priv_s, const void* priv_s_bf16, PassWs* w, void* stream) {
+  if (priv_s_bf16) w->a16 = (bf16_t*)priv_s_bf16;
+  else CK(hsad_cast_pad_bf16(priv_s, N, n->F, n->F, w->a16, n->Fp, stream));
+  return 0;
+}
+
+// one net from the observation to its heads in w->hd[k]: obs_bf16, net_step in w->step[k] (arguments as net_step's), the heads GEMM
+int net_heads(hsad_r2d2_net* n, int N, const float* priv_s, const void* priv_s_bf16, const float* h0, const float* c0, const bf16_t* h16_in,
+              float* h_out, float* c_out, PassWs* w, int k, StepOut* so, hipStream_t s, bf16_t* h16_dst = nullptr, bool x_ready = false,
+              bool with_skip = false) {
+  CK(obs_bf16(n, N, priv_s, priv_s_bf16, w, (void*)s));
+  CK(net_step(n, N, w->a16, h0, c0, h16_in, h_out, c_out, w->step[k], so, s, h16_dst, x_ready, with_skip));
+  return hsad_gemm_nt_bf16(so->o16, n->H, n->Wheads, n->H, N, n->NH, n->H, n->bheads, w->hd[k], n->NH, nullptr, 0, 0, 0, (void*)s);
+}
+
 }  // namespace
 
 // a stream about to read the net's LSTM operands: behind the side-stream half of the last split refresh
@@ -394,6 +432,57 @@ int hsad_r2d2_net_refresh(hsad_r2d2_net* n, void* stream) {
   return net_refresh(n, (hipStream_t)stream);
 }
 
+// an acting step on checked arguments: hsad_r2d2_act, and with temp / row_key / sample_seed hsad_r2d2_act_soft (no target there)
+static int act_step(hsad_r2d2_net* n, hsad_r2d2_net* target, int N, const float* priv_s, const void* priv_s_bf16, const float* legal_move,
+                    const float* eps, const float* temp, const int64_t* row_key, uint64_t sample_seed, const float* h0, const float* c0,
+                    const void* h0_bf16, uint64_t seed, uint64_t counter, int64_t* a, int64_t* greedy_a, float* h_out, float* c_out,
+                    void* h_out_bf16, float* q_online_a, float* q_target_greedy, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int H = n->H, A = n->A, NH = n->NH;
+  const bool hd_aligned = (size_t)N * NH * 4 % 16 == 0;
+  PassWs w;
+  CK(pass_ws(n, N, 2, 0, &w));
+  CK(obs_bf16(n, N, priv_s, priv_s_bf16, &w, stream));
+  StepOut so{}, st{};
+  // (the bf16 copy of the new state goes straight into the caller's buffer, which must not alias h0_bf16: layer 1 still reads that)
+  // both nets read the same observation: their input layers are ONE launch of two problems over a shared A operand
+  const bool pair_in = q_target_greedy && target->F == n->F && target->H == H && target->A == A && n->nfc == 1 && target->nfc == 1;
+  if (pair_in)
+    CK(hsad_gemm_nt_bf16_pair(w.a16, w.a16, n->Fp, n->W1, target->W1, n->Fp, N, H, n->Fp, n->w(n->iB1), target->w(target->iB1), nullptr, nullptr, 0,
+                              w.step[0], w.step[1], H, 1, stream));
+  // ... so are the LSTM layers (one launch of two cell problems per layer) when both nets take the fused inference path ...
+  const bool pair_trunk = pair_in && hd_aligned && N >= 1024 && n->Wcat16[0] && target->Wcat16[0] && !n->with_backward && !target->with_backward &&
+                          n->L == target->L && !n->skip && !target->skip;
+  if (pair_trunk || (pair_in && hd_aligned)) {
+    if (pair_trunk) {
+      CK(net_step_pair(n, target, N, h0, c0, (const bf16_t*)h0_bf16, h_out, c_out, w.step[0], w.step[1], &so, &st, s, (bf16_t*)h_out_bf16));
+    } else {
+      // ... and so are their head layers (N = A + 1 + 3 hand: one problem alone leaves half of the chip without a tile); the target's
+      // trunk therefore runs before the online heads.  Same kernels on the same operands as the sequence below: identical bits.
+      CK(net_step(n, N, w.a16, h0, c0, (const bf16_t*)h0_bf16, h_out, c_out, w.step[0], &so, s, (bf16_t*)h_out_bf16, true, true));
+      const bf16_t* h16_shared = (const bf16_t*)h0_bf16;
+      if (!h16_shared && so.h16_new) h16_shared = reinterpret_cast<const bf16_t*>(w.step[0] + (size_t)2 * N * H * 2);
+      CK(net_step(target, N, w.a16, h0, c0, h16_shared, nullptr, nullptr, w.step[1], &st, s, nullptr, true));
+    }
+    CK(hsad_gemm_nt_bf16_pair(so.o16, st.o16, H, n->Wheads, target->Wheads, H, N, NH, H, n->bheads, target->bheads, w.hd[0], w.hd[1], NH, nullptr,
+                              nullptr, 0, 0, stream));
+    return hsad_act_select_q2(w.hd[0], w.hd[1], NH, legal_move, eps, N, A, seed, counter, a, greedy_a, q_online_a, q_target_greedy, w.scratch, stream);
+  }
+  CK(net_heads(n, N, nullptr, w.a16, h0, c0, (const bf16_t*)h0_bf16, h_out, c_out, &w, 0, &so, s, (bf16_t*)h_out_bf16, pair_in, true));
+  // action, greedy action and Q_online(s, a) from one pass over the heads (same arithmetic as hsad_act_select + hsad_q_head); without a
+  // temperature this is hsad_act_select_q
+  CK(hsad_act_sample_q(w.hd[0], NH, legal_move, eps, temp, row_key, sample_seed, N, A, seed, counter, a, greedy_a, q_online_a, w.scratch, stream));
+  if (q_target_greedy) {
+    if (target->F != n->F || target->H != H || target->A != A) return afail(HSAD_ERR_INVALID, "r2d2_act: online / target shapes differ");
+    // the target pass shares the bf16 casts of the observation and (fused path) of the hidden state
+    const bf16_t* h16_shared = (const bf16_t*)h0_bf16;
+    if (!h16_shared && so.h16_new) h16_shared = reinterpret_cast<const bf16_t*>(w.step[0] + (size_t)2 * N * H * 2);   // the cast net_step made
+    CK(net_heads(target, N, nullptr, w.a16, h0, c0, h16_shared, nullptr, nullptr, &w, 1, &st, s, nullptr, pair_in));
+    CK(hsad_q_at(w.hd[1], NH, legal_move, greedy_a, N, A, q_target_greedy, stream));
+  }
+  return 0;
+}
+
 // R2D2Agent.act (pyhanabi/r2d2.py:247-303) for N rows (one row per (game, player)): eps-greedy action, greedy action, new
 // hidden state.  q_online_a / q_target_greedy (both or neither; `target` required with them): Q_online(s, a) of the pass just
 // run and Q_target(s, greedy_a) from one target-net pass -- what compute_priority needs from this time step.
@@ -411,76 +500,13 @@ int hsad_r2d2_act(hsad_r2d2_net* online, hsad_r2d2_net* target, int N, const flo
     return afail(HSAD_ERR_INVALID, "r2d2_act: cached Q-values are undefined for a skip_connect net -- R2D2Net.act adds the skip connection, "
                  "R2D2Net.forward (what compute_priority evaluates) ignores it (pyhanabi/r2d2.py:74-75 vs 99-105); use hsad_r2d2_compute_priority");
   if (target && (target->L != online->L || target->H != online->H)) return afail(HSAD_ERR_INVALID, "r2d2_act: online / target shapes differ");
-  hsad_r2d2_net* n = online;
-  hipStream_t s = (hipStream_t)stream;
-  const int H = n->H, A = n->A, NH = n->NH;
-  const size_t a16_b = (size_t)N * n->Fp * 2, hd_b = (size_t)N * NH * 4, sc_b = (4 + (N + 255) / 256) * 4;
-  const size_t step_b = step_ws_bytes(n, N);
-  CK(n->ws.need(a16_b + 2 * step_b + 2 * hd_b + sc_b + 1024));
-  char* p = n->ws.as<char>();
-  bf16_t* a16 = (bf16_t*)p;
-  p += a16_b;
-  char* ws_on = p;
-  p += step_b;
-  char* ws_tg = p;
-  p += step_b;
-  float* hd = (float*)p;
-  p += hd_b;
-  float* hd_t = (float*)p;
-  p += hd_b;
-  float* scratch = (float*)p;
-  if (priv_s_bf16) a16 = (bf16_t*)priv_s_bf16;   // [N, Fp] as hsad_env_bind_packed writes it: no cast pass
-  else CK(hsad_cast_pad_bf16(priv_s, N, n->F, n->F, a16, n->Fp, stream));
-  StepOut so{};
-  // (the bf16 copy of the new state goes straight into the caller's buffer: it must not alias h0_bf16, which layer 1 still reads)
   if (h_out_bf16 && h_out_bf16 == h0_bf16) return afail(HSAD_ERR_INVALID, "r2d2_act: h_out_bf16 must not alias h0_bf16");
-  // both nets read the same observation: their input layers are ONE launch of two problems over a shared A operand
-  const bool pair_in = q_target_greedy && target->F == n->F && target->H == H && target->A == A && n->nfc == 1 && target->nfc == 1;
-  if (pair_in)
-    CK(hsad_gemm_nt_bf16_pair(a16, a16, n->Fp, n->W1, target->W1, n->Fp, N, H, n->Fp, n->w(n->iB1), target->w(target->iB1), nullptr, nullptr, 0,
-                              ws_on, ws_tg, H, 1, stream));
-  // ... so are the LSTM layers (one launch of two cell problems per layer) when both nets take the fused inference path ...
-  const bool pair_trunk = pair_in && hd_b % 16 == 0 && N >= 1024 && n->Wcat16[0] && target->Wcat16[0] && !n->with_backward && !target->with_backward &&
-                          n->L == target->L && !n->skip && !target->skip;
-  if (pair_trunk) {
-    StepOut st{};
-    CK(net_step_pair(n, target, N, h0, c0, (const bf16_t*)h0_bf16, h_out, c_out, ws_on, ws_tg, &so, &st, s, (bf16_t*)h_out_bf16));
-    CK(hsad_gemm_nt_bf16_pair(so.o16, st.o16, H, n->Wheads, target->Wheads, H, N, NH, H, n->bheads, target->bheads, hd, hd_t, NH, nullptr,
-                              nullptr, 0, 0, stream));
-    CK(hsad_act_select_q2(hd, hd_t, NH, legal_move, eps, N, A, seed, counter, a, greedy_a, q_online_a, q_target_greedy, scratch, stream));
-    return 0;
-  }
-  CK(net_step(n, N, a16, h0, c0, (const bf16_t*)h0_bf16, h_out, c_out, ws_on, &so, s, (bf16_t*)h_out_bf16, pair_in, true));
-  if (pair_in && hd_b % 16 == 0) {
-    // ... and so are their head layers (N = A + 1 + 3 hand: one problem alone leaves half of the chip without a tile); the target's
-    // trunk therefore runs before the online heads.  Same kernels on the same operands as the sequence below: identical bits.
-    StepOut st{};
-    const bf16_t* h16_shared = (const bf16_t*)h0_bf16;
-    if (!h16_shared && so.h16_new) h16_shared = reinterpret_cast<const bf16_t*>(ws_on + (size_t)2 * N * H * 2);
-    CK(net_step(target, N, a16, h0, c0, h16_shared, nullptr, nullptr, ws_tg, &st, s, nullptr, true));
-    CK(hsad_gemm_nt_bf16_pair(so.o16, st.o16, H, n->Wheads, target->Wheads, H, N, NH, H, n->bheads, target->bheads, hd, hd_t, NH, nullptr,
-                              nullptr, 0, 0, stream));
-    CK(hsad_act_select_q2(hd, hd_t, NH, legal_move, eps, N, A, seed, counter, a, greedy_a, q_online_a, q_target_greedy, scratch, stream));
-    return 0;
-  }
-  CK(hsad_gemm_nt_bf16(so.o16, H, n->Wheads, H, N, NH, H, n->bheads, hd, NH, nullptr, 0, 0, 0, stream));
-  // action, greedy action and Q_online(s, a) from one pass over the heads (same arithmetic as hsad_act_select + hsad_q_head)
-  CK(hsad_act_select_q(hd, NH, legal_move, eps, N, A, seed, counter, a, greedy_a, q_online_a, scratch, stream));
-  if (q_target_greedy) {
-    if (target->F != n->F || target->H != H || target->A != A) return afail(HSAD_ERR_INVALID, "r2d2_act: online / target shapes differ");
-    StepOut st{};
-    // the target pass shares the bf16 casts of the observation and (fused path) of the hidden state
-    const bf16_t* h16_shared = (const bf16_t*)h0_bf16;
-    if (!h16_shared && so.h16_new) h16_shared = reinterpret_cast<const bf16_t*>(ws_on + (size_t)2 * N * H * 2);   // the cast net_step made
-    CK(net_step(target, N, a16, h0, c0, h16_shared, nullptr, nullptr, ws_tg, &st, s, nullptr, pair_in));
-    CK(hsad_gemm_nt_bf16(st.o16, H, target->Wheads, H, N, NH, H, target->bheads, hd_t, NH, nullptr, 0, 0, 0, stream));
-    CK(hsad_q_at(hd_t, NH, legal_move, greedy_a, N, A, q_target_greedy, stream));
-  }
-  return 0;
+  return act_step(online, target, N, priv_s, priv_s_bf16, legal_move, eps, nullptr, nullptr, 0, h0, c0, h0_bf16, seed, counter, a, greedy_a, h_out,
+                  c_out, h_out_bf16, q_online_a, q_target_greedy, stream);
 }
 
-// hsad_r2d2_act's single-net path with the sampling tail (hsad_act_sample_q): the same workspace layout, cast, net_step and heads GEMM
-// as hsad_r2d2_act(online = net, target = NULL), so the new state and -- with temp == NULL -- every output are that call's bits
+// hsad_r2d2_act(online = net, target = NULL) with the sampling tail (hsad_act_sample_q): the same step, so the new state and -- with
+// temp == NULL -- every output are that call's bits
 int hsad_r2d2_act_soft(hsad_r2d2_net* net, int N, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const float* eps,
                        const float* temp, const int64_t* row_key, uint64_t sample_seed, const float* h0, const float* c0,
                        const void* h0_bf16, uint64_t seed, uint64_t counter, int64_t* a, int64_t* greedy_a, float* h_out, float* c_out,
@@ -490,28 +516,9 @@ int hsad_r2d2_act_soft(hsad_r2d2_net* net, int N, const float* priv_s, const voi
     return afail(HSAD_ERR_INVALID, "r2d2_act_soft: null argument");
   if (q_online_a && net->skip)
     return afail(HSAD_ERR_INVALID, "r2d2_act_soft: cached Q-values are undefined for a skip_connect net (see hsad_r2d2_act)");
-  hsad_r2d2_net* n = net;
-  hipStream_t s = (hipStream_t)stream;
-  const int H = n->H, A = n->A, NH = n->NH;
-  const size_t a16_b = (size_t)N * n->Fp * 2, hd_b = (size_t)N * NH * 4, sc_b = (4 + (N + 255) / 256) * 4;
-  const size_t step_b = step_ws_bytes(n, N);
-  CK(n->ws.need(a16_b + 2 * step_b + 2 * hd_b + sc_b + 1024));
-  char* p = n->ws.as<char>();
-  bf16_t* a16 = (bf16_t*)p;
-  p += a16_b;
-  char* ws_on = p;
-  p += 2 * step_b;
-  float* hd = (float*)p;
-  p += 2 * hd_b;
-  float* scratch = (float*)p;
-  if (priv_s_bf16) a16 = (bf16_t*)priv_s_bf16;
-  else CK(hsad_cast_pad_bf16(priv_s, N, n->F, n->F, a16, n->Fp, stream));
   if (h_out_bf16 && h_out_bf16 == h0_bf16) return afail(HSAD_ERR_INVALID, "r2d2_act_soft: h_out_bf16 must not alias h0_bf16");
-  StepOut so{};
-  CK(net_step(n, N, a16, h0, c0, (const bf16_t*)h0_bf16, h_out, c_out, ws_on, &so, s, (bf16_t*)h_out_bf16, false, true));
-  CK(hsad_gemm_nt_bf16(so.o16, H, n->Wheads, H, N, NH, H, n->bheads, hd, NH, nullptr, 0, 0, 0, stream));
-  CK(hsad_act_sample_q(hd, NH, legal_move, eps, temp, row_key, sample_seed, N, A, seed, counter, a, greedy_a, q_online_a, scratch, stream));
-  return 0;
+  return act_step(net, nullptr, N, priv_s, priv_s_bf16, legal_move, eps, temp, row_key, sample_seed, h0, c0, h0_bf16, seed, counter, a, greedy_a,
+                  h_out, c_out, h_out_bf16, q_online_a, nullptr, stream);
 }
 
 // Q_target(s, greedy_a) alone: the target-net half of an acting step as its own call, so that a caller can issue the env step
@@ -521,54 +528,28 @@ int hsad_r2d2_target_q(hsad_r2d2_net* target, int N, const float* priv_s, const 
   if (target) CK(net_wait(target, (hipStream_t)stream));
   if (!target || (!priv_s && !priv_s_bf16) || !legal_move || !h0 || !c0 || !greedy_a || !q_target_greedy || N < 1)
     return afail(HSAD_ERR_INVALID, "r2d2_target_q: null argument");
-  hsad_r2d2_net* n = target;
-  hipStream_t s = (hipStream_t)stream;
-  const int H = n->H, A = n->A, NH = n->NH;
-  const size_t a16_b = (size_t)N * n->Fp * 2, hd_b = (size_t)N * NH * 4, step_b = step_ws_bytes(n, N);
-  CK(n->ws.need(a16_b + step_b + hd_b + 1024));
-  char* p = n->ws.as<char>();
-  bf16_t* a16 = (bf16_t*)p;
-  p += a16_b;
-  char* ws = p;
-  p += step_b;
-  float* hd = (float*)p;
-  if (priv_s_bf16) a16 = (bf16_t*)priv_s_bf16;
-  else CK(hsad_cast_pad_bf16(priv_s, N, n->F, n->F, a16, n->Fp, stream));
+  PassWs w;
+  CK(pass_ws(target, N, 1, 0, &w));
   StepOut st{};
-  CK(net_step(n, N, a16, h0, c0, (const bf16_t*)h0_bf16, nullptr, nullptr, ws, &st, s));
-  CK(hsad_gemm_nt_bf16(st.o16, H, n->Wheads, H, N, NH, H, n->bheads, hd, NH, nullptr, 0, 0, 0, stream));
-  CK(hsad_q_at(hd, NH, legal_move, greedy_a, N, A, q_target_greedy, stream));
-  return 0;
+  CK(net_heads(target, N, priv_s, priv_s_bf16, h0, c0, (const bf16_t*)h0_bf16, nullptr, nullptr, &w, 0, &st, (hipStream_t)stream));
+  return hsad_q_at(w.hd[0], target->NH, legal_move, greedy_a, N, target->A, q_target_greedy, stream);
 }
 
 // Q_net(s, action) [N] for one step from the carried hidden state
 static int net_q_of(hsad_r2d2_net* n, int N, const float* priv_s, const float* legal, const int64_t* action, const float* h0,
                     const float* c0, float* qa, int64_t* greedy_out, hipStream_t s) {
   void* stream = (void*)s;
-  const int H = n->H, A = n->A, NH = n->NH;
-  const size_t a16_b = (size_t)N * n->Fp * 2, hd_b = (size_t)N * NH * 4, q_b = (size_t)N * A * 4, sc_b = (4 + (N + 255) / 256) * 4;
-  const size_t step_b = step_ws_bytes(n, N);
-  CK(n->ws.need(a16_b + 2 * step_b + 2 * hd_b + q_b + sc_b + 1024 + (size_t)N * 8));
-  char* p = n->ws.as<char>();
-  bf16_t* a16 = (bf16_t*)p;
-  p += a16_b;
-  char* ws_on = p;
-  p += 2 * step_b;
-  float* hd = (float*)p;
-  p += 2 * hd_b;
-  float* q = (float*)p;
-  p += q_b;
-  float* scratch = (float*)p;
-  p += sc_b;
-  int64_t* junk = (int64_t*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-  CK(hsad_cast_pad_bf16(priv_s, N, n->F, n->F, a16, n->Fp, stream));
+  const size_t q_b = ((size_t)N * n->A * 4 + 15) & ~(size_t)15;
+  PassWs w;
+  CK(pass_ws(n, N, 2, q_b + (size_t)N * 8, &w));
+  float* q = (float*)w.extra;
+  int64_t* junk = (int64_t*)(w.extra + q_b);
   StepOut so{};
   // the greedy action of compute_priority comes from R2D2Agent.greedy_act = R2D2Net.act (skip connection applies), Q(s, a) from
   // R2D2Net.forward (it does not): pyhanabi/r2d2.py:234-244, 340-345
-  CK(net_step(n, N, a16, h0, c0, nullptr, nullptr, nullptr, ws_on, &so, s, nullptr, false, greedy_out != nullptr));
-  CK(hsad_gemm_nt_bf16(so.o16, H, n->Wheads, H, N, NH, H, n->bheads, hd, NH, nullptr, 0, 0, 0, stream));
-  if (greedy_out) CK(hsad_act_select(hd, NH, legal, nullptr, N, A, 0, 0, junk, greedy_out, scratch, stream));
-  if (qa) CK(hsad_q_head(hd, NH, legal, action, N, A, q, qa, nullptr, scratch, stream));
+  CK(net_heads(n, N, priv_s, nullptr, h0, c0, nullptr, nullptr, nullptr, &w, 0, &so, s, nullptr, false, greedy_out != nullptr));
+  if (greedy_out) CK(hsad_act_select(w.hd[0], n->NH, legal, nullptr, N, n->A, 0, 0, junk, greedy_out, w.scratch, stream));
+  if (qa) CK(hsad_q_head(w.hd[0], n->NH, legal, action, N, n->A, q, qa, nullptr, w.scratch, stream));
   return 0;
 }
 

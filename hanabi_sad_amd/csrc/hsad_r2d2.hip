@@ -51,7 +51,6 @@ namespace {
 #include "r2d2/clone_loss.inc"
 #include "r2d2/clone_value.inc"
 #include "r2d2/act.inc"
-#include "r2d2/act_sample.inc"
 }  // namespace
 
 // ---- launch helpers for the persistent recurrences (nrec independent recurrences per launch) ----
@@ -914,8 +913,8 @@ int hsad_lstm_sync_timed_out(const void* sync_scratch, int T, int Bn, int32_t* t
   return HSAD_OK;
 }
 
-// rows of heads + legal a 256-thread block stages in <= 60 KB of LDS
-static int staged_rows(int ldh, int A) { return std::min(256, (60 * 1024) / ((ldh + A) * 4)); }
+// rows of heads (of `nets` networks) + legal a 256-thread block stages in <= 60 KB of LDS
+static int staged_rows(int ldh, int A, int nets = 1) { return std::min(256, (60 * 1024) / ((nets * ldh + A) * 4)); }
 
 int hsad_q_head(const float* heads, int ldh, const float* legal, const int64_t* action, int M, int A, float* q,
                 float* qa, int64_t* greedy, float* scratch, void* stream) {
@@ -1225,18 +1224,33 @@ int hsad_act_select(const float* heads, int ldh, const float* legal, const float
   return HSAD_OK;
 }
 
+// the staged acting tail (behind adv_min_kernel: act_tail_kernel, or with temperatures act_sample_q_kernel): what hsad_act_select_q, _q2
+// and hsad_act_sample_q launch.  `who` names the entry point in the error text
+static int act_tail(const char* who, const float* heads, const float* heads_target, int ldh, const float* legal, const float* eps,
+                    const float* temp, const int64_t* row_key, uint64_t sample_seed, int N, int A, uint64_t seed, uint64_t counter,
+                    int64_t* a_out, int64_t* greedy_out, float* qa_out, float* q_target_greedy, float* scratch, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = (N + 255) / 256, nets = heads_target ? 2 : 1;
+  const int R = staged_rows(ldh, A, nets);
+  if (R < 1) return nfail(HSAD_ERR_INVALID, "%s: heads / legal rows too wide for the staged kernel", who);
+  const dim3 grid((N + R - 1) / R);
+  const size_t lds = (size_t)R * (nets * ldh + A) * 4;
+  hipLaunchKernelGGL(adv_min_kernel, dim3(nb), dim3(256), 0, s, heads, ldh, N, A, scratch + 1);
+  if (temp)      // (never with target heads: hsad_act_sample_q has none)
+    hipLaunchKernelGGL(act_sample_q_kernel, grid, dim3(256), lds, s, heads, ldh, legal, eps, temp, row_key, (unsigned long long)sample_seed,
+                       scratch + 1, nb, N, A, (unsigned long long)seed, (unsigned long long)counter, a_out, greedy_out, qa_out, R);
+  else
+    hipLaunchKernelGGL(act_tail_kernel, grid, dim3(256), lds, s, heads, heads_target, ldh, legal, eps, scratch + 1, nb, N, A,
+                       (unsigned long long)seed, (unsigned long long)counter, a_out, greedy_out, qa_out, q_target_greedy, R);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
 int hsad_act_select_q(const float* heads, int ldh, const float* legal, const float* eps, int N, int A, uint64_t seed,
                       uint64_t counter, int64_t* a_out, int64_t* greedy_out, float* qa_out, float* scratch, void* stream) {
   if (!heads || !legal || !a_out || !greedy_out || !scratch) return nfail(HSAD_ERR_INVALID, "act_select_q: null");
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = (N + 255) / 256;
-  const int R = staged_rows(ldh, A);
-  if (R < 1) return nfail(HSAD_ERR_INVALID, "act_select_q: heads / legal rows too wide for the staged kernel");
-  hipLaunchKernelGGL(adv_min_kernel, dim3(nb), dim3(256), 0, s, heads, ldh, N, A, scratch + 1);
-  hipLaunchKernelGGL(act_select_q_kernel, dim3((N + R - 1) / R), dim3(256), (size_t)R * (ldh + A) * 4, s, heads, ldh, legal, eps, scratch + 1,
-                     nb, N, A, (unsigned long long)seed, (unsigned long long)counter, a_out, greedy_out, qa_out, R);
-  HIP_TRY(hipGetLastError());
-  return HSAD_OK;
+  return act_tail("act_select_q", heads, nullptr, ldh, legal, eps, nullptr, nullptr, 0, N, A, seed, counter, a_out, greedy_out, qa_out, nullptr,
+                  scratch, stream);
 }
 
 // hsad_act_select_q on the online heads AND hsad_q_at(target heads, greedy action) as one launch: the tail of an acting step whose
@@ -1246,16 +1260,8 @@ int hsad_act_select_q2(const float* heads, const float* heads_target, int ldh, c
                        float* scratch, void* stream) {
   if (!heads || !heads_target || !legal || !a_out || !greedy_out || !q_target_greedy || !scratch)
     return nfail(HSAD_ERR_INVALID, "act_select_q2: null");
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = (N + 255) / 256;
-  const int R = std::min(256, (60 * 1024) / ((2 * ldh + A) * 4));
-  if (R < 1) return nfail(HSAD_ERR_INVALID, "act_select_q2: heads / legal rows too wide for the staged kernel");
-  hipLaunchKernelGGL(adv_min_kernel, dim3(nb), dim3(256), 0, s, heads, ldh, N, A, scratch + 1);
-  hipLaunchKernelGGL(act_select_q_kernel, dim3((N + R - 1) / R), dim3(256), (size_t)R * (2 * ldh + A) * 4, s, heads, ldh, legal, eps,
-                     scratch + 1, nb, N, A, (unsigned long long)seed, (unsigned long long)counter, a_out, greedy_out, qa_out, R, heads_target,
-                     q_target_greedy);
-  HIP_TRY(hipGetLastError());
-  return HSAD_OK;
+  return act_tail("act_select_q2", heads, heads_target, ldh, legal, eps, nullptr, nullptr, 0, N, A, seed, counter, a_out, greedy_out, qa_out,
+                  q_target_greedy, scratch, stream);
 }
 
 // hsad_act_select_q for seats that play their softmax policy: rows with temp[m] > 0 sample from the softmax over the legal advantages at
@@ -1265,16 +1271,8 @@ int hsad_act_sample_q(const float* heads, int ldh, const float* legal, const flo
                       float* qa_out, float* scratch, void* stream) {
   if (!heads || !legal || !a_out || !greedy_out || !scratch) return nfail(HSAD_ERR_INVALID, "act_sample_q: null");
   if (N < 1 || A < 1 || ldh <= A) return nfail(HSAD_ERR_INVALID, "act_sample_q: needs N >= 1 and rows of A advantages and the value (ldh > A)");
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = (N + 255) / 256;
-  const int R = staged_rows(ldh, A);
-  if (R < 1) return nfail(HSAD_ERR_INVALID, "act_sample_q: heads / legal rows too wide for the staged kernel");
-  hipLaunchKernelGGL(adv_min_kernel, dim3(nb), dim3(256), 0, s, heads, ldh, N, A, scratch + 1);
-  hipLaunchKernelGGL(act_sample_q_kernel, dim3((N + R - 1) / R), dim3(256), (size_t)R * (ldh + A) * 4, s, heads, ldh, legal, eps, temp, row_key,
-                     (unsigned long long)sample_seed, scratch + 1, nb, N, A, (unsigned long long)seed, (unsigned long long)counter, a_out,
-                     greedy_out, qa_out, R);
-  HIP_TRY(hipGetLastError());
-  return HSAD_OK;
+  return act_tail("act_sample_q", heads, nullptr, ldh, legal, eps, temp, row_key, sample_seed, N, A, seed, counter, a_out, greedy_out, qa_out,
+                  nullptr, scratch, stream);
 }
 
 int hsad_q_at(const float* heads, int ldh, const float* legal, const int64_t* action, int M, int A, float* qa, void* stream) {

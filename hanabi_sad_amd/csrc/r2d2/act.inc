@@ -3,16 +3,10 @@
 // the acting tail: epsilon-greedy action selection with cached Q-values, per-row Q lookups, state zeroing of ended games, n-step priority
 // ---------------------------------------------------------------------------------------------------
 // R2D2Agent.act tail (r2d2.py:235-277): greedy by ADVANTAGE only, legal_adv = (1 + adv - min(adv)) * legal with the
-// global min, uniform-random legal action, eps-greedy mix.  Randomness: counter-based hash keyed (seed, row, counter)
-// (the reference draws from torch's global generator, which no implementation can reproduce bit-for-bit).
+// global min, uniform-random legal action, eps-greedy mix; on rows with a temperature, an action sampled from the softmax over the legal
+// advantages.  The row itself -- argmax, draws, Q(s, a) -- is as_tail_row / as_q_at of csrc/hsad_act_sample.h, which the CPU suite
+// compiles alone; the kernels here bring a row and the global minimum to it and store what it returns.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long act_mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 __global__ void adv_min_kernel(const float* __restrict__ heads, int ldh, int N, int A, float* __restrict__ block_min) {
   __shared__ float smin[256];
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -28,63 +22,76 @@ __global__ void adv_min_kernel(const float* __restrict__ heads, int ldh, int N, 
   if (threadIdx.x == 0) block_min[blockIdx.x] = smin[0];
 }
 
+// the unstaged form (hsad_act_select): rows read from global memory, any row width; the global minimum comes from min_reduce_kernel
 __global__ void act_select_kernel(const float* __restrict__ heads, int ldh, const float* __restrict__ legal,
                                   const float* __restrict__ eps, const float* __restrict__ advmin, int N, int A,
                                   unsigned long long seed, unsigned long long counter, int64_t* __restrict__ a_out,
                                   int64_t* __restrict__ greedy_out) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= N) return;
-  const float mn = advmin[0];
-  float best = -3.4e38f;
-  int bi = 0, nlegal = 0;
-  for (int j = 0; j < A; ++j) {
-    const float l = legal[(size_t)m * A + j];
-    const float sc = (1.f + heads[(size_t)m * ldh + j] - mn) * l;
-    if (sc > best) {
-      best = sc;
-      bi = j;
-    }
-    nlegal += l != 0.f;
-  }
-  greedy_out[m] = bi;
-  int act = bi;
-  const float e = eps ? eps[m] : 0.f;
-  if (e > 0.f && nlegal > 0) {
-    const unsigned long long h = act_mix64(act_mix64(seed ^ (0xD1342543DE82EF95ull * (unsigned long long)m)) + counter);
-    const float u = (float)((h >> 40) & 0xFFFFFFull) * (1.f / 16777216.f);
-    if (u < e) {
-      int k = (int)(((h & 0xFFFFFFFFull) * (unsigned long long)nlegal) >> 32);
-      for (int j = 0; j < A; ++j)
-        if (legal[(size_t)m * A + j] != 0.f && k-- == 0) {
-          act = j;
-          break;
-        }
-    }
-  }
-  a_out[m] = act;
+  const as_tail t = as_tail_row(heads + (size_t)m * ldh, legal + (size_t)m * A, A, advmin[0], eps ? eps[m] : 0.f, 0.f, (uint64_t)m, seed,
+                                counter, nullptr, 0, false);
+  greedy_out[m] = t.greedy;
+  a_out[m] = t.act;
 }
 
-
-// ---- the acting tail with everything an actor step needs from the online heads in ONE kernel (after adv_min_kernel): eps-greedy
-// action, greedy action AND Q_online(s, a) of the chosen action -- the numbers act_select_kernel + q_head_kernel + min_reduce give,
-// in the same arithmetic, from one coalesced pass: a block stages its 256 rows of heads / legal through LDS (row strides 37 / 21
-// floats are odd: conflict-free), and reduces the per-block minima itself instead of waiting for a one-block reduction launch.
-__global__ __launch_bounds__(256) void act_select_q_kernel(const float* __restrict__ heads, int ldh, const float* __restrict__ legal,
-                                                           const float* __restrict__ eps, const float* __restrict__ block_min, int nb,
-                                                           int N, int A, unsigned long long seed, unsigned long long counter,
-                                                           int64_t* __restrict__ a_out, int64_t* __restrict__ greedy_out,
-                                                           float* __restrict__ qa_out, int R,
-                                                           const float* __restrict__ heads_t = nullptr, float* __restrict__ tq_out = nullptr) {
+// ---- the acting tail with everything an actor step needs from the heads in ONE kernel (after adv_min_kernel): the action, the greedy
+// action, Q_online(s, a) of the chosen action and, with the target net's heads, Q_target(s, greedy) -- the numbers act_select_kernel +
+// min_reduce + q_at_kernel give, in the same arithmetic, from one coalesced pass: a block stages its R rows of heads / legal (and target
+// heads) through LDS (row strides 37 / 21 floats are odd: conflict-free), and reduces the per-block minima itself instead of waiting for
+// a one-block reduction launch.  eps, qa_out and heads_t (with tq_out) may be NULL: the same for every lane.  One row per lane.
+__global__ __launch_bounds__(256) void act_tail_kernel(const float* __restrict__ heads, const float* __restrict__ heads_t, int ldh,
+                                                       const float* __restrict__ legal, const float* __restrict__ eps,
+                                                       const float* __restrict__ block_min, int nb, int N, int A,
+                                                       unsigned long long seed, unsigned long long counter,
+                                                       int64_t* __restrict__ a_out, int64_t* __restrict__ greedy_out,
+                                                       float* __restrict__ qa_out, float* __restrict__ tq_out, int R) {
   extern __shared__ float s_act[];
   float* s_h = s_act;                    // [R][ldh]   (R <= 256 rows per block: what fits 60 KB of LDS)
   float* s_l = s_act + R * ldh;          // [R][A]
-  float* s_t = s_l + R * A;              // [R][ldh]   the TARGET net's heads (hsad_act_select_q2): Q_target(s, greedy) in the same pass
+  float* s_t = s_l + R * A;              // [R][ldh]   the target net's heads, when given
   __shared__ float s_red[256];
   const int tid = threadIdx.x, m0 = blockIdx.x * R, rows = min(R, N - m0);
   for (int i = tid; i < rows * ldh; i += 256) s_h[i] = heads[(size_t)m0 * ldh + i];
   for (int i = tid; i < rows * A; i += 256) s_l[i] = legal[(size_t)m0 * A + i];
   if (heads_t)
     for (int i = tid; i < rows * ldh; i += 256) s_t[i] = heads_t[(size_t)m0 * ldh + i];
+  float mn = 3.4e38f;
+  for (int i = tid; i < nb; i += 256) mn = fminf(mn, block_min[i]);
+  s_red[tid] = mn;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if (tid < k) s_red[tid] = fminf(s_red[tid], s_red[tid + k]);
+    __syncthreads();
+  }
+  mn = s_red[0];
+  if (tid >= rows) return;
+  const int m = m0 + tid;
+  const float* lg = s_l + tid * A;
+  const as_tail t = as_tail_row(s_h + tid * ldh, lg, A, mn, eps ? eps[m] : 0.f, 0.f, (uint64_t)m, seed, counter, nullptr, 0, qa_out != nullptr);
+  greedy_out[m] = t.greedy;
+  a_out[m] = t.act;
+  if (qa_out) qa_out[m] = t.qa;
+  if (heads_t) tq_out[m] = as_q_at(s_t + tid * ldh, lg, A, t.greedy);
+}
+
+// act_tail_kernel's row (no target heads) at a temperature: as_tail_row WRITTEN OUT in the kernel.  Kept next to the one above for its
+// measured speed alone (DESIGN.md section 3c: the same row through as_tail_row costs 0.5 us more of 20.5 at 32,768 rows); launched only
+// when temp is given, and held to as_tail_row's restatement and to act_tail_kernel's rows by tests/test_act_sample_kernel_gpu.py.
+__global__ __launch_bounds__(256) void act_sample_q_kernel(const float* __restrict__ heads, int ldh, const float* __restrict__ legal,
+                                                           const float* __restrict__ eps, const float* __restrict__ temp,
+                                                           const int64_t* __restrict__ row_key, unsigned long long sample_seed,
+                                                           const float* __restrict__ block_min, int nb, int N, int A,
+                                                           unsigned long long seed, unsigned long long counter,
+                                                           int64_t* __restrict__ a_out, int64_t* __restrict__ greedy_out,
+                                                           float* __restrict__ qa_out, int R) {
+  extern __shared__ float s_act[];
+  float* s_h = s_act;                    // [R][ldh]
+  float* s_l = s_act + R * ldh;          // [R][A]
+  __shared__ float s_red[256];
+  const int tid = threadIdx.x, m0 = blockIdx.x * R, rows = min(R, N - m0);
+  for (int i = tid; i < rows * ldh; i += 256) s_h[i] = heads[(size_t)m0 * ldh + i];
+  for (int i = tid; i < rows * A; i += 256) s_l[i] = legal[(size_t)m0 * A + i];
   float mn = 3.4e38f;
   for (int i = tid; i < nb; i += 256) mn = fminf(mn, block_min[i]);
   s_red[tid] = mn;
@@ -113,30 +120,26 @@ __global__ __launch_bounds__(256) void act_select_q_kernel(const float* __restri
   greedy_out[m] = bi;
   int act = bi;
   const float e = eps ? eps[m] : 0.f;
-  if (e > 0.f && nlegal > 0) {
-    const unsigned long long hh = act_mix64(act_mix64(seed ^ (0xD1342543DE82EF95ull * (unsigned long long)m)) + counter);
-    const float u = (float)((hh >> 40) & 0xFFFFFFull) * (1.f / 16777216.f);
-    if (u < e) {
-      int k = (int)(((hh & 0xFFFFFFFFull) * (unsigned long long)nlegal) >> 32);
+  const float tau = temp ? temp[m] : 0.f;
+  if ((e > 0.f || tau > 0.f) && nlegal > 0) {
+    const unsigned long long hh = as_eps_hash(seed, (unsigned long long)m, counter);
+    bool explore = false;
+    if (e > 0.f && as_uniform(hh) < e) {
+      explore = true;
+      int k = as_eps_index(hh, nlegal);
       for (int j = 0; j < A; ++j)
         if (lg[j] != 0.f && k-- == 0) {
           act = j;
           break;
         }
     }
+    if (!explore && tau > 0.f) {
+      const unsigned long long hs = row_key ? as_sample_hash_keyed(sample_seed, row_key[m]) : as_sample_hash(hh);
+      act = as_pick(h, lg, A, tau, as_uniform(hs));
+    }
   }
   a_out[m] = act;
-  if (qa_out) {
-    mean /= (float)A;
-    qa_out[m] = h[A] + h[act] * lg[act] - mean;     // q_head_kernel's v + a*legal - mean_A(a*legal) at the chosen action
-  }
-  if (heads_t) {                                    // q_at_kernel's arithmetic on the target heads at the greedy action
-    const float* ht = s_t + tid * ldh;
-    float mt = 0.f;
-    for (int j = 0; j < A; ++j) mt += ht[j] * lg[j];
-    mt /= (float)A;
-    tq_out[m] = ht[A] + ht[bi] * lg[bi] - mt;
-  }
+  if (qa_out) qa_out[m] = as_q_from_sum(h, lg, A, act, mean);
 }
 
 // Q(s, action) only (the target pass of an actor step: Q_target(s, greedy)): q_head_kernel's value at one action, no [M,A] matrix,
@@ -153,11 +156,7 @@ __global__ __launch_bounds__(256) void q_at_kernel(const float* __restrict__ hea
   if (tid >= rows) return;
   const float* h = s_h + tid * ldh;
   const float* lg = s_l + tid * A;
-  float mean = 0.f;
-  for (int j = 0; j < A; ++j) mean += h[j] * lg[j];
-  mean /= (float)A;
-  const int act = (int)action[m0 + tid];
-  qa[m0 + tid] = h[A] + h[act] * lg[act] - mean;
+  qa[m0 + tid] = as_q_at(h, lg, A, (int)action[m0 + tid]);
 }
 
 // fp32 h / c [L,N,H] and the bf16 copy of h an acting step carries, zeroed together for the rows whose env terminated.  A wave looks at

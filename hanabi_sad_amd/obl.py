@@ -13,7 +13,7 @@ reply["greedy_a"] = action)."""
 import torch
 
 from . import _lib
-from .r2d2 import R2D2NetKernels, _pad64, _s, cast_pad_bf16, gemm_nt
+from .r2d2 import R2D2NetKernels, _pad64, _s, act_select, cast_pad_bf16, gemm_nt
 
 OBL_IN_DIM = (783, 658, 533)     # (full, private, public) feature counts of the 2-player game (obl_model.py:305-315)
 
@@ -95,17 +95,9 @@ class OBLAgent:
         return {"h0": z, "c0": z.clone()}
 
     def act(self, obs, hid, with_q=False):
-        lib = _lib.load_library()
-        n = obs["priv_s"].shape[0]
         hd, new_hid = self.net.advantage(obs["priv_s"], hid)
         hd = hd.contiguous()
-        a = torch.empty(n, dtype=torch.int64, device=self.device)
-        g = torch.empty(n, dtype=torch.int64, device=self.device)
-        scratch = torch.empty(2 + (n + 255) // 256, dtype=torch.float32, device=self.device)
-        eps = None if self.greedy else obs.get("eps")
-        _lib.check(lib.hsad_act_select(hd.data_ptr(), hd.stride(0), obs["legal_move"].contiguous().data_ptr(),
-                                       None if eps is None else eps.contiguous().data_ptr(), n, self.net.A, self.seed,
-                                       self.counter, a.data_ptr(), g.data_ptr(), scratch.data_ptr(), _s(self.device)))
+        a, _ = act_select(hd, obs["legal_move"], None if self.greedy else obs.get("eps"), self.net.A, self.seed, self.counter)
         self.counter += 1
         return {"a": a, "greedy_a": a}, new_hid          # obl_model.py:296-297: both fields hold the chosen action
 

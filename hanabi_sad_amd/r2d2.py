@@ -946,8 +946,6 @@ class R2D2Agent:
         Q_online(s, a) from the pass that was just run, and `q_target_greedy` = Q_target(s, greedy_a) from one target-net
         pass -- so that an actor loop can form the n-step priorities from them (priority_from_q) instead of re-running both
         nets n steps later; `versions` = (online.version, target.version) of the weights they were computed with."""
-        lib = _lib.load_library()
-        n = obs["priv_s"].shape[0]
         on, tg = self.online, self.target
         pre = None
         if with_q and self._fused(on, obs["priv_s"], hid["h0"], hid["c0"]) and (on.Fp, on.H, on.L) == (tg.Fp, tg.H, tg.L):
@@ -959,13 +957,7 @@ class R2D2Agent:
         new_hid = {"h0": h, "c0": c}
         if self._h16 is not None:
             new_hid["h0_16"] = self._h16     # bf16(h0), written by the cell kernels anyway; zero_hidden_rows keeps it in step
-        a = torch.empty(n, dtype=torch.int64, device=self.device)
-        g = torch.empty(n, dtype=torch.int64, device=self.device)
-        scratch = torch.empty(2 + (n + 255) // 256, dtype=torch.float32, device=self.device)
-        eps = obs.get("eps")
-        _lib.check(lib.hsad_act_select(hd.data_ptr(), hd.stride(0), obs["legal_move"].contiguous().data_ptr(),
-                                       None if eps is None else eps.contiguous().data_ptr(), n, self.online.A, self.seed,
-                                       self.counter, a.data_ptr(), g.data_ptr(), scratch.data_ptr(), _s(self.device)))
+        a, g = act_select(hd, obs["legal_move"], obs.get("eps"), self.online.A, self.seed, self.counter)
         self.counter += 1
         reply = {"a": a, "greedy_a": g}
         if with_q:
@@ -999,8 +991,7 @@ class R2D2Agent:
         next_greedy_a: argmax_a' adv_online(s') when the caller already has it.  In the actor loop (r2d2_actor.h:128-150)
         next_obs / next_hid of the popped transition ARE the inputs of the act() call of the same iteration, so its
         greedy_a is this argmax and the third network pass of the reference is a recomputation; None computes it here."""
-        lib = _lib.load_library()
-        on, tg, d = self.online, self.target, self.device
+        on, tg = self.online, self.target
         n = a.shape[0]
         hd, _, _ = self._adv(on, obs["priv_s"], hid["h0"], hid["c0"])
         _, qa, _ = on.q_head(hd, obs["legal_move"], a, want_greedy=False)
@@ -1009,13 +1000,21 @@ class R2D2Agent:
             assert na.dtype == torch.int64 and na.shape[0] == n
         else:
             nhd, _, _ = self._adv(on, next_obs["priv_s"], next_hid["h0"], next_hid["c0"], skip=True)     # greedy_act = R2D2Net.act
-            na = torch.empty(n, dtype=torch.int64, device=d)
-            junk = torch.empty(n, dtype=torch.int64, device=d)
-            scratch = torch.empty(2 + (n + 255) // 256, dtype=torch.float32, device=d)
-            _lib.check(lib.hsad_act_select(nhd.data_ptr(), nhd.stride(0), next_obs["legal_move"].contiguous().data_ptr(), None,
-                                           n, on.A, 0, 0, junk.data_ptr(), na.data_ptr(), scratch.data_ptr(), _s(d)))
+            _, na = act_select(nhd, next_obs["legal_move"], None, on.A, 0, 0)
         tqa = self.q_of(tg, next_obs, na, next_hid)
         return self.priority_from_q(qa, tqa, reward, bootstrap, num_player)
+
+
+def act_select(hd, legal_move, eps, A, seed, counter):
+    """hsad_act_select on heads hd [N, >= A] (rows hd.stride(0) apart), legal_move [N, A] and eps [N] or None -> a, greedy_a (int64 [N])"""
+    n, d = hd.shape[0], hd.device
+    a = torch.empty(n, dtype=torch.int64, device=d)
+    g = torch.empty(n, dtype=torch.int64, device=d)
+    scratch = torch.empty(2 + (n + 255) // 256, dtype=torch.float32, device=d)
+    _lib.check(_lib.load_library().hsad_act_select(hd.data_ptr(), hd.stride(0), legal_move.contiguous().data_ptr(),
+                                                   None if eps is None else eps.contiguous().data_ptr(), n, A, seed, counter,
+                                                   a.data_ptr(), g.data_ptr(), scratch.data_ptr(), _s(d)))
+    return a, g
 
 
 def zero_hidden_rows(hid, terminal_u8, rows_per_flag):

@@ -914,7 +914,11 @@ int hsad_adam_step_zero_grad(float* param, float* grad, float* exp_avg, float* e
                              float beta1, float beta2, float eps, int step, float* scratch2, float** grad_norm_sq, void* stream);
 /* R2D2Agent.act tail (r2d2.py:235-277): heads fp32 [N,ldh] (advantage in columns [0,A)), legal fp32 [N,A], eps fp32 [N]
  * (NULL = greedy) -> a, greedy_a int64 [N].  scratch fp32 [2 + ceil(N/256)].  Exploration draws come from a counter-based
- * hash of (seed, row, counter). */
+ * hash of (seed, row, counter).  Every acting-tail entry point below computes its rows with ONE row function (as_tail_row / as_q_at of
+ * csrc/hsad_act_sample.h, which states the arithmetic and its order): this one reads the rows from global memory (any row width);
+ * hsad_act_select_q, _q2 and hsad_act_sample_q without temperatures are one kernel that stages them through LDS, called with fewer or
+ * more of its optional arguments, so a row they share is the same bits by construction.  hsad_act_sample_q with temperatures runs the
+ * same row written out in a kernel of its own (kept for its speed). */
 int hsad_act_select(const float* heads, int ldh, const float* legal, const float* eps, int N, int A, uint64_t seed,
                     uint64_t counter, int64_t* a_out, int64_t* greedy_out, float* scratch, void* stream);
 /* |reward + bootstrap * gamma^n * target_qa - online_qa| (R2D2Agent.compute_priority, r2d2.py:355-360), all fp32 [N] */
@@ -927,7 +931,7 @@ int hsad_zero_rows(float* x, const uint8_t* flag, int L, int N, int H, int rows_
 int hsad_act_select_q(const float* heads, int ldh, const float* legal, const float* eps, int N, int A, uint64_t seed,
                       uint64_t counter, int64_t* a_out, int64_t* greedy_out, float* qa_out, float* scratch, void* stream);
 /* hsad_act_select_q for seats that play their softmax policy.  temp [N] (NULL = all 0): a row with temp[m] <= 0 is hsad_act_select_q's row
- * bit for bit (a, greedy, qa).  On a row with temp[m] > 0 the exploration draw comes first (same hash, same uniform legal action when it
+ * bit for bit (a, greedy, qa), and with temp == NULL the call is hsad_act_select_q.  On a row with temp[m] > 0 the exploration draw comes first (same hash, same uniform legal action when it
  * fires); otherwise a = an action sampled from softmax(adv_j / temp[m]) over the legal j -- at temp 1 the distribution whose
  * cross-entropy hsad_r2d2_clone_fwd minimises.  greedy_out is always hsad_act_select_q's; qa_out (optional) = hsad_q_at(heads, ..., a_out).
  * The sample uniform comes from the exploration hash of (seed, row, counter) by one more mixing round, or, with row_key int64 [N],

@@ -82,6 +82,39 @@ def judge(got, z, legal, tau, u, margin=MARGIN):
     return "excused"
 
 
+def q_at(h, lg, act):
+    """as_q_at in numpy float32 on rows h [n, A + 1] (A advantages, then the value), lg [n, A], act [n]:
+    h[A] + h[act] * lg[act] - (sum_j h[j] * lg[j]) / A, the sum in ascending j, every operation rounded to fp32 -> fp32 [n]"""
+    h, lg = np.atleast_2d(np.asarray(h, np.float32)), np.atleast_2d(np.asarray(lg, np.float32))
+    A, r = lg.shape[1], np.arange(lg.shape[0])
+    act = np.atleast_1d(act)
+    s = np.zeros(lg.shape[0], np.float32)
+    for j in range(A):
+        s = s + h[:, j] * lg[:, j]
+    return h[:, A] + h[r, act] * lg[r, act] - s / np.float32(A)
+
+
+def tail_row(h, lg, mn, eps, m0, seed, counter):
+    """as_tail_row without a temperature, in numpy float32, on rows m0, m0 + 1, .. (h [n, A + 1], lg [n, A], eps [n]; mn: the fp32 global
+    minimum) -> greedy [n] (argmax of (1 + h[j] - mn) * lg[j], strict >: ties to the lowest index), a [n] (the exploration draw's legal
+    action where it fires, else greedy), fires [n] (bool), nlegal [n].  On a row with a temperature whose draw does not fire the
+    action is Pick's (judge); greedy and the exploration draw are the same there."""
+    h, lg = np.atleast_2d(np.asarray(h, np.float32)), np.atleast_2d(np.asarray(lg, np.float32))
+    n, A = lg.shape
+    best, greedy = np.full(n, -3.4e38, np.float32), np.zeros(n, np.int64)
+    for j in range(A):
+        sc = (np.float32(1) + h[:, j] - np.float32(mn)) * lg[:, j]
+        up = sc > best
+        best, greedy = np.where(up, sc, best), np.where(up, j, greedy)
+    nlegal = (lg != 0).sum(1)
+    a, fires = greedy.copy(), np.zeros(n, bool)
+    for i in range(n):
+        k = eps_draw(eps_hash(seed, m0 + i, counter), eps[i], int(nlegal[i]))
+        if k >= 0:
+            a[i], fires[i] = np.nonzero(lg[i] != 0)[0][k], True
+    return greedy, a, fires, nlegal
+
+
 def bin_sigma(us, bins=21):
     """the largest deviation of the counts of `us` (values in [0, 1)) in equal bins from their mean, in standard deviations"""
     n = len(us)
@@ -128,3 +161,17 @@ def seeded_case(c, A, rows):
         r = g.raw()
         out["key"][i] = r - (1 << 64) if r >> 63 else r
     return out
+
+
+def tail_case(c, A, rows):
+    """the rows act_sample_main.cc gives as_tail_row in case c: the seeded rows, then three more that take z and the key of rows 0, 1, 2
+    with no legal action, one legal action ((7 c + 3) % A) and all legal, eps = 0.3 in the even cases and 0 in the odd ones.  h = z and the
+    value -z[A - 1] / 2 (exact) behind it; mn = the minimum of every z of the case, legal or not, as adv_min_kernel takes it."""
+    k = seeded_case(c, A, rows)
+    legal3 = np.zeros((3, A), np.float32)
+    legal3[1, (7 * c + 3) % A] = 1
+    legal3[2] = 1
+    z = np.concatenate([k["z"], k["z"][:3]])
+    return dict(k, h=np.concatenate([z, -z[:, A - 1:] * np.float32(0.5)], axis=1), legal=np.concatenate([k["legal"], legal3]),
+                eps=np.concatenate([k["eps"], np.full(3, 0.0 if c % 2 else 0.3, np.float32)]), key=np.concatenate([k["key"], k["key"][:3]]),
+                mn=np.float32(k["z"].min()))

@@ -1,4 +1,4 @@
-"""hsad_act_sample_q (csrc/r2d2/act_sample.inc; specified in include/hsad.h and DESIGN.md section 3c) on synthetic heads, against
+"""hsad_act_sample_q (act_sample_q_kernel / act_tail_kernel of csrc/r2d2/act.inc; specified in include/hsad.h and DESIGN.md section 3c) on synthetic heads, against
 hsad_act_select_q / hsad_q_at (bit for bit: greedy always, a and qa on rows without a temperature, qa at a_out everywhere) and the
 restatement tests/act_sample_ref.py (the sampled actions: the boundary rule, MARGIN = 1e-5, at most 1 % of the sampled rows excused).  Inputs come from numpy generators with fixed seeds, so which rows lie near a boundary is a property
 of this file alone (tests/test_act_soft_surface_cpu.py counts them without a device).

@@ -241,7 +241,9 @@ SIGNATURES = {
     "hsad_clone_tail": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P]),
     "hsad_clone_value_tail": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _P, C.c_int,
                                         _P]),
-    "hsad_colsum": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "hsad_clone_soft_tail": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _P,
+                                       C.c_int, _P]),
+    "hsad_colsum":(C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "hsad_colsum_acc": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "hsad_colsum_acc_ordered": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "hsad_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -370,6 +372,7 @@ SIGNATURES = {
     "hsad_r2d2_loss_bwd": (C.c_int, [_P, _P]),
     "hsad_r2d2_clone_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "hsad_r2d2_clone_value_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "hsad_r2d2_clone_soft_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "hsad_r2d2_optimizer_step": (C.c_int, [_P, C.c_float, C.c_float, C.POINTER(_P), _P]),
     "hsad_r2d2_learner_grad_norm_dev": (_P, [_P]),
     "hsad_r2d2_sync_target_with_online": (C.c_int, [_P, _P]),

@@ -13,6 +13,13 @@
 
     python -m hanabi_sad_amd.clone (--games FILE.jsonl | --teacher piers [--num_game N]) [--seat NAME] --sad 1 \\
            --num_epoch E --batchsize 128 --holdout 0.1 --save_dir D [--value_weight 1 --gamma 0.999]
+
+  Search distillation: the label need not be the one move made.  soft_targets turns action values (search.SearchValues.values, a mean
+  playout score per legal action) into a distribution per position, sequences_from_records(targets=...) carries it as
+  CloneDataset.target and the update takes the cross-entropy against it (hsad_r2d2_clone_soft_fwd).  --blueprint plays the deals with
+  search.play_with_search(records=True) on top of a weight file, so what the search found is fitted back into the net:
+
+    python -m hanabi_sad_amd.clone --blueprint FILE.pthw --search_worlds 8 --target_temperature 0.5 --num_game 1000 --sad 1 --save_dir D
 """
 import os
 
@@ -78,6 +85,89 @@ def returns_to_go(rewards, n_moves, gamma):
     return out.astype(np.float32)
 
 
+def soft_targets(values, legal, a, tau):
+    """action values -> target distributions for the cloning loss (CompositeLearner.clone_loss with batch["target"]).  values float32
+    [n, A], NaN where there is no estimate (SearchValues.values: illegal actions, moves without a search); legal [n, A] (nonzero =
+    legal); a int [n], the move made; tau > 0.  -> float32 [n, A] (a tensor on values' device if values is one, else numpy): a row with
+    >= 2 finite values is softmax((v_j - max v) / tau) over its finite entries and 0 elsewhere; any other row is the one-hot of a.
+    Softmax is shift-invariant, so mean final scores serve as well as returns-to-go.  Computed in float64 and rounded to float32 once: a
+    row sums to 1 within A 2^-24.  ValueError: tau not finite or not positive, shapes that do not agree, a finite value on an illegal
+    action, a move out of range."""
+    tau = float(tau)
+    if not np.isfinite(tau) or tau <= 0.0:
+        raise ValueError("the target temperature must be finite and positive; got %r" % tau)
+    as_tensor = torch.is_tensor(values)
+    v = (values.detach().cpu().numpy() if as_tensor else np.asarray(values)).astype(np.float64)
+    lg = np.asarray(legal.detach().cpu().numpy() if torch.is_tensor(legal) else legal) != 0
+    act = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a).astype(np.int64)
+    if v.ndim != 2 or lg.shape != v.shape or act.shape != (v.shape[0],):
+        raise ValueError("soft_targets takes values [n, A], legal [n, A], a [n]; got %s, %s, %s" % (v.shape, lg.shape, act.shape))
+    n, A = v.shape
+    if n and (act.min() < 0 or act.max() >= A):
+        raise ValueError("a move is outside 0..%d" % (A - 1))
+    finite = np.isfinite(v)
+    if (finite & ~lg).any():
+        raise ValueError("row %d has a value on an illegal action" % int(np.nonzero((finite & ~lg).any(1))[0][0]))
+    soft = finite.sum(1) >= 2
+    out = np.zeros((n, A), dtype=np.float64)
+    out[np.arange(n), act] = 1.0
+    if soft.any():
+        vs = np.where(finite[soft], v[soft], -np.inf)
+        e = np.exp((vs - vs.max(1, keepdims=True)) / tau)      # (exp(-inf) = 0: the entries without an estimate)
+        out[soft] = e / e.sum(1, keepdims=True)
+    out = out.astype(np.float32)
+    return torch.from_numpy(out).to(values.device) if as_tensor else out
+
+
+def search_targets(records, search_values, tau):
+    """[soft_targets(...)] per record of a search.play_with_search(records=True) run: SearchPlay.search_values[k] (float32 [n_moves, A],
+    finite on the legal actions of the searched moves) at temperature tau, the one-hot of the move made where no search ran.  The
+    legal set handed to soft_targets is the finite set plus the move made; the device checks every row against the position's legal
+    mask again when it is cloned (bad rows)."""
+    records, search_values = list(records), list(search_values)
+    if len(records) != len(search_values):
+        raise ValueError("%d records but %d value arrays" % (len(records), len(search_values)))
+    out = []
+    for j, (rec, v) in enumerate(zip(records, search_values)):
+        v = np.asarray(v, dtype=np.float32)
+        A = gr.num_actions(rec.rules)
+        if v.shape != (rec.n_moves, A):
+            raise ValueError("values of record %d must be [n_moves, A] = [%d, %d]; got %s" % (j, rec.n_moves, A, v.shape))
+        mv = np.asarray(rec.moves, dtype=np.int64)
+        legal = np.isfinite(v)
+        legal[np.arange(rec.n_moves), mv] = True
+        out.append(soft_targets(v, legal, mv, tau))
+    return out
+
+
+def check_targets(records, targets, A):
+    """targets as sequences_from_records takes them -> [float32 [n_moves, A]]; ValueError unless there is one array per record, of that
+    shape, every row a distribution: finite, not negative, summing to 1 within 1e-3 (the device's limit)"""
+    records, targets = list(records), list(targets)
+    if len(targets) != len(records):
+        raise ValueError("%d records but %d target arrays" % (len(records), len(targets)))
+    out = []
+    for j, (rec, tg) in enumerate(zip(records, targets)):
+        tg = np.asarray(tg.detach().cpu().numpy() if torch.is_tensor(tg) else tg)
+        if tg.shape != (rec.n_moves, A) or tg.dtype.kind != "f":
+            raise ValueError("targets of record %d must be float [n_moves, A] = [%d, %d]; got %s %s" % (j, rec.n_moves, A, tg.dtype, tg.shape))
+        tg = tg.astype(np.float32)
+        if not (np.isfinite(tg).all() and (tg >= 0).all() and (np.abs(tg.astype(np.float64).sum(1) - 1.0) <= 1e-3).all()):
+            raise ValueError("targets of record %d: every row must be a distribution (finite, not negative, summing to 1)" % j)
+        out.append(tg)
+    return out
+
+
+def target_entropy(data):
+    """-> the summed entropy -sum pi log pi of every target row of a CloneDataset (float; 0 log 0 = 0).  Padding, off-turn and
+    single-action rows are zero or one-hot rows and add nothing, so this is the entropy over the decisions, and the cross-entropy loss less
+    this is the KL divergence from the targets to the net's policy."""
+    if data.target is None:
+        return 0.0
+    p = data.target.double()
+    return float(-(torch.where(p > 0, p * torch.log(p.clamp(min=1e-300)), torch.zeros_like(p))).sum())
+
+
 def padding_rows(n_rows, rows):
     """rows of weight 0 that fill the last batch"""
     return (-int(n_rows)) % int(rows)
@@ -88,11 +178,13 @@ class CloneDataset:
     (the recorded move on the mover's row, the no-op on the others); seq_len float32 [N]; game, seat int64 [N] (game = the record's
     index); truncated = games cut at max_len.  Rows at and past seq_len are padding: zeros, no-op.  ret (None unless the sequences were
     made with a gamma): float32 [T, N], the discounted return-to-go of the WHOLE recorded game from step t on, the same on every seat's
-    row of a game, 0 at and past seq_len."""
+    row of a game, 0 at and past seq_len.  target (None unless the sequences were made with targets): float32 [T, N, A], the distribution
+    the cross-entropy is taken against -- the record's target row on the mover's row, the one-hot of the no-op on every other valid row,
+    zeros at and past seq_len."""
 
-    def __init__(self, priv_s, priv_s_bf16, legal_move, a, seq_len, game, seat, truncated=0, ret=None):
+    def __init__(self, priv_s, priv_s_bf16, legal_move, a, seq_len, game, seat, truncated=0, ret=None, target=None):
         self.priv_s, self.priv_s_bf16, self.legal_move, self.a = priv_s, priv_s_bf16, legal_move, a
-        self.seq_len, self.game, self.seat, self.truncated, self.ret = seq_len, game, seat, int(truncated), ret
+        self.seq_len, self.game, self.seat, self.truncated, self.ret, self.target = seq_len, game, seat, int(truncated), ret, target
 
     @property
     def n_rows(self):
@@ -110,7 +202,7 @@ class CloneDataset:
         rows = torch.as_tensor(rows, dtype=torch.int64, device=self.seq_len.device)
         sel = lambda x: None if x is None else x.index_select(1, rows)      # noqa: E731
         return CloneDataset(sel(self.priv_s), sel(self.priv_s_bf16), sel(self.legal_move), sel(self.a), self.seq_len[rows], self.game[rows],
-                            self.seat[rows], self.truncated, sel(self.ret))
+                            self.seat[rows], self.truncated, sel(self.ret), sel(self.target))
 
     def split(self, holdout, seed):
         """-> (train, held_out), split by GAME: every kept seat of a game goes to the same side.  holdout: the fraction of games held
@@ -148,18 +240,25 @@ class CloneDataset:
             batch = {key: pick(obs), "legal_move": pick(self.legal_move), "a": a, "seq_len": self.seq_len[src] * real.float()}
             if self.ret is not None:
                 batch["ret"] = pick(self.ret)
+            if self.target is not None:      # (a padding column has seq_len 0: its zero rows are never read)
+                batch["target"] = pick(self.target)
             yield batch, real.float(), index
 
 
 # ---- device side --------------------------------------------------------------------------------------------------------------------
-def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:0", bf16=True, gamma=None):
+def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:0", bf16=True, gamma=None, targets=None):
     """the observation sequences of the recorded games -> CloneDataset with T = max_len (None: game_record.capacity(rules)).
     Game j is records[j] reopened at its first deal (game_record.replay(records, stop=0) on an env of the records' rules, sad as
     given) and stepped with its recorded moves and greedy alternatives; step t's rows are the observations BEFORE move t.  One
     sequence per kept seat (select_seats), row order game-major.  Games longer than max_len are cut and counted in .truncated.
     gamma (None: no returns, and nothing below happens): env.reward is collected after every step and CloneDataset.ret is
     returns_to_go of it.  A game cut at max_len is then stepped on with its recorded moves to its recorded end, no observations
-    stored, so that its return is that of the whole recorded game and not of the kept part."""
+    stored, so that its return is that of the whole recorded game and not of the kept part.
+    targets (None: no target field, and nothing below happens): one float [n_moves, A] array per record whose rows ARE distributions over
+    the actions of the position before move t -- soft_targets / search_targets make them from action values; nothing is normalised here.
+    check_targets holds them to that (shape, finite, not negative, mass 1) before any device work; that the mass lies on legal actions is
+    checked by the update itself (bad rows).  CloneDataset.target then carries, at step t, the record's row t on the mover's row (seat
+    t % P) and the one-hot of the no-op on every other valid row."""
     from .env import BatchedHanabiEnv
     from .eval import _drain_errors
     records = list(records)
@@ -169,6 +268,8 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
             raise ValueError("record %d has %d moves and %d greedy moves" % (j, len(rec.moves), len(rec.greedy)))
     keep = select_seats(records, seats)
     G, P = len(records), r["players"]
+    if targets is not None:
+        targets = check_targets(records, targets, gr.num_actions(r))
     lens, truncated = sequence_lengths([rec.n_moves for rec in records], max_len, gr.capacity(r))
     T = int(gr.capacity(r) if max_len is None else max_len)
     n_all = np.asarray([rec.n_moves for rec in records], dtype=np.int64)
@@ -203,6 +304,14 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
         lens_d, step_lens_d = torch.from_numpy(lens).to(dev), torch.from_numpy(step_lens).to(dev)
         rewards = torch.zeros(max(steps, 1), G, dtype=torch.float32, device=dev) if gamma is not None else None
         a_step, g_step = torch.empty(G, P, dtype=torch.int64, device=dev), torch.empty(G, P, dtype=torch.int64, device=dev)
+        target = tg = None
+        if targets is not None:
+            tg_host = np.zeros((max(kept_steps, 1), G, A), dtype=np.float32)      # the movers' rows; past a game's kept moves: never read
+            for j, arr in enumerate(targets):
+                tg_host[:int(lens[j]), j] = arr[:int(lens[j])]
+            tg = torch.from_numpy(tg_host).to(dev)
+            target = torch.zeros(T, N, A, dtype=torch.float32, device=dev)
+            t_step = torch.empty(G, P, A, dtype=torch.float32, device=dev)
         for t in range(steps):
             live = t < lens_d                                   # [G]: the step is kept
             moving = t < step_lens_d                            # [G]: the game is stepped (past `live` only for the returns of cut games)
@@ -220,6 +329,11 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
             g_step[:, t % P] = torch.where(moving, gv[t], torch.full_like(gv[t], noop))
             if t < kept_steps:
                 act[t] = a_step.view(-1)[rows]                  # (t < kept_steps <= T: a game that still moves here is live here)
+                if target is not None:
+                    t_step.zero_()
+                    t_step[:, :, noop] = 1.0
+                    t_step[:, t % P] = tg[t]
+                    target[t] = t_step.view(G * P, A)[rows] * live_rows.view(-1, 1)
             env.step(a_step, g_step)                            # (a game past its moves is handed the no-op and left alone)
             if rewards is not None:
                 rewards[t] = env.reward[:G] * moving            # (the reward of move t; past a game's end: whatever, never read)
@@ -234,7 +348,7 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
         ret = torch.zeros(T, N, dtype=torch.float32, device=dev)
         ret[:kept_steps] = whole[:kept_steps][:, row_game] * (torch.arange(kept_steps, device=dev).view(-1, 1) < seq_len.view(1, -1))
     return CloneDataset(None if bf16 else priv, priv if bf16 else None, legal, act, seq_len, row_game.clone(), torch.from_numpy(flat % P).to(dev),
-                        truncated, ret)
+                        truncated, ret, target)
 
 
 def records_from_teacher(pool, num_game, seed, sad, *, seating=None, num_player=2, bomb=0, device="cuda:0", names=None, temperature=None,
@@ -256,7 +370,8 @@ def records_from_teacher(pool, num_game, seed, sad, *, seating=None, num_player=
 # ---- the driver ---------------------------------------------------------------------------------------------------------------------
 def run_epoch(learner, data, rows, seed, train, value_weight=0.0):
     """one pass over `data` in batches of `rows` -> (loss per decision, hits, decisions); train: backward + optimizer step per batch.
-    value_weight > 0 (data.ret needed): the updates carry the value term, and a fourth result is the value loss per step"""
+    value_weight > 0 (data.ret needed): the updates carry the value term, and a fourth result is the value loss per step.
+    A dataset with targets (data.target) hands them to every update: the loss is then the cross-entropy against them."""
     dev = data.seq_len.device
     total = torch.zeros(5 if value_weight else 3, dtype=torch.float64, device=dev)
     bad = torch.zeros((), dtype=torch.int64, device=dev)
@@ -271,7 +386,8 @@ def run_epoch(learner, data, rows, seed, train, value_weight=0.0):
         bad += stats["bad"].sum()
     if int(bad):
         from ._lib import HsadError
-        raise HsadError("%d recorded moves are illegal in their position or out of range" % int(bad))
+        raise HsadError("%d recorded moves are illegal in their position or out of range%s"
+                        % (int(bad), ", or their target rows are no distribution over the legal actions" if data.target is not None else ""))
     s, h, n = total.tolist()[:3]
     if value_weight:
         v, k = total.tolist()[3:]
@@ -316,6 +432,15 @@ def parse_args(argv=None):
     p.add_argument("--teacher_temperature", type=float, default=0.0, help="with --teacher: network teachers play their softmax policy at this "
                                                                           "temperature (rule bots ignore it)")
     p.add_argument("--gamma", type=float, default=0.999, help="with --value_weight: the discount of the returns (the one TD training will use)")
+    p.add_argument("--blueprint", type=str, default="", help="instead of --games / --teacher: a weight file; --num_game deals are played with "
+                                                             "blueprint-policy search on top of it (search.play_with_search), recorded and cloned")
+    p.add_argument("--search_worlds", type=int, default=0, help="with --blueprint: sampled worlds per legal action")
+    p.add_argument("--search_rounds", default=None, type=lambda s: tuple(int(x) for x in s.split(",")),
+                   help="with --blueprint: world counts per round, e.g. 8,8,16 (summing to --search_worlds)")
+    p.add_argument("--searcher", type=str, default="all", help="with --blueprint: all, or the one seat that searches")
+    p.add_argument("--search_threshold", type=float, default=0.05, help="with --blueprint: deviate from the blueprint only for a larger value gain")
+    p.add_argument("--target_temperature", type=float, default=0.0, help="with --blueprint: > 0 clones softmax(search values / this) "
+                                                                         "(clone.soft_targets) instead of the move made; 0 = hard labels")
     return p.parse_args(argv)
 
 
@@ -327,12 +452,31 @@ def main(argv=None):
     from .selfplay import game_rules, init_weights
     args = parse_args(argv)
     dev = args.train_device
-    if bool(args.games) == bool(args.teacher):
-        raise SystemExit("give either --games FILE or --teacher NAME")
-    for flag in ("eval_temperature", "teacher_temperature"):
+    if bool(args.games) + bool(args.teacher) + bool(args.blueprint) != 1:
+        raise SystemExit("give either --games FILE or --teacher NAME" + (" or --blueprint FILE" if args.blueprint else ""))
+    for flag in ("eval_temperature", "teacher_temperature", "target_temperature"):
         if not np.isfinite(getattr(args, flag)) or getattr(args, flag) < 0:
             raise SystemExit("--%s must be finite and not negative" % flag)
-    if args.games:
+    search_values = None
+    if args.blueprint:
+        if not os.path.isfile(args.blueprint):
+            raise SystemExit("--blueprint %s: no such weight file" % args.blueprint)
+        if args.search_worlds < 1:
+            raise SystemExit("--blueprint needs --search_worlds N > 0")
+        if args.searcher != "all" and not args.searcher.isdigit():
+            raise SystemExit("--searcher must be all or a seat number")
+    elif args.target_temperature > 0:
+        raise SystemExit("--target_temperature needs --blueprint: the targets are made from the search's action values")
+    if args.blueprint:
+        from .search import play_with_search
+        played = play_with_search(load_weights(args.blueprint), args.num_game, args.seed, args.eval_bomb, args.sad, worlds=args.search_worlds,
+                                  threshold=args.search_threshold, search_seed=args.seed, searcher="all" if args.searcher == "all" else int(args.searcher),
+                                  num_player=args.num_player, hand_size=args.hand_size, device=dev, rounds=args.search_rounds, records=True,
+                                  **game_rules(args))
+        records, search_values = played.records, played.search_values
+        print("blueprint + search (%d worlds): %.3f +/- %.3f over %d deals, %d moves changed by the search"
+              % (args.search_worlds, played.mean, played.sem, args.num_game, int(played.deviations.sum())), flush=True)
+    elif args.games:
         records = gr.load(args.games)
     else:
         pool = []
@@ -346,15 +490,18 @@ def main(argv=None):
                                        sample_seed=args.seed, **game_rules(args))
     if args.save_dir:
         os.makedirs(args.save_dir, exist_ok=True)
-        if args.teacher:     # the games that were cloned, for --games of a later run
+        if args.teacher or args.blueprint:     # the games that were cloned, for --games of a later run
             gr.save(os.path.join(args.save_dir, "games.jsonl"), records)
     r = check_rules(records)
     seats = None if not args.seat else ([int(args.seat)] if args.seat.isdigit() else args.seat)
     vw = float(args.value_weight)
     if vw < 0:
         raise SystemExit("--value_weight must not be negative")
-    data = sequences_from_records(records, args.sad, seats=seats, max_len=args.max_len, device=dev, gamma=args.gamma if vw > 0 else None)
+    targets = search_targets(records, search_values, args.target_temperature) if args.target_temperature > 0 else None
+    data = sequences_from_records(records, args.sad, seats=seats, max_len=args.max_len, device=dev, gamma=args.gamma if vw > 0 else None,
+                                  targets=targets)
     train, held = data.split(args.holdout, args.seed)
+    entropy = target_entropy(train)      # once, on the host: the loss less this is the KL divergence from the targets
     print("%d games (%d cut at %d moves, mean score %.2f), %d sequences: %d to fit, %d held out"
           % (len(records), data.truncated, args.max_len, float(np.mean([rec.score for rec in records])), data.n_rows, train.n_rows, held.n_rows))
     rules = {k: r[k] for k in ("colors", "ranks", "max_information_tokens", "max_life_tokens")}
@@ -377,6 +524,8 @@ def main(argv=None):
         else:
             score_text = "%.3f" % score
         value = ", value loss per step %.4f, held-out value loss per step %.4f" % (vtrain[0], vheld[0]) if vw > 0 else ""
+        if targets is not None:
+            value += ", KL per decision %.4f" % (loss - entropy / max(n, 1))
         print("epoch %d: loss per decision %.4f, agreement %.4f (%d / %d), held-out agreement %.4f (%d / %d), self-play score %s%s"
               % (epoch, loss, hits / max(n, 1), hits, n, hh / max(hn, 1), hh, hn, score_text, value), flush=True)
         if args.save_dir:

@@ -336,9 +336,14 @@ class CompositeLearner:
         gets no gradient.  CloneStats.read() -> (hits, decisions) as ints and raises if a recorded move was illegal or out of range.
         value_weight > 0 (hsad_r2d2_clone_value_fwd) also fits Q(o_t, a_t) to batch["ret"] float32 [T, B], the return-to-go of the recorded
         game (Huber, the TD loss's): the objective becomes (weight * (policy_weight * loss + value_weight * stats["value_loss"])).mean(), and
-        the value head learns.  With the defaults the calls are those of a learner without the value term."""
+        the value head learns.  With the defaults the calls are those of a learner without the value term.
+        batch["target"] float32 [T, B, A] (hsad_r2d2_clone_soft_fwd): a probability row per (step, sequence) takes the place of the one-hot
+        of batch["a"] in the cross-entropy -- clone.soft_targets of a search's action values, or a teacher's policy.  batch["a"] stays what
+        hits / decisions count against and what the value term reads; a row whose target is not a distribution over its legal actions is
+        counted in bad.  Without the key the calls above are what runs."""
         value_weight, policy_weight = float(value_weight), float(policy_weight)
-        with_value = value_weight != 0.0 or policy_weight != 1.0
+        target = batch.get("target")
+        with_value = value_weight != 0.0 or policy_weight != 1.0 or target is not None
         if value_weight != 0.0 and batch.get("ret") is None:
             raise _lib.HsadError("clone_loss(value_weight=%g) needs batch[\"ret\"], the returns-to-go [T, B] (sequences_from_records(gamma=...))" % value_weight)
         legal, a = batch["legal_move"], batch["a"]
@@ -349,6 +354,8 @@ class CompositeLearner:
         T, rows, _ = legal.shape
         if p16 is not None and (priv.dtype != torch.bfloat16 or tuple(priv.shape) != (T, rows, self.online.Fp)):
             raise _lib.HsadError("priv_s_bf16 must be bf16 [T, rows, %d]; got %s %s" % (self.online.Fp, priv.dtype, tuple(priv.shape)))
+        if target is not None and (not torch.is_tensor(target) or tuple(target.shape) != tuple(legal.shape) or not target.dtype.is_floating_point):
+            raise _lib.HsadError("target must be a float tensor [T, rows, A] = %s; got %s" % (tuple(legal.shape), tuple(getattr(target, "shape", ()))))
         self._ensure(T, rows)
         d = self.device
         loss = torch.empty(rows, dtype=torch.float32, device=d)
@@ -363,6 +370,18 @@ class CompositeLearner:
                 if tuple(ret.shape) != (T, rows):
                     raise _lib.HsadError("ret must be [T, rows] = [%d, %d]; got %s" % (T, rows, tuple(ret.shape)))
                 keep.append(ret)
+            if target is not None:
+                target = target.contiguous().float()
+                keep.append(target)
+                self._alive = keep
+                _lib.check(self.lib.hsad_r2d2_clone_soft_fwd(self.h, f32, f16, keep[1].data_ptr(), keep[2].data_ptr(), target.data_ptr(),
+                                                             None if ret is None else ret.data_ptr(), keep[3].data_ptr(), keep[4].data_ptr(), policy_weight,
+                                                             value_weight, loss.data_ptr(), vloss.data_ptr(), cnt[0].data_ptr(), cnt[1].data_ptr(),
+                                                             cnt[2].data_ptr(), cnt[3].data_ptr(), 1 if compute_grad else 0, _s(d)))
+                stats = CloneStats(hits=cnt[0], decisions=cnt[1], bad=cnt[2], steps=cnt[3], value_loss=vloss)
+                if compute_grad:
+                    _lib.check(self.lib.hsad_r2d2_loss_bwd(self.h, _s(d)))
+                return loss, stats
             self._alive = keep       # loss_bwd reads these
             _lib.check(self.lib.hsad_r2d2_clone_value_fwd(self.h, f32, f16, keep[1].data_ptr(), keep[2].data_ptr(), None if ret is None else ret.data_ptr(),
                                                           keep[3].data_ptr(), keep[4].data_ptr(), policy_weight, value_weight, loss.data_ptr(),

@@ -760,6 +760,8 @@ struct CloneValueTerm {
   const float* ret;
   float policy_weight, value_weight, *vloss;
   int32_t* steps;
+  bool soft = false;                // hsad_r2d2_clone_soft_fwd: the cross-entropy is against `target` (hsad_clone_soft_tail)
+  const float* target = nullptr;    // [T, rows, A]
 };
 
 int clone_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_bf16, const LossArgs& b, int32_t* hits, int32_t* decisions, int32_t* bad,
@@ -768,6 +770,7 @@ int clone_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s
     return afail(HSAD_ERR_INVALID, "r2d2_clone_fwd: bad arguments");
   if (vt) {      // (what hsad_clone_value_tail would refuse, before anything is launched)
     if (!vt->steps) return afail(HSAD_ERR_INVALID, "r2d2_clone_value_fwd: bad arguments");
+    if (vt->soft && !vt->target) return afail(HSAD_ERR_INVALID, "r2d2_clone_soft_fwd: no target rows (hsad_r2d2_clone_value_fwd is the call without them)");
     if (!(vt->policy_weight >= 0.f) || !(vt->value_weight >= 0.f) || std::isinf(vt->policy_weight) || std::isinf(vt->value_weight))
       return afail(HSAD_ERR_INVALID, "r2d2_clone_value_fwd: the weights of the two terms must be finite and not negative");
     if (vt->value_weight != 0.f && (!vt->ret || !vt->vloss)) return afail(HSAD_ERR_INVALID, "r2d2_clone_value_fwd: the value term needs the returns and vloss");
@@ -793,7 +796,10 @@ int clone_fwd_impl(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s
   if (hd.pre_T) CK(fwd_early_transposes(L, d, s));
   const int top = d.NL - 1;
   CK(hsad_gemm_nt_bf16(L->hseq[0][top], d.H, L->on->Wheads, d.H, d.M, d.NH, d.H, L->on->bheads, L->heads, d.NH, nullptr, 0, 0, 0, stream));
-  if (vt)
+  if (vt && vt->soft)
+    CK(hsad_clone_soft_tail(L->heads, d.NH, b.legal, b.a, vt->target, vt->ret, b.seq_len, b.weight, d.T, d.B, d.A, vt->policy_weight, vt->value_weight, b.loss,
+                            vt->vloss, hits, decisions, bad, vt->steps, b.want_grad ? L->dheads : nullptr, d.NHp, stream));
+  else if (vt)
     CK(hsad_clone_value_tail(L->heads, d.NH, b.legal, b.a, vt->ret, b.seq_len, b.weight, d.T, d.B, d.A, vt->policy_weight, vt->value_weight, b.loss, vt->vloss,
                              hits, decisions, bad, vt->steps, b.want_grad ? L->dheads : nullptr, d.NHp, stream));
   else
@@ -819,6 +825,17 @@ extern "C" int hsad_r2d2_clone_value_fwd(hsad_r2d2_learner* L, const float* priv
                                          float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps, int want_grad, void* stream) {
   const LossArgs b{legal_move, nullptr, nullptr, seq_len, nullptr, weight, a, 1, 0.f, loss, nullptr, want_grad != 0};
   const CloneValueTerm vt{ret, policy_weight, value_weight, vloss, steps};
+  const int rc = clone_fwd_impl(L, priv_s, priv_s_bf16, b, hits, decisions, bad, &vt, stream);
+  if (rc || want_grad) return rc;
+  return timeout_gather(L, (hipStream_t)stream);
+}
+
+extern "C" int hsad_r2d2_clone_soft_fwd(hsad_r2d2_learner* L, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a,
+                                        const float* target, const float* ret, const float* seq_len, const float* weight, float policy_weight,
+                                        float value_weight, float* loss, float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps,
+                                        int want_grad, void* stream) {
+  const LossArgs b{legal_move, nullptr, nullptr, seq_len, nullptr, weight, a, 1, 0.f, loss, nullptr, want_grad != 0};
+  const CloneValueTerm vt{ret, policy_weight, value_weight, vloss, steps, true, target};
   const int rc = clone_fwd_impl(L, priv_s, priv_s_bf16, b, hits, decisions, bad, &vt, stream);
   if (rc || want_grad) return rc;
   return timeout_gather(L, (hipStream_t)stream);

@@ -33,6 +33,7 @@
 #include "hsad.h"
 #include "hsad_gemm_plan.h"
 #include "hsad_act_sample.h"
+#include "hsad_clone_soft.h"
 
 extern "C" int hsad_internal_set_error(int code, const char* msg);
 
@@ -50,6 +51,7 @@ namespace {
 #include "r2d2/heads_loss_optim.inc"
 #include "r2d2/clone_loss.inc"
 #include "r2d2/clone_value.inc"
+#include "r2d2/clone_soft.inc"
 #include "r2d2/act.inc"
 }  // namespace
 
@@ -1096,6 +1098,26 @@ int hsad_clone_value_tail(const float* heads, int ldh, const float* legal, const
   CloneValueArgs p{heads, legal, ret, seq_len, weight, action, ldh, T, B, A, policy_weight, value_weight, loss, vloss, hits, decisions, bad, steps,
                    (bf16_t*)dheads16, ldo};
   hipLaunchKernelGGL(clone_value_tail_kernel, dim3(B), dim3(kCloneValueThreads), lds, (hipStream_t)stream, p);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_clone_soft_tail(const float* heads, int ldh, const float* legal, const int64_t* action, const float* target, const float* ret,
+                         const float* seq_len, const float* weight, int T, int B, int A, float policy_weight, float value_weight, float* loss,
+                         float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps, void* dheads16, int ldo, void* stream) {
+  if (!heads || !legal || !action || !seq_len || !loss || !hits || !decisions || !bad || !steps || T < 1 || B < 1 || A < 1 || ldh < A)
+    return nfail(HSAD_ERR_INVALID, "clone_soft_tail: null argument or bad shape");
+  if (!target) return nfail(HSAD_ERR_INVALID, "clone_soft_tail: no target rows (hsad_clone_value_tail is the call without them)");
+  if (dheads16 && (!weight || ldo < A + 1)) return nfail(HSAD_ERR_INVALID, "clone_soft_tail: the head gradient needs the weights and ldo >= A + 1");
+  if (!(policy_weight >= 0.f) || !(value_weight >= 0.f) || std::isinf(policy_weight) || std::isinf(value_weight))
+    return nfail(HSAD_ERR_INVALID, "clone_soft_tail: the weights of the two terms must be finite and not negative");
+  if (value_weight != 0.f && (!ret || !vloss || ldh < A + 1))
+    return nfail(HSAD_ERR_INVALID, "clone_soft_tail: the value term needs the returns, vloss and the value column (ldh >= A + 1)");
+  const size_t lds = (2 * (size_t)T + 4 * kCloneSoftWaves) * 4;
+  if (lds > 64 * 1024) return nfail(HSAD_ERR_INVALID, "clone_soft_tail: T too long for one workgroup's step buffers");
+  CloneSoftArgs p{heads, legal, target, ret, seq_len, weight, action, ldh, T, B, A, policy_weight, value_weight, loss, vloss, hits, decisions, bad,
+                  steps, (bf16_t*)dheads16, ldo};
+  hipLaunchKernelGGL(clone_soft_tail_kernel, dim3(B), dim3(kCloneSoftThreads), lds, (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
 }

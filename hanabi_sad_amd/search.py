@@ -669,21 +669,25 @@ def move_seed(search_seed, move):
 class SearchPlay:
     """what play_with_search returns: scores (list, one per deal), mean, perfect (fraction of perfect games), num_perfect,
     deviations int64 [num_game] (moves where search overrode the blueprint) and trace: per move a pair of int64 [num_game] CPU
-    tensors (chosen, blueprint), -1 where the game's player on turn did not search"""
+    tensors (chosen, blueprint), -1 where the game's player on turn did not search.  From play_with_search(records=...), else None:
+    records = the game_record.GameRecord list of the games played (moves = the moves made, search's choices included; greedy = the
+    blueprint's), meta = {game, deal_seed, worlds, search_seed}; search_values = one float32 [n_moves, A] numpy array per record, in the
+    same order: SearchValues.values of every move, NaN rows where the game's player on turn did not search"""
 
-    def __init__(self, scores, perfect_score, deviations, trace):
+    def __init__(self, scores, perfect_score, deviations, trace, records=None, search_values=None):
         self.scores = [int(s) for s in scores]
         self.mean = float(np.mean(scores))
         self.num_perfect = int((np.asarray(scores) == perfect_score).sum())
         self.perfect = self.num_perfect / len(self.scores)
         self.sem = float(np.std(scores) / np.sqrt(len(self.scores)))
         self.deviations, self.trace = deviations, trace
+        self.records, self.search_values = records, search_values
 
 
 def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05, search_seed=0, searcher="all", capacity=4096,
                      num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16", shuffle_color=False, colors=5, ranks=5,
                      max_information_tokens=8, max_life_tokens=3, replay_history=False, consistent_only=False, sampler="rejection",
-                     rounds=None, prune_z=2.0, deviate_z=0.0):
+                     rounds=None, prune_z=2.0, deviate_z=0.0, records=False):
     """eval.evaluate's lock-step loop over the deals seed .. seed + num_game - 1 with search on top of the blueprint -> SearchPlay.
     Before each step: PolicySearch values for the games whose player on turn searches (searcher: "all" or a seat number),
     choose_action, then the root steps with a = the chosen action and greedy_a = the blueprint's greedy action; the carried state
@@ -693,14 +697,22 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
     replay_history=True: the root tracks its deck history, a GameLog keeps the rows it was stepped with and the search rebuilds
     every world's LSTM states by replay (PolicySearch(replay=True)); consistent_only and sampler as there.
     rounds=(n0, n1, ...): every search runs in rounds with pruning at prune_z (policy_action_values) and the move is
-    choose_action_paired(sv, threshold, deviate_z) instead of choose_action."""
+    choose_action_paired(sv, threshold, deviate_z) instead of choose_action.
+    records=True, or a game_record.GameFilter (as in eval.play_seatings): the games are also written down.  The root tracks its deck
+    history, a game_record.GameRecorder appends (a, greedy_a) as the root is stepped with them -- a is the move made, search's choice
+    included, greedy_a the blueprint's move -- and every move's SearchValues.values is kept on the device ([max_steps, G, A] float32,
+    NaN where no search ran).  SearchPlay.records / .search_values hold the kept games; only those cross to the host.  What search
+    found can then be cloned back into the net: clone.search_targets, clone.sequences_from_records(targets=...).  records=False
+    changes nothing: no call more per move, the same scores, deviations and trace."""
+    if records is False:
+        records = None
     _check_sampler(sampler)
     if rounds is not None and worlds > 0:
         _check_rounds(rounds, worlds, prune_z, 2)
     from .eval import _acting_agent, _drain_errors
     agent = _acting_agent(agent, precision, device)
     env = BatchedHanabiEnv(num_game, players=num_player, hand_size=hand_size, seed=seed, bomb=bomb, eps_list=[0.0], max_len=-1, sad=bool(sad),
-                           shuffle_color=bool(shuffle_color), device=device, track_deck_history=bool(replay_history), colors=colors, ranks=ranks,
+                           shuffle_color=bool(shuffle_color), device=device, track_deck_history=bool(replay_history) or records is not None, colors=colors, ranks=ranks,
                            max_information_tokens=max_information_tokens, max_life_tokens=max_life_tokens)
     seat = None if searcher == "all" else int(searcher)
     if seat is not None and not 0 <= seat < num_player:
@@ -712,9 +724,16 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
     N = num_game * num_player
     deviations = torch.zeros(num_game, dtype=torch.int64, device=env.device)
     trace = []
+    recorder = kept = kept_values = all_values = None
     try:
+        if records is not None:
+            from .game_record import GameRecorder
+            recorder = GameRecorder(env)
+            all_values = torch.full((max_steps, num_game, env.A), float("nan"), dtype=torch.float32, device=env.device)
         hid = agent.get_h0(N)
         env.reset()
+        if recorder is not None:
+            recorder.clear()
         noop = env.A - 1
         for t in range(max_steps):
             q = env.query()
@@ -727,6 +746,8 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
             if ps is None:
                 live = (~done).unsqueeze(1)
                 a = torch.where(live, a.view(num_game, num_player), torch.full_like(a.view(num_game, num_player), noop)).contiguous()
+                if recorder is not None:
+                    recorder.append(a, a)
                 env.step(a, a)
             else:
                 sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat, log=log, rounds=rounds, prune_z=prune_z)
@@ -745,6 +766,9 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
                                                        env.a.data_ptr(), env.greedy_a.data_ptr(), env._stream()))
                 if log is not None:
                     log.append(env.a, env.greedy_a)
+                if recorder is not None:      # the move about to be made, on the position before it (as the tournament loop logs)
+                    recorder.append(env.a, env.greedy_a)
+                    all_values[t].copy_(sv.values)
                 env.step(env.a, env.greedy_a)
                 if log is not None:
                     log.observed(env)
@@ -753,8 +777,21 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
             hid = new_hid
         _drain_errors(env)
         scores = env.query()[:, 5].cpu().numpy().astype(np.int64)
+        if recorder is not None:      # filtered on the device; only the kept games' records and values cross to the host
+            lost = recorder.overflow_count()
+            if lost:
+                raise _lib.HsadError("the game log overflowed %d time(s): a game ran past the capacity the rules allow" % lost)
+            kept = recorder.collect(None if records is True else records)
+            index = torch.tensor([rec.meta["game"] for rec in kept], dtype=torch.int64, device=env.device)
+            values = all_values.index_select(1, index).cpu().numpy()      # [max_steps, kept, A]
+            kept_values = []
+            for k, rec in enumerate(kept):
+                rec.meta.update(deal_seed=int(seed + rec.meta["game"]), worlds=int(worlds), search_seed=int(search_seed))
+                kept_values.append(np.ascontiguousarray(values[:rec.n_moves, k]))
     finally:
+        if recorder is not None:
+            recorder.close()
         if ps is not None:
             ps.close()
         env.close()
-    return SearchPlay(scores, colors * ranks, deviations.cpu(), trace)
+    return SearchPlay(scores, colors * ranks, deviations.cpu(), trace, kept, kept_values)

@@ -892,6 +892,19 @@ int hsad_clone_tail(const float* heads, int ldh, const float* legal, const int64
 int hsad_clone_value_tail(const float* heads, int ldh, const float* legal, const int64_t* action, const float* ret, const float* seq_len,
                           const float* weight, int T, int B, int A, float policy_weight, float value_weight, float* loss, float* vloss, int32_t* hits,
                           int32_t* decisions, int32_t* bad, int32_t* steps, void* dheads16, int ldo, void* stream);
+/* hsad_clone_value_tail against a TARGET DISTRIBUTION per row instead of the one recorded move, one launch: target fp32 [M, A], a probability row
+ * pi for every row m = t B + b (search values at a temperature, a teacher's policy; clone.soft_targets).  z, mx, S and softmax_j as there; with
+ * sigma = sum_{legal j} pi_j in ascending j:  xent = sigma log S - sum_{legal j} pi_j (z_j - mx), the policy part of dheads16 column j < A is
+ * policy_weight (sigma softmax_j - pi_j), summed in fp32 with the unchanged value term (which still reads action[m] and ret[m]) and rounded to
+ * bf16 once.  hits and decisions are still counted against action[m].  A valid row is bad (counted in bad, all-zero gradient bits, no
+ * contribution) when action[m] is bad by hsad_clone_tail's rule, a pi_j is negative or NaN, an illegal column has pi_j != 0 or
+ * |sigma - 1| > 1e-3 -- a condition on the input, not a tolerance: a row made in fp32 from A <= 51 terms is within A 2^-23 of 1.  A single-legal
+ * row must carry its mass on that action; it is xent = 0 and no policy gradient, as there.  Rows past seq_len read no target.  Where pi is the
+ * one-hot of action[m] (1.0f and zeros) every output has the bits of hsad_clone_value_tail.  Refused: what hsad_clone_value_tail refuses, and
+ * target == NULL (that call is hsad_clone_value_tail).  No float atomics, the same bits run to run.  The row is csrc/hsad_clone_soft.h. */
+int hsad_clone_soft_tail(const float* heads, int ldh, const float* legal, const int64_t* action, const float* target, const float* ret,
+                         const float* seq_len, const float* weight, int T, int B, int A, float policy_weight, float value_weight, float* loss,
+                         float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps, void* dheads16, int ldo, void* stream);
 /* column sums (bias gradients) of a bf16 / fp32 [M, ld] matrix -> fp32 [N] */
 int hsad_colsum(const void* src, int is_bf16, int M, int N, int ld, float* out, void* stream);
 /* accumulating variant (no zeroing): out[col_map ? col_map[c] : c] += column sum c, and the same into out2 when given
@@ -1238,6 +1251,15 @@ int hsad_r2d2_clone_fwd(hsad_r2d2_learner* learner, const float* priv_s, const v
 int hsad_r2d2_clone_value_fwd(hsad_r2d2_learner* learner, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a,
                               const float* ret, const float* seq_len, const float* weight, float policy_weight, float value_weight, float* loss,
                               float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps, int want_grad, void* stream);
+/* hsad_r2d2_clone_value_fwd with hsad_clone_soft_tail at its end: target [T, rows, A], a probability row per (step, sequence), takes the place
+ * of the one-hot of a in the cross-entropy (a is still what hits / decisions count against and what the value term reads).  The same one-net
+ * schedule, the same hand-off to hsad_r2d2_loss_bwd + hsad_r2d2_optimizer_step, hsad_r2d2_loss_bwd_weighted behind it is refused, and every
+ * argument is checked before anything is launched (target == NULL included).  Distillation of a search into its blueprint is this call on
+ * clone.soft_targets of the search's action values. */
+int hsad_r2d2_clone_soft_fwd(hsad_r2d2_learner* learner, const float* priv_s, const void* priv_s_bf16, const float* legal_move, const int64_t* a,
+                             const float* target, const float* ret, const float* seq_len, const float* weight, float policy_weight,
+                             float value_weight, float* loss, float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps,
+                             int want_grad, void* stream);
 /* clip_grad_norm_ + Adam.step + operand refresh; grad_norm_sq_dev (may be NULL) receives a device pointer to the squared
  * pre-clip gradient norm */
 int hsad_r2d2_optimizer_step(hsad_r2d2_learner* learner, float beta1, float beta2, float** grad_norm_sq_dev, void* stream);

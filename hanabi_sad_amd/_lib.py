@@ -155,6 +155,8 @@ SIGNATURES = {
     "hsad_env_determinize": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "hsad_env_hand_belief": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "hsad_env_determinize_exact": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_int, _P, _P, _P]),
+    "hsad_env_hand_knowledge": (C.c_int, [_P, _P, _P, _P, _P]),
+    "hsad_env_determinize_belief": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_uint64, _P, _P, _P]),
     "hsad_env_playout_random": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
     "hsad_env_playout_random_keyed": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P, _P]),
     "hsad_env_policy_rule": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_uint64, _P, _P, _P, _P]),
@@ -243,6 +245,7 @@ SIGNATURES = {
                                         _P]),
     "hsad_clone_soft_tail": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _P,
                                        C.c_int, _P]),
+    "hsad_belief_tail": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "hsad_colsum":(C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "hsad_colsum_acc": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "hsad_colsum_acc_ordered": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -180,11 +180,15 @@ class CloneDataset:
     made with a gamma): float32 [T, N], the discounted return-to-go of the WHOLE recorded game from step t on, the same on every seat's
     row of a game, 0 at and past seq_len.  target (None unless the sequences were made with targets): float32 [T, N, A], the distribution
     the cross-entropy is taken against -- the record's target row on the mover's row, the one-hot of the no-op on every other valid row,
-    zeros at and past seq_len."""
+    zeros at and past seq_len.  pool int64 [T, N], compat / cards int32 [T, N, hand_size] (None unless the sequences were made with
+    knowledge=True): env.hand_knowledge() of the row's seat before move t -- what the seat knows about its own hand and the hand itself,
+    the labels of belief.BeliefHead; zeros and -1 at and past seq_len."""
 
-    def __init__(self, priv_s, priv_s_bf16, legal_move, a, seq_len, game, seat, truncated=0, ret=None, target=None):
+    def __init__(self, priv_s, priv_s_bf16, legal_move, a, seq_len, game, seat, truncated=0, ret=None, target=None, pool=None, compat=None,
+                 cards=None):
         self.priv_s, self.priv_s_bf16, self.legal_move, self.a = priv_s, priv_s_bf16, legal_move, a
         self.seq_len, self.game, self.seat, self.truncated, self.ret, self.target = seq_len, game, seat, int(truncated), ret, target
+        self.pool, self.compat, self.cards = pool, compat, cards
 
     @property
     def n_rows(self):
@@ -202,7 +206,7 @@ class CloneDataset:
         rows = torch.as_tensor(rows, dtype=torch.int64, device=self.seq_len.device)
         sel = lambda x: None if x is None else x.index_select(1, rows)      # noqa: E731
         return CloneDataset(sel(self.priv_s), sel(self.priv_s_bf16), sel(self.legal_move), sel(self.a), self.seq_len[rows], self.game[rows],
-                            self.seat[rows], self.truncated, sel(self.ret), sel(self.target))
+                            self.seat[rows], self.truncated, sel(self.ret), sel(self.target), sel(self.pool), sel(self.compat), sel(self.cards))
 
     def split(self, holdout, seed):
         """-> (train, held_out), split by GAME: every kept seat of a game goes to the same side.  holdout: the fraction of games held
@@ -242,11 +246,13 @@ class CloneDataset:
                 batch["ret"] = pick(self.ret)
             if self.target is not None:      # (a padding column has seq_len 0: its zero rows are never read)
                 batch["target"] = pick(self.target)
+            if self.pool is not None:
+                batch["pool"], batch["compat"], batch["cards"] = pick(self.pool), pick(self.compat), pick(self.cards)
             yield batch, real.float(), index
 
 
 # ---- device side --------------------------------------------------------------------------------------------------------------------
-def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:0", bf16=True, gamma=None, targets=None):
+def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:0", bf16=True, gamma=None, knowledge=False, targets=None):
     """the observation sequences of the recorded games -> CloneDataset with T = max_len (None: game_record.capacity(rules)).
     Game j is records[j] reopened at its first deal (game_record.replay(records, stop=0) on an env of the records' rules, sad as
     given) and stepped with its recorded moves and greedy alternatives; step t's rows are the observations BEFORE move t.  One
@@ -258,7 +264,9 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
     the actions of the position before move t -- soft_targets / search_targets make them from action values; nothing is normalised here.
     check_targets holds them to that (shape, finite, not negative, mass 1) before any device work; that the mass lies on legal actions is
     checked by the update itself (bad rows).  CloneDataset.target then carries, at step t, the record's row t on the mover's row (seat
-    t % P) and the one-hot of the no-op on every other valid row."""
+    t % P) and the one-hot of the no-op on every other valid row.
+    knowledge (False: no such fields, and nothing below happens): env.hand_knowledge() of the kept seats is stored at every kept step as
+    CloneDataset.pool / .compat / .cards (zeros and -1 on padding rows)."""
     from .env import BatchedHanabiEnv
     from .eval import _drain_errors
     records = list(records)
@@ -312,6 +320,12 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
             tg = torch.from_numpy(tg_host).to(dev)
             target = torch.zeros(T, N, A, dtype=torch.float32, device=dev)
             t_step = torch.empty(G, P, A, dtype=torch.float32, device=dev)
+        k_pool = k_compat = k_cards = None
+        if knowledge:
+            Hs = r["hand_size"]
+            k_pool = torch.zeros(T, N, dtype=torch.int64, device=dev)
+            k_compat = torch.zeros(T, N, Hs, dtype=torch.int32, device=dev)
+            k_cards = torch.full((T, N, Hs), -1, dtype=torch.int32, device=dev)
         for t in range(steps):
             live = t < lens_d                                   # [G]: the step is kept
             moving = t < step_lens_d                            # [G]: the game is stepped (past `live` only for the returns of cut games)
@@ -323,6 +337,11 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
                 else:
                     priv[t] = p_rows
                 legal[t] = env.legal_move.view(G * P, A)[rows] * live_rows.view(-1, 1)
+                if knowledge:
+                    hp, hc, hk = env.hand_knowledge()
+                    k_pool[t] = hp.view(G * P)[rows] * live_rows
+                    k_compat[t] = hc.view(G * P, Hs)[rows] * live_rows.view(-1, 1)
+                    k_cards[t] = torch.where(live_rows.view(-1, 1), hk.view(G * P, Hs)[rows], torch.full_like(k_cards[t], -1))
             a_step.fill_(noop)
             g_step.fill_(noop)
             a_step[:, t % P] = torch.where(moving, mv[t], torch.full_like(mv[t], noop))
@@ -348,7 +367,7 @@ def sequences_from_records(records, sad, seats=None, max_len=None, device="cuda:
         ret = torch.zeros(T, N, dtype=torch.float32, device=dev)
         ret[:kept_steps] = whole[:kept_steps][:, row_game] * (torch.arange(kept_steps, device=dev).view(-1, 1) < seq_len.view(1, -1))
     return CloneDataset(None if bf16 else priv, priv if bf16 else None, legal, act, seq_len, row_game.clone(), torch.from_numpy(flat % P).to(dev),
-                        truncated, ret, target)
+                        truncated, ret, target, k_pool, k_compat, k_cards)
 
 
 def records_from_teacher(pool, num_game, seed, sad, *, seating=None, num_player=2, bomb=0, device="cuda:0", names=None, temperature=None,

@@ -1,10 +1,13 @@
 // hsad_env_belief.inc — the exact belief over a hidden hand, and the sampler built on it: how many hands the viewer's card knowledge
 // allows and with what per-slot marginals (hsad_env_hand_belief), and the rejection-free, stratifiable counterpart of
-// hsad_env_determinize that turns a rank in [0, N) into a hand (hsad_env_determinize_exact).  Textually part of hsad_env.hip, after
+// hsad_env_determinize that turns a rank in [0, N) into a hand (hsad_env_determinize_exact); and the env side of the learned belief
+// (hsad_belief_head.h): every seat's knowledge of its own hand (hsad_env_hand_knowledge) and the sampler that draws a hand from the
+// exact belief tilted by a head's logits (hsad_env_determinize_belief).  Textually part of hsad_env.hip, after
 // hsad_env_search.inc: it uses that file's compat_mask, observe pass and SAD-section source as they are.  The integer arithmetic is
 // hsad_hand_count.h, shared with the CPU suite.  Nothing here is reached by any other entry point.
 
 #include "hsad_hand_count.h"
+#include "hsad_belief_head.h"
 
 namespace {
 
@@ -121,9 +124,89 @@ __global__ void env_determinize_exact_kernel(EnvParams ep, const int32_t* __rest
   sel[g] = rank >= 0 ? g : -1;
 }
 
+// ---- the knowledge of every seat, as the learned belief's dataset stores it: one thread per (game, seat) ---------------------------
+// pool / compat are hand_knowledge's (what env_hand_belief_kernel counts with for that viewer), cards the seat's true hand; a game
+// that is not live gets zeros and -1.  Reads the state only.
+__global__ void env_hand_knowledge_kernel(EnvParams ep, int64_t* __restrict__ pool_out, int32_t* __restrict__ compat_out,
+                                          int32_t* __restrict__ cards_out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= ep.G * ep.P) return;
+  const int g = r / ep.P, p = r - g * ep.P, H = ep.H;
+  HandKnowledge k;
+  const bool live = hand_knowledge(ep, g, p, &k);
+  pool_out[r] = live ? (int64_t)k.pool : 0;
+  for (int i = 0; i < H; ++i) {
+    const bool occ = live && i < k.L;
+    compat_out[(size_t)r * H + i] = occ ? (int32_t)k.cm[i] : 0;
+    cards_out[(size_t)r * H + i] = occ ? (int32_t)((k.hw >> (5 * i)) & 31u) : -1;
+  }
+}
+
+// ---- learned-belief determinise: one thread per game, the shape of env_determinize_exact_kernel ------------------------------------
+// The hand of viewer[g] becomes bh_row's sample (csrc/hsad_belief_head.h, sample mode) under the game's logits row, slot i drawing
+// with the policy hash of (seed, key[g], i) on stream 66; the deck counts become the pool the sample leaves.  A game left alone --
+// skipped, or a row the sampler refuses (non-finite logits) -- gets status 0, logp 0 and sel = -1.
+__global__ void env_determinize_belief_kernel(EnvParams ep, const int32_t* __restrict__ viewer, const float* __restrict__ logits, int ldz,
+                                              const int64_t* __restrict__ key, uint64_t seed, float* __restrict__ logp_out,
+                                              int32_t* __restrict__ status_out, int32_t* __restrict__ sel) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ep.G) return;
+  int status = 0;
+  float logp = 0.f;
+  HandKnowledge k;
+  if (hand_knowledge(ep, g, viewer[g], &k)) {
+    const int p = viewer[g];
+    const uint64_t k64 = (uint64_t)key[g];
+    uint32_t u[HC_MAX_SLOTS];
+    for (int i = 0; i < HC_MAX_SLOTS; ++i) u[i] = policy_hash(seed, k64, (uint64_t)i, 66ull);
+    const bh_row_out r = bh_row(logits + (size_t)g * ldz, k.pool, k.cm, nullptr, u, k.L, ep.H, 0.f, false, 0, [](int, float) {});
+    if (!r.bad) {
+      const uint32_t low = k.L >= 5 ? 0x1ffffffu : ((1u << (5 * k.L)) - 1u);
+      GP(PLH(p)) = (k.hw & ~low) | r.hand;
+      GP(PL_DECK_LO) = (uint32_t)r.q;
+      GP(PL_DECK_HI) = (uint32_t)(r.q >> 32);
+      status = 1;
+      logp = -r.nll;
+    }
+  }
+  if (logp_out) logp_out[g] = logp;
+  if (status_out) status_out[g] = status;
+  sel[g] = status ? g : -1;
+}
+
 }  // namespace
 
 extern "C" {
+
+int hsad_env_hand_knowledge(hsad_env* e, int64_t* pool_out, int32_t* compat_out, int32_t* cards_out, void* stream) {
+  if (!e || !pool_out || !compat_out || !cards_out) return set_error(HSAD_ERR_INVALID, "null argument");
+  if (e->ep.H > HC_MAX_SLOTS) return set_error(HSAD_ERR_INVALID, "hsad_env_hand_knowledge: hands of more than 5 slots");
+  const int n = e->ep.G * e->ep.P;
+  hipLaunchKernelGGL(env_hand_knowledge_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->ep, pool_out, compat_out, cards_out);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_env_determinize_belief(hsad_env* e, const int32_t* viewer, const float* logits, int ldz, const int64_t* key, uint64_t seed,
+                                float* logp_out, int32_t* status_out, void* stream) {
+  if (!e || !viewer || !logits || !key) return set_error(HSAD_ERR_INVALID, "null argument");
+  if (e->ep.H > HC_MAX_SLOTS) return set_error(HSAD_ERR_INVALID, "hsad_env_determinize_belief: hands of more than 5 slots");
+  if (ldz < e->ep.H * HC_TYPES) return set_error(HSAD_ERR_INVALID, "hsad_env_determinize_belief: ldz must be at least 25 logits per slot of the hand");
+  if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
+  ObserveArgs oa;
+  if (!sad_source(e, &oa) && e->ep.sad)
+    return set_error(HSAD_ERR_INVALID, "hsad_env_determinize_belief: sad = 1 needs the env's own observation rows (float32 or bit words)");
+  if (!e->d_sel) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMalloc((void**)&e->d_sel, sizeof(int32_t) * (size_t)e->ep.Gpad));
+  }
+  oa.sel = e->d_sel;
+  oa.sel_limit = e->ep.G;
+  hipLaunchKernelGGL(env_determinize_belief_kernel, dim3((e->ep.G + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->ep, viewer, logits, ldz, key,
+                     seed, logp_out, status_out, e->d_sel);
+  HIP_TRY(hipGetLastError());
+  return launch_observe(e, oa, (hipStream_t)stream);
+}
 
 int hsad_env_hand_belief(hsad_env* e, const int32_t* viewer, int64_t* total_out, int64_t* counts_out, int64_t* trinary_out, void* stream) {
   if (!e || !viewer || !total_out || !counts_out) return set_error(HSAD_ERR_INVALID, "null argument");

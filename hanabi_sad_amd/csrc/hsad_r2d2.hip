@@ -34,6 +34,7 @@
 #include "hsad_gemm_plan.h"
 #include "hsad_act_sample.h"
 #include "hsad_clone_soft.h"
+#include "hsad_belief_head.h"
 
 extern "C" int hsad_internal_set_error(int code, const char* msg);
 
@@ -52,6 +53,7 @@ namespace {
 #include "r2d2/clone_loss.inc"
 #include "r2d2/clone_value.inc"
 #include "r2d2/clone_soft.inc"
+#include "r2d2/belief_tail.inc"
 #include "r2d2/act.inc"
 }  // namespace
 
@@ -1118,6 +1120,21 @@ int hsad_clone_soft_tail(const float* heads, int ldh, const float* legal, const 
   CloneSoftArgs p{heads, legal, target, ret, seq_len, weight, action, ldh, T, B, A, policy_weight, value_weight, loss, vloss, hits, decisions, bad,
                   steps, (bf16_t*)dheads16, ldo};
   hipLaunchKernelGGL(clone_soft_tail_kernel, dim3(B), dim3(kCloneSoftThreads), lds, (hipStream_t)stream, p);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_belief_tail(const float* logits, int ldz, const int64_t* pool, const int32_t* compat, const int32_t* cards, const float* seq_len,
+                     const float* weight, int T, int B, int Hs, float* nll, float* nll0, int32_t* cards_n, int32_t* hits, int32_t* hits0, int32_t* bad,
+                     void* dlogits16, int ldo, void* stream) {
+  if (!logits || !pool || !compat || !cards || !seq_len || !nll || !nll0 || !cards_n || !hits || !hits0 || !bad || T < 1 || B < 1)
+    return nfail(HSAD_ERR_INVALID, "belief_tail: null argument or bad shape");
+  if (Hs < 1 || Hs > HC_MAX_SLOTS || ldz < Hs * HC_TYPES) return nfail(HSAD_ERR_INVALID, "belief_tail: hands of 1..5 slots, ldz >= 25 slots");
+  if (dlogits16 && (!weight || ldo < Hs * HC_TYPES)) return nfail(HSAD_ERR_INVALID, "belief_tail: the gradient needs the weights and ldo >= 25 slots");
+  const size_t lds = sizeof(BeliefWaveLds) * kBeliefTailWaves + 2 * (size_t)T * 4;
+  if (lds > 64 * 1024) return nfail(HSAD_ERR_INVALID, "belief_tail: T too long for one workgroup's step buffers");
+  BeliefTailArgs p{logits, pool, compat, cards, seq_len, weight, ldz, T, B, Hs, nll, nll0, cards_n, hits, hits0, bad, (bf16_t*)dlogits16, ldo};
+  hipLaunchKernelGGL(belief_tail_kernel, dim3(B), dim3(kBeliefTailThreads), lds, (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
 }

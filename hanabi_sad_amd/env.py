@@ -296,6 +296,34 @@ class BatchedHanabiEnv:
                                                        rk.data_ptr() if rk is not None else None, out.data_ptr(), self._stream()))
         return out
 
+    def hand_knowledge(self):
+        """what every seat knows about its own hand, as the learned belief (belief.py) is trained on it -> (pool int64 [G, P],
+        compat int32 [G, P, H], cards int32 [G, P, H]): the pool and per-slot masks hand_belief counts with for that viewer, and the
+        seat's true cards (-1 = empty slot); zeros and -1 for a game that is not live.  Reads the state only.
+        See hsad_env_hand_knowledge."""
+        pool = torch.zeros(self.G, self.P, dtype=torch.int64, device=self.device)
+        compat = torch.zeros(self.G, self.P, self.H, dtype=torch.int32, device=self.device)
+        cards = torch.zeros(self.G, self.P, self.H, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.hsad_env_hand_knowledge(self.h, pool.data_ptr(), compat.data_ptr(), cards.data_ptr(), self._stream()))
+        return pool, compat, cards
+
+    def determinize_belief(self, viewer, logits, key, seed):
+        """determinize_exact's counterpart for the learned belief: the hand of player viewer[g] (int32 [G]; -1 = skip) is sampled
+        slot by slot from the belief that logits (float32 [G, >= 25 H], row g: 25 logits per slot) tilt the exact belief into; key
+        (int64 [G]) and seed select the world.  All-zero logits sample the exact belief.  Returns (status int32 [G]: 1 sampled,
+        0 left alone; logp float32 [G]: the sampled hand's log-probability).  See hsad_env_determinize_belief."""
+        v = self._i32(viewer, self.G)
+        k = torch.as_tensor(key, device=self.device).to(torch.int64).contiguous()
+        assert k.shape == (self.G,)
+        if not (torch.is_tensor(logits) and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == self.G
+                and logits.shape[1] >= 25 * self.H and logits.stride(1) == 1 and logits.is_cuda):
+            raise ValueError("logits must be float32 [%d, >= %d] on %s with unit column stride" % (self.G, 25 * self.H, self.device))
+        status = torch.zeros(self.G, dtype=torch.int32, device=self.device)
+        logp = torch.zeros(self.G, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hsad_env_determinize_belief(self.h, v.data_ptr(), logits.data_ptr(), int(logits.stride(0)), k.data_ptr(),
+                                                        int(seed) & (2 ** 64 - 1), logp.data_ptr(), status.data_ptr(), self._stream()))
+        return status, logp
+
     def playout_random(self, max_iter, policy_seed, key=None):
         """random-legal policy -> step until every live game has ended (at most max_iter iterations), finished games left alone.
         The observation rows are NOT rewritten (stale until the next fork_from / reset / step); terminal and query() are current.

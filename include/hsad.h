@@ -336,6 +336,23 @@ int hsad_env_hand_belief(hsad_env* env, const int32_t* viewer, int64_t* total_ou
 int hsad_env_determinize_exact(hsad_env* env, const int32_t* viewer, const int64_t* key, uint64_t seed, const int32_t* stratum, int n_strata,
                                const int64_t* rank_in, int64_t* rank_out, void* stream);
 
+/* The learned hand belief on the env (model: hsad_belief_tail below; row: csrc/hsad_belief_head.h).
+ * hsad_env_hand_knowledge: for every seat p of every game g, what hsad_env_hand_belief counts with for viewer p, and the seat's true
+ * hand: pool_out device int64 [G, P] (deck count + copies in the seat's hand, two bits per card type), compat_out device int32
+ * [G, P, H] (the 25-bit mask of the types plausible for the slot; 0 for an empty slot), cards_out device int32 [G, P, H] (the card
+ * type, -1 for an empty slot).  A game that was never started or is finished gets zeros and -1.  Reads the state only.
+ * hsad_env_determinize_belief: hsad_env_determinize_exact's counterpart that samples the hand of viewer[g] from the learned belief
+ * under logits fp32 [G, ldz] (row g: 25 logits per slot, ldz >= 25 H): slot by slot with u_i = hash(seed, key[g], i, 66), the
+ * policy's hash on stream 66, as hsad_belief_tail's model prescribes in sample mode.  Same skip rules, same LEFT ALONE semantics
+ * (also for a row with a non-finite logit on an occupied slot), same observe pass afterwards and the same sad = 1 precondition.  The
+ * deck counts become the pool the sample leaves.  status_out device int32 [G] or NULL: 1 sampled, 0 left alone; logp_out device
+ * float [G] or NULL: the log-probability of the sampled hand under the belief (0 when left alone).  With all-zero logits the
+ * distribution is hsad_env_determinize_exact's.  Every sampled hand is consistent with the card knowledge and the card counts.
+ * Launch-only. */
+int hsad_env_hand_knowledge(hsad_env* env, int64_t* pool_out, int32_t* compat_out, int32_t* cards_out, void* stream);
+int hsad_env_determinize_belief(hsad_env* env, const int32_t* viewer, const float* logits, int ldz, const int64_t* key, uint64_t seed,
+                                float* logp_out, int32_t* status_out, void* stream);
+
 /* hsad_env_playout_random: up to max_iter iterations of random-legal policy -> step for every game that is started and not
  * finished, in one launch.  A finished game is left alone (no restart, no error, no counter advance); a live game's trajectory --
  * actions in a / greedy_a, state, draws -- is that of hsad_env_policy_random + hsad_env_step.  NO observation rows are written
@@ -905,6 +922,25 @@ int hsad_clone_value_tail(const float* heads, int ldh, const float* legal, const
 int hsad_clone_soft_tail(const float* heads, int ldh, const float* legal, const int64_t* action, const float* target, const float* ret,
                          const float* seq_len, const float* weight, int T, int B, int A, float policy_weight, float value_weight, float* loss,
                          float* vloss, int32_t* hits, int32_t* decisions, int32_t* bad, int32_t* steps, void* dheads16, int ldo, void* stream);
+/* The loss of the learned hand belief, one launch.  Row m = t B + b; logits fp32 [T B, ldz], z[i 25 + type] for slot i; pool device
+ * int64 [T, B], compat / cards device int32 [T, B, Hs] as hsad_env_hand_knowledge writes them (cards -1 = empty slot; the occupied
+ * slots are the n before the first -1).  The belief factorises slot by slot with the exact belief as base measure; q = pool before
+ * slot 0, rem = the slots after i, C as in hsad_env_hand_belief:
+ *   w_i[type] = q[type] compat_i[type] C(rem, q - e_type)   (int64, exact);  F_i = the types with w_i != 0
+ *   mx_i = max of z over F_i;  v = (float)w_i exp(z - mx_i);  S_i = sum of v over F_i, types ascending (fp32);  p_i = v (1 / S_i)
+ *   then q[card_i] -= 1 with the true card of slot i.
+ * Per valid row (t < seq_len[b]): nll = sum_i (log S_i - log (float)w_i[card_i]) - (z[card_i] - mx_i); nll0 = the same at z = 0 (the
+ * score of the exact public belief); cards = the slots with |F_i| >= 2; hits / hits0 = of those, the slots where the true card is the
+ * argmax of p_i / of w_i (lowest type on ties).  A row is bad -- counted in bad, nothing else, all-zero gradient bits -- when a true
+ * card is outside F_i, a card id is outside 0..24 on an occupied slot, a card follows an empty slot, or an occupied slot has a
+ * non-finite logit.  nll[b], nll0[b] float [B]: sums in ascending t; cards_n, hits, hits0, bad int32 [B].  dlogits16 (NULL = no
+ * gradient): bf16 [T B, ldo], column i 25 + type = s (p_i[type] - [type == card_i]) on F_i with s = weight[b] / B, 0 elsewhere, for
+ * empty slots and up to ldo; rows at or past seq_len are zero rows.  Zero logits give nll == nll0 bit for bit.  Refused
+ * (HSAD_ERR_INVALID, nothing launched): a null argument, T or B < 1, Hs outside 1..5, ldz < 25 Hs, a gradient without weights or with
+ * ldo < 25 Hs, T too long for one workgroup's step buffers.  No float atomics, the same bits run to run. */
+int hsad_belief_tail(const float* logits, int ldz, const int64_t* pool, const int32_t* compat, const int32_t* cards, const float* seq_len,
+                     const float* weight, int T, int B, int Hs, float* nll, float* nll0, int32_t* cards_n, int32_t* hits, int32_t* hits0, int32_t* bad,
+                     void* dlogits16, int ldo, void* stream);
 /* column sums (bias gradients) of a bf16 / fp32 [M, ld] matrix -> fp32 [N] */
 int hsad_colsum(const void* src, int is_bf16, int M, int N, int ld, float* out, void* stream);
 /* accumulating variant (no zeroing): out[col_map ? col_map[c] : c] += column sum c, and the same into out2 when given

@@ -157,6 +157,7 @@ SIGNATURES = {
     "hsad_env_determinize_exact": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_int, _P, _P, _P]),
     "hsad_env_hand_knowledge": (C.c_int, [_P, _P, _P, _P, _P]),
     "hsad_env_determinize_belief": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_uint64, _P, _P, _P]),
+    "hsad_env_determinize_belief_worlds": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_uint64, _P, _P, _P, _P]),
     "hsad_env_playout_random": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P]),
     "hsad_env_playout_random_keyed": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, _P, _P]),
     "hsad_env_policy_rule": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_uint64, _P, _P, _P, _P]),
@@ -345,6 +346,7 @@ SIGNATURES = {
     "hsad_game_log_gather": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
     "hsad_env_playout_logged": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P]),
     "hsad_search_fork_state": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "hsad_search_belief_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "hsad_search_actions": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "hsad_search_job_stats": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "hsad_search_world_scores": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),

@@ -17,8 +17,11 @@ and because the trunk is frozen and the head linear, the negative log-likelihood
     python -m hanabi_sad_amd.belief --blueprint FILE.pthw (--teacher NAME|FILE ... | --games FILE [--seat ..]) --num_game N --sad 1 \\
            --num_epoch E --batchsize B --holdout 0.1 --lr 1e-3 --save_dir D
 
-Not here: sampler="learned" in search._sample_hands / PolicySearch, training the trunk through the head, a hidden layer,
-a temperature, seats other than the viewer's own hand."""
+In the searches: BeliefSampler holds a head's two tensors and turns the acting agent's state after the root act into logits
+(hsad_search_belief_rows, then the head's GEMM); search.PolicySearch(sampler="learned", belief=...) draws every world's hand with
+env.determinize_belief_worlds under them, the worlds of a game stratified slot by slot (csrc/hsad_belief_world.h).
+
+Not here: training the trunk through the head, a hidden layer, a temperature, seats other than the viewer's own hand."""
 import os
 
 import numpy as np
@@ -257,6 +260,60 @@ def check_state(sd, hand_size=None, H=None):
     if (hand_size is not None and hs != int(hand_size)) or (H is not None and h != int(H)):
         raise ValueError("the saved head is for hand_size %d, H %d; this one is hand_size %s, H %s" % (hs, h, hand_size, H))
     return hs, h
+
+
+class BeliefSampler:
+    """A head as the searches use it (search.PolicySearch(sampler="learned", belief=...)): belief.weight / belief.bias alone -- no
+    blueprint, no trunk, no optimiser state.  The features are the acting agent's own: the top LSTM layer's new h after the root
+    act.  head: a BeliefHead (its bf16 operand and bias are shared, so a head that is still being fitted is sampled as it stands),
+    a state dict (BeliefHead.state()) or the path of a saved one.  ValueError when the dict is no head (check_state), before the
+    device is touched."""
+
+    def __init__(self, head, device="cuda:0"):
+        if isinstance(head, BeliefHead):
+            self.device, self.lib = head.device, head.lib
+            self.hand_size, self.H, self.NZ, self.NZp = head.hand_size, head.H, head.NZ, head.NZp
+            self.w16, self.b32 = head.w16, head.b32
+        else:
+            sd = torch.load(head, map_location="cpu") if isinstance(head, (str, os.PathLike)) else head
+            if not isinstance(sd, dict):
+                raise ValueError("not a belief head: expected a BeliefHead, its state dict or a saved one; got %s" % type(sd).__name__)
+            self.hand_size, self.H = check_state(sd)
+            self.NZ, self.NZp = TYPES * self.hand_size, padded_logits(self.hand_size)
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise _lib.HsadError("BeliefSampler needs a ROCm device (got %s); there is no CPU path" % device)
+            self.lib = _lib.load_library()
+            w32 = torch.zeros(self.NZp, self.H, dtype=torch.float32, device=self.device)
+            self.b32 = torch.zeros(self.NZp, dtype=torch.float32, device=self.device)
+            w32[:self.NZ].copy_(sd["belief.weight"].to(self.device, torch.float32))
+            self.b32[:self.NZ].copy_(sd["belief.bias"].to(self.device, torch.float32))
+            self.w16 = torch.zeros(self.NZp, self.H, dtype=torch.bfloat16, device=self.device)
+            _lib.check(self.lib.hsad_prepare_weight(w32.data_ptr(), self.NZp, self.H, w32.stride(0), None, self.w16.data_ptr(),
+                                                    self.w16.stride(0), None, 0, _s(self.device)))
+
+    def rows(self, h_top, player):
+        """h_top float32 [G * P, H] (row g * P + p: the top LSTM layer's h), player int32 [G] -> bfloat16 [G, H]: the row of
+        player[g] per game, zeros where it is out of range (hsad_search_belief_rows)"""
+        G = int(player.shape[0])
+        if (h_top.dtype != torch.float32 or h_top.dim() != 2 or h_top.shape[1] != self.H or h_top.shape[0] % max(G, 1) or not h_top.is_contiguous()
+                or G < 1 or player.dtype != torch.int32):
+            raise ValueError("h_top must be contiguous float32 [G * P, %d] and player int32 [G]; got %s %s and %s %s"
+                             % (self.H, h_top.dtype, tuple(h_top.shape), player.dtype, tuple(player.shape)))
+        out = torch.empty(G, self.H, dtype=torch.bfloat16, device=self.device)
+        _lib.check(self.lib.hsad_search_belief_rows(h_top.data_ptr(), player.contiguous().data_ptr(), G, int(h_top.shape[0]) // G, self.H,
+                                                    out.data_ptr(), out.stride(0), _s(self.device)))
+        return out
+
+    def logits(self, h_top, player):
+        """-> float32 [G, NZp]: the head's logits for the seat player[g] of every game, from the acting agent's state (rows, then
+        the head's GEMM): two launches, once per search call"""
+        from .r2d2 import gemm_nt
+        o16 = self.rows(h_top, player)
+        G = int(o16.shape[0])
+        out = torch.empty(G, self.NZp, dtype=torch.float32, device=self.device)
+        gemm_nt(o16, self.w16, G, self.NZp, self.H, bias=self.b32, out32=out)
+        return out
 
 
 def belief_batches(data, o16, rows, seed):

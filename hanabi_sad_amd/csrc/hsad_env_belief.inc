@@ -2,7 +2,8 @@
 // allows and with what per-slot marginals (hsad_env_hand_belief), and the rejection-free, stratifiable counterpart of
 // hsad_env_determinize that turns a rank in [0, N) into a hand (hsad_env_determinize_exact); and the env side of the learned belief
 // (hsad_belief_head.h): every seat's knowledge of its own hand (hsad_env_hand_knowledge) and the sampler that draws a hand from the
-// exact belief tilted by a head's logits (hsad_env_determinize_belief).  Textually part of hsad_env.hip, after
+// exact belief tilted by a head's logits (hsad_env_determinize_belief; hsad_env_determinize_belief_worlds, appended at the end of
+// the file, for a search env: logits by root game, the worlds of a game stratified per slot).  Textually part of hsad_env.hip, after
 // hsad_env_search.inc: it uses that file's compat_mask, observe pass and SAD-section source as they are.  The integer arithmetic is
 // hsad_hand_count.h, shared with the CPU suite.  Nothing here is reached by any other entry point.
 
@@ -239,3 +240,77 @@ int hsad_env_determinize_exact(hsad_env* e, const int32_t* viewer, const int64_t
 }
 
 }  // extern "C"
+
+// ---- learned-belief determinise for a search env: logits by root game, the worlds of a game stratified per slot --------------------
+// env_determinize_belief_kernel's shape (one thread per game, 64 games per workgroup) and bh_row call; what differs is where the row
+// and the uniforms come from: game g reads logits row row[g] (NULL: g), and its slot uniforms are hsad_belief_world.h's for world
+// world[g] of n_worlds of the root game group[g] (hash stream 67).  A game left alone -- skipped, row or world out of range, a row
+// the sampler refuses -- gets status 0, logp = logp0 = 0 and sel = -1.
+#include "hsad_belief_world.h"
+
+namespace {
+
+__global__ __launch_bounds__(64) void env_determinize_belief_worlds_kernel(EnvParams ep, const int32_t* __restrict__ viewer,
+                                                                           const float* __restrict__ logits, int ldz, int n_rows,
+                                                                           const int32_t* __restrict__ row, const int64_t* __restrict__ group,
+                                                                           const int32_t* __restrict__ world, int n_worlds, uint64_t seed,
+                                                                           float* __restrict__ logp_out, float* __restrict__ logp0_out,
+                                                                           int32_t* __restrict__ status_out, int32_t* __restrict__ sel) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ep.G) return;
+  int status = 0;
+  float logp = 0.f, logp0 = 0.f;
+  HandKnowledge k;
+  const int zr = row ? row[g] : g;
+  if (zr >= 0 && zr < n_rows && hand_knowledge(ep, g, viewer[g], &k)) {
+    const int p = viewer[g];
+    const uint64_t k64 = (uint64_t)group[g];
+    uint32_t u[HC_MAX_SLOTS];
+    if (bw_uniforms([seed, k64](uint64_t c) { return policy_hash(seed, k64, c, (uint64_t)BW_STREAM); }, (int64_t)n_worlds, (int64_t)world[g], u,
+                    nullptr)) {
+      const bh_row_out r = bh_row(logits + (size_t)zr * ldz, k.pool, k.cm, nullptr, u, k.L, ep.H, 0.f, false, 0, [](int, float) {});
+      if (!r.bad) {
+        const uint32_t low = k.L >= 5 ? 0x1ffffffu : ((1u << (5 * k.L)) - 1u);
+        GP(PLH(p)) = (k.hw & ~low) | r.hand;
+        GP(PL_DECK_LO) = (uint32_t)r.q;
+        GP(PL_DECK_HI) = (uint32_t)(r.q >> 32);
+        status = 1;
+        logp = -r.nll;
+        logp0 = -r.nll0;
+      }
+    }
+  }
+  if (logp_out) logp_out[g] = logp;
+  if (logp0_out) logp0_out[g] = logp0;
+  if (status_out) status_out[g] = status;
+  sel[g] = status ? g : -1;
+}
+
+}  // namespace
+
+extern "C" int hsad_env_determinize_belief_worlds(hsad_env* e, const int32_t* viewer, const float* logits, int ldz, int n_rows, const int32_t* row,
+                                                  const int64_t* group, const int32_t* world, int n_worlds, uint64_t seed, float* logp_out,
+                                                  float* logp0_out, int32_t* status_out, void* stream) {
+  if (!e || !viewer || !logits || !group || !world) return set_error(HSAD_ERR_INVALID, "null argument");
+  if (e->ep.H > HC_MAX_SLOTS) return set_error(HSAD_ERR_INVALID, "hsad_env_determinize_belief_worlds: hands of more than 5 slots");
+  if (ldz < e->ep.H * HC_TYPES)
+    return set_error(HSAD_ERR_INVALID, "hsad_env_determinize_belief_worlds: ldz must be at least 25 logits per slot of the hand");
+  if (n_rows < 1 || (!row && n_rows < e->ep.G))
+    return set_error(HSAD_ERR_INVALID, "hsad_env_determinize_belief_worlds: n_rows must be >= 1, and >= the env's games without a row index");
+  if (n_worlds < 1 || n_worlds > (int)BW_MAX_WORLDS)
+    return set_error(HSAD_ERR_INVALID, "hsad_env_determinize_belief_worlds: n_worlds must be in [1, 2^20]");
+  if (!e->bound) return set_error(HSAD_ERR_STATE, "hsad_env_bind_outputs must be called first");
+  ObserveArgs oa;
+  if (!sad_source(e, &oa) && e->ep.sad)
+    return set_error(HSAD_ERR_INVALID, "hsad_env_determinize_belief_worlds: sad = 1 needs the env's own observation rows (float32 or bit words)");
+  if (!e->d_sel) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMalloc((void**)&e->d_sel, sizeof(int32_t) * (size_t)e->ep.Gpad));
+  }
+  oa.sel = e->d_sel;
+  oa.sel_limit = e->ep.G;
+  hipLaunchKernelGGL(env_determinize_belief_worlds_kernel, dim3((e->ep.G + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->ep, viewer, logits, ldz,
+                     n_rows, row, group, world, n_worlds, seed, logp_out, logp0_out, status_out, e->d_sel);
+  HIP_TRY(hipGetLastError());
+  return launch_observe(e, oa, (hipStream_t)stream);
+}

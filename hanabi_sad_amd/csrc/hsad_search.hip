@@ -10,6 +10,8 @@
 //               candidate action forced on the searcher's seat (first move only: the caller passes no override afterwards).
 //               greedy_a keeps the agent's greedy action -- what SAD shows the partner when the searcher deviates
 //   job_stats   the finished slots' scores summed per job (sum, sum of squares, count) with integer atomics: exact and order-free
+//   belief_rows the searcher's rows of the top layer's h after the root act -> the bf16 operand of the learned belief's head
+//               (hsad_search_belief_rows; belief.BeliefSampler, sampler = "learned")
 // and, for the replay stage that rebuilds every sampled world's LSTM states from the game's history (PolicySearch(replay=True)):
 //   world_script    the root's deal order with the viewer's current cards replaced by the world's sampled hand: what
 //                   hsad_env_rewind_scripted takes, so that the world can be played again from its first move
@@ -372,9 +374,44 @@ __global__ __launch_bounds__(kThreads) void search_round_kernel(const uint8_t* _
   }
 }
 
+// one thread per 8 consecutive values of one output row (H % 8 == 0): two 16-byte loads of the searcher's fp32 row, one 16-byte
+// store of its bf16 image; a game whose player is out of range gets a zero row.  Columns H .. ldo - 1 are not written.
+__global__ __launch_bounds__(kThreads) void belief_rows_kernel(const float* __restrict__ h_top, const int32_t* __restrict__ player, int G, int P,
+                                                               int H, unsigned short* __restrict__ out, int ldo) {
+  const int per_row = H / 8;
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= (long long)G * per_row) return;
+  const int g = (int)(i / per_row);
+  const int v = (int)(i - (long long)g * per_row);
+  const int p = player[g];
+  uint4 w = make_uint4(0u, 0u, 0u, 0u);
+  if (p >= 0 && p < P) {
+    const float* src = h_top + ((size_t)g * P + p) * H + (size_t)v * 8;
+    const float4 a = *reinterpret_cast<const float4*>(src);
+    const float4 b = *reinterpret_cast<const float4*>(src + 4);
+    w = make_uint4(f2bf_bits(a.x) | (f2bf_bits(a.y) << 16), f2bf_bits(a.z) | (f2bf_bits(a.w) << 16), f2bf_bits(b.x) | (f2bf_bits(b.y) << 16),
+                   f2bf_bits(b.z) | (f2bf_bits(b.w) << 16));
+  }
+  *reinterpret_cast<uint4*>(out + (size_t)g * ldo + (size_t)v * 8) = w;
+}
+
 }  // namespace
 
 extern "C" {
+
+int hsad_search_belief_rows(const float* h_top, const int32_t* player, int G, int P, int H, void* out_bf16, int ldo, void* stream) {
+  if (!h_top || !player || !out_bf16) return efail(HSAD_ERR_INVALID, "hsad_search_belief_rows: null argument");
+  if (G < 1 || P < 1 || H < 8 || H % 8) return efail(HSAD_ERR_INVALID, "hsad_search_belief_rows: G and P must be >= 1, H a positive multiple of 8");
+  if (ldo < H || ldo % 8) return efail(HSAD_ERR_INVALID, "hsad_search_belief_rows: ldo = %d must be a multiple of 8 and at least H = %d", ldo, H);
+  if (((uintptr_t)h_top | (uintptr_t)out_bf16) & 15u) return efail(HSAD_ERR_INVALID, "hsad_search_belief_rows: the tensors must be 16-byte aligned");
+  const long long total = (long long)G * (H / 8);
+  const long long blocks = (total + kThreads - 1) / kThreads;
+  if (blocks > 0x7fffffffLL) return efail(HSAD_ERR_INVALID, "hsad_search_belief_rows: %lld values are too many for one launch", total * 8);
+  hipLaunchKernelGGL(belief_rows_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, h_top, player, G, P, H,
+                     static_cast<unsigned short*>(out_bf16), ldo);
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
 
 int hsad_search_fork_state(const int32_t* src_index, int G_dst, int G_src, int P, int L, int H, const float* h_src, const float* c_src,
                            float* h_dst, float* c_dst, void* h16_dst, void* stream) {

@@ -324,6 +324,35 @@ class BatchedHanabiEnv:
                                                         int(seed) & (2 ** 64 - 1), logp.data_ptr(), status.data_ptr(), self._stream()))
         return status, logp
 
+    def determinize_belief_worlds(self, viewer, logits, row, group, world, n_worlds, seed):
+        """determinize_belief for a search env whose slots are forks of a few root games: game g reads logits row row[g] (int32
+        [G], None = row g; logits float32 [n_rows, >= 25 H]) and is world world[g] (int32 [G]) of n_worlds of the root game with
+        key group[g] (int64 [G]): the worlds of a group fall into every one of the n_worlds equal parts of each slot's conditional
+        exactly once.  A hand depends on (seed, group, world), the logits row and the game's state, never on the slot.  A game is
+        left alone when it is skipped, when row[g] or world[g] is out of range or when its row holds a non-finite logit.  Returns
+        (status int32 [G]: 1 sampled, 0 left alone; logp, logp0 float32 [G]: the sampled hand's log-probability under the belief
+        and under the exact belief).  See hsad_env_determinize_belief_worlds."""
+        v = self._i32(viewer, self.G)
+        r = self._i32(row, self.G) if row is not None else None
+        w = self._i32(world, self.G)
+        k = torch.as_tensor(group, device=self.device).to(torch.int64).contiguous()
+        assert k.shape == (self.G,)
+        if not (torch.is_tensor(logits) and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] >= 1
+                and (row is not None or logits.shape[0] >= self.G) and logits.shape[1] >= 25 * self.H and logits.stride(1) == 1
+                and logits.is_cuda):
+            raise ValueError("logits must be float32 [%s, >= %d] on %s with unit column stride"
+                             % ("n_rows >= 1" if row is not None else ">= %d" % self.G, 25 * self.H, self.device))
+        if not 1 <= int(n_worlds) <= 1 << 20:
+            raise ValueError("n_worlds must be in [1, 2^20]; got %r" % (n_worlds,))
+        status = torch.zeros(self.G, dtype=torch.int32, device=self.device)
+        logp = torch.zeros(self.G, dtype=torch.float32, device=self.device)
+        logp0 = torch.zeros(self.G, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.hsad_env_determinize_belief_worlds(self.h, v.data_ptr(), logits.data_ptr(), int(logits.stride(0)),
+                                                               int(logits.shape[0]), r.data_ptr() if r is not None else None, k.data_ptr(),
+                                                               w.data_ptr(), int(n_worlds), int(seed) & (2 ** 64 - 1), logp.data_ptr(),
+                                                               logp0.data_ptr(), status.data_ptr(), self._stream()))
+        return status, logp, logp0
+
     def playout_random(self, max_iter, policy_seed, key=None):
         """random-legal policy -> step until every live game has ended (at most max_iter iterations), finished games left alone.
         The observation rows are NOT rewritten (stale until the next fork_from / reset / step); terminal and query() are current.

@@ -14,6 +14,8 @@ layout.
                                                         (game_record; read it with python -m hanabi_sad_amd.game_record g.jsonl)
   --paper op  --method sad --idx 0 --search_worlds 8    M0 in self-play, blueprint only and blueprint + search over the same deals
   ... --search_worlds 32 --search_rounds 8,8,16         the same with the search in rounds (paired statistics, pruning)
+  ... --search_worlds 8 --search_sampler learned --search_belief belief.pthw    the worlds' hands drawn from a learned belief head
+                                                        (python -m hanabi_sad_amd.belief fits one)
 
 As in the reference the deals are seeds 1 .. num_game * num_run, bombing out keeps the score (bomb 0) and everyone acts greedily.
 Whether the env appends SAD's greedy-action section is read off the models' input width (838 vs 783 features in the 2-player
@@ -62,9 +64,12 @@ def parse_args(argv=None):
     p.add_argument("--search_consistent", default=0, type=int, help="1 (with --search_replay 1): count only the worlds in which the "
                    "blueprint shows the partners' observed greedy actions")
     p.add_argument("--search_seat", default=None, type=int, help="the one seat that searches (default: every seat)")
-    p.add_argument("--search_sampler", default="rejection", type=str, choices=["rejection", "stratified"],
-                   help="how the sampled worlds' hidden hands are drawn: hsad_env_determinize, or hsad_env_determinize_exact with the "
-                   "worlds of a game stratified over its exact belief")
+    p.add_argument("--search_sampler", default="rejection", type=str, choices=["rejection", "stratified", "learned"],
+                   help="how the sampled worlds' hidden hands are drawn: hsad_env_determinize, hsad_env_determinize_exact with the "
+                   "worlds of a game stratified over its exact belief, or (with --search_belief) hsad_env_determinize_belief_worlds under "
+                   "a learned belief head")
+    p.add_argument("--search_belief", default=None, type=str, metavar="FILE", help="with --search_sampler learned: the saved belief head "
+                   "(belief.BeliefHead.save; python -m hanabi_sad_amd.belief writes belief.pthw)")
     p.add_argument("--search_rounds", default=None, type=lambda s: tuple(int(x) for x in s.split(",")),
                    help="world counts per round, e.g. 8,8,16 (their sum must be --search_worlds): search in rounds, dropping hopeless "
                    "actions in between, and choose by the paired statistics (search.choose_action_paired)")
@@ -98,6 +103,29 @@ def load_pool(args):
     return [load_obl_model(args.obl_path, args.device, args.precision)], ["OBL"], "OBL", 2
 
 
+def load_search_belief(args):
+    """--search_sampler learned --search_belief FILE -> the head's state dict (None for the other samplers); a usage error when one is
+    given without the other, when the file is missing or when it holds no belief head.  Touches no device."""
+    if (args.search_sampler == "learned") != (args.search_belief is not None):
+        raise SystemExit("--search_sampler learned and --search_belief FILE go together")
+    if args.search_belief is None:
+        return None
+    if not os.path.isfile(args.search_belief):
+        raise SystemExit("--search_belief %s: no such file" % args.search_belief)
+    import torch
+    from .belief import check_state
+    try:
+        sd = torch.load(args.search_belief, map_location="cpu")
+        if not isinstance(sd, dict):
+            raise ValueError("not a belief head: the file holds a %s" % type(sd).__name__)
+        check_state(sd)
+    except ValueError as e:
+        raise SystemExit("--search_belief %s: %s" % (args.search_belief, e))
+    except Exception as e:      # not a torch file at all
+        raise SystemExit("--search_belief %s: not a saved belief head (%s)" % (args.search_belief, type(e).__name__))
+    return sd
+
+
 def search_report(args):
     """--search_worlds N with a single --idx: the model in self-play over the deals 1 .. num_game * num_run, blueprint only and
     blueprint + search -> (SearchPlay without search, SearchPlay with it)"""
@@ -105,6 +133,7 @@ def search_report(args):
     from .search import play_with_search
     if args.paper != "op" or args.cross_play or not args.idx or len(args.idx) != 1:
         raise SystemExit("--search_worlds needs --paper op and a single --idx I (no --cross_play)")
+    belief = load_search_belief(args)
     agent = load_op_model(args.method, args.idx[0], None, args.device, root=args.root, precision=args.precision)[0]
     sad = getattr(agent.online, "F", None) == env_dims(2, 5, sad=True)[0]
     n = args.num_game * args.num_run
@@ -114,7 +143,7 @@ def search_report(args):
     if args.search_rounds is not None:
         kw.update(rounds=args.search_rounds, prune_z=args.search_prune_z, deviate_z=args.search_deviate_z)
     res = play_with_search(agent, n, 1, 0, sad, worlds=args.search_worlds, replay_history=bool(args.search_replay),
-                           consistent_only=bool(args.search_consistent), sampler=args.search_sampler, **kw)
+                           consistent_only=bool(args.search_consistent), sampler=args.search_sampler, belief=belief, **kw)
     print("blueprint: %f +/- %f" % (base.mean, base.sem), "; perfect: ", base.perfect)
     print("blueprint + search (%d worlds): %f +/- %f" % (args.search_worlds, res.mean, res.sem), "; perfect: ", res.perfect,
           "; deviations per game: %f" % float(res.deviations.double().mean()))
@@ -136,6 +165,7 @@ def main(argv=None):
             raise SystemExit("--save_games_where: %s" % e)
     if args.temperature is not None and any(not t >= 0 or t == float("inf") for t in args.temperature):
         raise SystemExit("--temperature must be finite and not negative")
+    load_search_belief(args)      # the usage errors, before anything is loaded
     if args.search_worlds > 0:
         if args.temperature is not None:
             raise SystemExit("--temperature samples tournament seats (no --search_worlds: the search plays the blueprint's greedy moves)")

@@ -45,7 +45,7 @@ def world_key(g, w):
     return (int(g) << 32) | int(w)
 
 
-SAMPLERS = ("rejection", "stratified")
+SAMPLERS = ("rejection", "stratified", "learned")
 
 
 def _check_sampler(sampler):
@@ -54,13 +54,53 @@ def _check_sampler(sampler):
     return sampler
 
 
-def _sample_hands(env, sampler, viewer, key, seed, world, worlds):
+def _check_belief(sampler, belief, agent=None, hand_size=None):
+    """the refusals of sampler="learned", all before anything touches the device.  belief: None, or what carries a head's shape --
+    a belief.BeliefSampler / BeliefHead (hand_size, H), a head's state dict or the path of a saved one.  -> (hand_size, H) | None"""
+    _check_sampler(sampler)
+    if sampler != "learned":
+        if belief is not None:
+            raise ValueError("belief= is what sampler=\"learned\" draws from; sampler=%r takes none" % (sampler,))
+        return None
+    if belief is None:
+        raise ValueError("sampler=\"learned\" needs belief=: a belief.BeliefSampler, a BeliefHead, a head's state dict or its file")
+    if hasattr(belief, "hand_size") and hasattr(belief, "H"):
+        hs, H = int(belief.hand_size), int(belief.H)
+    else:
+        import os
+        from .belief import check_state
+        if isinstance(belief, (str, os.PathLike)):
+            if not os.path.isfile(belief):
+                raise ValueError("belief=%r: no such file" % (belief,))
+            belief = torch.load(belief, map_location="cpu")
+        if not isinstance(belief, dict):
+            raise ValueError("belief= must be a belief.BeliefSampler, a BeliefHead, a head's state dict or its file; got %s" % type(belief).__name__)
+        hs, H = check_state(belief)
+    if hand_size is not None and hs != int(hand_size):
+        raise ValueError("the belief head is for hands of %d, the env deals hands of %d" % (hs, int(hand_size)))
+    if agent is not None:
+        net = getattr(agent, "online", None)
+        if getattr(net, "skip", False):
+            raise ValueError("sampler=\"learned\" reads the top LSTM layer's h as the head's features; a skip_connect agent's trunk output "
+                             "is not that")
+        if getattr(net, "H", None) is not None and int(net.H) != H:
+            raise ValueError("the belief head reads a trunk of width %d, the agent's is %d" % (H, int(net.H)))
+    return hs, H
+
+
+def _sample_hands(env, sampler, viewer, key, seed, world, worlds, belief=None):
     """the hidden hands of the slots' worlds: "rejection" = determinize, independent draws per world; "stratified" =
-    determinize_exact with world w of a game drawing from the w-th of `worlds` equal parts of that game's exact belief"""
+    determinize_exact with world w of a game drawing from the w-th of `worlds` equal parts of that game's exact belief; "learned"
+    = determinize_belief_worlds under belief = (logits float32 [root games, >= 25 H], src int32 [slots]: the root game of each
+    slot), the worlds of a game stratified per slot of the hand -> its (status, logp, logp0), else None"""
     if sampler == "rejection":
         env.determinize(viewer, key, seed)
-    else:
+    elif sampler == "stratified":
         env.determinize_exact(viewer, key, seed, stratum=world, n_strata=worlds)
+    else:
+        logits, src = belief
+        return env.determinize_belief_worlds(viewer, logits, src, key - world.to(key.device, torch.int64), world, worlds, seed)
+    return None
 
 
 def search_jobs(root):
@@ -82,8 +122,11 @@ def mc_action_values(root, worlds, seed, capacity=4096, max_iter=None, sampler="
     hands with determinize_exact instead: never gives up, and the worlds of a game cover its exact belief evenly (world w takes the
     w-th of `worlds` equal parts); keys, seeds and everything after the draw are the same.  playout: None plays the worlds out with
     random legal moves; a rulebot.RuleBot plays them out with that bot on every seat (playout_rule in place of playout_random:
-    jobs, keys, seeds and samplers are unchanged)."""
+    jobs, keys, seeds and samplers are unchanged).  sampler="learned" is refused (ValueError): there is no agent state here."""
     _check_sampler(sampler)
+    if sampler == "learned":
+        raise ValueError("mc_action_values has no learned sampler: random and rule-bot playouts carry no network state for the head to "
+                         "read (policy_action_values / PolicySearch take sampler=\"learned\")")
     if playout is not None:
         from .rulebot import RuleBot
         if not isinstance(playout, RuleBot):
@@ -181,12 +224,17 @@ class SearchValues:
     A search in rounds (search(rounds=...), else all None) adds: paired int64 [G, A, 3] = (sum d, sum d^2, worlds) of d = the action's
     score minus the blueprint action's in the same world, over the worlds both were played in; paired_mean / paired_sem float32
     [G, A] from those integers as values / sem are (NaN where no world is shared); pruned_round int32 [G, A] = the round after which
-    the action was dropped, -1 if never; world_scores uint8 [G, A, worlds] = the score per world, 0xFF where not played."""
+    the action was dropped, -1 if never; world_scores uint8 [G, A, worlds] = the score per world, 0xFF where not played.
+    sampler="learned" (else both None) adds belief_logp / belief_logp0 float32 [G, worlds]: the log-probability of world w's sampled
+    hand under the learned belief and under the exact belief (their difference is the log importance ratio), NaN where no world was
+    sampled."""
 
-    def __init__(self, totals, blueprint_a, mismatch=None, paired=None, pruned_round=None, world_scores=None):
+    def __init__(self, totals, blueprint_a, mismatch=None, paired=None, pruned_round=None, world_scores=None, belief_logp=None,
+                 belief_logp0=None):
         self.totals = totals = torch.as_tensor(totals).to(torch.int64)
         self.blueprint_a = torch.as_tensor(blueprint_a).to(torch.int64)
         self.mismatch = mismatch
+        self.belief_logp, self.belief_logp0 = belief_logp, belief_logp0
         s, sq, n = totals[..., 0], totals[..., 1], totals[..., 2]
         nan = torch.full(s.shape, float("nan"), dtype=torch.float32, device=totals.device)
         counted = n > 0
@@ -265,21 +313,49 @@ class _WorldChunk:
         self.env, self.h, self.c = env, None, None
 
 
+class _Drawn:
+    """sampler="learned", one search call: the root games' logits and where the kernel's log-probabilities are kept per (game,
+    world) -- row G takes the writes of the spare slots"""
+
+    def __init__(self, logits, G, worlds, dev):
+        self.logits, self.G = logits, G
+        self.logp = torch.full((G + 1, worlds), float("nan"), dtype=torch.float32, device=dev)
+        self.logp0 = torch.full((G + 1, worlds), float("nan"), dtype=torch.float32, device=dev)
+
+    def scatter(self, g_c, w_c, valid, got):
+        status, logp, logp0 = got
+        dev = self.logp.device
+        gi = torch.from_numpy(np.where(valid, g_c, self.G).astype(np.int64)).to(dev)
+        wi = torch.from_numpy(np.asarray(w_c, dtype=np.int64)).to(dev)
+        nan = torch.full_like(logp, float("nan"))
+        # every slot of a (game, world) holds the same hand, so the duplicate writes carry the same bits
+        self.logp[gi, wi] = torch.where(status == 1, logp, nan)
+        self.logp0[gi, wi] = torch.where(status == 1, logp0, nan)
+
+
 class PolicySearch:
     """The search env of `capacity` slots, the agent's state buffers for its capacity * P rows and the host loop that plays one
     chunk of jobs; search() may be called move after move (play_with_search does).  `like` is any env with the root's rules.
     replay=True: search() takes the root's GameLog and rebuilds the LSTM states of every sampled world by replay (world envs of
     `capacity` slots each, made when first needed and kept); consistent_only=True then counts only the worlds without a mismatch.
     sampler: "rejection" (determinize) or "stratified" (determinize_exact, world w of a game in stratum w of `worlds`), for the
-    act chunks and the world envs of the replay stage alike."""
+    act chunks and the world envs of the replay stage alike; or "learned" with belief= (a belief.BeliefSampler, or what makes
+    one: a BeliefHead, a head's state dict, its file): determinize_belief_worlds under the head's logits for the root act's state.
+    ValueError -- before any device work -- for "learned" without a belief, a belief with another sampler, a head whose trunk
+    width or hand size is not the agent's / the env's, and a skip_connect agent."""
 
-    def __init__(self, like, agent, capacity=4096, max_steps=200, replay=False, consistent_only=False, sampler="rejection"):
+    def __init__(self, like, agent, capacity=4096, max_steps=200, replay=False, consistent_only=False, sampler="rejection", belief=None):
         self.agent, self.capacity, self.max_steps = agent, int(capacity), int(max_steps)
         self.sampler = _check_sampler(sampler)
+        _check_belief(sampler, belief, agent, like.H)
+        self.belief = belief
         self.replay, self.consistent_only = bool(replay), bool(consistent_only)
         if self.consistent_only and not self.replay:
             raise ValueError("consistent_only needs replay=True: the mismatch count comes from the replay")
         self.device = dev = like.device
+        if belief is not None and not hasattr(belief, "logits"):
+            from .belief import BeliefSampler
+            self.belief = BeliefSampler(belief, str(dev))
         self.bf16 = bool(getattr(agent, "accepts_bf16_obs", False))
         self.env = env = self._make_env(like.config)
         self.config, self.worlds_env = dict(like.config), []
@@ -350,7 +426,7 @@ class PolicySearch:
             raise RuntimeError("%d game(s) of the search env still running after %d steps" % (int(self.unfinished.cpu()[0]), self.max_steps))
         return bp
 
-    def _replay(self, root, log, games, cur, worlds, seed, seed_of):
+    def _replay(self, root, log, games, cur, worlds, seed, seed_of, drawn=None):
         """the replay stage: world slot i * worlds + w = world w of root game games[i], `capacity` slots per world env.  Per env: fork
         the root with the world seeds, determinize, hsad_search_world_script, hsad_env_rewind_scripted, zero agent state, then per
         logged move agent.act -> hsad_search_replay_actions -> step -> (sad = 1) hsad_env_observe_sad with the section the root's
@@ -385,7 +461,10 @@ class PolicySearch:
             viewer = torch.from_numpy(np.where(valid, cur[g_c], -1).astype(np.int32)).to(dev)
             env.reseed(0)       # every slot "not started": the spare ones get the noop and never hold a world of an earlier search
             env.fork_from(root, src, seeds)
-            _sample_hands(env, self.sampler, viewer, key, seed, torch.from_numpy(w_c.astype(np.int32)), worlds)
+            world_d = torch.from_numpy(w_c.astype(np.int32)).to(dev)
+            got = _sample_hands(env, self.sampler, viewer, key, seed, world_d, worlds, (drawn.logits, src) if drawn is not None else None)
+            if drawn is not None:
+                drawn.scatter(g_c, w_c, valid, got)
             _lib.check(lib.hsad_search_world_script(env.h, src.data_ptr(), viewer.data_ptr(), dh.data_ptr(), cnt.data_ptr(), G,
                                                     la.data_ptr() if n_moves else None, n_moves, script.data_ptr(), count.data_ptr(),
                                                     env._stream()))
@@ -462,10 +541,12 @@ class PolicySearch:
             alive = now
         return paired_bp, pruned_round
 
-    def search(self, root, hid, worlds, seed, searcher=None, log=None, rounds=None, prune_z=2.0, min_n=2):
+    def search(self, root, hid, worlds, seed, searcher=None, log=None, rounds=None, prune_z=2.0, min_n=2, hid_next=None):
         """-> SearchValues for the root env's games; root and hid ({"h0", "c0"}: [L, root.G * root.P, H], the agent's state entering
         the root step) are only read.  log: the root's GameLog (replay=True).  rounds: None, or world counts per round (their sum is
-        `worlds`) for the search in rounds with pruning at prune_z paired standard errors.  See policy_action_values."""
+        `worlds`) for the search in rounds with pruning at prune_z paired standard errors.  hid_next (sampler="learned" only): the
+        agent's state AFTER the root act, whose top layer's h is what the belief head reads; None: the search runs that one act on
+        the root's float32 rows itself.  See policy_action_values."""
         from .eval import _drain_errors
         z2 = None
         if rounds is not None:
@@ -492,6 +573,20 @@ class PolicySearch:
                              world_scores=torch.full((G, A, worlds), 0xFF, dtype=torch.uint8, device=dev))
             return SearchValues(totals, blueprint, torch.zeros(G, max(worlds, 0), dtype=torch.int32, device=dev) if self.replay else None,
                                 **extra)
+        drawn = None
+        if self.sampler == "learned":
+            if hid_next is None:
+                N, counter = G * P, getattr(self.agent, "counter", None)
+                obs = {"priv_s": root.priv_s.view(N, root.F), "legal_move": root.legal_move.view(N, A),
+                       "eps": torch.zeros(N, dtype=torch.float32, device=dev)}
+                hid_next = self.agent.act(obs, {"h0": h_src, "c0": c_src})[1]
+                if counter is not None:      # the extra act is no move of the agent's: its exploration counter stays where it was
+                    self.agent.counter = counter
+            h_top = hid_next["h0"]
+            if tuple(h_top.shape) != tuple(h_src.shape):
+                raise ValueError("hid_next must hold h0 of shape %s; got %s" % (tuple(h_src.shape), tuple(h_top.shape)))
+            player = torch.from_numpy(cur.astype(np.int32)).to(dev)
+            drawn = _Drawn(self.belief.logits(h_top[h_top.shape[0] - 1].contiguous(), player), G, worlds, dev)
         n_job = len(pairs)
         n = n_job * worlds                                   # jobs in (game, action, world) order; job k works for pair k // worlds
         games, first_pair = np.unique(pairs[:, 0], return_index=True)
@@ -503,7 +598,7 @@ class PolicySearch:
         L, H = self.h.shape[0], self.h.shape[2]
         keep = mismatch = None
         if self.replay:
-            mism = self._replay(root, log, games, cur, worlds, seed, seed_of).view(len(games), worlds)
+            mism = self._replay(root, log, games, cur, worlds, seed, seed_of, drawn).view(len(games), worlds)
             mismatch = torch.zeros(G, worlds, dtype=torch.int32, device=dev)
             mismatch[torch.from_numpy(games).to(dev)] = mism
             if self.consistent_only:      # a game with no consistent world falls back to all of its worlds
@@ -525,7 +620,10 @@ class PolicySearch:
             job = torch.from_numpy(np.where(valid, pj, -1).astype(np.int32)).to(dev)
             if not self.replay:
                 env.fork_from(root, src, seeds)
-                _sample_hands(env, self.sampler, player, key, seed, torch.from_numpy(w_c.astype(np.int32)), worlds)
+                world_d = torch.from_numpy(w_c.astype(np.int32)).to(dev)
+                got = _sample_hands(env, self.sampler, player, key, seed, world_d, worlds, (drawn.logits, src) if drawn is not None else None)
+                if drawn is not None:
+                    drawn.scatter(g_c, w_c, valid, got)
                 _lib.check(lib.hsad_search_fork_state(src.data_ptr(), cap, G, P, L, H, h_src.data_ptr(), c_src.data_ptr(), self.h.data_ptr(),
                                                       self.c.data_ptr(), self.h16.data_ptr() if self.h16 is not None else None, env._stream()))
             else:
@@ -564,19 +662,20 @@ class PolicySearch:
         _drain_errors(env)        # finished games were handed the noop: the "step on a finished game" notes
         pd = torch.from_numpy(pairs).to(dev)
         totals[pd[:, 0], pd[:, 1]] = stats
+        lp = dict(belief_logp=drawn.logp[:G], belief_logp0=drawn.logp0[:G]) if drawn is not None else {}
         if rounds is None:
-            return SearchValues(totals, blueprint, mismatch)
+            return SearchValues(totals, blueprint, mismatch, **lp)
         paired = torch.zeros(G, A, 3, dtype=torch.int64, device=dev)
         pruned = torch.full((G, A), -1, dtype=torch.int32, device=dev)
         table = torch.full((G, A, worlds), 0xFF, dtype=torch.uint8, device=dev)
         paired[pd[:, 0], pd[:, 1]] = extra[0]
         pruned[pd[:, 0], pd[:, 1]] = torch.from_numpy(extra[1]).to(dev)
         table[pd[:, 0], pd[:, 1]] = scores
-        return SearchValues(totals, blueprint, mismatch, paired=paired, pruned_round=pruned, world_scores=table)
+        return SearchValues(totals, blueprint, mismatch, paired=paired, pruned_round=pruned, world_scores=table, **lp)
 
 
 def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_steps=200, searcher=None, replay=False, log=None,
-                         consistent_only=False, sampler="rejection", rounds=None, prune_z=2.0, min_n=2):
+                         consistent_only=False, sampler="rejection", rounds=None, prune_z=2.0, min_n=2, belief=None, hid_next=None):
     """SearchValues: values[g, a] = mean final score (HSAD_Q_SCORE) over `worlds` sampled worlds when the player on turn of root game
     g plays a and EVERY player, the searcher included, then follows the blueprint `agent` greedily to the end of the game.
 
@@ -613,6 +712,18 @@ def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_step
     sampler="stratified": the hands come from determinize_exact(stratum = world, n_strata = worlds) wherever determinize is named
     above, the world envs of the replay included (see mc_action_values).
 
+    sampler="learned" with belief= (belief.BeliefSampler, or a BeliefHead / state dict / file to make one from): the hands come from
+    the learned belief instead.  Once per call the head's logits are computed for the player on turn of every root game from
+    hid_next["h0"][L - 1] -- the agent's state AFTER the root act (play_with_search has it; None: one agent.act on the root's
+    rows here) -- by hsad_search_belief_rows and the head's GEMM; every sampler call is then determinize_belief_worlds with row =
+    the slot's root game, group = world_key(g, 0), world = w, n_worlds = worlds and the search seed.  A (game, world) hand depends
+    on (seed, game, world) and the root's logits only -- not on the action, chunk, slot or capacity -- and is the same in the
+    replay stage's world envs; the worlds of a game are stratified per slot of the hand (include/hsad.h,
+    hsad_env_determinize_belief_worlds).  SearchValues.belief_logp / belief_logp0 carry each world's log-probability under the
+    learned and the exact belief.  A game whose logits row is not finite keeps its true hand in every world.  ValueError for
+    "learned" without belief, belief with another sampler, a head not matching the agent's width or the env's hand size, a
+    skip_connect agent.
+
     rounds=(n0, n1, ...) (positive, summing to `worlds` <= 4,096; None = the flat search above, untouched): the worlds are played in
     rounds and actions that are already hopeless are dropped in between.  A game's worlds are taken in round_world_order; round r
     plays its next rounds[r] worlds for every action still alive (jobs in (action, world-order) order, chunked as above -- a (game,
@@ -624,9 +735,9 @@ def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_step
     action are never dropped; a game down to one action plays no more.  The host reads `alive` once per round.  The replay stage is
     not split: it replays all worlds up front.  SearchValues then carries paired / paired_mean / paired_sem (against the blueprint's
     action), pruned_round and world_scores; totals / values count the worlds each action was played in."""
-    ps = PolicySearch(root, agent, capacity, max_steps, replay=replay, consistent_only=consistent_only, sampler=sampler)
+    ps = PolicySearch(root, agent, capacity, max_steps, replay=replay, consistent_only=consistent_only, sampler=sampler, belief=belief)
     try:
-        return ps.search(root, hid, worlds, seed, searcher, log=log, rounds=rounds, prune_z=prune_z, min_n=min_n)
+        return ps.search(root, hid, worlds, seed, searcher, log=log, rounds=rounds, prune_z=prune_z, min_n=min_n, hid_next=hid_next)
     finally:
         ps.close()
 
@@ -687,7 +798,7 @@ class SearchPlay:
 def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05, search_seed=0, searcher="all", capacity=4096,
                      num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16", shuffle_color=False, colors=5, ranks=5,
                      max_information_tokens=8, max_life_tokens=3, replay_history=False, consistent_only=False, sampler="rejection",
-                     rounds=None, prune_z=2.0, deviate_z=0.0, records=False):
+                     rounds=None, prune_z=2.0, deviate_z=0.0, records=False, belief=None):
     """eval.evaluate's lock-step loop over the deals seed .. seed + num_game - 1 with search on top of the blueprint -> SearchPlay.
     Before each step: PolicySearch values for the games whose player on turn searches (searcher: "all" or a seat number),
     choose_action, then the root steps with a = the chosen action and greedy_a = the blueprint's greedy action; the carried state
@@ -703,10 +814,13 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
     included, greedy_a the blueprint's move -- and every move's SearchValues.values is kept on the device ([max_steps, G, A] float32,
     NaN where no search ran).  SearchPlay.records / .search_values hold the kept games; only those cross to the host.  What search
     found can then be cloned back into the net: clone.search_targets, clone.sequences_from_records(targets=...).  records=False
-    changes nothing: no call more per move, the same scores, deviations and trace."""
+    changes nothing: no call more per move, the same scores, deviations and trace.
+    sampler="learned", belief=...: every search draws its worlds from the learned belief (policy_action_values), with the root act's
+    new state -- which this loop has anyway -- as the head's features.  worlds = 0 never looks at the belief beyond the argument
+    checks."""
     if records is False:
         records = None
-    _check_sampler(sampler)
+    _check_belief(sampler, belief, None, hand_size)
     if rounds is not None and worlds > 0:
         _check_rounds(rounds, worlds, prune_z, 2)
     from .eval import _acting_agent, _drain_errors
@@ -719,7 +833,7 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
         raise ValueError("searcher must be \"all\" or a seat in 0..%d" % (num_player - 1))
     # no move has more jobs than games x playable actions x worlds: a smaller batch needs no more slots than that
     ps = PolicySearch(env, agent, min(int(capacity), num_game * (env.A - 1) * worlds), max_steps, replay=bool(replay_history),
-                      consistent_only=bool(consistent_only), sampler=sampler) if worlds > 0 else None
+                      consistent_only=bool(consistent_only), sampler=sampler, belief=belief) if worlds > 0 else None
     log = GameLog(num_game, num_player, env.device) if ps is not None and replay_history else None
     N = num_game * num_player
     deviations = torch.zeros(num_game, dtype=torch.int64, device=env.device)
@@ -750,7 +864,8 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
                     recorder.append(a, a)
                 env.step(a, a)
             else:
-                sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat, log=log, rounds=rounds, prune_z=prune_z)
+                sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat, log=log, rounds=rounds, prune_z=prune_z,
+                               hid_next=new_hid if belief is not None else None)
                 player = q[:, Q_CUR_PLAYER].contiguous()
                 # the blueprint's move is the root act's own greedy action (the search's first act gives the same one while both
                 # run in one acting regime; this one holds in any)

@@ -353,6 +353,29 @@ int hsad_env_hand_knowledge(hsad_env* env, int64_t* pool_out, int32_t* compat_ou
 int hsad_env_determinize_belief(hsad_env* env, const int32_t* viewer, const float* logits, int ldz, const int64_t* key, uint64_t seed,
                                 float* logp_out, int32_t* status_out, void* stream);
 
+/* hsad_env_determinize_belief_worlds: hsad_env_determinize_belief for a search env, whose slots are forks of a few root games.  Env
+ * game g reads logits row row[g] of fp32 [n_rows, ldz] (row device int32 [G]; NULL = row g, which needs n_rows >= G), and its slot
+ * uniforms are stratified over the worlds of its root game (csrc/hsad_belief_world.h): W = n_worlds, w = world[g] (device int32
+ * [G]), h(c) = hash(seed, group[g], c, 67), the policy's hash on stream 67 (group device int64 [G]: the root game's key).  Slot i:
+ *   a_i = the first cand_k = 1 + ((h(16 + 8 i + k) (W - 1)) >> 32), k = 0 .. 7, with gcd(cand_k, W) == 1; 1 if there is none
+ *   o_i = (h(2 i) W) >> 32;   s_i = (a_i w + o_i) mod W;   j_i = h((1 << 8) | i) >> 8  (the same in every world)
+ *   k_i = ((s_i << 24) + j_i) / W  (uint64);   u_i = k_i << 8
+ * and the hand is hsad_belief_tail's sample mode under u_0 .. u_4.  w -> s_i is a bijection of [0, W) for every slot: the W worlds
+ * of a group fall into each of the W equal parts of every slot's conditional distribution exactly once, and -- the jitter j_i being
+ * one per group and slot -- a slot's W points are a lattice of spacing 1 / W: any interval of length p holds floor(W p) or
+ * ceil(W p) of them (slot 0's conditional is the same in all worlds of a group, so the number of them that hold type t there is
+ * within 1 of W p_0[t]); one world alone is a plain draw from the belief (its stratum and the jitter are uniform), and W = 1 is
+ * one.  The result depends on (seed, group[g], world[g]), the logits row and the game's state only: not on the slot g.  Skip rules, observe pass and the sad = 1 precondition are hsad_env_determinize_belief's.  A game is LEFT ALONE
+ * -- state and rows, status 0, logp = logp0 = 0 -- when it is skipped, when row[g] is outside [0, n_rows), when world[g] is outside
+ * [0, W), or when its row has a non-finite logit on an occupied slot.  logp_out / logp0_out device float [G] or NULL: the sampled
+ * hand's log-probability under the belief, and under the exact belief (all-zero logits); their difference is the log importance
+ * ratio.  status_out device int32 [G] or NULL.  HSAD_ERR_INVALID: a null viewer / logits / group / world, ldz < 25 H, n_rows < 1,
+ * n_worlds outside [1, 2^20], hands of more than 5 slots; HSAD_ERR_STATE: the env's outputs are not bound.  No float atomics.
+ * Launch-only. */
+int hsad_env_determinize_belief_worlds(hsad_env* env, const int32_t* viewer, const float* logits, int ldz, int n_rows, const int32_t* row,
+                                       const int64_t* group, const int32_t* world, int n_worlds, uint64_t seed, float* logp_out,
+                                       float* logp0_out, int32_t* status_out, void* stream);
+
 /* hsad_env_playout_random: up to max_iter iterations of random-legal policy -> step for every game that is started and not
  * finished, in one launch.  A finished game is left alone (no restart, no error, no counter advance); a live game's trajectory --
  * actions in a / greedy_a, state, draws -- is that of hsad_env_policy_random + hsad_env_step.  NO observation rows are written
@@ -1633,6 +1656,13 @@ int hsad_seating_behaviour(const hsad_env* env, int games_per_seating, const int
  * HSAD_ERR_INVALID: H % 4 != 0, a size < 1, a null or not 16-byte aligned tensor. */
 int hsad_search_fork_state(const int32_t* src_index, int G_dst, int G_src, int P, int L, int H, const float* h_src, const float* c_src,
                            float* h_dst, float* c_dst, void* h16_dst, void* stream);
+/* The learned belief's features at search time (belief.BeliefSampler): the searcher's rows of the top LSTM layer's new h after the
+ * root act, as the bf16 operand of the head's GEMM.  h_top fp32 [G * P, H] (row g * P + p), player device int32 [G], out_bf16 bf16
+ * [G, ldo]: out[g, 0 .. H - 1] = bf16(h_top[g * P + player[g], :]), rounded to nearest even as hsad_cast_pad_bf16 does; an all-zero
+ * row where player[g] is outside [0, P).  Columns H .. ldo - 1 are not written.  h_top is only read.  Rows move as 16-byte vectors:
+ * HSAD_ERR_INVALID when H is no positive multiple of 8, ldo < H or ldo % 8 != 0, G or P < 1, a null or not 16-byte aligned tensor.
+ * One pass, launch-only. */
+int hsad_search_belief_rows(const float* h_top, const int32_t* player, int G, int P, int H, void* out_bf16, int ldo, void* stream);
 /* What act returned for all G * P rows of `env` (a_src / greedy_src int64 [G * P]) -> what hsad_env_step takes (a / greedy_a int64
  * [G, P]; may be the same memory as the sources).  Every seat of a game that is finished or not started receives the noop uid A - 1
  * in both outputs.  In a live game g with override[g] >= 0 (device int64 [G]) and player[g] (device int32 [G]) in [0, P):

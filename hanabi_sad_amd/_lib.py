@@ -137,6 +137,8 @@ SIGNATURES = {
     "hsad_env_rollout_compact_active": (C.c_int, [_P]),
     "hsad_env_set_rollout_unit": (C.c_int, [_P, C.c_int]),
     "hsad_env_rollout_unit": (C.c_int, [_P]),
+    "hsad_env_set_rollout_prio": (C.c_int, [_P, C.c_int]),
+    "hsad_env_rollout_prio": (C.c_int, [_P]),
     "hsad_env_debug_units": (C.c_int, [_P, _P]),
     "hsad_env_debug_pace_bias": (C.c_int, [_P, C.c_int64]),
     "hsad_env_debug_pace_word": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

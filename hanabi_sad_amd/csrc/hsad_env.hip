@@ -454,7 +454,8 @@ __device__ __forceinline__ uint32_t hand_match_mask(uint32_t hw, bool by_color, 
 //                              13 delta stream (EnvParams::delta): 128-byte lines of priv_s the stream wave stored for the rows of `it - 1`
 //                                 (with half-line units: lines with any change); the units themselves go to EnvParams::dbg_units_lo / _hi
 //                              14 / 15 last record only: lines wave 0 / wave 1 stored in the epilogue stream
-//   both, trace layout:        9 HW_REG_HW_ID, 10 HW_REG_XCC_ID of the workgroup (written with slot 0)
+//   both, trace layout:        9 HW_REG_HW_ID, 10 HW_REG_XCC_ID of the workgroup (written with slot 0); env_rollout_pipe_kernel: 9 is
+//                              the logic wave's, and the upper 32 bits of 10 hold the stream wave's HW_REG_HW_ID
 __device__ __forceinline__ void env_stamp(const EnvParams& ep, int it, int k, unsigned long long v) {
   const size_t blk = (size_t)(ep.g_begin / ep.gpw) + blockIdx.x;
   if (ep.dbg_iters > 0)
@@ -478,6 +479,21 @@ __device__ __forceinline__ void env_stamp(const EnvParams& ep, int it, int k, un
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));                          \
         env_stamp(ep, dbg_it, 9, hw_id);                                                                \
         env_stamp(ep, dbg_it, 10, xcc_id);                                                              \
+      }                                                                                                 \
+    }                                                                                                   \
+  } while (0)
+// env_rollout_pipe_kernel's form: slot 10 also carries the stream wave's HW_REG_HW_ID (`stream_hw`, an LDS word that wave wrote
+// in the prologue) in its upper 32 bits; the XCC id stays in bits 0-3
+#define STAMP_START_PIPE(stream_hw)                                                                     \
+  do {                                                                                                  \
+    if (ep.dbg && threadIdx.x == 0) {                                                                   \
+      env_stamp(ep, dbg_it, 0, wall_clock64());                                                         \
+      if (ep.dbg_iters > 0) {                                                                           \
+        unsigned hw_id, xcc_id;                                                                         \
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));                            \
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));                          \
+        env_stamp(ep, dbg_it, 9, hw_id);                                                                \
+        env_stamp(ep, dbg_it, 10, ((unsigned long long)(stream_hw) << 32) | xcc_id);                    \
       }                                                                                                 \
     }                                                                                                   \
   } while (0)
@@ -1984,6 +2000,7 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v) {
 // `prev` of its first stream, which then is a delta stream like every later one instead of 448 MB of lines HBM already holds.
 // Blocks, g_begin and gpw are the same in every launch of a call: the slice index is the block index.
 constexpr int kChainIn = 2, kChainOut = 4;   // in EnvParams::delta, next to bit 0 = the delta stream is on
+constexpr int kPrioShift = 3;                // bits 3-4 of EnvParams::delta: the wave-priority mode (hsad_env_set_rollout_prio)
 __device__ __forceinline__ uint4* chain_slice(const EnvParams& ep) {
   return reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(ep.phase) + (size_t)blockIdx.x * ep.obs_words);
 }
@@ -2012,7 +2029,10 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
   // unless it is chained in (chain_slice above).
   // (the copy's address is worked out where it is used: as one more launch-long value it costs the generic instance a register it
   // does not have)
-#define S_OBS1(z) (ep.delta ? s_pace + 4 + (z) : s_obs)
+#define S_OBS1(z) (delta ? s_pace + 4 + (z) : s_obs)
+  // bits 0-2 of ep.delta are the delta stream and its chain (kChainIn, kChainOut); bits 3-4 carry the wave-priority mode
+  // (kPrioShift, hsad_env_set_rollout_prio), which is no business of the stream
+  const int delta = ep.delta & 7;
 
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
@@ -2021,6 +2041,17 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
   const int ng = min(ep.gpw, ep.G - g0);
   if (ng <= 0) return;
   const int P = TP ? TP : ep.P, H = TH ? TH : ep.H;
+
+  // Wave priority (EnvParams::delta bits 3-4; hsad_env_set_rollout_prio).  Two waves share every SIMD for the whole launch, and
+  // between equal priorities the older one wins the VALU arbitration every time.  Bit 0 (alternation): each wave takes priority
+  // (iter ^ its hardware wave slot) & 1, so two co-tenants whose slots differ in bit 0 win in alternate iterations.  Bit 1 (role):
+  // the stream wave, the iteration's critical chain, runs 2 above the logic wave.  Priority decides which wave issues first and
+  // nothing else: no wave waits for another, and the results are the same in every mode.
+  unsigned hw_self;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_self));
+  const int prio_mode = (ep.delta >> kPrioShift) & 3;
+  const int prio_role = (prio_mode & 2) ? 2 * __builtin_amdgcn_readfirstlane(wave) : 0;
+  const int prio_alt = prio_mode & 1, prio_slot = (int)(hw_self & 15u);   // HW_ID [3:0]: the wave's slot on its SIMD
 
   // prologue: the logic wave stages the state planes and its act counters, the stream wave clears the rows and copies the eps list
   uint32_t act_counter = 0u;   // this lane's EnvParams::act_count, carried in a register for the launch (LogicCarry)
@@ -2049,13 +2080,14 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     }
   } else {
     clear_rows(ep, s_obs, lane, kWave);
-    if (ep.delta & kChainIn) {   // the rows priv_s holds, into the copy the stream of iteration 1 compares against
+    if (delta & kChainIn) {   // the rows priv_s holds, into the copy the stream of iteration 1 compares against
       const uint4* src = chain_slice(ep);
       uint4* dst = reinterpret_cast<uint4*>(S_OBS1(0));
       for (int k = lane; k < (ep.obs_words >> 2); k += kWave) dst[k] = src[k];
     }
     for (int k = lane; k < min(ep.n_eps, 128); k += kWave) s_eps[k] = ep.eps_list[k];
     if (lane == 0) s_pace[0] = 0u;
+    if (ep.dbg && ep.dbg_iters > 0 && lane == 0) s_pace[1] = hw_self;   // trace only: where the stream wave runs (STAMP_START_PIPE)
   }
   __syncthreads();
 
@@ -2067,7 +2099,15 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     const int g = g0 + zero + lane;
     const bool valid = lane < ep.gpw && g < ep.G;
     const int dbg_it = iter;
-    STAMP_START();
+    // one s_setprio per wave and iteration.  The instruction takes an immediate and ignores EXEC, so each form stands alone under
+    // a condition formed through readfirstlane (scalar compare and branch, not an exec mask around an unconditional s_setprio).
+    switch (__builtin_amdgcn_readfirstlane(prio_role + ((iter ^ prio_slot) & prio_alt))) {
+      case 0: __builtin_amdgcn_s_setprio(0); break;
+      case 1: __builtin_amdgcn_s_setprio(1); break;
+      case 2: __builtin_amdgcn_s_setprio(2); break;
+      default: __builtin_amdgcn_s_setprio(3); break;
+    }
+    STAMP_START_PIPE(s_pace[1]);
     // pacing: count this iteration start; the returned value is consumed in phase B, behind the logic's own waited loads
     unsigned long long pace_s = 0ull;
     if (ep.pace && tid == 0) pace_s = pace_count(ep);
@@ -2111,7 +2151,7 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
       int sl = lane;
       asm volatile("" : "+v"(sl));   // opaque: the stream's per-lane addresses are worked out here, not kept in registers for the launch
       unsigned units = 0;
-      const bool all = !ep.delta || (iter == 1 && !(ep.delta & kChainIn));
+      const bool all = !delta || (iter == 1 && !(delta & kChainIn));
       unsigned stored = stream_rows_delta(ep, rows, prev, all, s_legal, s_own, g0, ng, P, H, sl, kWave, dbg_lines, ep.compact, units);
       clear_words(prev, ep.obs_words, sl, kWave);
       clear_words(s_legal, ep.legal_words + ep.own_words, sl, kWave);
@@ -2170,13 +2210,13 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(2, 
     uint32_t* prev = (ep.n_iter & 1) ? s_obs1 : s_obs;
     const bool dbg_lines = ep.dbg && ep.dbg_iters > 0;
     unsigned units = 0;
-    unsigned stored = stream_rows_delta(ep, rows, prev, !ep.delta || ep.n_iter == 1, s_legal, s_own, g0, ng, P, H, tid, ep.nthreads, dbg_lines,
+    unsigned stored = stream_rows_delta(ep, rows, prev, !delta || ep.n_iter == 1, s_legal, s_own, g0, ng, P, H, tid, ep.nthreads, dbg_lines,
                                         0, units);
     if (dbg_lines) {
       stored = wave_sum(stored);
       if (lane == 0) env_stamp(ep, dbg_it, 14 + wave, stored);
     }
-    if (ep.delta & kChainOut) {   // the rows just streamed, for the next launch of the call (the stream left them as they were)
+    if (delta & kChainOut) {   // the rows just streamed, for the next launch of the call (the stream left them as they were)
       const uint4* src = reinterpret_cast<const uint4*>(rows);
       uint4* dst = chain_slice(ep);
       for (int k = tid; k < (ep.obs_words >> 2); k += ep.nthreads) dst[k] = src[k];
@@ -2399,6 +2439,8 @@ struct hsad_env {
   // launch of every call streams in full and never reads the buffer, so the rule above holds between calls as it did between
   // launches.
   int rollout_chain;              // hsad_env_set_rollout_chain; HSAD_ENV_CHAIN=0 at creation: every launch on its own, for A/B
+  int rollout_prio;               // hsad_env_set_rollout_prio; HSAD_ENV_PRIO=0..3 at creation: wave priority in the pipelined kernel
+                                  // (bit 0 alternation, bit 1 role; EnvParams::delta bits 3-4)
   uint32_t* d_chain;              // [workgroups][obs_words], allocated on first use
   bool chain_unavailable;         // that allocation failed: the env runs unchained
   unsigned long long* d_pace;     // the progress word (allocated with the env, zero)
@@ -2474,6 +2516,10 @@ EnvScriptedStepFn pick_scripted_step_kernel(int P, int H, bool variant) {
 }
 
 typedef void (*EnvRolloutFn)(EnvParams);
+// wave priority of the pipelined kernel (env_rollout_pipe_kernel, kPrioShift): the mode an env starts with.  2 = role: every SIMD
+// holds the logic wave of one workgroup and the stream wave of another, and with the stream wave on top no workgroup's rate
+// depends on which of the two arrived first (profiles/r18_env_prio_trace.json; headline profiles/r18_env_prio_ab.json)
+constexpr int kRolloutPrioDefault = 2;
 // pacing defaults (pace_delay): no dead band beyond the one the lead's definition brings (a workgroup in step with the others reads
 // a lead of (-1, 0], so 0 already is half an iteration), one delay at most 35 us and never more than half the workgroup's own last
 // iteration.  Measured against dead bands of 0.25 / 0.5 and caps of 20 / 60 us: profiles/r08_env_pace_ab.json
@@ -2560,6 +2606,8 @@ void launch_env(hsad_env* e, int mode, const int64_t* a, const int64_t* g, hipSt
     ep.phase = reinterpret_cast<unsigned long long*>(e->d_chain);
     ep.delta |= chain;
   }
+  // the wave-priority mode rides above the chain bits; only env_rollout_pipe_kernel looks at EnvParams::delta
+  if (mode == 3 && n_iter > 1 && rollout_pipelined(e)) ep.delta |= e->rollout_prio << kPrioShift;
   ep.n_part = n_part;
   ep.g_begin = g_begin;
   ep.g_count = g_count;
@@ -2724,6 +2772,7 @@ int hsad_env_create_rules(const hsad_env_config* cfg, const hsad_env_rules* rule
   e->rollout_unit = getenv("HSAD_ENV_UNIT") && atoi(getenv("HSAD_ENV_UNIT")) == 128 ? 128 : 64;
   e->delta_fits = false;
   e->rollout_chain = getenv("HSAD_ENV_CHAIN") ? (atoi(getenv("HSAD_ENV_CHAIN")) != 0 ? 1 : 0) : 1;
+  e->rollout_prio = getenv("HSAD_ENV_PRIO") ? atoi(getenv("HSAD_ENV_PRIO")) & 3 : kRolloutPrioDefault;
   e->d_chain = nullptr;
   e->chain_unavailable = false;
   e->d_pace = nullptr;
@@ -3059,6 +3108,14 @@ int hsad_env_set_rollout_chain(hsad_env* e, int mode) {
 }
 
 int hsad_env_rollout_chain_active(const hsad_env* e) { return e ? rollout_chain_mode(e) : 0; }
+
+int hsad_env_set_rollout_prio(hsad_env* e, int mode) {
+  if (!e || mode < 0 || mode > 3) return set_error(HSAD_ERR_INVALID, "the rollout priority mode is 0..3");
+  e->rollout_prio = mode;
+  return HSAD_OK;
+}
+
+int hsad_env_rollout_prio(const hsad_env* e) { return e && rollout_pipelined(e) ? e->rollout_prio : 0; }
 
 int hsad_env_set_rollout_compact(hsad_env* e, int on) {
   if (!e) return set_error(HSAD_ERR_INVALID, "null env");

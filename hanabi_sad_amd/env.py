@@ -224,6 +224,15 @@ class BatchedHanabiEnv:
         active"""
         return int(self.lib.hsad_env_rollout_unit(self.h))
 
+    def set_rollout_prio(self, mode):
+        """pipelined persistent rollout: wave priority per iteration (bit 0: co-tenants of a SIMD alternate, bit 1: the stream
+        wave above the logic wave; timing only, results are identical, see include/hsad.h)"""
+        _lib.check(self.lib.hsad_env_set_rollout_prio(self.h, int(mode)))
+
+    def rollout_prio(self):
+        """the priority mode persistent launches use as the env stands: 0 wherever the pipelined kernel does not run"""
+        return int(self.lib.hsad_env_rollout_prio(self.h))
+
     def debug_pace_bias(self, bias):
         """test seam: offset of the counter base the paced kernels are told"""
         _lib.check(self.lib.hsad_env_debug_pace_bias(self.h, int(bias)))

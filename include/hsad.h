@@ -204,6 +204,15 @@ int hsad_env_rollout_compact_active(const hsad_env* env);
  * wherever hsad_env_rollout_compact_active is false (the direct form and the epilogue stream always go by lines). */
 int hsad_env_set_rollout_unit(hsad_env* env, int bytes);
 int hsad_env_rollout_unit(const hsad_env* env);
+/* Wave priority in the pipelined persistent kernel (HSAD_ENV_PRIO=0..3 when the env is created, or mode here; default 2).  Four workgroups
+ * of two waves share a CU for the whole launch, two waves per SIMD, and between equal priorities the older wave wins the issue
+ * arbitration every time.  Bit 0, alternation: at the top of every iteration a wave takes priority (iteration ^ its hardware
+ * wave slot) & 1, so co-tenants whose slots differ in bit 0 win in turn.  Bit 1, role: the stream wave runs 2 above the logic
+ * wave.  Priority only decides which wave issues first: no workgroup waits for another and results are bit-identical in every
+ * mode.  hsad_env_rollout_prio: the mode persistent launches use as the env stands, 0 wherever the pipelined kernel does not
+ * run (256-thread workgroups, knowledge_mode 1, variants).  DESIGN.md 3a has the measurements behind the default. */
+int hsad_env_set_rollout_prio(hsad_env* env, int mode);
+int hsad_env_rollout_prio(const hsad_env* env);
 /* Test seams of the pacing.  bias is added to the counter base every later persistent launch is told (not to the host's own
  * record), so that every workgroup's lead reads bias / workgroups iterations too high: all far ahead (bias > 0) or far behind (bias < 0); 0
  * restores the truth.  A lead no launch could produce (beyond its iteration count) switches the delay off.

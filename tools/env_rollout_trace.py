@@ -1,7 +1,7 @@
 """Per-iteration trace of one persistent rollout launch at configs[1] (65,536 two-player games): where each workgroup's time goes,
 and how many workgroups stream observations on each CU and on the chip over time.
 
-  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--delta on|off] [--compact on|off] [--unit 128|64] [--chain 0|1] [--launches N] [--json OUT]
+  python tools/env_rollout_trace.py [--iters 20] [--warmup 5] [--schedule pipe|single] [--pace on|off] [--delta on|off] [--compact on|off] [--unit 128|64] [--chain 0|1] [--launches N] [--prio 0..3] [--json OUT]
 
 The driver's shape is --warmup 5 --iters 20 (one 5-iteration launch, then the traced 20-iteration launch).  --schedule single runs
 env_rollout_kernel (HSAD_ENV_PIPE=0), pipe the default env_rollout_pipe_kernel.  Stamps are wall_clock64 (100 MHz, 10 ns) of
@@ -13,7 +13,10 @@ where the workgroup runs (XCC; SE; SH; CU = the four co-resident workgroups) and
 position of its rows in the output buffers); per grouping the spread between the group means is set against the spread inside the
 groups (`share_of_variance_between_groups` is the usual eta squared).  --pace off traces the unpaced launch (HSAD_ENV_PACE=0); with
 pacing on, `pace` says how many iterations delayed their stream and by how much (--l0-q8 / --cap-us: the developer switches
-HSAD_ENV_PACE_L0_Q8 / HSAD_ENV_PACE_CAP_US).  --delta off traces the full observation stream (HSAD_ENV_DELTA=0),
+HSAD_ENV_PACE_L0_Q8 / HSAD_ENV_PACE_CAP_US).  The pipelined kernel's trace also carries the stream wave's HW_ID: the groupings then
+include the workgroup's start rank among the workgroups of its CU, the SIMD and wave slot of either wave, and the co-tenant class
+of either wave (who shares its SIMD, and which of the two workgroups started first); every grouping also splits the variance of
+the workgroups' end times.  --prio sets the wave-priority mode (HSAD_ENV_PRIO).  --delta off traces the full observation stream (HSAD_ENV_DELTA=0),
 --compact off the direct form of the delta stream (HSAD_ENV_COMPACT=0), --unit the bytes the compacted form decides "changed" by
 (HSAD_ENV_UNIT; default: the library's).  `stored` gives what the stream wave stored per workgroup-iteration: 128-byte lines with any
 change (slot 13) and, where the library has hsad_env_debug_units, the units themselves and their bytes.
@@ -52,6 +55,7 @@ def main():
     ap.add_argument("--cap-us", type=int, default=None)
     ap.add_argument("--chain", type=int, choices=(0, 1), default=None)
     ap.add_argument("--launches", type=int, default=1)
+    ap.add_argument("--prio", type=int, choices=(0, 1, 2, 3), default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     if args.chain is not None:
@@ -62,6 +66,8 @@ def main():
     os.environ["HSAD_ENV_COMPACT"] = "1" if args.compact == "on" else "0"
     if args.unit is not None:
         os.environ["HSAD_ENV_UNIT"] = str(args.unit)
+    if args.prio is not None:
+        os.environ["HSAD_ENV_PRIO"] = str(args.prio)
     if args.l0_q8 is not None:
         os.environ["HSAD_ENV_PACE_L0_Q8"] = str(args.l0_q8)
     if args.cap_us is not None:
@@ -104,6 +110,8 @@ def main():
     rec["launches_in_the_traced_call"] = args.launches
     if hasattr(env.lib, "hsad_env_rollout_chain_active"):
         rec["chain_mode_active"] = env.rollout_chain_active()
+    if hasattr(env.lib, "hsad_env_rollout_prio"):
+        rec["prio_mode"] = env.rollout_prio()
     rec["delta_stream_active"] = bool(env.rollout_delta_active())
     rec["compact_stream_active"] = bool(env.rollout_compact_active())
     rec["pace"] = dict(rec.get("pace", {}), on=args.pace == "on", cap_us=env.rollout_pace_cap_us(),
@@ -153,7 +161,9 @@ def analyse(s, pipe, args):
     rec["start_spread_us"] = round(float(t[:, 0, 0].max() - t[:, 0, 0].min()), 2)
     rec["end_spread_us"] = round(float(end.max() - end.min()), 2)
     if n > 2:
-        rec["who_lags"] = who_lags(t, hw, xcc, cu)
+        # the pipelined kernel packs the stream wave's HW_ID into the upper half of slot 10 (0 from a library that does not)
+        hw_stream = (xcc >> 32) & 0xFFFFFFFF
+        rec["who_lags"] = who_lags(t, hw, xcc, cu, hw_stream if pipe and hw_stream.any() else None, end)
     if pipe and n > 3:
         rec["edges"] = edges(t, xcc)
     if pipe:
@@ -219,18 +229,72 @@ def edges(t, xcc):
     return out
 
 
-def who_lags(t, hw, xcc, cu):
-    """per-workgroup rate, grouped by place of execution and by place in the output buffers"""
+def co_tenants(cu, start, simd_logic, simd_stream):
+    """Per workgroup, for its logic wave and for its stream wave: who shares the wave's SIMD among the waves of the workgroups on the
+    same CU, and whether this wave's workgroup started before or after the other's.  Returns two integer arrays and the class
+    names they index.  `own_...`: the other wave of the same workgroup; `several`: more than one co-tenant (more than two waves on
+    the SIMD: not the placement the kernel is scheduled for)."""
+    names = ["alone", "several", "own_logic", "own_stream", "logic_of_a_workgroup_started_before", "logic_of_a_workgroup_started_after",
+             "stream_of_a_workgroup_started_before", "stream_of_a_workgroup_started_after"]
+    nwg = len(cu)
+    out = np.zeros((2, nwg), dtype=np.int64)
+    for c in np.unique(cu):
+        idx = np.nonzero(cu == c)[0]
+        waves = [(w, role, int((simd_logic, simd_stream)[role][w])) for w in idx for role in (0, 1)]   # role 0 logic, 1 stream
+        for w, role, simd in waves:
+            others = [(v, r) for v, r, s in waves if s == simd and (v, r) != (w, role)]
+            if not others:
+                k = "alone"
+            elif len(others) > 1:
+                k = "several"
+            else:
+                v, r = others[0]
+                what = ("logic", "stream")[r]
+                k = "own_" + what if v == w else "%s_of_a_workgroup_started_%s" % (what, "before" if (start[v], v) < (start[w], w) else "after")
+            out[role, w] = names.index(k)
+    return out[0], out[1], names
+
+
+def who_lags(t, hw, xcc, cu, hw_stream=None, end=None):
+    """per-workgroup rate, grouped by place of execution and by place in the output buffers; with the stream wave's HW_ID (the
+    pipelined kernel's trace) also by dispatch order inside the CU, by the SIMDs the two waves took and by who shares them.  `end`:
+    the workgroups' end times, whose variance is split by the same groupings."""
     nwg, n = t.shape[0], t.shape[1]
     rate = (t[:, n - 1, 0] - t[:, 1, 0]) / (n - 2)                    # us per iteration, iteration 1 .. start of the last
     se, sh = (hw >> 13) & 7, (hw >> 12) & 1
     keys = {"xcc": xcc & 0xF, "se": se, "xcc_se": ((xcc & 0xF) << 3) | se, "xcc_se_sh": ((xcc & 0xF) << 4) | (se << 1) | sh,
             "cu_co_resident_workgroups": cu, "block_index_octile": np.arange(nwg) * 8 // nwg}
+    labels = {}
+    placement = None
+    if hw_stream is not None:
+        start = t[:, 0, 0]
+        rank = np.zeros(nwg, dtype=np.int64)                         # 0 = the first workgroup of its CU to start
+        for c in np.unique(cu):
+            idx = np.nonzero(cu == c)[0]
+            rank[idx[np.lexsort((idx, start[idx]))]] = np.arange(len(idx))
+        simd_l, simd_s = (hw >> 4) & 3, (hw_stream >> 4) & 3
+        slot_l, slot_s = hw & 0xF, hw_stream & 0xF
+        co_l, co_s, names = co_tenants(cu, start, simd_l, simd_s)
+        keys.update({"start_rank_in_cu": rank, "logic_wave_simd": simd_l, "stream_wave_simd": simd_s,
+                     "simd_pair_logic_stream": simd_l * 4 + simd_s, "logic_wave_slot": slot_l, "stream_wave_slot": slot_s,
+                     "logic_wave_co_tenant": co_l, "stream_wave_co_tenant": co_s})
+        labels = {"logic_wave_co_tenant": names, "stream_wave_co_tenant": names,
+                  "simd_pair_logic_stream": ["%d_%d" % (a, b) for a in range(4) for b in range(4)]}
+        per_cu = np.array([(cu == c).sum() for c in np.unique(cu)])
+        # does alternation have something to work with: co-tenant pairs (a stream wave and its one co-tenant) whose slots differ in bit 0
+        placement = {"workgroups_per_cu_min_max": [int(per_cu.min()), int(per_cu.max())],
+                     "share_of_workgroups_with_both_waves_on_one_simd": round(float((simd_l == simd_s).mean()), 4),
+                     "share_of_workgroups_on_simds_0_1_or_2_3": round(float(((simd_l ^ simd_s) == 1).mean()), 4),
+                     "share_of_workgroups_whose_waves_have_the_same_slot": round(float((slot_l == slot_s).mean()), 4),
+                     "wave_slots_seen": sorted(int(x) for x in np.unique(np.concatenate([slot_l, slot_s])))}
     out = {"rate_us_per_iteration": {"mean": round(float(rate.mean()), 2), "std": round(float(rate.std()), 2),
                                      "min": round(float(rate.min()), 2), "p5": round(float(np.percentile(rate, 5)), 2),
                                      "p50": round(float(np.median(rate)), 2), "p95": round(float(np.percentile(rate, 95)), 2),
                                      "max": round(float(rate.max()), 2)}, "groupings": {}}
+    if placement is not None:
+        out["placement"] = placement
     total = float(((rate - rate.mean()) ** 2).sum())
+    end_total = float(((end - end.mean()) ** 2).sum()) if end is not None else 0.0
     for name, key in keys.items():
         ids = np.unique(key)
         means = np.array([rate[key == i].mean() for i in ids])
@@ -241,8 +305,16 @@ def who_lags(t, hw, xcc, cu):
              "within_groups_std_us": round(float(np.sqrt(within / nwg)), 3),
              "share_of_variance_between_groups": round(1.0 - within / total, 4) if total > 0 else None,
              "group_means_min_max_us": [round(float(means.min()), 2), round(float(means.max()), 2)]}
+        label = (lambda i: labels[name][int(i)]) if name in labels else (lambda i: str(int(i)))
         if len(ids) <= 16:
-            g["group_means_us"] = {str(int(i)): round(float(m), 2) for i, m in zip(ids, means)}
+            g["group_means_us"] = {label(i): round(float(m), 2) for i, m in zip(ids, means)}
+            if name in labels:
+                g["group_sizes"] = {label(i): int(z) for i, z in zip(ids, sizes)}
+        if end is not None:
+            end_within = float(sum(((end[key == i] - end[key == i].mean()) ** 2).sum() for i in ids))
+            g["end_share_of_variance_between_groups"] = round(1.0 - end_within / end_total, 4) if end_total > 0 else None
+            if len(ids) <= 16:
+                g["end_group_means_us"] = {label(i): round(float(end[key == i].mean()), 1) for i in ids}
         out["groupings"][name] = g
     return out
 

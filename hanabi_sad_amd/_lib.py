@@ -351,6 +351,7 @@ SIGNATURES = {
     "hsad_search_belief_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "hsad_search_actions": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "hsad_search_job_stats": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "hsad_search_horizon_stats": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
     "hsad_search_world_scores": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "hsad_search_round": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "hsad_search_world_script": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),

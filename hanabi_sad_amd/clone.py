@@ -456,6 +456,10 @@ def parse_args(argv=None):
     p.add_argument("--search_worlds", type=int, default=0, help="with --blueprint: sampled worlds per legal action")
     p.add_argument("--search_rounds", default=None, type=lambda s: tuple(int(x) for x in s.split(",")),
                    help="with --blueprint: world counts per round, e.g. 8,8,16 (summing to --search_worlds)")
+    p.add_argument("--search_depth", default=None, type=int, metavar="D", help="with --blueprint --search_worlds: stop every sampled world D "
+                   "moves after the candidate action and value it as its score so far + the blueprint's own Q; not with --search_rounds")
+    p.add_argument("--search_horizon_value", default="mover", type=str, choices=["mover", "team"],
+                   help="with --search_depth: the Q of the seat on turn at the horizon, or the sum over the game's seats")
     p.add_argument("--searcher", type=str, default="all", help="with --blueprint: all, or the one seat that searches")
     p.add_argument("--search_threshold", type=float, default=0.05, help="with --blueprint: deviate from the blueprint only for a larger value gain")
     p.add_argument("--target_temperature", type=float, default=0.0, help="with --blueprint: > 0 clones softmax(search values / this) "
@@ -477,6 +481,13 @@ def main(argv=None):
         if not np.isfinite(getattr(args, flag)) or getattr(args, flag) < 0:
             raise SystemExit("--%s must be finite and not negative" % flag)
     search_values = None
+    if args.search_depth is not None:
+        if not args.blueprint or args.search_worlds < 1:
+            raise SystemExit("--search_depth needs --blueprint FILE --search_worlds N > 0")
+        if args.search_rounds is not None:
+            raise SystemExit("--search_depth and --search_rounds do not combine (the round kernel compares whole scores)")
+        if args.search_depth < 0:
+            raise SystemExit("--search_depth must not be negative")
     if args.blueprint:
         if not os.path.isfile(args.blueprint):
             raise SystemExit("--blueprint %s: no such weight file" % args.blueprint)
@@ -491,10 +502,13 @@ def main(argv=None):
         played = play_with_search(load_weights(args.blueprint), args.num_game, args.seed, args.eval_bomb, args.sad, worlds=args.search_worlds,
                                   threshold=args.search_threshold, search_seed=args.seed, searcher="all" if args.searcher == "all" else int(args.searcher),
                                   num_player=args.num_player, hand_size=args.hand_size, device=dev, rounds=args.search_rounds, records=True,
-                                  **game_rules(args))
+                                  depth=args.search_depth, horizon_value=args.search_horizon_value, **game_rules(args))
         records, search_values = played.records, played.search_values
         print("blueprint + search (%d worlds): %.3f +/- %.3f over %d deals, %d moves changed by the search"
               % (args.search_worlds, played.mean, played.sem, args.num_game, int(played.deviations.sum())), flush=True)
+        if args.search_depth is not None:
+            print("depth %d (%s): %.4f of the worlds cut at the horizon" % (args.search_depth, args.search_horizon_value, played.cut_share),
+                  flush=True)
     elif args.games:
         records = gr.load(args.games)
     else:

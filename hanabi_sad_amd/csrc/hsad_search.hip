@@ -1,5 +1,5 @@
 // hsad_search.hip — the glue kernels of blueprint-policy search (include/hsad.h: hsad_search_fork_state / hsad_search_actions /
-// hsad_search_job_stats / hsad_search_world_scores / hsad_search_round; search.PolicySearch drives them).
+// hsad_search_job_stats / hsad_search_horizon_stats / hsad_search_world_scores / hsad_search_round; search.PolicySearch drives them).
 //
 // What they serve: SPARTA-style single-agent search.  A search env holds `capacity` slots; slot j plays one (root game, candidate
 // action, sampled world) job: hsad_env_fork + hsad_env_determinize put the world there, the R2D2 agent acts for every seat of every
@@ -10,6 +10,8 @@
 //               candidate action forced on the searcher's seat (first move only: the caller passes no override afterwards).
 //               greedy_a keeps the agent's greedy action -- what SAD shows the partner when the searcher deviates
 //   job_stats   the finished slots' scores summed per job (sum, sum of squares, count) with integer atomics: exact and order-free
+//   horizon_stats  the same for a depth-limited search: live slots are valued as score so far + the blueprint's Q in 1/256 points
+//               (the row function is hsad_search_horizon.h), still integer atomics only
 //   belief_rows the searcher's rows of the top layer's h after the root act -> the bf16 operand of the learned belief's head
 //               (hsad_search_belief_rows; belief.BeliefSampler, sampler = "learned")
 // and, for the replay stage that rebuilds every sampled world's LSTM states from the game's history (PolicySearch(replay=True)):
@@ -30,11 +32,14 @@
 #include <cstdio>
 
 #include "hsad.h"
+#include "hsad_rulebot.h"
+#include "hsad_search_horizon.h"
 
 extern "C" int hsad_internal_set_error(int code, const char* msg);
 extern "C" int hsad_internal_env_status(const hsad_env* e, const uint32_t** misc, int* G, int* P, int* A, int* perfect_score);
 extern "C" int hsad_internal_env_hands(const hsad_env* e, const uint32_t** hand0, int* G, int* Gpad, int* P, int* H);
 extern "C" int hsad_internal_env_legal_bits(const hsad_env* e, const unsigned long long** legal_bits);
+extern "C" int hsad_internal_env_rulebot_view(const hsad_env* e, const uint32_t** planes, uint32_t** act_count, int* G, int* Gpad, RbRules* ru);
 
 namespace {
 
@@ -148,6 +153,35 @@ __global__ __launch_bounds__(kThreads) void job_stats_kernel(const uint32_t* __r
   atomicAdd(s + 0, (unsigned long long)sc);
   atomicAdd(s + 1, (unsigned long long)(sc * sc));
   atomicAdd(s + 2, 1ull);
+}
+
+// one thread per slot, laid out as job_stats_kernel: the slot's value at the horizon (sh_slot, hsad_search_horizon.h) from its two
+// status words and its P rows of Q; up to five 64-bit integer atomics and one 16-bit store per counted slot with a valid job
+__global__ __launch_bounds__(kThreads) void horizon_stats_kernel(const uint32_t* __restrict__ planes, int G, int Gpad, int P, int perfect,
+                                                                 const int32_t* __restrict__ job, int n_job, const float* __restrict__ q_rows,
+                                                                 int mode, unsigned long long* __restrict__ stats,
+                                                                 unsigned long long* __restrict__ cut, unsigned long long* __restrict__ nonfinite,
+                                                                 const int32_t* __restrict__ world, int worlds,
+                                                                 uint16_t* __restrict__ world_values) {
+  const int g = blockIdx.x * kThreads + threadIdx.x;
+  if (g >= G) return;
+  const int j = job[g];
+  if (j < 0 || j >= n_job) return;
+  const uint32_t misc = planes[(size_t)PL_MISC * Gpad + g], board = planes[(size_t)PL_BOARD * Gpad + g];
+  const float* row = q_rows + (size_t)g * P;
+  const ShValue r = sh_slot(misc, board, P, perfect, mode, [row](int p) { return row[p]; });
+  if (!r.counted) return;
+  const long long v = r.v;
+  unsigned long long* s = stats + (size_t)j * 3;
+  atomicAdd(s + 0, (unsigned long long)v);
+  atomicAdd(s + 1, (unsigned long long)(v * v));
+  atomicAdd(s + 2, 1ull);
+  if (r.cut) atomicAdd(cut + j, 1ull);
+  if (r.nonfinite) atomicAdd(nonfinite, 1ull);
+  if (world_values) {
+    const int w = world[g];
+    if (w >= 0 && w < worlds) world_values[(size_t)j * worlds + w] = (uint16_t)r.v;
+  }
 }
 
 // one thread per world slot.  The env's move uids (HanabiGame::GetMove order): discard slot i = i, play slot i = H + i, hints above.
@@ -459,6 +493,27 @@ int hsad_search_job_stats(const hsad_env* env, const int32_t* job, int n_job, in
   CK(hsad_internal_env_status(env, &misc, &G, &P, &A, &perfect));
   hipLaunchKernelGGL(job_stats_kernel, dim3((G + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, misc, G, job, n_job,
                      reinterpret_cast<unsigned long long*>(stats));
+  HIP_TRY(hipGetLastError());
+  return HSAD_OK;
+}
+
+int hsad_search_horizon_stats(const hsad_env* env, const int32_t* job, int n_job, const float* q_rows, int mode, int64_t* stats,
+                              int64_t* cut, int64_t* nonfinite, const int32_t* world, int worlds, uint16_t* world_values, void* stream) {
+  if (!job || !q_rows || !stats || !cut || !nonfinite) return efail(HSAD_ERR_INVALID, "hsad_search_horizon_stats: null argument");
+  if (n_job < 1) return efail(HSAD_ERR_INVALID, "hsad_search_horizon_stats: n_job must be >= 1");
+  if (mode != HSAD_SEARCH_HORIZON_MOVER && mode != HSAD_SEARCH_HORIZON_TEAM)
+    return efail(HSAD_ERR_INVALID, "hsad_search_horizon_stats: mode = %d is neither HSAD_SEARCH_HORIZON_MOVER nor _TEAM", mode);
+  if (world_values && !world) return efail(HSAD_ERR_INVALID, "hsad_search_horizon_stats: world_values needs the world of every slot");
+  if (world_values && worlds < 1) return efail(HSAD_ERR_INVALID, "hsad_search_horizon_stats: worlds must be >= 1 with world_values");
+  const uint32_t* planes;
+  uint32_t* act_count;
+  int G, Gpad;
+  RbRules ru;
+  CK(hsad_internal_env_rulebot_view(env, &planes, &act_count, &G, &Gpad, &ru));
+  hipLaunchKernelGGL(horizon_stats_kernel, dim3((G + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, planes, G, Gpad, ru.P,
+                     ru.nC * ru.nR, job, n_job, q_rows, mode, reinterpret_cast<unsigned long long*>(stats),
+                     reinterpret_cast<unsigned long long*>(cut), reinterpret_cast<unsigned long long*>(nonfinite), world, worlds,
+                     world_values);
   HIP_TRY(hipGetLastError());
   return HSAD_OK;
 }

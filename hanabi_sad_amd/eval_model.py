@@ -14,6 +14,8 @@ layout.
                                                         (game_record; read it with python -m hanabi_sad_amd.game_record g.jsonl)
   --paper op  --method sad --idx 0 --search_worlds 8    M0 in self-play, blueprint only and blueprint + search over the same deals
   ... --search_worlds 32 --search_rounds 8,8,16         the same with the search in rounds (paired statistics, pruning)
+  ... --search_worlds 8 --search_depth 2                the same with every world stopped 2 moves after the candidate action and
+                                                        valued as score so far + the blueprint's Q
   ... --search_worlds 8 --search_sampler learned --search_belief belief.pthw    the worlds' hands drawn from a learned belief head
                                                         (python -m hanabi_sad_amd.belief fits one)
 
@@ -77,7 +79,24 @@ def parse_args(argv=None):
                    "than this many paired standard errors below the round's leader")
     p.add_argument("--search_deviate_z", default=0.0, type=float, help="with --search_rounds: deviate only where the paired gain over "
                    "the blueprint's action also exceeds this many of its standard errors")
+    p.add_argument("--search_depth", default=None, type=int, metavar="D", help="with --search_worlds: stop every sampled world D moves "
+                   "after the candidate action and value it as its score so far + the blueprint's own Q "
+                   "(play_with_search(depth=D)); not with --search_rounds")
+    p.add_argument("--search_horizon_value", default="mover", type=str, choices=["mover", "team"],
+                   help="with --search_depth: the Q of the seat on turn at the horizon, or the sum over the game's seats")
     return p.parse_args(argv)
+
+
+def check_search_depth(args):
+    """the usage errors of --search_depth; touches no device"""
+    if args.search_depth is None:
+        return
+    if args.search_worlds < 1:
+        raise SystemExit("--search_depth needs --search_worlds N > 0")
+    if args.search_rounds is not None:
+        raise SystemExit("--search_depth and --search_rounds do not combine (the round kernel compares whole scores)")
+    if args.search_depth < 0:
+        raise SystemExit("--search_depth must not be negative")
 
 
 def load_pool(args):
@@ -142,11 +161,15 @@ def search_report(args):
     base = play_with_search(agent, n, 1, 0, sad, worlds=0, **kw)
     if args.search_rounds is not None:
         kw.update(rounds=args.search_rounds, prune_z=args.search_prune_z, deviate_z=args.search_deviate_z)
+    if args.search_depth is not None:
+        kw.update(depth=args.search_depth, horizon_value=args.search_horizon_value)
     res = play_with_search(agent, n, 1, 0, sad, worlds=args.search_worlds, replay_history=bool(args.search_replay),
                            consistent_only=bool(args.search_consistent), sampler=args.search_sampler, belief=belief, **kw)
     print("blueprint: %f +/- %f" % (base.mean, base.sem), "; perfect: ", base.perfect)
-    print("blueprint + search (%d worlds): %f +/- %f" % (args.search_worlds, res.mean, res.sem), "; perfect: ", res.perfect,
-          "; deviations per game: %f" % float(res.deviations.double().mean()))
+    line = "; deviations per game: %f" % float(res.deviations.double().mean())
+    if args.search_depth is not None:
+        line += " ; depth %d (%s): %f of the worlds cut at the horizon" % (args.search_depth, args.search_horizon_value, res.cut_share)
+    print("blueprint + search (%d worlds): %f +/- %f" % (args.search_worlds, res.mean, res.sem), "; perfect: ", res.perfect, line)
     return base, res
 
 
@@ -166,6 +189,7 @@ def main(argv=None):
     if args.temperature is not None and any(not t >= 0 or t == float("inf") for t in args.temperature):
         raise SystemExit("--temperature must be finite and not negative")
     load_search_belief(args)      # the usage errors, before anything is loaded
+    check_search_depth(args)
     if args.search_worlds > 0:
         if args.temperature is not None:
             raise SystemExit("--temperature samples tournament seats (no --search_worlds: the search plays the blueprint's greedy moves)")

@@ -14,7 +14,11 @@ hsad_env_rewind_scripted, hsad_search_replay_actions), so that each seat's LSTM 
 
 search(rounds=(n0, n1, ...)) plays the worlds in rounds: the per-world scores are kept (hsad_search_world_scores), and after each
 round hsad_search_round compares every action with the round's leader world by world -- the actions of a game meet the same worlds
--- and drops those that are already hopeless (round_world_order, SearchValues.paired / pruned_round, choose_action_paired)."""
+-- and drops those that are already hopeless (round_world_order, SearchValues.paired / pruned_round, choose_action_paired).
+
+PolicySearch(depth=D) does not play the worlds to the end: the forced action and D more blueprint moves, then one act(with_q=True)
+on the position reached, and hsad_search_horizon_stats values every world still running as its score so far + the blueprint's own Q,
+in 1/256 points (SearchValues.scale / cut / nonfinite / world_values).  D + 2 act calls per chunk, no host read-back."""
 from fractions import Fraction
 
 import numpy as np
@@ -86,6 +90,24 @@ def _check_belief(sampler, belief, agent=None, hand_size=None):
         if getattr(net, "H", None) is not None and int(net.H) != H:
             raise ValueError("the belief head reads a trunk of width %d, the agent's is %d" % (H, int(net.H)))
     return hs, H
+
+
+HORIZON_VALUES = ("mover", "team")          # include/hsad.h: HSAD_SEARCH_HORIZON_MOVER, HSAD_SEARCH_HORIZON_TEAM
+VALUE_SCALE = 256                           # HSAD_SEARCH_VALUE_SCALE
+
+
+def _check_depth(depth, horizon_value, max_steps, agent=None):
+    """the refusals of a depth-limited search, all before anything touches the device -> depth (None, or an int)"""
+    if horizon_value not in HORIZON_VALUES:
+        raise ValueError("horizon_value must be one of %s; got %r" % (", ".join(HORIZON_VALUES), horizon_value))
+    if depth is None:
+        return None
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 0 <= int(depth) < int(max_steps):
+        raise ValueError("depth must be None or an int with 0 <= depth < max_steps = %d; got %r" % (int(max_steps), depth))
+    if getattr(getattr(agent, "online", None), "skip", False):
+        raise ValueError("a depth-limited search values the horizon with the agent's cached Q (act(with_q=True)), which is undefined "
+                         "for a skip_connect agent")
+    return int(depth)
 
 
 def _sample_hands(env, sampler, viewer, key, seed, world, worlds, belief=None):
@@ -227,22 +249,37 @@ class SearchValues:
     the action was dropped, -1 if never; world_scores uint8 [G, A, worlds] = the score per world, 0xFF where not played.
     sampler="learned" (else both None) adds belief_logp / belief_logp0 float32 [G, worlds]: the log-probability of world w's sampled
     hand under the learned belief and under the exact belief (their difference is the log importance ratio), NaN where no world was
-    sampled."""
+    sampled.
+    A depth-limited search (PolicySearch(depth=D), else scale = 1, cut = None, nonfinite = 0) counts in fixed point: scale = 256
+    (HSAD_SEARCH_VALUE_SCALE), and totals is then (sum v, sum v^2, worlds) in units of 1 / scale and 1 / scale^2 -- v = a world's score
+    so far plus the blueprint's Q at the horizon, or scale x its final score (hsad_search_horizon_stats); values and sem are computed
+    in float64 from those integers, divided by scale and cast to float32, so they stay in points.  cut int64 [G, A] = the worlds
+    valued at the horizon (the others ended within the depth); nonfinite = how many of them had a Q that was NaN or infinite and
+    counted as 0.  world_values uint16 [G, A, worlds] (search(keep_world_values=True), else None) = v per world in units of 1 / scale,
+    0xFFFF where not played."""
 
     def __init__(self, totals, blueprint_a, mismatch=None, paired=None, pruned_round=None, world_scores=None, belief_logp=None,
-                 belief_logp0=None):
+                 belief_logp0=None, scale=1, cut=None, nonfinite=0, world_values=None):
         self.totals = totals = torch.as_tensor(totals).to(torch.int64)
         self.blueprint_a = torch.as_tensor(blueprint_a).to(torch.int64)
         self.mismatch = mismatch
         self.belief_logp, self.belief_logp0 = belief_logp, belief_logp0
+        self.scale, self.nonfinite, self.world_values = int(scale), int(nonfinite), world_values
+        if self.scale < 1:
+            raise ValueError("scale must be >= 1; got %r" % (scale,))
+        self.cut = None if cut is None else torch.as_tensor(cut).to(torch.int64)
         s, sq, n = totals[..., 0], totals[..., 1], totals[..., 2]
         nan = torch.full(s.shape, float("nan"), dtype=torch.float32, device=totals.device)
         counted = n > 0
         nf = torch.where(counted, n, torch.ones_like(n))
-        self.values = torch.where(counted, s.to(torch.float32) / nf.to(torch.float32), nan)
         var_n2 = (nf * sq - s * s).clamp(min=0).to(torch.float64)        # n^2 * population variance, exact in int64
         nd = nf.to(torch.float64)
-        self.sem = torch.where(counted, (torch.sqrt(var_n2) / nd / torch.sqrt(nd)).to(torch.float32), nan)
+        if self.scale == 1:
+            self.values = torch.where(counted, s.to(torch.float32) / nf.to(torch.float32), nan)
+            self.sem = torch.where(counted, (torch.sqrt(var_n2) / nd / torch.sqrt(nd)).to(torch.float32), nan)
+        else:
+            self.values = torch.where(counted, (s.to(torch.float64) / nd / self.scale).to(torch.float32), nan)
+            self.sem = torch.where(counted, (torch.sqrt(var_n2) / nd / torch.sqrt(nd) / self.scale).to(torch.float32), nan)
         self.paired, self.pruned_round, self.world_scores = paired, pruned_round, world_scores
         self.paired_mean = self.paired_sem = None
         if paired is not None:
@@ -342,10 +379,18 @@ class PolicySearch:
     act chunks and the world envs of the replay stage alike; or "learned" with belief= (a belief.BeliefSampler, or what makes
     one: a BeliefHead, a head's state dict, its file): determinize_belief_worlds under the head's logits for the root act's state.
     ValueError -- before any device work -- for "learned" without a belief, a belief with another sampler, a head whose trunk
-    width or hand size is not the agent's / the env's, and a skip_connect agent."""
+    width or hand size is not the agent's / the env's, and a skip_connect agent.
+    depth=D (None: every world is played to the end of its game, as ever): a chunk plays the forced action and D more blueprint
+    moves -- D + 1 act / step iterations with no host read-back -- then acts once more with with_q=True without stepping, and
+    hsad_search_horizon_stats values every world still running as its score so far + that Q (horizon_value "mover": the Q of the
+    seat on turn; "team": the sum over the game's seats), worlds that ended within the depth as their final score; SearchValues is
+    then in fixed point (scale = 256) and carries cut / nonfinite.  ValueError -- before any device work -- for a depth that is
+    no int in [0, max_steps), another horizon_value, and a skip_connect agent (its cached Q is undefined)."""
 
-    def __init__(self, like, agent, capacity=4096, max_steps=200, replay=False, consistent_only=False, sampler="rejection", belief=None):
+    def __init__(self, like, agent, capacity=4096, max_steps=200, replay=False, consistent_only=False, sampler="rejection", belief=None,
+                 depth=None, horizon_value="mover"):
         self.agent, self.capacity, self.max_steps = agent, int(capacity), int(max_steps)
+        self.depth, self.horizon_value = _check_depth(depth, horizon_value, max_steps, agent), horizon_value
         self.sampler = _check_sampler(sampler)
         _check_belief(sampler, belief, agent, like.H)
         self.belief = belief
@@ -373,6 +418,11 @@ class PolicySearch:
         self.iterations = 0        # env steps of the last search, over all its chunks
         self.open_games = []       # the "games still running" words the host read during the last search (one per step, one step late)
         self.round_jobs = []       # jobs played per round of the last search in rounds
+        self.acts = 0              # agent.act calls of the last search, over all its stages
+        self.q_rows = None         # depth-limited search: Q_online(s, a) of the search env's rows at the horizon of the last chunk
+        if self.depth is not None:
+            import inspect
+            self._defer = "defer_target" in inspect.signature(agent.act).parameters     # the online net alone, where the agent can
 
     def _make_env(self, config):
         env = BatchedHanabiEnv(self.capacity, seed=0, eps_list=(0.0,), device=str(self.device), track_deck_history=False, **config)
@@ -400,9 +450,12 @@ class PolicySearch:
         hid = {"h0": self.h, "c0": self.c}
         if self.h16 is not None:
             hid["h0_16"] = self.h16
+        if self.depth is not None:
+            return self._play_chunk_to_depth(player, override, bp_rows, hid)
         bp, done = None, False
         for t in range(self.max_steps):
             reply, hid = agent.act(self._obs(), hid)
+            self.acts += 1
             a, g = reply["a"].contiguous(), reply["greedy_a"].contiguous()
             if t == 0 and bp_rows is not None:
                 bp = g[bp_rows]
@@ -424,6 +477,31 @@ class PolicySearch:
                     break
         if not done and int(self.unfinished.cpu()[0]) != 0:
             raise RuntimeError("%d game(s) of the search env still running after %d steps" % (int(self.unfinished.cpu()[0]), self.max_steps))
+        return bp
+
+    def _play_chunk_to_depth(self, player, override, bp_rows, hid):
+        """the forced action and `depth` more greedy moves for every seat of every slot, then one act with Q on the position reached
+        and no step after it: nothing here reads the device, the host never waits.  -> as _play_chunk; the Q rows in self.q_rows"""
+        env, lib, agent = self.env, self.lib, self.agent
+        bp = None
+        for t in range(self.depth + 1):
+            reply, hid = agent.act(self._obs(), hid)
+            a, g = reply["a"].contiguous(), reply["greedy_a"].contiguous()
+            if t == 0 and bp_rows is not None:
+                bp = g[bp_rows]
+            _lib.check(lib.hsad_search_actions(env.h, a.data_ptr(), g.data_ptr(), player.data_ptr(), override.data_ptr() if t == 0 else None,
+                                               env.a.data_ptr(), env.greedy_a.data_ptr(), env._stream()))
+            env.step(env.a, env.greedy_a)
+            self.iterations += 1
+        counter = getattr(agent, "counter", None)
+        if self._defer:
+            reply, _ = agent.act(self._obs(), hid, with_q=True, defer_target=True)
+        else:
+            reply, _ = agent.act(self._obs(), hid, with_q=True)
+        if counter is not None:      # the valuing act is no move of the agent's: its exploration counter stays where it was
+            agent.counter = counter
+        self.acts += self.depth + 2
+        self.q_rows = reply["q_online_a"].contiguous()
         return bp
 
     def _replay(self, root, log, games, cur, worlds, seed, seed_of, drawn=None):
@@ -477,6 +555,7 @@ class PolicySearch:
             mm = mismatch[ci * cap:(ci + 1) * cap]
             for t in range(n_moves):
                 reply, hid = agent.act(self._obs(env), hid)
+                self.acts += 1
                 g = reply["greedy_a"].contiguous()
                 _lib.check(lib.hsad_search_replay_actions(env.h, src.data_ptr(), viewer.data_ptr(), la[t].data_ptr(), lg[t].data_ptr(), G,
                                                           g.data_ptr(), env.a.data_ptr(), env.greedy_a.data_ptr(), mm.data_ptr(),
@@ -541,14 +620,20 @@ class PolicySearch:
             alive = now
         return paired_bp, pruned_round
 
-    def search(self, root, hid, worlds, seed, searcher=None, log=None, rounds=None, prune_z=2.0, min_n=2, hid_next=None):
+    def search(self, root, hid, worlds, seed, searcher=None, log=None, rounds=None, prune_z=2.0, min_n=2, hid_next=None,
+               keep_world_values=False):
         """-> SearchValues for the root env's games; root and hid ({"h0", "c0"}: [L, root.G * root.P, H], the agent's state entering
         the root step) are only read.  log: the root's GameLog (replay=True).  rounds: None, or world counts per round (their sum is
         `worlds`) for the search in rounds with pruning at prune_z paired standard errors.  hid_next (sampler="learned" only): the
         agent's state AFTER the root act, whose top layer's h is what the belief head reads; None: the search runs that one act on
-        the root's float32 rows itself.  See policy_action_values."""
+        the root's float32 rows itself.  keep_world_values: SearchValues.world_values, every world's value by itself (one more
+        kernel per chunk without a depth; none with one).  See policy_action_values."""
         from .eval import _drain_errors
         z2 = None
+        depth = self.depth
+        if rounds is not None and depth is not None:
+            raise ValueError("search(rounds=...) with a depth is out of scope: hsad_search_round compares whole uint8 scores, a "
+                             "depth-limited search counts in 1/256 points")
         if rounds is not None:
             rounds, *z2 = _check_rounds(rounds, worlds, prune_z, min_n)
         G, P, A, cap = root.G, root.P, root.A, self.capacity
@@ -559,7 +644,8 @@ class PolicySearch:
         if tuple(h_src.shape) != (self.h.shape[0], G * P, self.h.shape[2]) or h_src.shape != c_src.shape:
             raise ValueError("hid must hold h0 / c0 of shape [%d, %d, %d]; got %s" % (self.h.shape[0], G * P, self.h.shape[2], tuple(h_src.shape)))
         h_src, c_src = h_src.contiguous(), c_src.contiguous()
-        self.iterations, self.open_games, self.round_jobs = 0, [], []
+        self.iterations, self.open_games, self.round_jobs, self.acts = 0, [], [], 0
+        scale = 1 if depth is None else VALUE_SCALE
         totals = torch.zeros(G, A, 3, dtype=torch.int64, device=dev)
         blueprint = torch.full((G,), -1, dtype=torch.int64, device=dev)
         pairs, cur = search_jobs(root)
@@ -571,6 +657,10 @@ class PolicySearch:
                 extra = dict(paired=torch.zeros(G, A, 3, dtype=torch.int64, device=dev),
                              pruned_round=torch.full((G, A), -1, dtype=torch.int32, device=dev),
                              world_scores=torch.full((G, A, worlds), 0xFF, dtype=torch.uint8, device=dev))
+            if depth is not None:
+                extra.update(scale=scale, cut=torch.zeros(G, A, dtype=torch.int64, device=dev))
+            if keep_world_values:
+                extra.update(world_values=torch.full((G, A, max(worlds, 0)), -1, dtype=torch.int16, device=dev).view(torch.uint16))
             return SearchValues(totals, blueprint, torch.zeros(G, max(worlds, 0), dtype=torch.int32, device=dev) if self.replay else None,
                                 **extra)
         drawn = None
@@ -580,6 +670,7 @@ class PolicySearch:
                 obs = {"priv_s": root.priv_s.view(N, root.F), "legal_move": root.legal_move.view(N, A),
                        "eps": torch.zeros(N, dtype=torch.float32, device=dev)}
                 hid_next = self.agent.act(obs, {"h0": h_src, "c0": c_src})[1]
+                self.acts += 1
                 if counter is not None:      # the extra act is no move of the agent's: its exploration counter stays where it was
                     self.agent.counter = counter
             h_top = hid_next["h0"]
@@ -606,7 +697,15 @@ class PolicySearch:
                 keep = torch.where(keep.any(dim=1, keepdim=True), keep, torch.ones_like(keep))
             game_pos = np.zeros(G, dtype=np.int64)
             game_pos[games] = np.arange(len(games))
-        scores = None if rounds is None else torch.full((n_job, worlds), 0xFF, dtype=torch.uint8, device=dev)
+        scores = None
+        if rounds is not None or (keep_world_values and depth is None):
+            scores = torch.full((n_job, worlds), 0xFF, dtype=torch.uint8, device=dev)
+        cut = nonfinite = wv = None
+        if depth is not None:
+            cut, nonfinite = torch.zeros(n_job, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+            mode = HORIZON_VALUES.index(self.horizon_value)
+            if keep_world_values:      # 0xFFFF = not played; index_put and fill know int16, the caller sees the same words as uint16
+                wv = torch.full((n_job, worlds), -1, dtype=torch.int16, device=dev)
 
         def play(pj, w_c, valid, bp_slot, here):
             """one chunk: slot i plays world w_c[i] of pair pj[i] where valid[i]; bp_slot[here] are the slots whose first act is the
@@ -646,6 +745,12 @@ class PolicySearch:
             bp = self._play_chunk(player, override, bp_rows)
             if bp is not None:
                 blueprint[torch.from_numpy(games[here]).to(dev)] = bp
+            if depth is not None:
+                world_d = torch.from_numpy(w_c.astype(np.int32)).to(dev) if wv is not None else None
+                _lib.check(lib.hsad_search_horizon_stats(env.h, job.data_ptr(), n_job, self.q_rows.data_ptr(), mode, stats.data_ptr(),
+                                                         cut.data_ptr(), nonfinite.data_ptr(), world_d.data_ptr() if wv is not None else None,
+                                                         worlds, wv.data_ptr() if wv is not None else None, env._stream()))
+                return
             _lib.check(lib.hsad_search_job_stats(env.h, job.data_ptr(), n_job, stats.data_ptr(), env._stream()))
             if scores is not None:
                 world_d = torch.from_numpy(w_c.astype(np.int32)).to(dev)
@@ -663,6 +768,15 @@ class PolicySearch:
         pd = torch.from_numpy(pairs).to(dev)
         totals[pd[:, 0], pd[:, 1]] = stats
         lp = dict(belief_logp=drawn.logp[:G], belief_logp0=drawn.logp0[:G]) if drawn is not None else {}
+        if depth is not None:
+            cut_ga = torch.zeros(G, A, dtype=torch.int64, device=dev)
+            cut_ga[pd[:, 0], pd[:, 1]] = cut
+            lp.update(scale=scale, cut=cut_ga, nonfinite=int(nonfinite.cpu()[0]))
+        if keep_world_values:
+            table = torch.full((G, A, worlds), -1, dtype=torch.int16, device=dev)
+            # without a depth the table is hsad_search_world_scores' bytes widened: whole points (scale = 1), 0xFF -> 0xFFFF
+            table[pd[:, 0], pd[:, 1]] = wv if wv is not None else torch.where(scores == 0xFF, -1, scores.to(torch.int16)).to(torch.int16)
+            lp.update(world_values=table.view(torch.uint16))
         if rounds is None:
             return SearchValues(totals, blueprint, mismatch, **lp)
         paired = torch.zeros(G, A, 3, dtype=torch.int64, device=dev)
@@ -675,7 +789,8 @@ class PolicySearch:
 
 
 def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_steps=200, searcher=None, replay=False, log=None,
-                         consistent_only=False, sampler="rejection", rounds=None, prune_z=2.0, min_n=2, belief=None, hid_next=None):
+                         consistent_only=False, sampler="rejection", rounds=None, prune_z=2.0, min_n=2, belief=None, hid_next=None,
+                         depth=None, horizon_value="mover", keep_world_values=False):
     """SearchValues: values[g, a] = mean final score (HSAD_Q_SCORE) over `worlds` sampled worlds when the player on turn of root game
     g plays a and EVERY player, the searcher included, then follows the blueprint `agent` greedily to the end of the game.
 
@@ -734,10 +849,28 @@ def policy_action_values(root, agent, hid, worlds, seed, capacity=4096, max_step
     Fraction(z * z).limit_denominator(1024), numerator <= 16,384; equality keeps the action).  The leader and the blueprint's own
     action are never dropped; a game down to one action plays no more.  The host reads `alive` once per round.  The replay stage is
     not split: it replays all worlds up front.  SearchValues then carries paired / paired_mean / paired_sem (against the blueprint's
-    action), pruned_round and world_scores; totals / values count the worlds each action was played in."""
-    ps = PolicySearch(root, agent, capacity, max_steps, replay=replay, consistent_only=consistent_only, sampler=sampler, belief=belief)
+    action), pruned_round and world_scores; totals / values count the worlds each action was played in.
+
+    depth=D (None = all of the above, untouched: the same calls, the same bits): the worlds are not played to the end.  A chunk runs
+    D + 1 iterations of act -> hsad_search_actions -> env.step (the candidate action, then D blueprint moves) with no
+    hsad_seating_stats and no host read-back, then ONE more act with with_q=True on the position reached (defer_target=True where
+    the agent takes it: the online net alone; the env is not stepped after it and the agent's counter is put back), and
+    hsad_search_horizon_stats in place of hsad_search_job_stats: a world that ended within the depth counts 256 x its final score,
+    a world still running counts 256 x its score so far + the blueprint's Q rounded to 1/256 -- horizon_value="mover": Q_online(s, a)
+    of the seat on turn; "team": the fp32 sum over the game's seats in seat order (VDN's joint value) -- clamped to [0, 256 x the
+    perfect score]; a Q that is not finite counts as 0 and is reported (SearchValues.nonfinite).  A searched move then costs D + 2
+    act calls per chunk whatever the game's length.  SearchValues.scale = 256, totals in 1/256 points, values / sem in points, cut =
+    the worlds valued at the horizon.  How good the value is depends on how well the agent's Q is calibrated (clone --value_weight
+    fits it to recorded returns); a random net's Q says nothing.  Samplers, replay, searcher and consistent_only work as above.
+    ValueError before any device work: depth no int in [0, max_steps), horizon_value not "mover" / "team", a skip_connect agent;
+    and for rounds= together with a depth (hsad_search_round compares whole uint8 scores: out of scope).
+    keep_world_values=True: SearchValues.world_values uint16 [G, A, worlds], every world's own value in units of 1 / scale (0xFFFF =
+    not played) -- with a depth written by hsad_search_horizon_stats, without one hsad_search_world_scores' table widened."""
+    ps = PolicySearch(root, agent, capacity, max_steps, replay=replay, consistent_only=consistent_only, sampler=sampler, belief=belief,
+                      depth=depth, horizon_value=horizon_value)
     try:
-        return ps.search(root, hid, worlds, seed, searcher, log=log, rounds=rounds, prune_z=prune_z, min_n=min_n, hid_next=hid_next)
+        return ps.search(root, hid, worlds, seed, searcher, log=log, rounds=rounds, prune_z=prune_z, min_n=min_n, hid_next=hid_next,
+                         keep_world_values=keep_world_values)
     finally:
         ps.close()
 
@@ -783,9 +916,15 @@ class SearchPlay:
     tensors (chosen, blueprint), -1 where the game's player on turn did not search.  From play_with_search(records=...), else None:
     records = the game_record.GameRecord list of the games played (moves = the moves made, search's choices included; greedy = the
     blueprint's), meta = {game, deal_seed, worlds, search_seed}; search_values = one float32 [n_moves, A] numpy array per record, in the
-    same order: SearchValues.values of every move, NaN rows where the game's player on turn did not search"""
+    same order: SearchValues.values of every move, NaN rows where the game's player on turn did not search.
+    A depth-limited run (play_with_search(depth=D), else all None) adds: worlds_played / worlds_cut = the worlds counted over all
+    moves and how many of them were valued at the horizon, cut_share = their ratio, nonfinite = the Q-values that were not finite;
+    its records' meta also carry depth and horizon_value"""
 
-    def __init__(self, scores, perfect_score, deviations, trace, records=None, search_values=None):
+    def __init__(self, scores, perfect_score, deviations, trace, records=None, search_values=None, worlds_played=None, worlds_cut=None,
+                 nonfinite=None):
+        self.worlds_played, self.worlds_cut, self.nonfinite = worlds_played, worlds_cut, nonfinite
+        self.cut_share = None if worlds_cut is None else (worlds_cut / worlds_played if worlds_played else 0.0)
         self.scores = [int(s) for s in scores]
         self.mean = float(np.mean(scores))
         self.num_perfect = int((np.asarray(scores) == perfect_score).sum())
@@ -798,7 +937,7 @@ class SearchPlay:
 def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05, search_seed=0, searcher="all", capacity=4096,
                      num_player=2, hand_size=5, device="cuda:0", max_steps=200, precision="bf16", shuffle_color=False, colors=5, ranks=5,
                      max_information_tokens=8, max_life_tokens=3, replay_history=False, consistent_only=False, sampler="rejection",
-                     rounds=None, prune_z=2.0, deviate_z=0.0, records=False, belief=None):
+                     rounds=None, prune_z=2.0, deviate_z=0.0, records=False, belief=None, depth=None, horizon_value="mover"):
     """eval.evaluate's lock-step loop over the deals seed .. seed + num_game - 1 with search on top of the blueprint -> SearchPlay.
     Before each step: PolicySearch values for the games whose player on turn searches (searcher: "all" or a seat number),
     choose_action, then the root steps with a = the chosen action and greedy_a = the blueprint's greedy action; the carried state
@@ -817,9 +956,16 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
     changes nothing: no call more per move, the same scores, deviations and trace.
     sampler="learned", belief=...: every search draws its worlds from the learned belief (policy_action_values), with the root act's
     new state -- which this loop has anyway -- as the head's features.  worlds = 0 never looks at the belief beyond the argument
-    checks."""
+    checks.
+    depth=D, horizon_value=...: every search stops D moves after the candidate action and values the worlds still running with the
+    blueprint's Q (policy_action_values); SearchPlay then carries worlds_played / worlds_cut / cut_share / nonfinite and the records'
+    meta depth and horizon_value.  ValueError as there, rounds= with a depth included.  depth=None changes nothing."""
     if records is False:
         records = None
+    _check_depth(depth, horizon_value, max_steps, agent)
+    if depth is not None and rounds is not None:
+        raise ValueError("rounds= with a depth is out of scope: hsad_search_round compares whole uint8 scores, a depth-limited search "
+                         "counts in 1/256 points")
     _check_belief(sampler, belief, None, hand_size)
     if rounds is not None and worlds > 0:
         _check_rounds(rounds, worlds, prune_z, 2)
@@ -833,7 +979,10 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
         raise ValueError("searcher must be \"all\" or a seat in 0..%d" % (num_player - 1))
     # no move has more jobs than games x playable actions x worlds: a smaller batch needs no more slots than that
     ps = PolicySearch(env, agent, min(int(capacity), num_game * (env.A - 1) * worlds), max_steps, replay=bool(replay_history),
-                      consistent_only=bool(consistent_only), sampler=sampler, belief=belief) if worlds > 0 else None
+                      consistent_only=bool(consistent_only), sampler=sampler, belief=belief, depth=depth,
+                      horizon_value=horizon_value) if worlds > 0 else None
+    counted = torch.zeros(2, dtype=torch.int64, device=env.device) if depth is not None else None     # worlds played, worlds cut
+    nonfinite = 0
     log = GameLog(num_game, num_player, env.device) if ps is not None and replay_history else None
     N = num_game * num_player
     deviations = torch.zeros(num_game, dtype=torch.int64, device=env.device)
@@ -866,6 +1015,9 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
             else:
                 sv = ps.search(env, hid, worlds, move_seed(search_seed, t), seat, log=log, rounds=rounds, prune_z=prune_z,
                                hid_next=new_hid if belief is not None else None)
+                if counted is not None:
+                    counted += torch.stack([sv.totals[..., 2].sum(), sv.cut.sum()])
+                    nonfinite += sv.nonfinite
                 player = q[:, Q_CUR_PLAYER].contiguous()
                 # the blueprint's move is the root act's own greedy action (the search's first act gives the same one while both
                 # run in one acting regime; this one holds in any)
@@ -902,6 +1054,8 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
             kept_values = []
             for k, rec in enumerate(kept):
                 rec.meta.update(deal_seed=int(seed + rec.meta["game"]), worlds=int(worlds), search_seed=int(search_seed))
+                if depth is not None:
+                    rec.meta.update(depth=int(depth), horizon_value=horizon_value)
                 kept_values.append(np.ascontiguousarray(values[:rec.n_moves, k]))
     finally:
         if recorder is not None:
@@ -909,4 +1063,8 @@ def play_with_search(agent, num_game, seed, bomb, sad, *, worlds, threshold=0.05
         if ps is not None:
             ps.close()
         env.close()
-    return SearchPlay(scores, colors * ranks, deviations.cpu(), trace, kept, kept_values)
+    if counted is None:
+        return SearchPlay(scores, colors * ranks, deviations.cpu(), trace, kept, kept_values)
+    played, cut = (int(x) for x in counted.cpu())
+    return SearchPlay(scores, colors * ranks, deviations.cpu(), trace, kept, kept_values, worlds_played=played, worlds_cut=cut,
+                      nonfinite=nonfinite)

@@ -1686,6 +1686,30 @@ int hsad_search_actions(const hsad_env* env, const int64_t* a_src, const int64_t
  * Integer atomics: exact, order-free.  The "games still running" word of the host loop is hsad_seating_stats(env, G, ...)'s. */
 int hsad_search_job_stats(const hsad_env* env, const int32_t* job, int n_job, int64_t* stats, void* stream);
 
+/* ---- depth-limited search (PolicySearch(depth = D)): the worlds are played D + 1 moves and then valued as score so far + the
+ * blueprint's own Q, in fixed point so that the reduction stays integer. ---- */
+#define HSAD_SEARCH_VALUE_SCALE 256 /* a slot's value is an integer number of 1/256 points */
+enum { HSAD_SEARCH_HORIZON_MOVER = 0, HSAD_SEARCH_HORIZON_TEAM = 1 };
+/* hsad_search_job_stats for a search that stops at a horizon.  job as there; q_rows device fp32 [G * P]: Q_online(s, a) of every
+ * row of `env` at the position it now holds (act(with_q) run on it, the env not stepped since).  Per slot g with a valid job
+ * (the row function is csrc/hsad_search_horizon.h, S = HSAD_SEARCH_VALUE_SCALE):
+ *   finished game (started and terminated): v = score * S with the score hsad_search_job_stats sums; the slot is not "cut".
+ *   live game (started, not terminated): score = the sum of the fireworks (HSAD_Q_SCORE of a live board);
+ *     q = q_rows[g * P + num_step % P], the row of the seat on turn (mode HSAD_SEARCH_HORIZON_MOVER), or the fp32 sum
+ *     q_rows[g * P + 0] + ... + q_rows[g * P + P - 1] added in that order (mode HSAD_SEARCH_HORIZON_TEAM: VDN's joint value);
+ *     b = (int)rintf(fminf(fmaxf(q, -64), 64) * S), round-half-even; a q that is NaN or infinite gives b = 0 and adds 1 to
+ *     nonfinite[0]; v = min(max(score * S + b, 0), perfect_score * S); the slot is "cut".
+ *   any other game (never started): nothing.
+ * stats int64 [n_job, 3] += (v, v^2, 1), cut int64 [n_job] += 1 for a cut slot, nonfinite int64 [1].  All three ACCUMULATE
+ * (the caller zeroes them once per search); 64-bit integer atomics only: exact, order-free.  world_values (NULL = not wanted)
+ * device uint16 [n_job, worlds] with world device int32 [G]: world_values[job[g] * worlds + world[g]] = v for every counted slot
+ * whose world lies in [0, worlds) -- plain 16-bit stores, a (job, world) is played once; the caller fills the table with 0xFFFF
+ * ("not played") once per search.  `env` and q_rows are only read.
+ * HSAD_ERR_INVALID before any launch: n_job <= 0, a mode other than the two, a null job / q_rows / stats / cut / nonfinite,
+ * world_values without world, worlds <= 0 with world_values.  Launch-only, one pass. */
+int hsad_search_horizon_stats(const hsad_env* env, const int32_t* job, int n_job, const float* q_rows, int mode, int64_t* stats,
+                              int64_t* cut, int64_t* nonfinite, const int32_t* world, int worlds, uint16_t* world_values, void* stream);
+
 /* ---- round-wise search (PolicySearch.search(rounds = ...)): the per-world scores are kept, so that actions can be compared world
  * by world (common random numbers: every action of a game meets the same worlds) and hopeless ones dropped between rounds. ---- */
 /* The finished slots' scores, one byte each.  pair / world device int32 [G]: the (root game, action) pair and the world slot g
